@@ -16,10 +16,14 @@ random-init weights of the reference architecture (synthetic data: no datasets/c
 Multi-GPU: the path shards by cloud (one volume per GPU); the forward has no exchange step, so there
 is no data-path collective -- ranks only meet at the barriers around the timed region ("scaling": "weak").
 
-One JSON line on rank 0; besides the contract's keys it carries
+One JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the contract's keys ("metric", "value",
+"unit", "higher_is_better", "dtype", "ms_per_step", ...); --dump-outputs DIR also writes the last timed step's logits.  With --full
+the line also carries
   "roofline"      for the dominant stage: algorithmic bytes or FLOPs per launch (SURVEY 8d formulas, reference
                   formulation) / its average duration measured with hipEvents on the launch stream
   "stages"        the same for every stage (name, ms per step, bound, achieved, frac)
+  "serial", "include_pcie", "coalesced_pairs", "att_fp32_mfma", "batch2", "config5", "train_b8", "train_b1"
+                  the sub-results: other passes and BASELINE configurations timed after the headline
   "cpu_baseline"  the oracle (a port of the reference CPU path) timed on this host on one cloud
 """
 import argparse
@@ -321,6 +325,23 @@ def timed_region(step, steps, sync, dist=None):
 def whole_job_value(world, batch_per_gpu, points, steps, elapsed):
     """points/s over ALL ranks: every rank processes batch_per_gpu clouds of `points` points per step (weak scaling)."""
     return world * batch_per_gpu * points * steps / elapsed
+
+
+DUMP_BUDGET_BYTES = (64 << 20) - (1 << 20)  # 64 MB, less room for the .npy headers
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  Past `budget` bytes in all, every array keeps the same fixed, seeded
+    sample of its rows (leading dimensions flattened, rows in ascending order), so two runs of equal arguments write equal files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, int(len(rows) * budget / total))
+            a = rows[np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 BF16_MFMA_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA
@@ -732,17 +753,27 @@ def main():
     ap.add_argument("--overlap-wgrad", action="store_true", help="train mode: weight-gradient products on a second HIP stream of the trainer (A/B: measured slower)")
     ap.add_argument("--local-bn", action="store_true", help="train mode, N > 1: per-GPU BatchNorm statistics instead of statistics shared by all ranks")
     ap.add_argument("--clouds", type=int, default=8, help="distinct resident clouds every rank rotates through (one per step)")
-    ap.add_argument("--no-sub-results", action="store_true", help="skip the PCIe-inclusive sub-result of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-stage timing and rooflines, the serial and PCIe-inclusive passes, the other "
+                         "BASELINE configurations, the CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="forward mode: write the logits of the last timed step to DIR/logits.npy (float32; a fixed, seeded sample of rows "
+                         "beyond 64 MB).  The timed steps always start at the first resident cloud, so equal arguments give equal inputs")
+    ap.add_argument("--no-sub-results", action="store_true", help="--full: skip the sub-results (serial-pass figures excepted)")
     ap.add_argument("--att-fp32-mfma", action="store_true",
                     help="forward: attentive pooling at d_out = 64 / 128 on the fp32 MFMA instead of bf16 MFMA over exact three-way splits (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stage-timing", action="store_true", help="do not record hipEvents around the stages (A/B of their cost)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-stage-timing", action="store_true", help="--full: do not record hipEvents around the stages (A/B of their cost)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend (nccl = RCCL, the default; gloo lets several ranks share ONE GPU for a functional check "
                          "of the N > 1 path on a single-GPU box together with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="map every rank onto the GPUs that exist (local_rank %% device_count)")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the rank's process to a slice of the CPUs next to its GPU")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_sub_results = args.no_cpu_baseline = args.no_stage_timing = True
+    if args.dump_outputs and args.mode != "forward":
+        raise SystemExit("--dump-outputs: forward mode only (a training step's outputs depend on how many steps the time-based pre-heat took)")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher set the rendezvous up, so this process (which has not touched the GPU and
@@ -938,14 +969,16 @@ def main():
     # over the serial pass that follows the timed region instead (one cloud in flight, same kernels, same inputs).
     if dominant and args.no_pipeline:
         timing_begin(only=dominant)
+    counter[0] = 0  # (the pre-heat runs for a time, not a step count: the timed steps start at cloud 0 so that their last input is fixed)
     elapsed, logits = timed_region(main_step, args.steps, sync, dist)
     dom_rows, dom_steps, dom_where = [], args.steps, "timed region"
     if dominant and args.no_pipeline:
         dom_rows = [r for r in timing_end() if r[0] == dominant]
     assert bool(torch.isfinite(logits).all())
+    outputs = {"logits": logits.float().cpu().numpy()} if args.dump_outputs else None  # (before any later pass reuses the buffers)
     serial_ms = None
     sub = {}
-    if not args.no_pipeline:  # per-cloud latency next to the pipelined throughput
+    if args.full and not args.no_pipeline:  # per-cloud latency next to the pipelined throughput
         dom_steps, dom_where = max(3, args.steps // 2), "serial pass after the timed region (one cloud in flight)"
         if dominant:
             timing_begin(only=dominant)
@@ -1138,6 +1171,8 @@ def main():
         if not args.att_fp32_mfma:
             roofline_network["note"] = ("the single figure above is quoted against the fp32 MFMA peak although fourteen stages run on the bf16 pipe: it is a "
                                         "rate in reference-formulation FLOPs, not the utilisation of one pipe -- see by_pipe")
+        if not prof_rows:  # no profile pass (a plain run, or --no-stage-timing): nothing per stage was measured
+            stages, split, roofline_network, dev_ms = None, None, None, None
         out = {
             "metric": "points_per_sec_forward",
             "value": whole_job_value(world, B, n0, args.steps, elapsed),
@@ -1175,7 +1210,7 @@ def main():
             "include_pcie": sub.get("include_pcie"),
             "coalesced_pairs": sub.get("coalesced_pairs"),
             "att_fp32_mfma": sub.get("att_fp32_mfma"),
-            "device_ms_per_step": round(dev_ms, 4),
+            "device_ms_per_step": round(dev_ms, 4) if dev_ms is not None else None,
             "split": split,
             "algorithmic": {"gflop_per_step": total_cost["flops"] / 1e9, "gbyte_per_step": total_cost["bytes"] / 1e9},
             "stages": stages,
@@ -1220,6 +1255,8 @@ def main():
         if train_ranks is not None:  # N > 1: configs[3], one cloud per GPU (SyncBN / per-GPU BatchNorm): ms per step, calls into the collective, their device ms
             out["summary"]["train_config3"] = {k: [r3(v["ms_per_step"]), v["collectives_per_step"], r3(v["collective_ms"])]
                                                for k, v in train_ranks.items() if isinstance(v, dict)}
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     if dist:
         dist.barrier()

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Copies the summaries profiles/regen_r6.sh left under gpurun_out/ into profiles/ (tracked)."""
+"""Copies the summaries profiles/regen_r6.sh left under $OUT (default profiles/out) into profiles/ (tracked)."""
 import glob
 import json
 import os
 import shutil
 
 here = os.path.dirname(os.path.abspath(__file__))
-src = os.path.join(os.path.dirname(here), "gpurun_out")
+src = os.path.join(os.path.dirname(here), os.environ.get("OUT", "profiles/out"))
 pairs = {"prof_pipe/pipe_kernel_stats.csv": "r6_bench_kernel_stats.csv", "prof_serial/serial_kernel_stats.csv": "r6_serial_kernel_stats.csv",
          "prof_train_b8/train_b8_kernel_stats.csv": "r6_train_b8_kernel_stats.csv",
          "prof_train_b8_bf16/train_b8_bf16_kernel_stats.csv": "r6_train_b8_bf16_kernel_stats.csv",

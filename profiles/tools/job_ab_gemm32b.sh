@@ -3,7 +3,7 @@
 # against the split-bf16 form (gemm32b.hip) -- serial one-lane and 4-lane figures of both.  (tuning flavour: the default build ignores PS_*)
 cd "$GRAFT_REPO_ROOT"
 for v in 3e8 1e30; do
-  PS_GEMM32B_MIN_FLOPS=$v python3 profiles/tools/with_variant.py tuning bench.py --steps 300 --warmup 40 --no-cpu-baseline --no-sub-results 2>/dev/null | python3 -c "
+  PS_GEMM32B_MIN_FLOPS=$v python3 profiles/tools/with_variant.py tuning bench.py --full --steps 300 --warmup 40 --no-cpu-baseline --no-sub-results 2>/dev/null | python3 -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=l.get('sub_results',{}).get('serial',{})

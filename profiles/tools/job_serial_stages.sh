@@ -2,7 +2,7 @@
 # serial (one stream) forward with hipEvent stage timing: prints ms per cloud and the stage table.  usage: bash profiles/tools/job_serial_stages.sh [reps]
 cd "$GRAFT_REPO_ROOT"
 for i in $(seq 1 ${1:-2}); do
-python3 bench.py --no-pipeline --steps 60 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+python3 bench.py --full --no-pipeline --steps 60 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 st={r['name']: r for r in j['stages']}

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"
 for v in "$@"; do for rep in 1 2; do
 if [ "$v" = default ]; then cmd="python3 bench.py"; else cmd="python3 profiles/tools/with_variant.py $v bench.py"; fi
-$cmd --no-pipeline --steps 60 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+$cmd --full --no-pipeline --steps 60 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 st={r['name']: r for r in j['stages']}

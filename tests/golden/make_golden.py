@@ -154,3 +154,32 @@ sp, sf, sl = ob.canonical_rows(sub[0], sub[1], np.asarray(sub[2]).reshape(-1, 1)
 proj_d = np.linalg.norm(full[0].astype(np.float64) - sub[0][proj_idx].astype(np.float64), axis=1)
 save("volume_to_cloud", raw=raw, seg=segv, xyz=full[0], colors=full[1], labels=full[2], xyz_origin=origin.astype(np.int32),
      sub_grid_size=np.float32(0.11), sub_xyz=sp, sub_colors=sf, sub_labels=sl, proj_dist=proj_d)
+
+# SHA-256 digests of the REAL reference's outputs on the fresh inputs of tests/test_oracle.py (the outputs themselves are 2.3 MB):
+# where oracle/_ref cannot be built, those tests compare the oracle against these.  digest() is the one in tests/test_oracle.py.
+import hashlib  # noqa: E402
+import json  # noqa: E402
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(("%s%s" % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+dig = {}
+for K in (1, 16, 32):
+    for j, c in enumerate((uniform_cloud(9000, 21), brats_cloud(9000, 22, grid=(48, 48, 32)))):
+        dig["knn_k%d_cloud%d" % (K, j)] = digest(ob.ref_knn_batch(c[None], c[None], K))
+        dig["upsample_cloud%d" % j] = digest(ob.ref_knn_batch(c[:2250][None], c[None], 1))
+trng = np.random.default_rng(5)
+ts, tq = trng.random((4, 2500, 3), dtype=np.float32), trng.random((4, 700, 3), dtype=np.float32)
+dig["threading_k16"] = digest(ob.ref_knn_batch(ts, tq, 16, omp=False))
+grng = np.random.default_rng(3)
+gp = grng.random((30000, 3), dtype=np.float32)
+gf = grng.standard_normal((30000, 3)).astype(np.float32)
+gp, gf, _ = ob.canonical_rows(*ob.ref_grid_subsample(gp, gf, None, 0.05))
+dig["grid_points"], dig["grid_features"] = digest(gp), digest(gf)
+with open(os.path.join(HERE, "ref_digests.json"), "w") as fh:
+    json.dump(dig, fh, indent=1, sort_keys=True)
+    fh.write("\n")
+print("ref_digests", len(dig))

@@ -7,6 +7,9 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKER = textwrap.dedent("""
@@ -154,3 +157,39 @@ def test_ranks_pin_themselves_to_disjoint_cpu_slices_before_any_gpu_call():
     src = open(os.path.join(ROOT, "bench.py")).read()
     main = src[src.index("def main():"):]
     assert main.index("os.sched_setaffinity(0, mine)") < main.index("import torch") and "--no-pin" in main
+
+
+def test_write_outputs_keeps_small_outputs_whole_and_samples_large_ones_the_same_way(tmp_path):
+    """--dump-outputs: float32 .npy files; over the byte budget every array keeps the same seeded rows, within the budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    logits = np.random.default_rng(1).standard_normal((2, 3000, 4))
+    bench.write_outputs(str(tmp_path / "whole"), {"logits": logits})
+    got = np.load(tmp_path / "whole" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logits.astype(np.float32))
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"logits": logits, "other": logits[0]}, budget=40000)
+    a, b = np.load(tmp_path / "a" / "logits.npy"), np.load(tmp_path / "b" / "logits.npy")
+    assert np.array_equal(a, b) and a.shape[1] == 4 and a.nbytes + np.load(tmp_path / "a" / "other.npy").nbytes <= 40000
+    rows = logits.reshape(-1, 4).astype(np.float32)
+    assert all(np.all(rows == r, axis=1).any() for r in a)                 # rows of the output, not made up
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_logits(tmp_path):
+    """A plain run (no --full) prints the headline keys with --steps timed steps and nothing per stage; --dump-outputs writes the last
+    timed step's logits, which depend on --steps only (not on the warm-up or the time-based pre-heat)."""
+    def run(warmup, out):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", str(warmup),
+                            "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.lstrip().startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0]), np.load(out / "logits.npy")
+    line, a = run(1, tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["stages"] is None and "cpu_baseline" not in line
+    assert a.dtype == np.float32 and a.shape == (1, 180000, 4) and np.isfinite(a).all()
+    _, b = run(3, tmp_path / "b")
+    assert np.array_equal(a, b)

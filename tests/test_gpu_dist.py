@@ -59,7 +59,7 @@ def test_train_bench_through_rccl_world_size_one():
     order than the one-rank kernels, and the bench line's loss is the one after some forty optimisation steps (pre-heat + warm-up + timed):
     the two trajectories agree to a few per cent, not to rounding -- the numerics of SyncBN are test_gpu_train.py's business
     (two ranks on this GPU = one rank with batch 2)."""
-    common = ["--gpus", "1", "--mode", "train", "--batch", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--mode", "train", "--batch", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     with_pg = _bench(common + ["--dist-backend", "nccl"], True)
     without = _bench(common + ["--no-stage-timing"], False)
     assert with_pg["ranks_seen"] == 1 and with_pg["metric"] == "points_per_sec_train_step"
