@@ -20,6 +20,9 @@
  *                                      (PointSegment/helper_tf_util.py:115-250) in inference mode
  *   ps_op_*                            the individual Network.* static methods (RandLANet.py:337-401) for
  *                                      callers that keep the reference's op-by-op graph
+ *   ps_confusion_accumulate,           Network.evaluate (RandLANet.py:208-264), genSegmentation
+ *   ps_probs_to_labels, ps_seg_metrics (utils/genSegmentationBraTS.py:67-79), utils/evaluationBraTS.py:13-64 (Dice + medpy's hd95),
+ *                                      utils/evaluationPancreas.py:14-37
  *
  * Conventions
  * -----------
@@ -242,6 +245,34 @@ int ps_op_half_to_float(ps_context* ctx, const uint16_t* in, int64_t n, float* o
 int ps_op_probs_to_volume(ps_context* ctx, const float* logits, int64_t n, int64_t C, const int32_t* p_idx,
                           const int32_t* xyz_origin, int64_t total, int64_t Z, int64_t X, int64_t Y, float* volume,
                           int32_t* scratch);
+
+/* ---- evaluation (csrc/metrics.hip) --------------------------------------------------------------------------------------------------
+ * What turns logits and probability volumes into reported numbers, on the device. */
+/* Confusion matrix of a cloud (Network.evaluate's argmax + sklearn confusion_matrix, PointSegment/RandLANet.py:208-264): logits
+ * f32[n, C], labels i32[n], optional label_map i32[L] (truth class = label_map[label]; -1 = ignored, Trainer.label_map's convention,
+ * which restates the ignored-label handling of :226-233; a label outside [0, L), or a class outside [0, C), is skipped).  ACCUMULATES
+ * into the caller-zeroed confusion int64[C, C] (rows truth, columns prediction, as sklearn), so a validation loop sums many clouds
+ * without a copy.  Prediction = argmax of the logits, ties to the lowest index (np.argmax; the reference takes the argmax of the softmax,
+ * which differs only where distinct logits round to equal fp32 probabilities).  C <= 32.  Device pointers, asynchronous. */
+int ps_confusion_accumulate(ps_context* ctx, const float* logits, const int32_t* labels, int64_t n, int64_t C, const int32_t* label_map,
+                            int64_t L, int64_t* confusion);
+/* Probability volume -> label volume (genSegmentation, utils/genSegmentationBraTS.py:67-79): probs f32[V, C] (point2prod's layout,
+ * flattened) -> labels u8[V] = label_values[argmax], ties to the lowest index (an all-zero voxel gets label_values[0], as np.argmax).
+ * label_values: HOST i32[C], each in [0, 255] ({0, 1, 2, 4} for BraTS, :73-76).  C <= 32.  Device pointers, asynchronous. */
+int ps_probs_to_labels(ps_context* ctx, const float* probs, int64_t V, int64_t C, const int32_t* label_values, uint8_t* labels);
+/* Region metrics of a label pair (utils/evaluationBraTS.py:22-64 dice_coefficient / preprocess_label, evaluationPancreas.py:14-37, and
+ * medpy's hd95(result, reference, voxelspacing, connectivity=1) whose scipy parts evaluationBraTS.py:13-21 imports): pred and truth
+ * u8[D0, D1, D2] (device, same layout, any axis order), spacing HOST f64[3] (per array axis), regions HOST u32[R] (bit L set = label L is
+ * in region r; labels 0..31), R <= 8.  Writes HOST counts int64[R, 3] = (n_pred, n_truth, n_both) and scores f64[R, 2] = (dice, hd95):
+ * dice = 1 when both masks are empty, else 2 n_both / (n_pred + n_truth); hd95 = np.percentile(hstack(d_PT, d_TP), 95) over the
+ * surface distances of the 6-neighbourhood borders (a mask voxel on a face of the array is a border voxel), 0 when both masks are
+ * empty, +inf when exactly one is (medpy raises there).  Every axis <= 6144 voxels, D0*D1*D2 < 2^31.  scratch: device memory of at
+ * least ps_seg_metrics_scratch_bytes(D0, D1, D2, R) bytes, 256-byte aligned (nothing is allocated per call).  One synchronisation;
+ * results are bitwise reproducible. */
+int ps_seg_metrics(ps_context* ctx, const uint8_t* pred, const uint8_t* truth, int64_t D0, int64_t D1, int64_t D2, const double* spacing,
+                   const uint32_t* regions, int32_t R, void* scratch, int64_t scratch_bytes, int64_t* counts, double* scores);
+/* bytes of scratch ps_seg_metrics needs (2R float64 volumes + one u16 flag volume + 17 KB), -1 for a bad shape or R */
+int64_t ps_seg_metrics_scratch_bytes(int64_t D0, int64_t D1, int64_t D2, int32_t R);
 
 /* The op-level kernels of the training step -- forward / backward pairs of the ops above, BatchNorm in training mode, the fused and
  * recompute forms the native trainer chooses between, the deterministic scatter-adds, loss and Adam -- are declared in

@@ -1,0 +1,246 @@
+"""point_unet_amd.metrics on the MI355X (csrc/metrics.hip): confusion matrices, probability volume -> labels, Dice / HD95 of label
+volumes, validate().  Oracles: numpy (bincount, argmax, the brute-force hd95 of tests/seg_metrics_oracle.py) and the scipy goldens of
+tests/golden/seg_metrics.npz -- no scipy on the GPU machine is needed."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import seg_metrics_oracle as so
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seg_metrics.npz")
+REGS = list(so.BRATS_REGIONS)
+
+
+@pytest.fixture(scope="module")
+def M():
+    from point_unet_amd import metrics
+    return metrics
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+@pytest.fixture(scope="module")
+def brats_pair():
+    return so.label_pair(so.BRATS_SHAPE, 0)
+
+
+def _np_confusion(logits, labels, C, lmap=None):
+    t = labels.astype(np.int64)
+    if lmap is not None:
+        inside = (t >= 0) & (t < len(lmap))
+        t = np.where(inside, np.asarray(lmap)[np.clip(t, 0, len(lmap) - 1)], -1)
+    keep = (t >= 0) & (t < C)
+    pred = np.argmax(logits, 1)
+    return np.bincount(t[keep] * C + pred[keep], minlength=C * C).reshape(C, C)
+
+
+def _check_golden(got, golden, case, rel):
+    for i, r in enumerate(REGS):
+        assert [got[r]["n_pred"], got[r]["n_truth"], got[r]["n_both"]] == golden[case + "/counts"][i].tolist(), (case, r)
+        assert got[r]["dice"] == golden[case + "/dice"][i], (case, r)
+        assert got[r]["hd95"] == pytest.approx(golden[case + "/hd95"][i], rel=rel, abs=0), (case, r)
+
+
+# ---- confusion ----------------------------------------------------------------------------------------------------------------------
+def test_confusion_c4_with_ties_and_accumulation(M):
+    rng = np.random.default_rng(0)
+    n, C = 180000, 4
+    logits = rng.standard_normal((n, C)).astype(np.float32)
+    logits[::7, 2] = logits[::7, 1]            # ties: the lower index wins
+    logits[::11] = 0.5                          # all four equal
+    labels = rng.integers(0, C, n).astype(np.int32)
+    lg, lb = torch.from_numpy(logits).cuda(), torch.from_numpy(labels).cuda()
+    cm = M.confusion(lg, lb, C)
+    want = _np_confusion(logits, labels, C)
+    assert cm.dtype == torch.int64 and np.array_equal(cm.cpu().numpy(), want)
+    M.confusion(lg[:1000], lb[:1000], C, out=cm)  # accumulates
+    assert np.array_equal(cm.cpu().numpy(), want + _np_confusion(logits[:1000], labels[:1000], C))
+
+
+def test_confusion_c13_with_ignored_label(M):
+    rng = np.random.default_rng(1)
+    n, C = 50000, 13
+    logits = rng.standard_normal((n, C)).astype(np.float32)
+    labels = rng.integers(0, C + 1, n).astype(np.int32)  # raw labels 0..13, label 5 ignored
+    cm = M.confusion(torch.from_numpy(logits).cuda(), torch.from_numpy(labels).cuda(), C, ignored_label_inds=(5,)).cpu().numpy()
+    lmap = list(range(5)) + [-1] + list(range(5, C))
+    assert np.array_equal(cm, _np_confusion(logits, labels, C, lmap))
+    assert cm.sum() == (labels != 5).sum()
+
+
+def test_confusion_rejects_bad_arguments(M):
+    x = torch.zeros((10, 4), device="cuda")
+    with pytest.raises(ValueError):
+        M.confusion(x, torch.zeros(9, dtype=torch.int32, device="cuda"), 4)
+    with pytest.raises(ValueError):
+        M.confusion(x, torch.zeros(10, dtype=torch.int32, device="cuda"), 5)
+
+
+# ---- probabilities -> labels --------------------------------------------------------------------------------------------------------
+def _chain_volume(pred_chain, sel, seed=3):
+    """point2prod of 180 000 points whose logits pick the class of pred's label at their voxel, with tied rows; the rest unsampled"""
+    from point_unet_amd.postprocess import point2prod
+    rng = np.random.default_rng(seed)
+    n = len(sel)
+    cls = np.vectorize(so.CLASS_OF_LABEL.get)(pred_chain[sel[:, 0], sel[:, 1], sel[:, 2]])
+    logits = rng.standard_normal((n, 4)).astype(np.float32)
+    logits[np.arange(n), cls] = 6.0
+    tie = np.flatnonzero(cls == 0)[::5]  # class 0 tied with 3: still class 0 (the lowest index)
+    logits[tie, 3] = 6.0
+    xyz = np.stack([sel[:, 2], sel[:, 1], sel[:, 0]], 1).astype(np.int32)  # (x, y, z) of the [Z, Y, X] volume
+    Z, Y, X = so.BRATS_SHAPE
+    return point2prod(torch.from_numpy(logits).cuda(), None, torch.from_numpy(xyz).cuda(), (Z, X, Y))
+
+
+def test_probs_to_labels_point2prod_volume(M, brats_pair):
+    sel, chain = so.chain_points(brats_pair[0])
+    vol = _chain_volume(chain, sel)
+    assert tuple(vol.shape) == so.BRATS_SHAPE + (4,)
+    v = vol.cpu().numpy()
+    v[::3, ::5, ::7, :] = 0.25  # tied rows of four
+    vol = torch.from_numpy(v).cuda()
+    got = M.probs_to_labels(vol)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == so.BRATS_SHAPE
+    want = np.array([0, 1, 2, 4], np.uint8)[np.argmax(v, -1)]
+    assert np.array_equal(got.cpu().numpy(), want)
+    # any C, any table
+    w = v[:20, :, :, :3].copy()
+    got3 = M.probs_to_labels(torch.from_numpy(w).cuda(), (7, 0, 9)).cpu().numpy()
+    assert np.array_equal(got3, np.array([7, 0, 9], np.uint8)[np.argmax(w, -1)])
+
+
+# ---- region metrics -----------------------------------------------------------------------------------------------------------------
+def test_region_metrics_brats_unit_spacing(M, golden, brats_pair):
+    p, t = (torch.from_numpy(a).cuda() for a in brats_pair)
+    _check_golden(M.segmentation_metrics(p, t), golden, "brats", 1e-12)
+
+
+def test_region_metrics_brats_anisotropic(M, golden, brats_pair):
+    p, t = (torch.from_numpy(a).cuda() for a in brats_pair)
+    _check_golden(M.segmentation_metrics(p, t, spacing=(0.8, 0.8, 2.5)), golden, "brats_aniso", 1e-6)
+
+
+@pytest.mark.parametrize("case,shape,variant,spacing", [("small", (24, 24, 24), 1, (1.0, 1.0, 1.0)),
+                                                        ("small_aniso", (24, 24, 24), 1, (1.5, 0.7, 1.1)),
+                                                        ("thin", (9, 17, 13), 0, (1.0, 1.0, 1.0))])
+def test_region_metrics_small_against_golden_and_brute_force(M, golden, case, shape, variant, spacing):
+    pred, truth = so.label_pair(shape, variant)
+    got = M.segmentation_metrics(torch.from_numpy(pred).cuda(), torch.from_numpy(truth).cuda(), spacing=spacing)
+    rel = 1e-12 if case != "small_aniso" else 1e-6
+    _check_golden(got, golden, case, rel)
+    want = so.region_metrics(pred, truth, so.BRATS_REGIONS, spacing, brute=True)
+    for r in REGS:
+        assert got[r]["hd95"] == pytest.approx(want[r]["hd95"], rel=rel)
+
+
+@pytest.mark.parametrize("shape,variant,spacing", [((31, 12, 40), 2, (1.0, 1.0, 1.0)), ((16, 33, 9), 1, (0.8, 0.8, 2.5)),
+                                                   ((1, 20, 25), 0, (1.0, 1.0, 1.0))])
+def test_region_metrics_other_shapes_against_brute_force(M, shape, variant, spacing):
+    pred, truth = so.label_pair(shape, variant)
+    got = M.segmentation_metrics(torch.from_numpy(pred).cuda(), torch.from_numpy(truth).cuda(), spacing=spacing)
+    want = so.region_metrics(pred, truth, so.BRATS_REGIONS, spacing, brute=True)
+    for r in REGS:
+        assert {k: got[r][k] for k in ("dice", "n_pred", "n_truth", "n_both")} == {k: want[r][k] for k in ("dice", "n_pred", "n_truth", "n_both")}
+        assert got[r]["hd95"] == pytest.approx(want[r]["hd95"], rel=1e-6 if spacing[2] != 1.0 else 1e-12)
+
+
+def test_region_metrics_edge_cases(M):
+    shape = (10, 12, 14)
+    z = torch.zeros(shape, dtype=torch.uint8, device="cuda")
+    one = z.clone()
+    one[3, 4, 5] = 4
+    other = z.clone()
+    other[7, 1, 13] = 4
+    full = torch.full(shape, 2, dtype=torch.uint8, device="cuda")
+    regs = {"ET": (4,), "WT": (1, 2, 4)}
+    both_empty = M.segmentation_metrics(z, z, regs)
+    assert both_empty["ET"] == {"dice": 1.0, "hd95": 0.0, "n_pred": 0, "n_truth": 0, "n_both": 0}
+    one_empty = M.segmentation_metrics(one, z, regs)
+    assert one_empty["ET"]["dice"] == 0.0 and math.isinf(one_empty["ET"]["hd95"]) and one_empty["ET"]["n_pred"] == 1
+    assert M.segmentation_metrics(z, one, regs, empty_hd95=373.13)["ET"]["hd95"] == 373.13
+    assert M.segmentation_metrics(one, z, regs, empty_hd95=373.13)["WT"]["hd95"] == 373.13
+    all_vox = M.segmentation_metrics(full, full, regs)["WT"]
+    assert all_vox == {"dice": 1.0, "hd95": 0.0, "n_pred": 10 * 12 * 14, "n_truth": 10 * 12 * 14, "n_both": 10 * 12 * 14}
+    single = M.segmentation_metrics(one, other, regs, spacing=(2.0, 1.0, 0.5))["ET"]
+    assert single["dice"] == 0.0 and single["hd95"] == pytest.approx(math.sqrt((4 * 2.0) ** 2 + 3.0 ** 2 + (8 * 0.5) ** 2), rel=1e-15)
+    # integer dtypes are converted on the device
+    assert M.segmentation_metrics(one.to(torch.int64), one.to(torch.int32), regs)["ET"]["dice"] == 1.0
+    with pytest.raises(ValueError):
+        M.segmentation_metrics(one, z[:, :, :3], regs)
+    with pytest.raises(ValueError):
+        M.segmentation_metrics(one.float(), z, regs)
+
+
+def test_region_metrics_are_bitwise_reproducible(M, brats_pair):
+    p, t = (torch.from_numpy(a).cuda() for a in brats_pair)
+    a = M.segmentation_metrics(p, t, spacing=(0.8, 0.8, 2.5))
+    b = M.segmentation_metrics(p, t, spacing=(0.8, 0.8, 2.5))
+    for r in REGS:
+        for k in ("dice", "hd95"):
+            assert np.float64(a[r][k]).tobytes() == np.float64(b[r][k]).tobytes()
+        assert a[r] == b[r]
+
+
+def test_full_chain_point2prod_labels_metrics(M, golden, brats_pair):
+    pred, truth = brats_pair
+    sel, chain = so.chain_points(pred)
+    vol = _chain_volume(chain, sel)
+    labels = M.probs_to_labels(vol)
+    assert np.array_equal(labels.cpu().numpy(), np.array([0, 1, 2, 4], np.uint8)[np.argmax(vol.cpu().numpy(), -1)])
+    assert np.array_equal(labels.cpu().numpy(), chain)
+    _check_golden(M.segmentation_metrics(labels, torch.from_numpy(truth).cuda()), golden, "chain", 1e-12)
+
+
+# ---- validate -----------------------------------------------------------------------------------------------------------------------
+def test_validate_matches_the_reference_restatement(M):
+    from conftest import uniform_cloud
+    from netcase import config1
+    from point_unet_amd import weights
+    from point_unet_amd.pyramid import build_pyramid
+    from point_unet_amd.RandLANet import Network
+
+    cfg, xyz, feats = config1()
+    params = weights.init_params(cfg, seed=4, randomize_bn=True)
+    net = Network(cfg, params=params)
+    batches, raw = [], []
+    for s in range(2):
+        x = xyz if s == 0 else uniform_cloud(xyz.shape[1], 7)[None]
+        f = feats.copy()
+        f[..., :3] = x
+        lab = np.random.default_rng(10 + s).integers(0, cfg.num_classes, (1, x.shape[1])).astype(np.int32)
+        pyr = build_pyramid(torch.from_numpy(x).cuda(), cfg)
+        ft = torch.from_numpy(f).cuda()
+        batches.append((pyr, ft, torch.from_numpy(lab).cuda()))
+        raw.append((net.inference({"pyramid": pyr, "features": ft}).cpu().numpy().reshape(-1, cfg.num_classes), lab.reshape(-1)))
+    got = M.validate(net, batches)
+    # RandLANet.py:213-251 with the same logits
+    C = cfg.num_classes
+    gt, pos, tp = np.zeros(C), np.zeros(C), np.zeros(C)
+    correct = seen = 0
+    for logits, labels in raw:
+        pred = np.argmax(logits, 1)
+        correct += int((pred == labels).sum())
+        seen += len(labels)
+        cm = np.bincount(labels * C + pred, minlength=C * C).reshape(C, C)
+        gt += cm.sum(1)
+        pos += cm.sum(0)
+        tp += np.diagonal(cm)
+    iou = tp / (gt + pos - tp)
+    assert np.array_equal(got["confusion"].cpu().numpy().sum(), seen)
+    assert got["accuracy"] == correct / float(seen)
+    np.testing.assert_array_equal(got["iou"], iou)
+    assert got["mean_iou"] == pytest.approx(sum(iou) / float(C), rel=1e-15)
+
+
+def test_validate_undefined_iou_is_nan(M):
+    cm = np.array([[5, 0, 0], [1, 3, 0], [0, 0, 0]])
+    s = M.scores_from_confusion(cm)
+    assert math.isnan(s["iou"][2]) and s["mean_iou"] == pytest.approx((5 / 6 + 3 / 4) / 2) and s["accuracy"] == 8 / 9
