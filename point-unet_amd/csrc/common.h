@@ -117,7 +117,8 @@ namespace ps {
 // Experiment knobs of profiles/tools/*.  The DEFAULT build never reads the environment: the values below are what ships, every context holds
 // the same ones, and nothing else in the library calls getenv.  A library built with -DPS_TUNING_ENV (profiles/tools/build_variant.sh) fills
 // the struct ONCE, in ps_create (tuning_from_env, context.hip), from the PS_* variables named here, clamped to what the kernels are compiled
-// for; the trainer reads its knobs from its context when it is created.  No function-static caches, no per-call getenv.
+// for; the trainer reads its knobs from its context when it is created.  No function-static caches, no per-call getenv.  The test library
+// sets them per context through ps_debug_set_tuning (debug_hooks.h), with the same value rules.
 struct Tuning {
     // gemm32b.hip / gemm32.hip (forward dense layers of the deep levels)
     double gemm32b_min_flops = 3e8;  // PS_GEMM32B_MIN_FLOPS: products at least this large run on split-bf16 MFMA (0 = all that fit, 1e30 = none)
@@ -134,7 +135,7 @@ struct Tuning {
     bool bn_slice = false;           // PS_BN_SLICE=1: the one-launch BatchNorm for small tensors (measured no faster: DESIGN.md 4.3)
     // invidx.hip
     bool inv_bucket = true;          // PS_INV_BUCKET=0: the radix-sort form of the inverse index
-    int inv_tile = 4096;             // PS_INV_TILE in {4096, 8192}
+    int inv_tile = 4096;             // PS_INV_TILE in {4096, 6144, 8192}
     bool gather_reduce_ordered = true;  // PS_GATHER_REDUCE_ORDERED=0
     int maxpool_bwd_ordered = 1;     // PS_MAXPOOL_BWD_ORDERED=0: the one-entry cloud-order walk
     // trainer.hip (read at ps_trainer_create)

@@ -171,7 +171,7 @@ void tuning_from_env(Tuning& t)
     clampi("PS_WGRAD_WGS", 64, 4096, t.wgrad_wgs);
     flag("PS_BN_SLICE", t.bn_slice);
     flag("PS_INV_BUCKET", t.inv_bucket);
-    if (num("PS_INV_TILE", v) && (v == 4096 || v == 8192)) t.inv_tile = (int)v;
+    if (num("PS_INV_TILE", v) && (v == 4096 || v == 6144 || v == 8192)) t.inv_tile = (int)v;
     flag("PS_GATHER_REDUCE_ORDERED", t.gather_reduce_ordered);
     if (num("PS_MAXPOOL_BWD_ORDERED", v)) t.maxpool_bwd_ordered = v != 0;
     flag("PS_TRAIN_ACT_BF16", t.train_act_bf16);

@@ -30,6 +30,19 @@ int ps_debug_pack_b3(const float* W, int cin, int cout, uint16_t* out);
  * shape does not fit the kernel. */
 int ps_debug_gemm32(ps_context* ctx, int split_bf16, const float* x1, int ld1, int c1, const int32_t* g1, const float* x2, int ld2, int c2,
                     const int32_t* g2, int gm, int gn, const float* W, const float* bias, int64_t R, int cout, int leaky, float* y, int ldy);
+/* The launch ps_debug_gemm32 (and the network's own dense layers) make on this context for R x cin x cout: out4 = {rw, cw, sk, pd} -- rw x cw
+ * blocks of 32 x 32 per wave, sk waves splitting the K axis (chunks of 8 inputs for the fp32 kernel, 16 for the split form) into slices
+ * [nq k / sk, nq (k + 1) / sk), pd chunks in flight.  Host only: no GPU work. */
+int ps_debug_gemm32_plan(ps_context* ctx, int split_bf16, int64_t R, int cin, int cout, int* out4);
+
+/* The experiment knobs of one context (csrc/common.h, struct ps::Tuning), by C++ field name ("inv_bucket", "gemm32b_rw", ...).  Set accepts
+ * exactly the values the kernels are compiled for (the rules of the -DPS_TUNING_ENV build, without its clamping) and refuses anything else,
+ * and unknown names, with PS_EINVAL.  Kernel dispatch reads the knobs per call; the native trainer reads its train_* knobs (and
+ * convbn_max_c / convbn_rect_max per step, from the same context) -- set them BEFORE ps_trainer_create. */
+int ps_debug_set_tuning(ps_context* ctx, const char* field, double value);
+int ps_debug_get_tuning(ps_context* ctx, const char* field, double* value);
+/* The field names the two doors above know, '\n'-separated and NUL-terminated, into buf[cap]; PS_EINVAL when cap is too small.  No context. */
+int ps_debug_tuning_fields(char* buf, int cap);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,8 @@ extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, i
     PS_CHECK(c && x1 && W && bias && y && R >= 0 && c1 > 0 && c2 >= 0 && cout > 0, "ps_debug_gemm32: bad argument");
     PS_HIP(hipSetDevice(c->device));
     const int cin = c1 + c2;
-    PS_CHECK(cin % 16 == 0 && cout % 32 == 0, "ps_debug_gemm32: cin %% 16 and cout %% 32 must be 0");
+    // (gemm32_fits: 8-wide K chunks for the fp32 kernel, 16-wide for the split form)
+    PS_CHECK(cin % (split_bf16 ? 16 : 8) == 0 && cout % 32 == 0, "ps_debug_gemm32: cin %% %d and cout %% 32 must be 0", split_bf16 ? 16 : 8);
     std::vector<float> img((size_t)cin * cout * (split_bf16 ? 3 : 2) / 2);
     if (split_bf16) pack_p32b(W, cin, cout, reinterpret_cast<uint16_t*>(img.data()));
     else pack_p32(W, cin, cout, img.data());
@@ -60,6 +61,89 @@ extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, i
     (void)hipFree(d_img);
     (void)hipFree(d_bias);
     return rc;
+}
+
+extern "C" int ps_debug_gemm32_plan(ps_context* c, int split_bf16, int64_t R, int cin, int cout, int* out4)
+{
+    PS_CHECK(c && out4 && R >= 1 && cin > 0 && cout > 0 && cin % (split_bf16 ? 16 : 8) == 0 && cout % 32 == 0, "ps_debug_gemm32_plan: bad argument");
+    const Gemm32Plan p = split_bf16 ? gemm32b_plan(c->tune, R, cin, cout) : gemm32_plan(c->tune, R, cin, cout);
+    out4[0] = p.rw;
+    out4[1] = p.cw;
+    out4[2] = p.sk;
+    out4[3] = p.pd;
+    return PS_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------
+// the knobs of struct Tuning (common.h) by field name.  X(field, accepted values of v): the rules of tuning_from_env (context.hip) without
+// its clamping -- every field of the struct is listed (tests/test_host_logic.py parses the struct and compares with ps_debug_tuning_fields).
+// --------------------------------------------------------------------------------------------------------
+static bool is_bool(double v) { return v == 0 || v == 1; }
+static bool is_int_in(double v, double lo, double hi) { return v >= lo && v <= hi && v == (double)(int64_t)v; }
+
+#define PS_TUNING_FIELDS(X)                                                \
+    X(gemm32b_min_flops, v >= 0 && v <= 1e300)                             \
+    X(gemm32b_rw, v == 0 || v == 1 || v == 2)                              \
+    X(gemm32b_cw, v == 0 || v == 1 || v == 2)                              \
+    X(gemm32_no_sk8, is_bool(v))                                           \
+    X(att64_gemm, is_bool(v))                                              \
+    X(att64_occ, v == 0 || v == 1 || v == 2)                               \
+    X(att_no_split, is_bool(v))                                            \
+    X(wgrad_b3_min_rows, is_int_in(v, 0, (double)(1ll << 40)))             \
+    X(gemm_b3_min_rows, is_int_in(v, 0, (double)(1ll << 40)))              \
+    X(wgrad_wgs, is_int_in(v, 64, 4096))                                   \
+    X(bn_slice, is_bool(v))                                                \
+    X(inv_bucket, is_bool(v))                                              \
+    X(inv_tile, v == 4096 || v == 6144 || v == 8192)                       \
+    X(gather_reduce_ordered, is_bool(v))                                   \
+    X(maxpool_bwd_ordered, is_bool(v))                                     \
+    X(train_act_bf16, is_bool(v))                                          \
+    X(train_att_gemm_split, v == -1 || v == 0 || v == 1)                   \
+    X(train_att_gemm, is_bool(v))                                          \
+    X(train_att128_fwd_gemm, is_bool(v))                                   \
+    X(train_fuse_residual, is_bool(v))                                     \
+    X(train_merge_syncbn, is_bool(v))                                      \
+    X(convbn_max_c, is_int_in(v, 0, 4096))                                 \
+    X(convbn_rect_max, is_int_in(v, 0, (double)(1 << 30)))                 \
+    X(wgrad_debug, is_bool(v))
+
+extern "C" int ps_debug_set_tuning(ps_context* c, const char* field, double v)
+{
+    PS_CHECK(c && field, "ps_debug_set_tuning: NULL argument");
+#define PS_SET(f, ok)                                                                                 \
+    if (std::strcmp(field, #f) == 0) {                                                                \
+        PS_CHECK(ok, "ps_debug_set_tuning: %g is not a value %s is compiled for", v, #f);             \
+        c->tune.f = static_cast<decltype(c->tune.f)>(v);                                              \
+        return PS_OK;                                                                                 \
+    }
+    PS_TUNING_FIELDS(PS_SET)
+#undef PS_SET
+    PS_CHECK(false, "ps_debug_set_tuning: no knob named '%s'", field);
+}
+
+extern "C" int ps_debug_get_tuning(ps_context* c, const char* field, double* out)
+{
+    PS_CHECK(c && field && out, "ps_debug_get_tuning: NULL argument");
+#define PS_GET(f, ok)                               \
+    if (std::strcmp(field, #f) == 0) {              \
+        *out = static_cast<double>(c->tune.f);      \
+        return PS_OK;                               \
+    }
+    PS_TUNING_FIELDS(PS_GET)
+#undef PS_GET
+    PS_CHECK(false, "ps_debug_get_tuning: no knob named '%s'", field);
+}
+
+extern "C" int ps_debug_tuning_fields(char* buf, int cap)
+{
+    static const char names[] =
+#define PS_NAME(f, ok) #f "\n"
+        PS_TUNING_FIELDS(PS_NAME)
+#undef PS_NAME
+        ;
+    PS_CHECK(buf && cap >= (int)sizeof(names), "ps_debug_tuning_fields: need %d bytes", (int)sizeof(names));
+    std::memcpy(buf, names, sizeof(names));
+    return PS_OK;
 }
 
 // --------------------------------------------------------------------------------------------------------

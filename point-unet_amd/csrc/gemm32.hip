@@ -30,6 +30,12 @@ struct Gemm32Args {
 
 // waves of a workgroup: SK along K (same output block), 4 / SK consecutive row blocks (SK = 8: eight waves, one row block -- the
 // few-row / long-K layers of levels 3-4 and the decoder, whose launch is one exposed chain of loads and MFMAs per wave: half the chain)
+#ifdef PS_G32_PD
+constexpr int kGemm32Pd = PS_G32_PD;
+#else
+constexpr int kGemm32Pd = 2;  // (measured, serial cloud, same box: 2 / 3 chunks ahead 1.306-1.308 ms, 4: 1.325, 8: 1.315 -- the K slices are 4-16 chunks)
+#endif
+
 template <int CW, int SK>
 __global__ __launch_bounds__(SK > 4 ? 64 * SK : 256) void gemm32_kernel(Gemm32Args a)
 {
@@ -74,11 +80,7 @@ __global__ __launch_bounds__(SK > 4 ? 64 * SK : 256) void gemm32_kernel(Gemm32Ar
         // A ring of PD K-chunks in flight, refilled in place behind its reader (gemm32b.hip's scheme; here PD = 2: a double buffer).  Round 6: the `#pragma unroll 8` loop
         // this replaces was NOT unrolled ("-Wpass-failed: loop not unrolled", silenced by the Makefile's -Wno-pass-failed): every 8-wide K chunk
         // was a load, a wait for it and four MFMAs -- one exposed L2 round trip per chunk, eight to sixteen of them per ~9 us launch.
-#ifdef PS_G32_PD
-        constexpr int PD = PS_G32_PD;
-#else
-        constexpr int PD = 2;  // (measured, serial cloud, same box: 2 / 3 chunks ahead 1.306-1.308 ms, 4: 1.325, 8: 1.315 -- the K slices are 4-16 chunks)
-#endif
+        constexpr int PD = kGemm32Pd;
         float4 axr[PD], bwr[PD][CW];
         auto fetch = [&](int slot, int q) __attribute__((always_inline)) {
             q = min(q, qb - 1);  // (past the end: a harmless repeat of the last chunk, never used)
@@ -162,6 +164,25 @@ bool gemm32_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int6
            (s2.c == 0 || (reinterpret_cast<uintptr_t>(s2.x) & 15) == 0) && ldy > 0;
 }
 
+Gemm32Plan gemm32_plan(const Tuning& tn, int64_t R, int cin, int cout)
+{
+    Gemm32Plan p;
+    const int rblocks = (int)((R + 31) / 32);
+    // two column blocks per wave (a row fragment feeds eight MFMAs) once that still leaves a wave for every SIMD
+    p.cw = (cout % 64 == 0 && (int64_t)rblocks * (cout / 64) >= 1024) ? 2 : 1;
+    p.cgroups = cout / (32 * p.cw);
+    // split K across the waves of a workgroup while the plain grid leaves SIMDs idle (1 024 of them) and the slices stay >= 8 chunks
+    const int64_t units = (int64_t)rblocks * p.cgroups;
+    p.sk = 1;
+    while (p.sk < 8 && units * p.sk < 1536 && cin / 8 / (p.sk * 2) >= 8) p.sk *= 2;
+    if (p.sk == 8 && tn.gemm32_no_sk8) p.sk = 4;
+    const int rb_per_wg = p.sk > 4 ? 1 : 4 / p.sk;
+    p.rgroups = (rblocks + rb_per_wg - 1) / rb_per_wg;
+    p.rw = 1;
+    p.pd = kGemm32Pd;
+    return p;
+}
+
 int gemm32(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy)
 {
     if (R <= 0) return PS_OK;
@@ -170,19 +191,11 @@ int gemm32(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc&
     a.x1 = s1.x; a.g1 = s1.gather; a.ld1 = s1.ld; a.c1 = s1.c; a.g1m = s1.gm; a.g1n = s1.gn;
     a.x2 = s2.x; a.g2 = s2.gather; a.ld2 = s2.ld; a.c2 = s2.c; a.g2m = s2.gm; a.g2n = s2.gn;
     a.wp = L.w32; a.bias = L.bias; a.y = y; a.ldy = ldy; a.R = (int)R; a.cin = L.cin; a.cout = L.cout; a.leaky = L.leaky;
-    const int rblocks = (int)((R + 31) / 32);
-    // two column blocks per wave (a row fragment feeds eight MFMAs) once that still leaves a wave for every SIMD
-    const int cw = (L.cout % 64 == 0 && (int64_t)rblocks * (L.cout / 64) >= 1024) ? 2 : 1;
-    const int cgroups = L.cout / (32 * cw);
-    // split K across the waves of a workgroup while the plain grid leaves SIMDs idle (1 024 of them) and the slices stay >= 8 chunks
-    const int64_t units = (int64_t)rblocks * cgroups;
-    int sk = 1;
-    while (sk < 8 && units * sk < 1536 && L.cin / 8 / (sk * 2) >= 8) sk *= 2;
-    if (sk == 8 && c->tune.gemm32_no_sk8) sk = 4;
+    const Gemm32Plan p = gemm32_plan(c->tune, R, L.cin, L.cout);
+    const int cw = p.cw, sk = p.sk;
+    a.cgroups = p.cgroups;
+    a.rgroups = p.rgroups;
     const dim3 block(sk > 4 ? 64 * sk : 256);
-    const int rb_per_wg = sk > 4 ? 1 : 4 / sk;
-    a.cgroups = cgroups;
-    a.rgroups = (rblocks + rb_per_wg - 1) / rb_per_wg;
     const unsigned grid = 8u * (unsigned)((a.rgroups * a.cgroups + 7) / 8);
 #define PS_G32(CW)                                                                                       \
     if (sk == 1) hipLaunchKernelGGL((gemm32_kernel<CW, 1>), dim3(grid), block, 0, c->stream, a);         \

@@ -91,6 +91,20 @@ struct Gemm32bArgs {
     int rgroups, cgroups;  // workgroup grid: row groups x column groups (XCD mapping as gemm32.hip)
 };
 
+// PD chunks ahead: a wave's loop is a chain of dependent round trips to L2 / MALL (the weight planes of a layer are read once per 32-row
+// block), and one chunk in flight left the launch latency-bound (23 us for 0.74 GFLOP); the ring is refilled in place behind its last reader.
+// Round 6, serial cloud on one box: 2 chunks ahead 1.280-1.286 ms, 3: 1.283-1.296, 4 (rounds 4-5): 1.295-1.306; 6 / 8 take 256 VGPRs and run
+// the enc2-4 dense stages 0.086 / 0.097 / 0.086 and 0.090 / 0.102 / 0.090 ms against 0.078 / 0.077 / 0.075 -- the K slices of these launches
+// are 8-24 chunks, and every chunk fetched past the end of a slice is a wasted request
+constexpr int gemm32b_pd(int rw, int cw)
+{
+#ifdef PS_G32B_PD
+    return rw * cw >= 4 ? 3 : PS_G32B_PD;  // (experiment: ring depth of the (1, 1) / (1, 2) tiles)
+#else
+    return rw * cw >= 4 ? 3 : 2;
+#endif
+}
+
 // waves of a workgroup: SK along K (same output block), 4 / SK consecutive row units of 32 RW rows
 template <int RW, int CW, int SK>
 __global__ __launch_bounds__(SK > 4 ? 64 * SK : 256) void gemm32b_kernel(Gemm32bArgs a)
@@ -140,17 +154,7 @@ __global__ __launch_bounds__(SK > 4 ? 64 * SK : 256) void gemm32b_kernel(Gemm32b
         }
         const uint4* wq = a.wp + (size_t)cb * nq * 3 * 64 + lane;
         const size_t wstride = (size_t)nq * 3 * 64;  // uint4s between consecutive column blocks
-        // PD chunks ahead: a wave's loop is a chain of dependent round trips to L2 / MALL (the weight planes of a layer are read once per
-        // 32-row block), and one chunk in flight left the launch latency-bound (23 us for 0.74 GFLOP); the ring is refilled in place
-        // behind its last reader
-#ifdef PS_G32B_PD
-        constexpr int PD = RW * CW >= 4 ? 3 : PS_G32B_PD;  // (experiment: ring depth of the (1, 1) / (1, 2) tiles)
-#else
-        // Round 6, serial cloud on one box: 2 chunks ahead 1.280-1.286 ms, 3: 1.283-1.296, 4 (rounds 4-5): 1.295-1.306; 6 / 8 take 256 VGPRs
-        // and run the enc2-4 dense stages 0.086 / 0.097 / 0.086 and 0.090 / 0.102 / 0.090 ms against 0.078 / 0.077 / 0.075 -- the K slices
-        // of these launches are 8-24 chunks, and every chunk fetched past the end of a slice is a wasted request
-        constexpr int PD = RW * CW >= 4 ? 3 : 2;
-#endif
+        constexpr int PD = gemm32b_pd(RW, CW);
         float4 xl[PD][RW], xh[PD][RW];
         uint4 bw[PD][CW][3];
         auto fetch = [&](int slot, int q) __attribute__((always_inline)) {
@@ -291,6 +295,31 @@ bool gemm32b_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int
            (s2.c == 0 || (reinterpret_cast<uintptr_t>(s2.x) & 15) == 0) && ldy > 0;
 }
 
+Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout)
+{
+    Gemm32Plan p;
+    const int rblocks = (int)((R + 31) / 32);
+    // two column blocks per wave (an activation split feeds twelve MFMAs) whenever the layer has them; two row blocks per wave (a weight
+    // fragment feeds both: half the weight stream) once that still leaves every SIMD a wave
+    p.cw = cout % 64 == 0 ? 2 : 1;
+    p.rw = (int64_t)(rblocks / 2) * (cout / (32 * p.cw)) >= 1024 ? 2 : 1;
+    // (A/B overrides of the tile shape, Tuning::gemm32b_rw / _cw: only the compiled shapes 1 and 2; anything else is ignored)
+    if (tn.gemm32b_rw == 1 || tn.gemm32b_rw == 2) p.rw = tn.gemm32b_rw;
+    if ((tn.gemm32b_cw == 1 || tn.gemm32b_cw == 2) && cout % (32 * tn.gemm32b_cw) == 0) p.cw = tn.gemm32b_cw;
+    p.cgroups = cout / (32 * p.cw);
+    const int runits = (rblocks + p.rw - 1) / p.rw;
+    // split K across the waves of a workgroup while the plain grid leaves SIMDs idle (1 024 of them) and the slices keep >= 4 chunks
+    const int64_t units = (int64_t)runits * p.cgroups;
+    p.sk = 1;
+    // (eight waves per workgroup -- gemm32.hip's form for the long-K layers -- measured SLOWER here: dec1 24.8 -> 30.8 us, pipelined step
+    //  0.857 -> 0.875 ms: twice the partial sums through LDS for a chain that the register ring already keeps fed)
+    while (p.sk < 4 && units * p.sk < 1536 && cin / 16 / (p.sk * 2) >= 4) p.sk *= 2;
+    const int ru_per_wg = 4 / p.sk;
+    p.rgroups = (runits + ru_per_wg - 1) / ru_per_wg;
+    p.pd = gemm32b_pd(p.rw, p.cw);
+    return p;
+}
+
 int gemm32b(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy)
 {
     if (R <= 0) return PS_OK;
@@ -299,25 +328,10 @@ int gemm32b(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc
     a.x1 = s1.x; a.g1 = s1.gather; a.ld1 = s1.ld; a.c1 = s1.c; a.g1m = s1.gm; a.g1n = s1.gn;
     a.x2 = s2.x; a.g2 = s2.gather; a.ld2 = s2.ld; a.c2 = s2.c; a.g2m = s2.gm; a.g2n = s2.gn;
     a.wp = reinterpret_cast<const uint4*>(L.w32b); a.bias = L.bias; a.y = y; a.ldy = ldy; a.R = (int)R; a.cin = L.cin; a.cout = L.cout; a.leaky = L.leaky;
-    const int rblocks = (int)((R + 31) / 32);
-    // two column blocks per wave (an activation split feeds twelve MFMAs) whenever the layer has them; two row blocks per wave (a weight
-    // fragment feeds both: half the weight stream) once that still leaves every SIMD a wave
-    int cw = L.cout % 64 == 0 ? 2 : 1;
-    int rw = (int64_t)(rblocks / 2) * (L.cout / (32 * cw)) >= 1024 ? 2 : 1;
-    // (A/B overrides of the tile shape, PS_GEMM32B_RW / PS_GEMM32B_CW: only the compiled shapes 1 and 2; anything else is ignored)
-    if (c->tune.gemm32b_rw == 1 || c->tune.gemm32b_rw == 2) rw = c->tune.gemm32b_rw;
-    if ((c->tune.gemm32b_cw == 1 || c->tune.gemm32b_cw == 2) && L.cout % (32 * c->tune.gemm32b_cw) == 0) cw = c->tune.gemm32b_cw;
-    const int cgroups = L.cout / (32 * cw);
-    const int runits = (rblocks + rw - 1) / rw;
-    // split K across the waves of a workgroup while the plain grid leaves SIMDs idle (1 024 of them) and the slices keep >= 4 chunks
-    const int64_t units = (int64_t)runits * cgroups;
-    int sk = 1;
-    // (eight waves per workgroup -- gemm32.hip's form for the long-K layers -- measured SLOWER here: dec1 24.8 -> 30.8 us, pipelined step
-    //  0.857 -> 0.875 ms: twice the partial sums through LDS for a chain that the register ring already keeps fed)
-    while (sk < 4 && units * sk < 1536 && L.cin / 16 / (sk * 2) >= 4) sk *= 2;
-    const int ru_per_wg = 4 / sk;
-    a.cgroups = cgroups;
-    a.rgroups = (runits + ru_per_wg - 1) / ru_per_wg;
+    const Gemm32Plan p = gemm32b_plan(c->tune, R, L.cin, L.cout);
+    const int rw = p.rw, cw = p.cw, sk = p.sk;
+    a.cgroups = p.cgroups;
+    a.rgroups = p.rgroups;
     const unsigned grid = 8u * (unsigned)((a.rgroups * a.cgroups + 7) / 8);
     const dim3 block(256);
 #define PS_G32B(RW_, CW_)                                                                                            \

@@ -62,6 +62,15 @@ struct RowSrc {
     int gm = 0, gn = 0;               // batched gather: row r reads x[(r / gm) * gn + gather[r]] when gm != 0
 };
 
+// The launch gemm32() / gemm32b() make for R rows x cin x cout: a wave owns rw x cw blocks of 32 x 32, sk waves of a workgroup split the K
+// axis (chunks of 8 / 16 inputs) into slices [nq k / sk, nq (k + 1) / sk), pd chunks are in flight ahead of the products.  The launchers call
+// these, and so does the test door ps_debug_gemm32_plan (debug_hooks.h).
+struct Gemm32Plan {
+    int rw = 1, cw = 1, sk = 1, pd = 2;
+    int rgroups = 0, cgroups = 0;  // workgroup grid
+};
+Gemm32Plan gemm32_plan(const Tuning& tn, int64_t R, int cin, int cout);
+Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout);
 // the same layer on 32x32x2 tiles (gemm32.hip): few rows x wide channels (encoder levels 2-4, decoder); rowgemm() takes this
 // route by itself when the layer carries a w32 image and the shape qualifies
 bool gemm32_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy);

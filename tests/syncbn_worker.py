@@ -1,6 +1,8 @@
 """Worker of tests/test_gpu_train.py::test_sync_bn_ranks_equal_one_rank_with_the_batch: rank r trains on cloud r of a WORLD_SIZE-cloud
 batch with BatchNorm statistics shared over the process group (gloo here: all ranks use the same GPU), and writes its loss, the averaged
-gradient buffer and the step's collective counts (shared statistics, then one more step with per-GPU statistics) to <out>.rank<r>.npz."""
+gradient buffer and the step's collective counts (shared statistics, then one more step with per-GPU statistics) to <out>.rank<r>.npz.
+`--unmerged`: the shared-statistics trainer is created with the knob train_merge_syncbn = 0 on this process's context (tests/tuning.py; the
+trainer reads it when it is created): every BatchNorm layer its own all-reduces."""
 import os
 import sys
 
@@ -16,11 +18,18 @@ def main():
     import netcase
     import test_gpu_train as T
     out = sys.argv[1]
+    unmerged = "--unmerged" in sys.argv[2:]
     rank = int(os.environ["RANK"])
     dist.init_process_group("gloo", rank=rank, world_size=int(os.environ["WORLD_SIZE"]))
     cfg, xyz, feats = T.syncbn_case(int(os.environ["WORLD_SIZE"]))
+    if unmerged:
+        from point_unet_amd import runtime
+        from tuning import set_tuning
+        set_tuning(runtime.default_context(0), "train_merge_syncbn", 0)
     tr, pyr, params, labels, cw, _ = T._setup(cfg, xyz[rank:rank + 1], feats[rank:rank + 1], labels=T.syncbn_labels(cfg, xyz)[rank:rank + 1],
                                               sync_bn=True, oracle_pyramid=False)
+    if unmerged:
+        set_tuning(runtime.default_context(0), "train_merge_syncbn", 1)
     loss = tr.train_step(pyr, torch.from_numpy(feats[rank:rank + 1]).cuda(), torch.from_numpy(labels).cuda(), dist=dist)
     torch.cuda.synchronize()
     st = tr.collective_stats()

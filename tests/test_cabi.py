@@ -52,7 +52,8 @@ def test_version_and_error_strings(lib):
 
 def test_debug_doors_live_in_their_own_library(lib, dbg):
     """The ps_debug_* test doors are not in the product library (and not in its header): csrc/debug_hooks.h / libpointseg_debug.so."""
-    for name in ("ps_debug_knn_host", "ps_debug_kdtree_host", "ps_debug_kdtree_device", "ps_debug_pack_weights", "ps_debug_pack_b3"):
+    for name in ("ps_debug_knn_host", "ps_debug_kdtree_host", "ps_debug_kdtree_device", "ps_debug_pack_weights", "ps_debug_pack_b3",
+                 "ps_debug_gemm32", "ps_debug_gemm32_plan", "ps_debug_set_tuning", "ps_debug_get_tuning", "ps_debug_tuning_fields"):
         assert not hasattr(lib, name) and hasattr(dbg, name)
     for hname in HEADERS:
         assert "ps_debug" not in open(os.path.join(ROOT, "include", hname)).read()

@@ -42,15 +42,15 @@ def syncbn_labels(cfg, xyz):
     return np.random.default_rng(11).integers(0, cfg.num_classes, xyz.shape[:2]).astype(np.int32)
 
 
-@pytest.mark.parametrize("world", [2, 8])
-def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world):
+@pytest.mark.parametrize("world,merged", [(2, True), (8, True), (2, False)], ids=["2", "8", "2-unmerged"])
+def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world, merged):
     """BASELINE configs[3] semantics: `world` ranks with one cloud each and shared BatchNorm statistics take the same
     optimisation step as one rank with the batch of `world` clouds -- at 2 and at the 8 ranks of the node configs[3] names.  The ranks are
     processes on this one GPU joined by gloo (the collective is backend-agnostic; RCCL carries it on the 8-GPU node).  Also asserted at
     that world size: the number of all-reduce calls a step makes (ps_trainer_collective_stats) -- one for the flat gradient buffer plus
     two per BatchNorm layer with shared statistics (89 for the five-layer network's 44 layers) MINUS the merged ones: the independent
     pairs share a call (mlp2 || shortcut in both directions, mlp1 || LocSE-mlp1 forward: 15 calls less, 74) --, exactly one with per-GPU
-    statistics."""
+    statistics.  Unmerged (the worker sets train_merge_syncbn = 0 on its context before its trainer is created): the same step, 89 calls."""
     import os
     import subprocess
     import sys
@@ -73,7 +73,7 @@ def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world):
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, worker, out], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        procs.append(subprocess.Popen([sys.executable, worker, out] + ([] if merged else ["--unmerged"]), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     logs = [p.communicate(timeout=900)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n".join(l[-2000:] for l in logs)
     got = [np.load(out + ".rank%d.npz" % r) for r in range(world)]
@@ -95,7 +95,7 @@ def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world):
     # collectives of one step at this world size
     assert n_bn == 44, n_bn
     for g in got:
-        assert 1 + 2 * n_bn == 89 and int(g["calls_sync_bn"]) == 89 - 15, int(g["calls_sync_bn"])
+        assert 1 + 2 * n_bn == 89 and int(g["calls_sync_bn"]) == (89 - 15 if merged else 89), int(g["calls_sync_bn"])
         assert int(g["calls_local_bn"]) == 1, int(g["calls_local_bn"])
         assert int(g["bytes_local_bn"]) == 4 * want_grad.size
 
@@ -1328,7 +1328,8 @@ def test_inverse_index_and_gather_reduction(oracle):
     g = torch.Generator().manual_seed(5)
     # (2, 700, ...) .. (1, 40, ...): the count / fill / sort form of small tables; from 65 536 rows on the bucket form (one stable bucket pass
     # + a sort inside every bucket): ragged bucket and tile counts, a 1-NN table, destinations nobody gathers, and "skew" = most rows gather
-    # ONE destination (a bucket far beyond what is sorted through LDS).  PS_INV_BUCKET=0 in the environment runs the radix-sort form instead.
+    # ONE destination (a bucket far beyond what is sorted through LDS).  The radix-sort form and the other bucket tiles run this list in
+    # test_gpu_tuning_paths.py (knobs inv_bucket / inv_tile on a context of their own).
     for B, N, M, K, d, skew in [(2, 700, 700, 16, 8, 0), (1, 300, 1200, 1, 64, 0), (3, 500, 125, 16, 32, 0), (1, 40, 40, 16, 5, 0), (2, 40000, 40000, 16, 4, 0),
                                 (3, 4133, 4133, 16, 8, 0), (2, 70001, 70001, 1, 4, 0), (1, 1000, 9000, 16, 4, 1), (5, 513, 1100, 16, 4, 0),
                                 (1, 262144, 30000, 16, 4, 0), (1, 300000, 5000, 16, 4, 0)]:  # (the last: beyond 512 x 512 destinations per cloud -> the radix-sort form)

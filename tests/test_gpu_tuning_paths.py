@@ -1,0 +1,514 @@
+"""The kernel paths behind the experiment knobs of struct ps::Tuning (csrc/common.h).  The default library never changes a knob, so every
+branch a non-default value selects still ships but runs in no other test.  Each test here sets knobs on a FRESH context through the test
+door ps_debug_set_tuning (tests/tuning.py: tuned_context), runs the op or the step on it and holds the result to the bar the suite
+applies to the default path of that op, against a float64 reference.  Each also shows that the targeted path ran (a plan, a launch count
+or a collective count), or says in its docstring that nothing is observable.  tests/test_tuning_coverage.py checks on the CPU that every
+knob is set somewhere in this file."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import netcase
+from tuning import gemm32_plan, get_tuning, set_tuning, tuned_context
+
+pytestmark = pytest.mark.gpu
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _launches(rows, stage):
+    return sum(n for name, _, n in rows if name == stage)
+
+
+def test_the_door_refuses_values_the_kernels_are_not_compiled_for():
+    from point_unet_amd import _lib, runtime
+    default = runtime.default_context(0)
+    with tuned_context(inv_tile=6144) as ctx:
+        for name, bad in [("inv_tile", 5000), ("inv_tile", 16384), ("gemm32b_rw", 3), ("gemm32b_cw", -1), ("att64_occ", 3), ("wgrad_wgs", 63),
+                          ("wgrad_wgs", 4097), ("wgrad_wgs", 100.5), ("bn_slice", 0.5), ("train_att_gemm_split", 2), ("convbn_max_c", 4097),
+                          ("gemm32b_min_flops", -1), ("wgrad_b3_min_rows", float(1 << 41)), ("no_such_knob", 1)]:
+            with pytest.raises(_lib.PointSegError):
+                set_tuning(ctx, name, bad)
+        assert get_tuning(ctx, "inv_tile") == 6144 and get_tuning(ctx, "wgrad_wgs") == 512  # (a refused value changes nothing)
+    assert get_tuning(default, "inv_tile") == 4096  # (the session's context keeps the shipped values)
+
+
+# ---- gemm32.hip / gemm32b.hip: tile shapes, K splits and the tails of the register ring --------------------------------------------------
+def _slices(nq, sk):
+    return [(nq * (k + 1)) // sk - (nq * k) // sk for k in range(sk)]
+
+
+def _gemm32_cases():
+    """(split, knobs, R, cin, cout, expected (rw, cw, sk, pd)).  A K slice of L chunks runs (L - PD) // PD ... groups of the ring loop, then the
+    tail code for the last PD .. 2 PD - 1 chunks (or fewer than PD when L < PD).  Slices of one chunk up to 2 PD + 1 exist only without a K
+    split (sk > 1 needs >= 8 fp32 / >= 4 bf16 chunks per slice): there every length is run, with a split every residue mod PD and a split
+    of unequal slices."""
+    cases = []
+    for L in range(1, 8):  # no K split
+        for R in (1, 31, 33):
+            if L <= 5:
+                cases.append((0, {}, R, 8 * L, 32, (1, 1, 1, 2)))
+        if L <= 5:
+            cases.append((0, {}, 32768, 8 * L, 32, (1, 1, 1, 2)))     # the row limit
+            cases.append((0, {}, 32768, 8 * L, 64, (1, 2, 1, 2)))     # two column blocks per wave
+        for rw in (1, 2):
+            for cw in (1, 2):
+                pd = 3 if rw * cw >= 4 else 2
+                if L <= 2 * pd + 1:
+                    cases.append((1, {"gemm32b_rw": rw, "gemm32b_cw": cw}, 33 if L % 2 else 31, 16 * L, 64, (rw, cw, 1, pd)))
+    for nq in (16, 17, 19):
+        cases.append((0, {}, 33, 8 * nq, 32, (1, 1, 2, 2)))
+    cases.append((0, {}, 32768, 8 * 17, 64, (1, 2, 2, 2)))
+    for nq in (33, 34):
+        cases.append((0, {}, 31, 8 * nq, 32, (1, 1, 4, 2)))
+    for nq in (65, 66):
+        cases.append((0, {}, 1, 8 * nq, 32, (1, 1, 8, 2)))
+        cases.append((0, {"gemm32_no_sk8": 1}, 1, 8 * nq, 32, (1, 1, 4, 2)))
+    for rw in (1, 2):
+        for cw in (1, 2):
+            pd = 3 if rw * cw >= 4 else 2
+            for nq, sk in [(9, 2), (11, 2), (13, 2), (17, 4), (26, 4)]:
+                cases.append((1, {"gemm32b_rw": rw, "gemm32b_cw": cw}, 1 if nq in (9, 17) else 33, 16 * nq, 64, (rw, cw, sk, pd)))
+    # the heuristic's own choices at the row limit: two row blocks and two column blocks per wave (PD = 3)
+    cases.append((1, {}, 32768, 16 * 5, 128, (2, 2, 1, 3)))
+    cases.append((1, {}, 32768, 16 * 9, 128, (2, 2, 2, 3)))
+    return cases
+
+
+def test_gemm32_tile_shapes_and_ring_tails_against_float64(lib, dbg):
+    """ps_debug_gemm32 (gemm32.hip fp32 MFMA, gemm32b.hip split-bf16 MFMA) on every tile shape and K split the kernels compile and the
+    dispatch can reach (gemm32b_rw / _cw override the split form's shape; gemm32_no_sk8 turns the fp32 kernel's eight-way K split into four),
+    with K slices of every length 1 .. 2 PD + 1 for PD = 2 and 3, unequal slices, fp32 rows of an odd number of 8-wide chunks, two sources
+    with gathers, strided rows and R = 1, 31, 33 and 32768.  ps_debug_gemm32_plan shows which launch each case makes; the set of reached
+    (split, rw, cw, sk, pd, slice length) must cover the list.  Bar as test_deep_level_dense_layers_against_float64: 2e-6 of |x| . |w|."""
+    import torch
+    reached = set()
+    for i, (split, knobs, R, cin, cout, want_plan) in enumerate(_gemm32_cases()):
+        with tuned_context(**knobs) as ctx:
+            plan = gemm32_plan(ctx, split, R, cin, cout)
+            assert plan == want_plan, (split, knobs, R, cin, cout, plan)
+            rw, cw, sk, pd = plan
+            chunk = 16 if split else 8
+            for L in _slices(cin // chunk, sk):
+                reached.add((split, rw, cw, sk, pd, L if sk == 1 else L % pd))
+            if sk > 1 and len(set(_slices(cin // chunk, sk))) > 1:
+                reached.add((split, rw, cw, sk, pd, "unequal"))
+            rng = np.random.default_rng(1000 + i)
+            two = cin >= 2 * chunk and i % 2 == 1
+            c1 = chunk * ((cin // chunk) // 2) if two else cin
+            c2 = cin - c1
+            n = max(R // 3, 1)
+            ld1, ld2, ldy = c1 + 4, c2 + 8, cout + 32
+            x1 = rng.standard_normal((n if i % 2 else R, ld1)).astype(np.float32) * rng.uniform(0.01, 4.0, (1, ld1)).astype(np.float32)
+            x2 = rng.standard_normal((n, ld2)).astype(np.float32)
+            gm = gn = 0
+            if i % 2:  # gathered rows, both sources batched: row r reads x[(r / gm) * gn + g[r]]
+                if R > 1:
+                    gm, gn = max(R // 2, 1), n // 3
+                base = (np.arange(R) // gm) * gn if gm else np.zeros(R, np.int64)
+                g1 = np.array([rng.integers(0, n - b) for b in base], np.int32)
+                g2 = np.array([rng.integers(0, n - b) for b in base], np.int32)
+                s1, s2 = base + g1, base + g2
+            else:  # plain rows, one source
+                g1 = g2 = None
+                s1 = np.arange(R)
+            W = (rng.standard_normal((cin, cout)) / np.sqrt(cin)).astype(np.float32)
+            b = rng.standard_normal(cout).astype(np.float32)
+            leaky = i % 3 != 0
+            d_x1, d_x2 = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda()
+            d_g1 = torch.from_numpy(g1).cuda() if g1 is not None else None
+            d_g2 = torch.from_numpy(g2).cuda() if (g2 is not None and c2) else None
+            y = torch.full((R, ldy), float("nan"), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            rc = dbg.ps_debug_gemm32(ctx.handle, split, _p(d_x1), ld1, c1, _p(d_g1), _p(d_x2) if c2 else None, ld2, c2, _p(d_g2), gm, gn,
+                                     W.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), R, cout, int(leaky), _p(y), ldy)
+            assert rc == 0, lib.ps_last_error()
+            torch.cuda.synchronize()
+            X = x1[s1, :c1].astype(np.float64)
+            if c2:
+                X = np.concatenate([X, x2[s2, :c2].astype(np.float64)], 1)
+            want = X @ W.astype(np.float64) + b.astype(np.float64)
+            if leaky:
+                want = np.where(want >= 0, want, 0.2 * want)
+            scale = np.abs(X) @ np.abs(W.astype(np.float64)) + np.abs(b)
+            got = y.cpu().numpy().astype(np.float64)
+            assert np.isnan(got[:, cout:]).all(), "wrote past the last column"
+            rel = float((np.abs(got[:, :cout] - want) / scale).max())
+            assert rel <= 2e-6, (split, knobs, R, cin, cout, plan, rel)
+    need = set()
+    for split, shapes in ((0, [(1, 1, 1), (1, 2, 1), (1, 1, 2), (1, 2, 2), (1, 1, 4), (1, 1, 8)]),
+                          (1, [(rw, cw, sk) for rw in (1, 2) for cw in (1, 2) for sk in (1, 2, 4)])):
+        for rw, cw, sk in shapes:
+            pd = 3 if (split and rw * cw >= 4) else 2
+            if sk == 1:
+                need |= {(split, rw, cw, 1, pd, L) for L in (1, pd - 1, pd, pd + 1, 2 * pd - 1, 2 * pd, 2 * pd + 1)}
+            else:
+                need |= {(split, rw, cw, sk, pd, r) for r in range(pd)} | {(split, rw, cw, sk, pd, "unequal")}
+    assert need <= reached, sorted(need - reached, key=str)
+
+
+# ---- BatchNorm: the one-launch form for small tensors ---------------------------------------------------------------------------------------
+def test_one_launch_batchnorm_against_float64_autograd():
+    """bn_slice = 1: ps_op_bn_train_fwd_ex / _bwd_ex run bn_slice_fwd_kernel / bn_slice_bwd_kernel (R <= 4096, C % 32 == 0) -- one launch each
+    (stage timing), three and two otherwise (R = 4097: the fallback).  Against torch float64 autograd: y, mean, invstd, dx, dgamma, dbeta.
+    Bars as test_training_ops_against_torch (y and dx 1e-4 absolute), the statistics 1e-5 relative, each widened by what the fp32 one-pass
+    variance that both forms share is entitled to in a column of small spread (5e-7 E[x^2] / var, relative), dx also by (1e-6 + 2 rel) of
+    |gamma| invstd max|dy| (the cancellation inside the normalisation's gradient).  A CPU restatement of the kernels' fp32 arithmetic meets
+    these bars on the same inputs with a factor 2 to spare on the rel term.  Strided y and dy."""
+    import torch
+    from point_unet_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(7)
+    with tuned_context(bn_slice=1) as ctx:
+        h = ctx.handle
+        for R in (1, 2, 33, 4095, 4096, 4097):
+            for C in (32, 96):
+                for leaky in (0, 1):
+                    wide = C + 8
+                    x = (torch.randn(R, C, generator=g) * 2 + 0.5).cuda()
+                    gamma = (torch.rand(C, generator=g) + 0.5).cuda()
+                    beta = torch.randn(C, generator=g).cuda()
+                    ybuf = torch.full((R, wide), 9.0, device="cuda")
+                    st = torch.empty(5, C, device="cuda")
+                    scratch = torch.empty(2 * C, device="cuda")
+                    ctx.timing_begin()
+                    _lib.check(L.ps_op_bn_train_fwd_ex(h, _p(x), _p(gamma), _p(beta), R, C, 1e-6, leaky, _p(ybuf), wide, _p(st[0]), _p(st[1]), _p(st[2]),
+                                                       _p(scratch)))
+                    dybuf = torch.randn(R, wide, generator=g).cuda()
+                    dy = dybuf[:, 4:4 + C]
+                    dx = torch.empty(R, C, device="cuda")
+                    dg, dbt = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
+                    _lib.check(L.ps_op_bn_train_bwd_ex(h, _p(dy), wide, _p(x), _p(gamma), _p(beta), _p(st[0]), _p(st[1]), R, C, leaky, _p(dx), _p(dg),
+                                                       _p(dbt)))
+                    rows = ctx.timing_end()
+                    assert (_launches(rows, "train_bn_fwd"), _launches(rows, "train_bn_bwd")) == ((1, 1) if R <= 4096 else (3, 2)), (R, C, rows)
+                    xd = x.double().requires_grad_(True)
+                    gd, bd = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+                    mean, var = xd.mean(0), xd.var(0, unbiased=False)
+                    ref = (xd - mean) / torch.sqrt(var + 1e-6) * gd + bd
+                    if leaky:
+                        ref = torch.nn.functional.leaky_relu(ref, 0.2)
+                    # (both forms take the variance as E[x^2] - E[x]^2 in fp32: a column whose spread is small against its magnitude -- two
+                    #  near-equal rows -- loses digits in BOTH; `rel` is what that cancellation is entitled to, negligible at 1e-4 elsewhere)
+                    rel = (5e-7 * (xd.detach() ** 2).mean(0) / (var.detach() + 1e-6)).cpu()
+                    ref_d = ref.detach().cpu()
+                    err_y = (ybuf[:, :C].double().cpu() - ref_d).abs()
+                    assert bool((err_y <= 1e-4 + rel * ref_d.abs().max(0).values).all()), (R, C, leaky, float(err_y.max()))
+                    assert bool((ybuf[:, C:] == 9.0).all()), "wrote past the row"
+                    assert float((st[0].double() - mean.detach()).abs().max()) <= 1e-5 * max(1.0, float(mean.detach().abs().max())), (R, C)
+                    istd = (1 / torch.sqrt(var.detach() + 1e-6)).cpu()
+                    assert bool(((st[1].double().cpu() - istd).abs() / istd <= 1e-5 + rel).all()), (R, C)
+                    ref.backward(dy.double())
+                    gx, gg, gb = xd.grad.cpu(), gd.grad.cpu(), bd.grad.cpu()
+                    # (dx = gamma invstd (g - mean g - xhat mean(g xhat)): a cancellation of O(|g|) terms scaled by invstd, and x_hat^2 carries the
+                    #  variance's relative error -- both large in a column of small spread, e.g. R = 2, where x_hat = +-1 whatever x is)
+                    amp = (1e-6 + 2 * rel) * gamma.double().cpu().abs() * istd * dy.double().cpu().abs().max(0).values
+                    assert bool(((dx.double().cpu() - gx).abs() <= 1e-4 + amp + rel * gx.abs().max(0).values).all()), (R, C, leaky)
+                    assert float((dbt.double().cpu() - gb).abs().max()) <= 1e-4 * max(1.0, float(gb.abs().max())), (R, C, leaky)
+                    assert bool(((dg.double().cpu() - gg).abs() <= 1e-4 * max(1.0, float(gg.abs().max())) + rel * gg.abs()).all()), (R, C, leaky)
+
+
+# ---- inverse index (the three forms, every compiled tile) and the max-pool backward -------------------------------------------------
+_INV_TABLES = [(2, 700, 700, 16, 0), (1, 300, 1200, 1, 0), (3, 500, 125, 16, 0), (1, 40, 40, 16, 0), (2, 40000, 40000, 16, 0), (3, 4133, 4133, 16, 0),
+               (2, 70001, 70001, 1, 0), (1, 1000, 9000, 16, 1), (5, 513, 1100, 16, 0), (1, 262144, 30000, 16, 0), (1, 300000, 5000, 16, 0)]
+
+
+@pytest.mark.parametrize("knobs", [{"inv_tile": 4096}, {"inv_tile": 6144}, {"inv_tile": 8192}, {"inv_bucket": 0}], ids=str)
+def test_inverse_index_forms_equal_the_stable_argsort(knobs):
+    """The table list of test_inverse_index_and_gather_reduction through the bucket form at every compiled tile (inv_tile 4096 / 6144 / 8192)
+    and through the radix-sort form (inv_bucket = 0).  Offsets and src must be IDENTICAL to numpy's stable argsort.  Which form ran: the
+    stage's launch count (5: count / fill, 6: bucket passes, 12: radix sort)."""
+    import torch
+    from point_unet_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(5)
+    forms = []
+    with tuned_context(**knobs) as ctx:
+        h = ctx.handle
+        for B, N, M, K, skew in _INV_TABLES:
+            idx = torch.randint(0, N, (B, M, K), generator=g).int()
+            if skew:
+                idx[:, M // 8:, 1:] = 77
+            idx[:, : M // 7, K // 2:] = 0
+            idx[idx == N - 1] = 0
+            d_idx = idx.cuda()
+            n_dst, rpc = B * N, M * K
+            off = torch.empty(n_dst + 1, dtype=torch.int32, device="cuda")
+            src = torch.empty(B * rpc, dtype=torch.int32, device="cuda")
+            ws = torch.empty(int(L.ps_op_inverse_index_workspace(n_dst, B * rpc)), dtype=torch.int32, device="cuda")
+            ctx.timing_begin()
+            _lib.check(L.ps_op_inverse_index(h, _p(d_idx), B, N, rpc, _p(off), _p(src), _p(ws)))
+            n = _launches(ctx.timing_end(), "train_inverse_index")
+            forms.append(n)
+            flat = (idx.reshape(B, -1).numpy().astype(np.int64) + (np.arange(B) * N)[:, None]).reshape(-1)
+            off_h, src_h = off.cpu().numpy(), src.cpu().numpy()
+            assert np.array_equal(off_h, np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=n_dst))]).astype(np.int32)), (B, N, M, K)
+            assert np.array_equal(src_h, np.argsort(flat, kind="stable").astype(np.int32)), (B, N, M, K)
+            assert (n == 5) if B * rpc < 2048 else n in (6, 12), (B, N, M, K, n)  # (small tables: the count / fill form, whatever the knobs)
+    big = [n for (B, N, M, K, _), n in zip(_INV_TABLES, forms) if B * M * K >= 2048]
+    if knobs.get("inv_bucket", 1):
+        assert big.count(6) >= len(big) - 1 and big[-1] == 12, forms  # (the last table's bucket plan does not fit: radix)
+    else:
+        assert set(big) == {12}, forms
+
+
+@pytest.mark.parametrize("ordered,d", [(0, 4), (0, 32), (0, 64), (1, 12), (1, 20), (1, 2052)])
+def test_maxpool_backward_one_entry_walk_equals_the_share_form(ordered, d):
+    """ps_op_random_sample_bwd_inv with tie counts runs maxpool_bwd_inv4_kernel (the one-entry cloud-order walk) under maxpool_bwd_ordered = 0,
+    and in the default build whenever d / 4 does not divide 256 (d = 12, 20) or exceeds it (d = 2052).  As in
+    test_inverse_index_and_gather_reduction: torch.equal to the share form (no tie counts), and within 5e-5 of the atomics form.  The
+    kernel is not observable from outside (one launch either way): the d values and the knob are the evidence."""
+    import torch
+    from point_unet_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(31 + d)
+    with tuned_context(maxpool_bwd_ordered=ordered) as ctx:
+        h = ctx.handle
+        for B, N, K in [(2, 700, 16), (1, 4133, 16), (3, 500, 16)]:
+            if d > 256 and N > 1000:
+                continue
+            M = N
+            idx = torch.randint(0, N, (B, M, K), generator=g).int()
+            idx[:, : M // 7, K // 2:] = 0
+            d_idx = idx.cuda()
+            off = torch.empty(B * N + 1, dtype=torch.int32, device="cuda")
+            src = torch.empty(B * M * K, dtype=torch.int32, device="cuda")
+            ws = torch.empty(int(L.ps_op_inverse_index_workspace(B * N, B * M * K)), dtype=torch.int32, device="cuda")
+            _lib.check(L.ps_op_inverse_index(h, _p(d_idx), B, N, M * K, _p(off), _p(src), _p(ws)))
+            M2 = max(1, M // 4)
+            pool = idx[:, :M2].contiguous().cuda()
+            feat = (torch.randint(0, 4, (B * N, d), generator=g).float() / 2).cuda()
+            out = torch.empty(B * M2, d, device="cuda")
+            ties = torch.empty((B * M2, d), dtype=torch.uint8, device="cuda")
+            _lib.check(L.ps_op_random_sample_ties(h, _p(feat), _p(pool), B, N, M2, K, d, _p(out), _p(ties)))
+            dout = torch.randn(B * M2, d, generator=g).cuda()
+            a = torch.zeros(B * N, d, device="cuda")
+            _lib.check(L.ps_op_random_sample_bwd(h, _p(dout), _p(out), _p(feat), _p(pool), B, N, M2, K, d, _p(a)))
+            b = torch.zeros(B * N, d, device="cuda")
+            share = torch.empty(B * M2, d, device="cuda")
+            _lib.check(L.ps_op_random_sample_bwd_inv(h, _p(dout), _p(out), _p(feat), _p(pool), _p(off), _p(src), B, N, M2, K, d, None, _p(share), _p(b)))
+            b2 = torch.zeros(B * N, d, device="cuda")
+            _lib.check(L.ps_op_random_sample_bwd_inv(h, _p(dout), _p(out), _p(feat), _p(pool), _p(off), _p(src), B, N, M2, K, d, _p(ties), None, _p(b2)))
+            assert (a - b).abs().max() <= 5e-5 * max(1.0, float(a.abs().max())), (B, N, d)
+            assert torch.equal(b2, b), (B, N, d, float((b2 - b).abs().max()))
+
+
+# ---- attentive pooling: the per-point kernels, the other occupancies, the one-wave-per-point backward --------------------------------
+@pytest.mark.parametrize("mode,knobs", [("fp32", {"att64_gemm": 0}), ("bf16", {"att64_gemm": 0}), ("bf16", {"att64_occ": 1}),
+                                        ("fp32", {"att64_occ": 2}), ("bf16", {"att_no_split": 1})], ids=str)
+def test_attentive_pooling_other_forms_against_float64(mode, knobs):
+    """ps_op_att_pool_train_fwd / _bwd at d = 64 (and 128 in the bf16 mode) with att64_gemm = 0 (level 1 back on attpool_train.hip's
+    per-point kernels), att64_occ = 1 / 2 (launch_attg64<1, true, 4> in the bf16 mode, <3, true, 8> in fp32) and att_no_split = 1 (the
+    one-wave-per-point bf16 backward at d = 128), each in the mode it changes.  Harness and bars of test_fused_attentive_pooling_forward_backward: agg 2e-6 / 2e-5, dF and
+    dW 2e-5 (fp32) and 2e-3 / 1e-3 (bf16) of their max, dW bit-identical from run to run.  Which kernel ran is not observable from outside
+    (same stage, same launch count): the knob, read back from the context, is the evidence."""
+    import torch
+    from point_unet_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(11)
+    rb = (lambda t: t.float().bfloat16().double()) if mode == "bf16" else (lambda t: t)
+    K = 16
+    shapes = [(2049, 64, 64), (333, 64, 96), (7, 64, 64)]
+    if mode == "bf16":
+        shapes += [(1500, 128, 128), (333, 128, 192)]
+    with tuned_context(**knobs) as ctx:
+        h = ctx.handle
+        _lib.check(L.ps_set_train_gemm_bf16(h, 1 if mode == "bf16" else 0))
+        for R, d, wide in shapes:
+            buf = torch.randn(R * K, wide, generator=g).cuda()
+            F = buf[:, wide - d:]
+            W = (torch.randn(d, d, generator=g) / d ** 0.5).cuda()
+            dagg = torch.randn(R, d, generator=g).cuda()
+            agg = torch.empty(R, d).cuda()
+            _lib.check(L.ps_op_att_pool_train_fwd(h, _p(F), wide, _p(W), R, K, d, _p(agg)))
+            dF = torch.empty(R * K, d).cuda()
+            dW, dW2 = torch.empty(d, d).cuda(), torch.empty(d, d).cuda()
+            _lib.check(L.ps_op_att_pool_train_bwd(h, _p(F), wide, _p(W), _p(dagg), R, K, d, _p(dF), d, _p(dW)))
+            _lib.check(L.ps_op_att_pool_train_bwd(h, _p(F), wide, _p(W), _p(dagg), R, K, d, _p(dF), d, _p(dW2)))
+            assert torch.equal(dW, dW2)
+            Fd, Wd = F.double().reshape(R, K, d), W.double()
+            P = torch.softmax(rb(Fd) @ rb(Wd), 1)
+            ref = (P * Fd).sum(1)
+            assert (agg.double() - ref).abs().max() <= (2e-6 if mode == "fp32" else 2e-5) * ref.abs().max(), (R, d)
+            gd = dagg.double()[:, None, :]
+            dS = P * gd * (Fd - ref[:, None, :])
+            dF_ref = P * gd + rb(dS) @ rb(Wd).T
+            dW_ref = rb(Fd).reshape(-1, d).T @ rb(dS).reshape(-1, d)
+            assert (dF.double().reshape(R, K, d) - dF_ref).abs().max() <= (2e-5 if mode == "fp32" else 2e-3) * dF_ref.abs().max(), (R, d)
+            assert (dW.double() - dW_ref).abs().max() <= (2e-5 if mode == "fp32" else 1e-3) * dW_ref.abs().max(), (R, d)
+
+
+# ---- weight gradients and op-level GEMMs: slab counts, the b3 / fp32 switch-over ------------------------------------------------------------
+@pytest.mark.parametrize("knobs", [{"wgrad_wgs": 64}, {"wgrad_wgs": 100}, {"wgrad_wgs": 4096}, {"wgrad_b3_min_rows": 1, "gemm_b3_min_rows": 1},
+                                   {"wgrad_b3_min_rows": 1 << 40, "gemm_b3_min_rows": 1 << 40}], ids=str)
+def test_weight_gradients_and_gemms_at_other_thresholds(knobs):
+    """ps_op_linear_wgrad_ex and ps_op_conv1x1_ex at R = 1, 17, 4095, 4097, 16385 with wgrad_wgs = 64 / 100 / 4096 (other slab counts of the
+    weight-gradient partials) and wgrad_b3_min_rows / gemm_b3_min_rows = 1 (split-bf16 MFMA at every row count) or 2^40 (fp32 MFMA at every
+    row count).  Against float64, bars of test_weight_gradients_on_split_bf16_mfma / test_large_fp32_gemms_on_split_bf16_mfma: the split-bf16
+    weight gradient 3e-6 of the max (bias 1e-5), the GEMM 2e-6; the fp32 weight gradient 1e-4 (test_training_ops_against_torch).  Weight
+    gradients repeat bit for bit.  Which kernel ran shows where the two threshold settings give different results (R >= 4095); the slab
+    count is not observable from outside."""
+    import torch
+    from point_unet_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(41)
+    with tuned_context(**knobs) as ctx:
+        h = ctx.handle
+        for R in (1, 17, 4095, 4097, 16385):
+            for cin, cout in [(128, 128), (256, 128)]:
+                xw = torch.randn(R, cin + 8, generator=g).cuda()
+                dw = torch.randn(R, cout + 4, generator=g).cuda()
+                x, dy = xw[:, 4:cin + 4], dw[:, :cout]
+                ref_w, ref_b = x.double().t() @ dy.double(), dy.double().sum(0)
+                gW = torch.full((cin, cout), 7.0, device="cuda")
+                gb = torch.full((cout,), 7.0, device="cuda")
+                _lib.check(L.ps_op_linear_wgrad_ex(h, _p(x), cin + 8, _p(dy), cout + 4, R, cin, cout, _p(gW), _p(gb)))
+                gW2 = torch.empty(cin, cout, device="cuda")
+                _lib.check(L.ps_op_linear_wgrad_ex(h, _p(x), cin + 8, _p(dy), cout + 4, R, cin, cout, _p(gW2), _p(gb)))
+                assert torch.equal(gW, gW2)
+                b3 = knobs.get("wgrad_b3_min_rows") == 1 or (knobs.get("wgrad_b3_min_rows") is None and R >= 4096)
+                ew = float((gW.double() - ref_w).abs().max() / ref_w.abs().max())
+                eb = float((gb.double() - ref_b).abs().max() / ref_b.abs().max())
+                assert ew <= (3e-6 if b3 else 1e-4) and eb <= (1e-5 if b3 else 1e-4), (R, cin, cout, ew, eb)
+                Wt = (torch.randn(cin, cout, generator=g) / cin ** 0.5).cuda()
+                b = torch.randn(cout, generator=g).cuda()
+                y0 = torch.randn(R, cout + 4, generator=g).cuda()
+                y = y0.clone()
+                _lib.check(L.ps_op_conv1x1_ex(h, _p(x), cin + 8, _p(Wt), _p(b), R, cin, cout, 1, 0, _p(y), cout + 4))
+                ref = x.double() @ Wt.double() + b.double()
+                ref = torch.where(ref >= 0, ref, 0.2 * ref)
+                ey = float((y[:, :cout].double() - ref).abs().max() / ref.abs().max())
+                assert ey <= 2e-6 and torch.equal(y[:, cout:], y0[:, cout:]), (R, cin, cout, ey)
+                if (R, cin) == (4095, 128):
+                    probe = (x, dy, Wt, b, gW.clone(), y.clone())
+    forced = knobs.get("wgrad_b3_min_rows")
+    if forced:  # the other forced form is another kernel: other bits at a many-row shape
+        x, dy, Wt, b, gW, y = probe
+        R, cin, cout = x.shape[0], x.shape[1], dy.shape[1]
+        with tuned_context(wgrad_b3_min_rows=(1 << 40) + 1 - forced, gemm_b3_min_rows=(1 << 40) + 1 - forced) as other:
+            gW_o, y_o = torch.empty_like(gW), torch.zeros(R, cout + 4, device="cuda")
+            _lib.check(L.ps_op_linear_wgrad_ex(other.handle, _p(x), cin + 8, _p(dy), cout + 4, R, cin, cout, _p(gW_o), None))
+            _lib.check(L.ps_op_conv1x1_ex(other.handle, _p(x), cin + 8, _p(Wt), _p(b), R, cin, cout, 1, 0, _p(y_o), cout + 4))
+        assert not torch.equal(gW, gW_o) and not torch.equal(y[:, :cout], y_o[:, :cout])
+
+
+# ---- the whole forward network: which dense layers run on split-bf16 MFMA ------------------------------------------------------------
+def test_network_forward_with_every_and_no_dense_layer_on_split_bf16(oracle):
+    """test_all_five_widths_small_cloud's case with gemm32b_min_flops = 0 (every deep dense layer that fits runs on gemm32b.hip) and 1e30
+    (all on gemm32.hip): logits within 1e-4 of the float64 oracle.  The two settings must give different logits (different kernels)."""
+    import torch
+    from oracle import randla_oracle as ro
+    from point_unet_amd import weights
+    from point_unet_amd.RandLANet import Network
+    from point_unet_amd.pyramid import build_pyramid
+    cfg, xyz, feats = netcase.small_deep(6000)
+    params = weights.init_params(cfg, seed=2, randomize_bn=True)
+    pts, nbr, pool, up = ro.build_pyramid(lambda s, q, k: oracle.knn_batch(s, q, k), xyz, cfg.k_n, cfg.sub_sampling_ratio)
+    want = ro.inference(params, cfg.num_layers, pts, nbr, pool, up, feats, np.float64)
+    out = []
+    for flops in (0, 1e30):
+        with tuned_context(gemm32b_min_flops=flops) as ctx:
+            net = Network(cfg, params=params, ctx=ctx)
+            pyr = build_pyramid(torch.from_numpy(xyz).cuda(), cfg, ctx=ctx)
+            for i in range(cfg.num_layers):
+                assert np.array_equal(pyr.neigh_idx[i].cpu().numpy(), nbr[i])
+            logits = net.inference({"pyramid": pyr, "features": torch.from_numpy(feats).cuda()}).cpu().numpy()
+            del net, pyr
+        err = float(np.abs(logits - want).max())
+        assert err <= 1e-4, (flops, err)
+        out.append(logits)
+    assert not np.array_equal(out[0], out[1])
+
+
+# ---- the native training step with each trainer knob flipped -------------------------------------------------------------------------
+# (mode, knobs): each knob in the modes whose step it changes -- the LFA rows are stored as bfloat16 only in the bf16-MLP mode, and the
+# split-source pooling of the narrow levels defaults to on there and off in fp32 (trainer.hip), so each non-default value lives in one mode
+_STEP_CASES = [(mode, knobs) for knobs in ({"train_fuse_residual": 0}, {"train_att_gemm": 0}, {"train_att128_fwd_gemm": 0}, {"convbn_max_c": 0},
+                                           {"convbn_rect_max": 0}, {"gather_reduce_ordered": 0}, {"maxpool_bwd_ordered": 0}, {"inv_bucket": 0},
+                                           {"bn_slice": 1}) for mode in ("fp32", "bf16")]
+_STEP_CASES += [("bf16", {"train_act_bf16": 0}), ("bf16", {"train_att_gemm_split": 0}), ("fp32", {"train_att_gemm_split": 1})]
+
+
+@pytest.fixture(scope="module")
+def ladder_oracle(oracle):
+    """test_training_step_at_the_true_width_ladder's case and its float64 oracle step, once per mode (the bf16 mode also the float32
+    evaluation of the rounded model, whose distance is that test's bar)."""
+    import torch
+    import test_gpu_train as T
+    from oracle import randla_train_oracle as rto
+    from point_unet_amd import weights
+    cfg, xyz, feats = netcase.small_deep(6000, seed=12, B=2)
+    params = weights.init_params(cfg, seed=3, randomize_bn=True)
+    labels = np.random.default_rng(3).integers(0, cfg.num_classes, xyz.shape[:2]).astype(np.int32)
+    cw = np.linspace(1.0, 2.0, cfg.num_classes).astype(np.float32)
+    from oracle import randla_oracle as ro
+    pts, nbr, pool, up = ro.build_pyramid(lambda s, q, k: oracle.knn_batch(s, q, k), xyz, cfg.k_n, cfg.sub_sampling_ratio)
+    cache = {}
+
+    def get(mode):
+        if mode not in cache:
+            rule = T._bf16_rule if mode == "bf16" else None
+            arule = T._act_rule if mode == "bf16" else None
+            want = rto.train_step(params, cfg.num_layers, pts, nbr, pool, up, feats, labels, cw, lr=1e-3, step=1, bf16_rule=rule, act_rule=arule)
+            alt = None
+            if mode == "bf16":
+                alt = rto.train_step(params, cfg.num_layers, pts, nbr, pool, up, feats, labels, cw, lr=1e-3, step=1, bf16_rule=rule, act_rule=arule,
+                                     dtype=torch.float32)
+            cache[mode] = (want, alt)
+        return cache[mode]
+    return cfg, xyz, feats, params, labels, cw, get
+
+
+@pytest.mark.parametrize("mode,knobs", _STEP_CASES, ids=str)
+def test_training_step_with_a_trainer_knob_flipped(ladder_oracle, mode, knobs):
+    """One native training step at the true width ladder (d_out 16 .. 512, two clouds of 6 000 points) with one knob of the trainer set to its
+    other value on the trainer's own context (set before the trainer is created), against the float64 autograd oracle at the bars of
+    test_training_step_at_the_true_width_ladder: fp32 loss 2e-5, logits 1e-4, every gradient tensor 3e-2 of its max + 1e-4 of the global
+    max, whole-gradient relative L2 5e-3, the Adam update 5e-5 where the gradient is signal; bf16 within twice the model's own float32 /
+    float64 spread.  Most forms are not observable from outside the step; the inverse index form is (stage launch counts)."""
+    import torch
+    import test_gpu_train as T
+    from point_unet_amd.pyramid import build_pyramid
+    from point_unet_amd.train import Trainer
+    cfg, xyz, feats, params, labels, cw, get = ladder_oracle
+    want, alt = get(mode)
+    with tuned_context(**knobs) as ctx:
+        tr = Trainer(cfg, params=params, learning_rate=1e-3, class_weights=cw, keep_prob=1.0, mlp_dtype=mode, ctx=ctx)
+        pyr = build_pyramid(torch.from_numpy(xyz).cuda(), cfg, ctx=ctx)
+        if "inv_bucket" in knobs:
+            ctx.timing_begin()
+        loss = tr.train_step(pyr, torch.from_numpy(feats).cuda(), torch.from_numpy(labels).cuda())
+        torch.cuda.synchronize()
+        rows = ctx.timing_end() if "inv_bucket" in knobs else []
+        got = {n: tr.G[n].cpu().numpy() for n in tr.names}
+        logits = tr.last_logits.cpu().numpy().reshape(want["logits"].shape)
+        new = tr.export_params()
+        tr.close()
+        del pyr
+    if "inv_bucket" in knobs:
+        counts = [n for name, _, n in rows if name == "train_inverse_index"]
+        assert counts and 6 not in counts, rows
+    rel_loss = abs(float(loss) - want["loss"]) / max(1.0, abs(want["loss"]))
+    logit_err = float(np.abs(logits - want["logits"]).max())
+    rel_l2, worst = T._grad_stats(got, want["grads"], list(got))
+    print("%s %s: loss rel %.2e, logits %.2e, grad rel L2 %.2e, worst %s" % (mode, knobs, rel_loss, logit_err, rel_l2, worst[:3]))
+    if mode == "fp32":
+        assert rel_loss <= 2e-5 and logit_err < 1e-4, (rel_loss, logit_err)
+        assert worst[0][0] <= 1.0, worst[:5]
+        assert rel_l2 <= 5e-3, rel_l2
+        gscale = max(np.abs(g).max() for g in want["grads"].values())
+        checked = 0
+        for name in got:
+            mask = np.abs(want["grads"][name]) > 2e-2 * gscale
+            if mask.any():
+                checked += int(mask.sum())
+                assert np.abs(new[name] - want["new_params"][name])[mask].max() <= 5e-5, name
+        assert checked > 1000
+    else:
+        s_loss = abs(alt["loss"] - want["loss"]) / max(1.0, abs(want["loss"]))
+        s_logit = float(np.abs(alt["logits"] - want["logits"]).max())
+        s_l2, _ = T._grad_stats(alt["grads"], want["grads"], list(got))
+        assert rel_loss <= 2 * s_loss + 1e-3 and logit_err <= 2 * s_logit + 1e-3 and rel_l2 <= 2 * s_l2 + 1e-3, (rel_loss, logit_err, rel_l2)
