@@ -48,7 +48,10 @@ int ps_op_bn_train_bwd(ps_context* ctx, const float* dy, const float* x, const f
                        float* dgamma, float* dbeta);
 /* The same two ops split at their per-channel reduction, for BatchNorm statistics shared by the GPUs of a data-parallel job
  * (keeps "8 GPUs x 1 cloud" numerically equal to "1 GPU x 8 clouds"): the caller sums `sums2C` = [sum x | sum x^2]
- * (resp. dbeta = sum g, dgamma = sum g*xhat) over the ranks between the halves and passes the global row count R_total. */
+ * (resp. dbeta = sum g, dgamma = sum g*xhat) over the ranks between the halves and passes the global row count R_total.
+ * Precision: ps_op_bn_train_fwd[_ex|_mov] sum and finish the statistics in double; the split form hands float sums over, so its variance
+ * E[x^2] - mean^2 keeps a relative error of about 1e-7 r^2 for a channel whose mean is r standard deviations (tested to r <= 3).
+ * Every backward here uses the reference's LeakyReluGrad: slope 1 only where gamma*xhat + beta > 0, 0.2 at 0 and below. */
 int ps_op_bn_train_sums(ps_context* ctx, const float* x, int64_t R, int64_t C, float* sums2C);
 int ps_op_bn_train_apply(ps_context* ctx, const float* x, const float* gamma, const float* beta, const float* sums2C,
                          int64_t R, int64_t R_total, int64_t C, float eps, int leaky, float* y, float* mean, float* invstd,

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kCbThreads) void cb_bwd_sums_kernel(CbArgs a)
         for (int j = 0; j < C; ++j) {
             const float yc = y[j] - mu.v[j];
             const float xh = yc * is.v[j];
-            const float gv = __builtin_fmaf(yc, sc.v[j], be.v[j]) < 0.f ? 0.2f * g[j] : g[j];
+            const float gv = __builtin_fmaf(yc, sc.v[j], be.v[j]) <= 0.f ? 0.2f * g[j] : g[j];
             acc[j] += gv;
             acc[C + j] = __builtin_fmaf(gv, xh, acc[C + j]);
         }
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(kCbThreads) void cb_bwd_apply_kernel(CbArgs a)
         for (int j = 0; j < C; ++j) {
             const float yc = y[j] - mu.v[j];
             const float xh = yc * is.v[j];
-            const float gv = __builtin_fmaf(yc, sc.v[j], be.v[j]) < 0.f ? 0.2f * g[j] : g[j];
+            const float gv = __builtin_fmaf(yc, sc.v[j], be.v[j]) <= 0.f ? 0.2f * g[j] : g[j];
             dy[j] = sc.v[j] * (gv - m1[j] - xh * m2[j]);
             acc[C * C + j] += dy[j];
         }

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void locse_bwd_kernel(LocseArgs a)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             xh[q] = (y[q] - muv[q]) * isv[q];
-            g[q] = __builtin_fmaf(y[q] - muv[q], scv[q], shv[q]) < 0.f ? 0.2f * dzv[q] : dzv[q];
+            g[q] = __builtin_fmaf(y[q] - muv[q], scv[q], shv[q]) <= 0.f ? 0.2f * dzv[q] : dzv[q];
             s1[q] += g[q];
             s2[q] = __builtin_fmaf(g[q], xh[q], s2[q]);
             xs[q] += xh[q];

@@ -19,27 +19,30 @@ namespace ps {
 
 // ---- per-channel sums over rows: out0[c] += sum_r f0(r,c), out1[c] += sum_r f1(r,c) -------------------------------
 // Layout trick: a block covers a contiguous slab of rows; thread t handles elements t, t+T, ... of the slab; with
-// T % C == 0 its channel never changes.  (C that does not divide T falls back to per-element modulo.)
+// T % C == 0 its channel never changes.  (C that does not divide T falls back to per-element modulo.)  The sums run in F::acc: float for
+// the gradient sums, double for the BatchNorm statistics (SumSq), whose variance E[x^2] - mean^2 is a difference of nearly equal numbers
+// when a channel's mean is large against its spread.
 template <class F>
-__global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, int rows_per_block, int vec, float* __restrict__ part0,
-                                                         float* __restrict__ part1)
+__global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, int rows_per_block, int vec, typename F::acc* __restrict__ part0,
+                                                         typename F::acc* __restrict__ part1)
 {
     // part{0,1}[block][c]: per-block partial sums, merged in a fixed order by colreduce_finish_kernel (no float atomics:
     // the batch statistics, and with them which side of the leaky-ReLU kink an activation falls on, are run-to-run identical)
-    __shared__ float s0[256], s1[256];
+    using T = typename F::acc;
+    __shared__ T s0[256], s1[256];
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     const int64_t r1 = r0 + rows_per_block < R ? r0 + rows_per_block : R;
     const int64_t e0 = r0 * C, e1 = r1 * C;
     const bool fixed = (256 % C) == 0;
     if (vec) {
         // float4 path: thread t owns elements 4t..4t+3 of every 1024-element stripe of the slab, i.e. four fixed channels
-        __shared__ float v0s[1024], v1s[1024];
+        __shared__ T v0s[1024], v1s[1024];
         const int c = (4 * threadIdx.x) % C;
         f.init4(c);
-        float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+        T a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
         int64_t e = e0 + 4 * threadIdx.x;
         for (; e + 1024 < e1; e += 2048) {
-            float p0[4], p1[4], q0[4], q1[4];
+            T p0[4], p1[4], q0[4], q1[4];
             f.load4(e, c, p0, p1);
             f.load4(e + 1024, c, q0, q1);
 #pragma unroll
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, 
             for (int j = 0; j < 4; ++j) { a[j] += q0[j]; b[j] += q1[j]; }
         }
         if (e < e1) {
-            float p0[4], p1[4];
+            T p0[4], p1[4];
             f.load4(e, c, p0, p1);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { a[j] += p0[j]; b[j] += p1[j]; }
@@ -57,18 +60,18 @@ __global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, 
         for (int j = 0; j < 4; ++j) { v0s[4 * threadIdx.x + j] = a[j]; v1s[4 * threadIdx.x + j] = b[j]; }
         __syncthreads();
         for (int ch = threadIdx.x; ch < C; ch += 256) {
-            float t0 = 0.f, t1 = 0.f;
+            T t0 = 0, t1 = 0;
             for (int i = ch; i < 1024; i += C) { t0 += v0s[i]; t1 += v1s[i]; }
             part0[(size_t)blockIdx.x * C + ch] = t0;
             if (part1) part1[(size_t)blockIdx.x * C + ch] = t1;
         }
         return;
     }
-    float a0 = 0.f, a1 = 0.f;
+    T a0 = 0, a1 = 0;
     if (fixed) {
         const int c = threadIdx.x % C;
         for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) {
-            float v0, v1;
+            T v0, v1;
             f(e, c, v0, v1);
             a0 += v0;
             a1 += v1;
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, 
         s1[threadIdx.x] = a1;
         __syncthreads();
         if ((int)threadIdx.x < C) {
-            float t0 = 0.f, t1 = 0.f;
+            T t0 = 0, t1 = 0;
             for (int i = threadIdx.x; i < 256; i += C) { t0 += s0[i]; t1 += s1[i]; }
             part0[(size_t)blockIdx.x * C + threadIdx.x] = t0;
             if (part1) part1[(size_t)blockIdx.x * C + threadIdx.x] = t1;
@@ -85,9 +88,9 @@ __global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, 
     } else {
         // generic: thread per channel group, rows strided
         for (int c = threadIdx.x; c < C; c += 256) {
-            float t0 = 0.f, t1 = 0.f;
+            T t0 = 0, t1 = 0;
             for (int64_t r = r0; r < r1; ++r) {
-                float v0, v1;
+                T v0, v1;
                 f(r * C + c, c, v0, v1);
                 t0 += v0;
                 t1 += v1;
@@ -98,13 +101,15 @@ __global__ __launch_bounds__(256) void colreduce2_kernel(F f, int64_t R, int C, 
     }
 }
 
-// out{0,1}[c] = sum_b part{0,1}[b][c]; one 64-lane wave per channel, lane-strided partials then a fixed shuffle tree
-__global__ __launch_bounds__(64) void colreduce_finish_kernel(const float* __restrict__ part0, const float* __restrict__ part1, int blocks, int C,
+// out{0,1}[c] = sum_b part{0,1}[b][c]; one 64-lane wave per channel, lane-strided partials then a fixed shuffle tree (in T, rounded to
+// float at the end)
+template <class T>
+__global__ __launch_bounds__(64) void colreduce_finish_kernel(const T* __restrict__ part0, const T* __restrict__ part1, int blocks, int C,
                                                               float* __restrict__ out0, float* __restrict__ out1)
 {
     const int c = blockIdx.x;
     // (four independent load chains per lane and output: up to 2 048 partials were 32 dependent L2 round trips per lane)
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+    T a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     int b = threadIdx.x;
     for (; b + 192 < blocks; b += 256) {
         a0 += part0[(size_t)b * C + c]; a1 += part0[(size_t)(b + 64) * C + c]; a2 += part0[(size_t)(b + 128) * C + c]; a3 += part0[(size_t)(b + 192) * C + c];
@@ -116,29 +121,44 @@ __global__ __launch_bounds__(64) void colreduce_finish_kernel(const float* __res
         a0 += part0[(size_t)b * C + c];
         if (part1) b0 += part1[(size_t)b * C + c];
     }
-    float t0 = (a0 + a1) + (a2 + a3), t1 = (b0 + b1) + (b2 + b3);
+    T t0 = (a0 + a1) + (a2 + a3), t1 = (b0 + b1) + (b2 + b3);
     for (int o = 32; o; o >>= 1) {
         t0 += __shfl_down(t0, o);
         t1 += __shfl_down(t1, o);
     }
     if (threadIdx.x == 0) {
-        out0[c] = t0;
-        if (out1) out1[c] = t1;
+        out0[c] = (float)t0;
+        if (out1) out1[c] = (float)t1;
     }
 }
 
 // BatchNorm statistics finished in the reduction's own second stage: [sum | sum of squares] -> mean, population variance, invstd and
 // (optionally) the moving-statistics update  moving = momentum * moving + (1 - momentum) * batch  (the reference's extra_update_ops,
-// RandLANet.py:90,163) -- one launch instead of three
+// RandLANet.py:90,163) -- one launch instead of three.  Summed and finished in double: the float sums of a one-pass variance lose
+// ~1e-7 r^2 of it for a channel whose mean is r standard deviations (1e-3 at r = 100; fc0 sees raw voxel coordinates).
 struct BnFinish {
     float* mean; float* invstd; float* var; float* mov_mean; float* mov_var;
-    float rows, eps, momentum;
+    int64_t rows;
+    float eps, momentum;
 };
-__global__ __launch_bounds__(64) void colreduce_finish_bn_kernel(const float* __restrict__ part0, const float* __restrict__ part1, int blocks, int C,
+__device__ __forceinline__ void bn_finish_channel(double s, double q, int c, const BnFinish& bn)
+{
+    const double m = s / (double)bn.rows;
+    double v = q / (double)bn.rows - m * m;  // population variance (tf.nn.moments)
+    v = v < 0.0 ? 0.0 : v;
+    bn.mean[c] = (float)m;
+    bn.var[c] = (float)v;
+    bn.invstd[c] = (float)(1.0 / sqrt(v + (double)bn.eps));
+    if (bn.mov_mean) {
+        bn.mov_mean[c] = (float)((double)bn.mov_mean[c] * bn.momentum + m * (1.0 - bn.momentum));
+        bn.mov_var[c] = (float)((double)bn.mov_var[c] * bn.momentum + v * (1.0 - bn.momentum));
+    }
+}
+__global__ __launch_bounds__(64) void colreduce_finish_bn_kernel(const double* __restrict__ part0, const double* __restrict__ part1, int blocks, int C,
                                                                  float* __restrict__ out0, float* __restrict__ out1, BnFinish bn)
 {
     const int c = blockIdx.x;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     int b = threadIdx.x;
     for (; b + 192 < blocks; b += 256) {
         a0 += part0[(size_t)b * C + c]; a1 += part0[(size_t)(b + 64) * C + c]; a2 += part0[(size_t)(b + 128) * C + c]; a3 += part0[(size_t)(b + 192) * C + c];
@@ -148,30 +168,23 @@ __global__ __launch_bounds__(64) void colreduce_finish_bn_kernel(const float* __
         a0 += part0[(size_t)b * C + c];
         b0 += part1[(size_t)b * C + c];
     }
-    float t0 = (a0 + a1) + (a2 + a3), t1 = (b0 + b1) + (b2 + b3);
+    double t0 = (a0 + a1) + (a2 + a3), t1 = (b0 + b1) + (b2 + b3);
     for (int o = 32; o; o >>= 1) {
         t0 += __shfl_down(t0, o);
         t1 += __shfl_down(t1, o);
     }
     if (threadIdx.x == 0) {
-        out0[c] = t0;
-        out1[c] = t1;
-        const float m = t0 / bn.rows;
-        float v = t1 / bn.rows - m * m;  // population variance (tf.nn.moments)
-        v = v < 0.f ? 0.f : v;
-        bn.mean[c] = m;
-        bn.var[c] = v;
-        bn.invstd[c] = rsqrtf(v + bn.eps);
-        if (bn.mov_mean) {
-            bn.mov_mean[c] = bn.mov_mean[c] * bn.momentum + m * (1.f - bn.momentum);
-            bn.mov_var[c] = bn.mov_var[c] * bn.momentum + v * (1.f - bn.momentum);
-        }
+        out0[c] = (float)t0;
+        out1[c] = (float)t1;
+        bn_finish_channel(t0, t1, c, bn);
     }
 }
 
 template <class F>
 static int colreduce2(ps_context* c, F f, int64_t R, int C, float* out0, float* out1, const BnFinish* bn = nullptr)
 {
+    // (the statistics are finished from the double partials only: a float functor with a BnFinish would leave them unwritten)
+    PS_CHECK(!bn || (std::is_same<typename F::acc, double>::value && out1 && R >= 1), "colreduce2: BatchNorm statistics need SumSq over >= 1 row");
     if (R <= 0) {
         PS_HIP(hipMemsetAsync(out0, 0, sizeof(float) * C, c->stream));
         if (out1) PS_HIP(hipMemsetAsync(out1, 0, sizeof(float) * C, c->stream));
@@ -185,25 +198,32 @@ static int colreduce2(ps_context* c, F f, int64_t R, int C, float* out0, float* 
     if ((256 % C) != 0) blocks = blocks > 512 ? 512 : blocks;
     const int rpb = (int)((R + blocks - 1) / blocks);
     const int nb = (int)((R + rpb - 1) / rpb);
-    PS_TRY(c->red_ws.reserve(sizeof(float) * 2 * (size_t)nb * C));
-    float* p0 = c->red_ws.as<float>();
-    float* p1 = out1 ? p0 + (size_t)nb * C : nullptr;
+    using T = typename F::acc;
+    PS_TRY(c->red_ws.reserve(sizeof(T) * 2 * (size_t)nb * C));
+    T* p0 = c->red_ws.as<T>();
+    T* p1 = out1 ? p0 + (size_t)nb * C : nullptr;
     const int vec = (C & 3) == 0 && (1024 % C) == 0 && f.aligned16();
     hipLaunchKernelGGL(colreduce2_kernel<F>, dim3((unsigned)nb), dim3(256), 0, c->stream, f, R, C, rpb, vec, p0, p1);
-    if (bn)
-        hipLaunchKernelGGL(colreduce_finish_bn_kernel, dim3((unsigned)C), dim3(64), 0, c->stream, p0, p1, nb, C, out0, out1, *bn);
-    else
-        hipLaunchKernelGGL(colreduce_finish_kernel, dim3((unsigned)C), dim3(64), 0, c->stream, p0, p1, nb, C, out0, out1);
+    if constexpr (std::is_same<T, double>::value) {
+        if (bn) {
+            hipLaunchKernelGGL(colreduce_finish_bn_kernel, dim3((unsigned)C), dim3(64), 0, c->stream, p0, p1, nb, C, out0, out1, *bn);
+            PS_HIP(hipGetLastError());
+            return PS_OK;
+        }
+    }
+    hipLaunchKernelGGL(colreduce_finish_kernel<T>, dim3((unsigned)C), dim3(64), 0, c->stream, p0, p1, nb, C, out0, out1);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
 
+// [sum x | sum x^2] in double (the squares exact), the partials double too: see BnFinish
 struct SumSq {
+    using acc = double;
     const float* x;
-    __device__ void operator()(int64_t e, int, float& a, float& b) const { const float v = x[e]; a = v; b = v * v; }
+    __device__ void operator()(int64_t e, int, double& a, double& b) const { const double v = x[e]; a = v; b = v * v; }
     bool aligned16() const { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
     __device__ void init4(int) {}
-    __device__ void load4(int64_t e, int, float (&a)[4], float (&b)[4]) const
+    __device__ void load4(int64_t e, int, double (&a)[4], double (&b)[4]) const
     {
         const float4 v = *reinterpret_cast<const float4*>(x + e);
         a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
@@ -212,6 +232,7 @@ struct SumSq {
     }
 };
 struct SumOnly {
+    using acc = float;
     const float* x;
     __device__ void operator()(int64_t e, int, float& a, float& b) const { a = x[e]; b = 0.f; }
     bool aligned16() const { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
@@ -225,6 +246,7 @@ struct SumOnly {
 };
 // BatchNorm backward sums: g = dy * act'(z), z = gamma*xhat + beta;  a = sum g, b = sum g*xhat
 struct BnBwdSums {
+    using acc = float;
     const float* dy; const float* x; const float* gamma; const float* beta; const float* mean; const float* invstd;
     int leaky;
     int C;          // channels: element e of x is (row e / C, channel e % C)
@@ -233,7 +255,7 @@ struct BnBwdSums {
     {
         const float xh = (x[e] - mean[c]) * invstd[c];
         float g = dy[(e / C) * lddy + c];
-        if (leaky && gamma[c] * xh + beta[c] < 0.f) g *= 0.2f;
+        if (leaky && gamma[c] * xh + beta[c] <= 0.f) g *= 0.2f;
         a = g;
         b = g * xh;
     }
@@ -255,7 +277,7 @@ struct BnBwdSums {
         for (int j = 0; j < 4; ++j) {
             const float xh = (xs[j] - ms[j]) * ss[j];
             float g = gs[j];
-            if (leaky && gm[j] * xh + bt[j] < 0.f) g *= 0.2f;
+            if (leaky && gm[j] * xh + bt[j] <= 0.f) g *= 0.2f;
             a[j] = g;
             b[j] = g * xh;
         }
@@ -265,14 +287,15 @@ struct BnBwdSums {
 __global__ void bn_finish_stats_kernel(const float* __restrict__ sum, const float* __restrict__ sumsq, int64_t R, int C, float eps,
                                        float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ var)
 {
+    // (finished in double like BnFinish; the float sums the split protocol hands over bound the variance to ~1e-7 r^2 of itself)
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float m = sum[c] / (float)R;
-    float v = sumsq[c] / (float)R - m * m;  // population variance (tf.nn.moments)
-    v = v < 0.f ? 0.f : v;
-    mean[c] = m;
-    var[c] = v;
-    invstd[c] = rsqrtf(v + eps);
+    const double m = (double)sum[c] / (double)R;
+    double v = (double)sumsq[c] / (double)R - m * m;  // population variance (tf.nn.moments)
+    v = v < 0.0 ? 0.0 : v;
+    mean[c] = (float)m;
+    var[c] = (float)v;
+    invstd[c] = (float)(1.0 / sqrt(v + (double)eps));
 }
 
 // ---- BatchNorm of a SMALL tensor in one launch -------------------------------------------------------------------------------------------
@@ -289,7 +312,8 @@ constexpr int kBnSliceThreads = 1024;
 // few-thousand-row layers it exists for).  Sums in a fixed order: a shuffle tree over the eight row slots of a wave that share a channel
 // quad, then the sixteen wave totals in wave order -- one workgroup barrier.
 constexpr int kBnSliceCh = 32;
-__device__ __forceinline__ void bn_slice_reduce(float (&a)[4], float (&b)[4], float (*red)[8][8])
+template <class T>
+__device__ __forceinline__ void bn_slice_reduce(T (&a)[4], T (&b)[4], T (*red)[8][8])
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cq = lane & 7;
 #pragma unroll
@@ -307,7 +331,7 @@ __device__ __forceinline__ void bn_slice_reduce(float (&a)[4], float (&b)[4], fl
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        float s = 0.f, q = 0.f;
+        T s = 0, q = 0;
 #pragma unroll
         for (int w = 0; w < kBnSliceThreads / 64; ++w) { s += red[w][cq][j]; q += red[w][cq][4 + j]; }
         a[j] = s;
@@ -320,10 +344,11 @@ __global__ __launch_bounds__(kBnSliceThreads) void bn_slice_fwd_kernel(const flo
                                                            float* __restrict__ invstd, float* __restrict__ var, float* __restrict__ sums,
                                                            float* __restrict__ mov_mean, float* __restrict__ mov_var, float momentum)
 {
-    __shared__ float red[kBnSliceThreads / 64][8][8];
+    // (statistics summed and finished in double, like BnFinish)
+    __shared__ double red[kBnSliceThreads / 64][8][8];
     const int c0 = kBnSliceCh * blockIdx.x + 4 * (threadIdx.x & 7), r0 = threadIdx.x >> 3;
     constexpr int RS = kBnSliceThreads / 8;  // row slots
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     // (eight rows per trip: a thread's walk is a chain of dependent round trips -- one row per trip is 32 of them for 4 096 rows)
     for (int r = r0; r < R; r += 8 * RS) {
         float4 v[8];
@@ -331,28 +356,30 @@ __global__ __launch_bounds__(kBnSliceThreads) void bn_slice_fwd_kernel(const flo
         for (int u = 0; u < 8; ++u) v[u] = r + u * RS < R ? *reinterpret_cast<const float4*>(x + (size_t)(r + u * RS) * C + c0) : float4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            s[0] += v[u].x; s[1] += v[u].y; s[2] += v[u].z; s[3] += v[u].w;
-            q[0] += v[u].x * v[u].x; q[1] += v[u].y * v[u].y; q[2] += v[u].z * v[u].z; q[3] += v[u].w * v[u].w;
+            const double d[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { s[j] += d[j]; q[j] += d[j] * d[j]; }
         }
     }
     bn_slice_reduce(s, q, red);
     float m[4], is[4], ga[4], be[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        m[j] = s[j] / (float)R;
-        float v = q[j] / (float)R - m[j] * m[j];  // population variance (tf.nn.moments)
-        v = v < 0.f ? 0.f : v;
-        is[j] = rsqrtf(v + eps);
+        const double md = s[j] / (double)R;
+        double v = q[j] / (double)R - md * md;  // population variance (tf.nn.moments)
+        v = v < 0.0 ? 0.0 : v;
+        m[j] = (float)md;
+        is[j] = (float)(1.0 / sqrt(v + (double)eps));
         ga[j] = gamma[c0 + j];
         be[j] = beta[c0 + j];
         if (threadIdx.x < 8) {
             mean[c0 + j] = m[j];
-            var[c0 + j] = v;
+            var[c0 + j] = (float)v;
             invstd[c0 + j] = is[j];
-            if (sums) { sums[c0 + j] = s[j]; sums[C + c0 + j] = q[j]; }
+            if (sums) { sums[c0 + j] = (float)s[j]; sums[C + c0 + j] = (float)q[j]; }
             if (mov_mean) {
-                mov_mean[c0 + j] = mov_mean[c0 + j] * momentum + m[j] * (1.f - momentum);
-                mov_var[c0 + j] = mov_var[c0 + j] * momentum + v * (1.f - momentum);
+                mov_mean[c0 + j] = (float)((double)mov_mean[c0 + j] * momentum + md * (1.0 - momentum));
+                mov_var[c0 + j] = (float)((double)mov_var[c0 + j] * momentum + v * (1.0 - momentum));
             }
         }
     }
@@ -400,7 +427,7 @@ __global__ __launch_bounds__(kBnSliceThreads) void bn_slice_bwd_kernel(const flo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float xh = (xs[j] - m[j]) * is[j];
-                if (leaky && ga[j] * xh + be[j] < 0.f) g[j] *= 0.2f;
+                if (leaky && ga[j] * xh + be[j] <= 0.f) g[j] *= 0.2f;
                 sg[j] += g[j];
                 sgx[j] += g[j] * xh;
             }
@@ -427,7 +454,7 @@ __global__ __launch_bounds__(kBnSliceThreads) void bn_slice_bwd_kernel(const flo
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float xh = (xs[j] - m[j]) * is[j];
-                if (leaky && ga[j] * xh + be[j] < 0.f) g[j] *= 0.2f;
+                if (leaky && ga[j] * xh + be[j] <= 0.f) g[j] *= 0.2f;
                 g[j] = ga[j] * is[j] * (g[j] - sg[j] * invR - xh * sgx[j] * invR);
             }
             if (r + u * RS < R) *reinterpret_cast<float4*>(dx + (size_t)(r + u * RS) * C + c0) = float4{g[0], g[1], g[2], g[3]};
@@ -504,7 +531,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float xh = (xs[j] - sh[j]) * sc[j];
-                if (leaky && ga[j] * xh + be[j] < 0.f) g[j] *= 0.2f;
+                if (leaky && ga[j] * xh + be[j] <= 0.f) g[j] *= 0.2f;
                 g[j] = ga[j] * sc[j] * (g[j] - mg[j] - xh * mgx[j]);
             }
             *reinterpret_cast<float4*>(dx + e) = float4{g[0], g[1], g[2], g[3]};
@@ -515,7 +542,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         const int c = (int)(e % C);
         const float xh = (x[e] - mean[c]) * invstd[c];
         float g = dy[(e / C) * lddy + c];
-        if (leaky && gamma[c] * xh + beta[c] < 0.f) g *= 0.2f;
+        if (leaky && gamma[c] * xh + beta[c] <= 0.f) g *= 0.2f;
         dx[e] = gamma[c] * invstd[c] * (g - sg[c] * invR - xh * sgx[c] * invR);
     }
 }
@@ -899,7 +926,7 @@ __global__ __launch_bounds__(256) void add_lrelu_kernel(const float* __restrict_
 }
 __global__ __launch_bounds__(256) void add_lrelu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, int64_t n, float* __restrict__ ds)
 {
-    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) ds[e] = y[e] >= 0.f ? dy[e] : 0.2f * dy[e];
+    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) ds[e] = y[e] > 0.f ? dy[e] : 0.2f * dy[e];
 }
 __global__ __launch_bounds__(256) void axpy_kernel(float alpha, const float* __restrict__ x, int64_t n, float* __restrict__ y)
 {
@@ -1229,8 +1256,8 @@ int ps_op_bn_train_fwd_ex(ps_context* c, const float* x, const float* gamma, con
         return PS_OK;
     }
     Stage st(c, "train_bn_fwd", 3);
-    PS_TRY(colreduce2(c, SumSq{x}, R, (int)C, scratch2C, scratch2C + C));
-    hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, c->stream, scratch2C, scratch2C + C, R, (int)C, eps, mean, invstd, var);
+    const BnFinish bn = {mean, invstd, var, nullptr, nullptr, R, eps, 0.f};
+    PS_TRY(colreduce2(c, SumSq{x}, R, (int)C, scratch2C, scratch2C + C, &bn));
     if (bn_vec_ok(C, x, y, x, ldy))
         hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
                            ldy);
@@ -1255,7 +1282,7 @@ int ps_op_bn_train_fwd_mov(ps_context* c, const float* x, const float* gamma, co
         return PS_OK;
     }
     Stage st(c, "train_bn_fwd", 3);
-    const BnFinish bn = {mean, invstd, var, moving_mean, moving_var, (float)R, eps, momentum};
+    const BnFinish bn = {mean, invstd, var, moving_mean, moving_var, R, eps, momentum};
     PS_TRY(colreduce2(c, SumSq{x}, R, (int)C, scratch2C, scratch2C + C, &bn));
     if (bn_vec_ok(C, x, y, x, ldy))
         hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,

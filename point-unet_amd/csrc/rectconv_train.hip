@@ -328,7 +328,7 @@ __global__ __launch_bounds__((RcGeom<CI, CO>::WAVES * 64)) void rc_bwd_sums_kern
                 const float yc = (y[r] + bias.v[ct]) - mu.v[ct];
                 const float xh = live ? yc * is.v[ct] : 0.f;
                 float gv = live ? Z[(4 * g + r) * G::PZ + col] : 0.f;
-                if (a.leaky && __builtin_fmaf(yc, sc.v[ct], be.v[ct]) < 0.f) gv *= 0.2f;
+                if (a.leaky && __builtin_fmaf(yc, sc.v[ct], be.v[ct]) <= 0.f) gv *= 0.2f;
                 s1[ct] += gv;
                 s2[ct] = __builtin_fmaf(gv, xh, s2[ct]);
             }
@@ -414,7 +414,7 @@ __global__ __launch_bounds__((RcGeom<CI, CO>::WAVES * 64)) void rc_bwd_apply_ker
                 const float yc = (y[r] + bias.v[ct]) - mu.v[ct];
                 const float xh = yc * is.v[ct];
                 float gv = live ? Z[(4 * g + r) * G::PZ + col] : 0.f;
-                if (a.leaky && __builtin_fmaf(yc, sc.v[ct], be.v[ct]) < 0.f) gv *= 0.2f;
+                if (a.leaky && __builtin_fmaf(yc, sc.v[ct], be.v[ct]) <= 0.f) gv *= 0.2f;
                 const float dyv = live ? sc.v[ct] * (gv - m1.v[ct] - xh * m2.v[ct]) : 0.f;
                 Z[(4 * g + r) * G::PZ + col] = a.bf16 ? rc_round_bf16(dyv) : dyv;  // (operand of the two products; db sums the unrounded value)
                 dbs[ct] += dyv;

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(kScWaves * 64) void sc_bwd_sums_kernel(ScArgs a)
                 const float yc = (y[r] + bias.v[ct]) - mu.v[ct];
                 const float xh = live ? yc * is.v[ct] : 0.f;
                 float gv = !live ? 0.f : a.vec ? T1[(4 * g + r) * G::PA + col] : a.dz[(size_t)(r0 + 4 * g + r) * a.lddz + col];
-                if (__builtin_fmaf(yc, sc.v[ct], be.v[ct]) < 0.f) gv *= 0.2f;
+                if (__builtin_fmaf(yc, sc.v[ct], be.v[ct]) <= 0.f) gv *= 0.2f;
                 s1[ct] += gv;
                 s2[ct] = __builtin_fmaf(gv, xh, s2[ct]);
                 xs[ct] += xh;
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(kScWaves * 64) void sc_bwd_apply_kernel(ScArgs a)
                 const float yc = (y[r] + bias.v[ct]) - mu.v[ct];
                 const float xh = yc * is.v[ct];
                 float gv = !live ? 0.f : vec ? T1[(4 * g + r) * G::PA + col] : a.dz[(size_t)(r0 + 4 * g + r) * a.lddz + col];
-                if (__builtin_fmaf(yc, sc.v[ct], be.v[ct]) < 0.f) gv *= 0.2f;
+                if (__builtin_fmaf(yc, sc.v[ct], be.v[ct]) <= 0.f) gv *= 0.2f;
                 const float dyv = live ? sc.v[ct] * (gv - m1.v[ct] - xh * m2.v[ct]) : 0.f;
                 T1[(4 * g + r) * G::PA + col] = a.bf16 ? sc_round_bf16(dyv) : dyv;  // (operand of the two products; the bias gradient sums the unrounded value)
                 if (WG) dbs[ct] += dyv;
