@@ -23,6 +23,9 @@
  *   ps_confusion_accumulate,           Network.evaluate (RandLANet.py:208-264), genSegmentation
  *   ps_probs_to_labels, ps_seg_metrics (utils/genSegmentationBraTS.py:67-79), utils/evaluationBraTS.py:13-64 (Dice + medpy's hd95),
  *                                      utils/evaluationPancreas.py:14-37
+ *   ps_cloud_positive_counts,          the BraTS input generator's batch sampling, PointSegment/runBraTS.py:91-130 (every tumour point
+ *   ps_cloud_sample                    + random.sample of the background up to cfg.num_points, DP.shuffle_idx, queried_idx) and
+ *                                      tf_map's feature concat (:142), from clouds kept resident on the device
  *
  * Conventions
  * -----------
@@ -66,7 +69,7 @@ int ps_destroy(ps_context* ctx);
  * hip_stream == NULL selects the device's default (null) stream. */
 int ps_set_stream(ps_context* ctx, void* hip_stream);
 int ps_synchronize(ps_context* ctx);
-/* on != 0: ps_pyramid_build stops synchronising with the host; its device-side status words (tree deeper than the
+/* on != 0: ps_pyramid_build (and ps_cloud_sample) stop synchronising with the host; its device-side status words (tree deeper than the
  * traversal stack, builder queue overflow, unbalanced cloud needing the slow build path) are copied to pinned memory
  * and validated by the next ps_synchronize(), which then returns PS_ESTATE.  Lets the host enqueue the forward while
  * the pyramid is still being built.  Default off (every call validates before returning). */
@@ -273,6 +276,37 @@ int ps_seg_metrics(ps_context* ctx, const uint8_t* pred, const uint8_t* truth, i
                    const uint32_t* regions, int32_t R, void* scratch, int64_t scratch_bytes, int64_t* counts, double* scores);
 /* bytes of scratch ps_seg_metrics needs (2R float64 volumes + one u16 flag volume + 17 KB), -1 for a bad shape or R */
 int64_t ps_seg_metrics_scratch_bytes(int64_t D0, int64_t D1, int64_t D2, int32_t R);
+
+/* ---- training batches from resident clouds (csrc/cloud_sample.hip) ------------------------------------------------------------------
+ * A BANK is a dataset's full clouds concatenated row-wise in device memory: xyz f32[total, 3], modalities f32[total, C], labels i32[total]
+ * (may be NULL: every point is background); cloud c is rows [offsets[c], offsets[c+1]) (HOST int64[n_clouds + 1]).  A batch draws B slots,
+ * slot b from cloud c = cloud_ids[b] (HOST int32[B]; a cloud may fill several slots), with n = offsets[c+1] - offsets[c] points and
+ * cloud-local index i.  Positive = label > 0.  The rule, a pure function of (cloud, labels, N, seed, slot), all arithmetic mod 2^32, keys
+ * uint64, hash32 = lowbias32 (the dropout hash of the training step; restated in tests/cloud_sample_ref.py):
+ *     s_sel(b)    = hash32(seed + 0x9E3779B9 * (2b + 1))
+ *     s_perm(b)   = hash32(seed + 0x9E3779B9 * (2b + 2))
+ *     key_sel(i)  = hash32(i * 2654435761 ^ s_sel(b))  << 32 | i
+ *     key_perm(i) = hash32(i * 2654435761 ^ s_perm(b)) << 32 | i
+ *     S           = {positives} + the N - |positives| background points with the smallest key_sel     (|positives| <= N <= n)
+ *     row t       = the element of S with the t-th smallest key_perm
+ * i.e. the reference's distribution: every positive point, a uniform N - P subset of the background, a uniform permutation (whose
+ * prefixes are the pyramid's random subsamples, runBraTS.py:114, 147-149).  Outputs (device): out_idx i32[B, N] = i (the reference's
+ * queried_idx, point2prod's p_idx), out_xyz f32[B, N, 3], out_features f32[B, N, 3 + C] = [xyz | modalities], out_labels i32[B, N] (may be
+ * NULL; zeros without labels).  Limits: n < 2^31 per cloud, 1 <= C <= PS_CLOUD_SAMPLE_MAX_C, 1 <= B <= PS_CLOUD_SAMPLE_MAX_B, B * N < 2^31. */
+#define PS_CLOUD_SAMPLE_MAX_B 64
+#define PS_CLOUD_SAMPLE_MAX_C 16
+/* positives per cloud of a bank (labels device, NULL = all zero; offsets and counts HOST, int64[n_clouds + 1] / int64[n_clouds]): once per
+ * dataset; one synchronisation. */
+int ps_cloud_positive_counts(ps_context* ctx, const int32_t* labels, const int64_t* offsets, int64_t n_clouds, int64_t* counts);
+/* One batch by the rule above.  Data pointers are device memory; offsets, positives (ps_cloud_positive_counts' table; may be NULL when
+ * labels is) and cloud_ids are HOST arrays; asynchronous on the context's stream, workspace from the context's grow-only arena.  Every
+ * argument error (NULL, C, B, N > n, positives > N, a cloud id outside the bank) returns PS_EINVAL before anything is enqueued, the
+ * outputs untouched.  The device recounts the positives and draws with ITS count; nothing is ever written outside [B, N].  A count that
+ * disagrees with positives[c] (a stale table) is PS_ESTATE: returned by this call (which then synchronises once), or with
+ * ps_set_deferred_checks on by the next ps_synchronize (no synchronisation here). */
+int ps_cloud_sample(ps_context* ctx, const float* xyz, const float* modalities, int32_t C, const int32_t* labels, const int64_t* offsets,
+                    int64_t n_clouds, const int64_t* positives, const int32_t* cloud_ids, int32_t B, int64_t N, uint32_t seed, float* out_xyz,
+                    float* out_features, int32_t* out_labels, int32_t* out_idx);
 
 /* The op-level kernels of the training step -- forward / backward pairs of the ops above, BatchNorm in training mode, the fused and
  * recompute forms the native trainer chooses between, the deterministic scatter-adds, loss and Adam -- are declared in

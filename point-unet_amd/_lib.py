@@ -117,6 +117,10 @@ PROTOTYPES = {
     "ps_seg_metrics": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
                                       ctypes.c_int32, c_vp, ctypes.c_int64, c_i64p, ctypes.POINTER(ctypes.c_double)]),
     "ps_seg_metrics_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64] * 3 + [ctypes.c_int32]),
+    # training batches from resident clouds (csrc/cloud_sample.hip)
+    "ps_cloud_positive_counts": (ctypes.c_int, [c_vp, c_vp, c_i64p, ctypes.c_int64, c_i64p]),
+    "ps_cloud_sample": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_i64p, ctypes.c_int64, c_i64p, c_i32p, ctypes.c_int32, ctypes.c_int64,
+                                       ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
     "ps_op_bn_train_sums": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
     "ps_op_bn_train_apply": (ctypes.c_int, [c_vp] * 5 + [ctypes.c_int64] * 3 + [ctypes.c_float, ctypes.c_int] + [c_vp] * 4),
     "ps_op_bn_train_bwd_sums": (ctypes.c_int, [c_vp] * 7 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [c_vp] * 2),

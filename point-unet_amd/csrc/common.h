@@ -159,6 +159,7 @@ struct ps_context {
     hipStream_t stream = nullptr;
     ps::Arena knn_arena;     // kd-trees + query scratch
     ps::Arena net_arena;     // activations of the forward pass
+    ps::Arena sample_arena;  // ps_cloud_sample / ps_cloud_positive_counts: select state, sort pairs (cloud_sample.hip)
     ps::DevBuf stage_in;     // host<->device staging for device_ptrs == 0 calls
     ps::DevBuf stage_out;
     ps::DevBuf red_ws;       // per-block partial sums of the per-channel reductions (ops_train.hip)
@@ -188,7 +189,9 @@ struct ps_context {
     int32_t* h_flags = nullptr;   // pinned [8][4]
     unsigned pending_mask = 0;
     uint64_t builds = 0;          // ps_pyramid_build calls on this context so far (error messages name the failing one)
-    uint64_t flag_serial[8] = {}; // which build each pending slot belongs to
+    uint64_t samples = 0;         // ps_cloud_sample calls on this context so far
+    uint64_t flag_serial[8] = {}; // which build / sample each pending slot belongs to
+    int flag_kind[8] = {};        // what wrote the slot: 0 ps_pyramid_build (3 status words), 1 ps_cloud_sample (4 words)
     int flag_slot = 0;
     int sticky_rc = 0;            // a failed deferred check found while reusing its slot: reported by the next ps_synchronize
     std::string sticky_msg;
@@ -198,6 +201,8 @@ struct ps_context {
     std::vector<char>& ring_next() { ring_pos = (ring_pos + 1) & 7; return host_ring[ring_pos]; }
     int check_deferred();
     int check_flag_slot(int s);  // after a stream sync: PS_OK or PS_ESTATE with the message set
+    // enqueue the copy of `bytes` (<= 16) of device status words into the next pinned slot, validated by ps_synchronize
+    int defer_status(const void* d_words, size_t bytes, int kind, uint64_t serial);
     // small host->device uploads that never stall the host: the data is copied into a pinned ring slot first
     struct PinSlot { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
     PinSlot pin[16];

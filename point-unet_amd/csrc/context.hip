@@ -55,7 +55,14 @@ int ps_context::check_flag_slot(int s)
     if (pending_mask & (1u << s)) {
         const int32_t* f = h_flags + 4 * s;
         // (f[2], the "unfinished build" word of the first builder, is always 0: the straggler kernel finishes every tree)
-        if (f[1] != 0) {
+        if (flag_kind[s] == 1) {  // ps_cloud_sample: {mismatch, slot, device count, host count}
+            if (f[0] != 0) {
+                ps::set_error("deferred check: cloud sample #%llu of this context: slot %d has %d positive labels on the device, positives_host "
+                              "says %d: the table is stale (the batch was drawn with the device's count)", (unsigned long long)flag_serial[s], f[1],
+                              f[2], f[3]);
+                rc = PS_ESTATE;
+            }
+        } else if (f[1] != 0) {
             ps::set_error("deferred check: pyramid build #%llu of this context: kd-tree builder queue overflow (degenerate cloud); its index "
                           "tables were filled with index 0", (unsigned long long)flag_serial[s]);
             rc = PS_ESTATE;
@@ -83,6 +90,31 @@ int ps_context::check_deferred()
         sticky_msg.clear();
     }
     return rc;
+}
+
+int ps_context::defer_status(const void* d_words, size_t bytes, int kind, uint64_t serial)
+{
+    hipEvent_t& ev = flag_ev[flag_slot];
+    if (!ev) PS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (pending_mask & (1u << flag_slot)) {
+        // the slot still holds the status words of the call eight calls ago: wait for THAT copy (long done), not for the stream -- a
+        // stream synchronisation here would serialise the host with the GPU every eighth call.  A failure it reports is remembered in
+        // the context and raised by ps_synchronize: this call's slot, serial and event must line up with the caller's submission count
+        // whatever the old call did
+        PS_HIP(hipEventSynchronize(ev));
+        const int stale_rc = check_flag_slot(flag_slot);
+        if (stale_rc != PS_OK && sticky_rc == PS_OK) {  // kept for ps_synchronize (the caller's submit loop never sees it)
+            sticky_rc = stale_rc;
+            sticky_msg = ps_last_error();
+        }
+    }
+    PS_HIP(hipMemcpyAsync(h_flags + 4 * flag_slot, d_words, bytes, hipMemcpyDeviceToHost, stream));
+    PS_HIP(hipEventRecord(ev, stream));
+    pending_mask |= 1u << flag_slot;
+    flag_serial[flag_slot] = serial;
+    flag_kind[flag_slot] = kind;
+    flag_slot = (flag_slot + 1) & 7;
+    return PS_OK;
 }
 
 int ps_context::upload_async(void* dst, const void* src, size_t bytes)
@@ -221,6 +253,7 @@ int ps_destroy(ps_context* c)
     (void)hipStreamSynchronize(c->stream);
     c->knn_arena.buf.release();
     c->net_arena.buf.release();
+    c->sample_arena.buf.release();
     c->stage_in.release();
     c->stage_out.release();
     c->red_ws.release();

@@ -42,16 +42,20 @@ def volume_to_cloud(volumes, seg=None, device=0, ctx=None):
     return xyz, colors, labels.astype(np.uint8), origin
 
 
-def prepare_brats_volume(volumes, seg=None, sub_grid_size=0.01, merge_label_4=True, chained=True, device=0):
+def prepare_brats_volume(volumes, seg=None, sub_grid_size=0.01, merge_label_4=True, chained=True, device=0, on_device=False):
     """The arrays convert_pc2ply writes for one case: the full cloud, the sub-cloud and `proj_idx` (index of the nearest
     sub-cloud point for every point of the full cloud).  merge_label_4 applies load_volume's `img[img == 4] = 3`.
     chained (default): ONE pipeline on the device, as dataPrepareBraTS.py:75-116 is one pipeline on the host -- the volume goes up
     once, ps_volume_to_cloud_dev -> ps_grid_subsample_dev -> ps_knn_batch(device pointers) hand their rows on in HBM, the results come
-    down once.  chained=False: the three ops through their host-pointer entry points (three round trips over PCIe; same results, bit for bit)."""
+    down once.  chained=False: the three ops through their host-pointer entry points (three round trips over PCIe; same results, bit for bit).
+    on_device=True (chained only): nothing comes down -- the same keys as CUDA tensors (labels and sub_labels int32), e.g. for
+    dataset.CloudBank.add_prepared, so that volume -> bank stays in HBM."""
     if seg is not None and merge_label_4:
         seg = np.where(np.asarray(seg) == 4, 3, seg)
+    if on_device and not chained:
+        raise ValueError("prepare_brats_volume: on_device=True needs the chained path")
     if chained:
-        return _prepare_chained(volumes, seg, sub_grid_size, device)
+        return _prepare_chained(volumes, seg, sub_grid_size, device, on_device)
     xyz, colors, labels, origin = volume_to_cloud(volumes, seg)
     sub_xyz, sub_colors, sub_labels = DP.grid_sub_sampling(xyz, colors, labels.astype(np.int32), sub_grid_size)
     proj = DP.knn_search(sub_xyz[None], xyz[None], 1)[0, :, 0].astype(np.int32)
@@ -59,7 +63,7 @@ def prepare_brats_volume(volumes, seg=None, sub_grid_size=0.01, merge_label_4=Tr
                 sub_labels=np.asarray(sub_labels).reshape(-1).astype(np.uint8), proj_idx=proj)
 
 
-def _prepare_chained(volumes, seg, sub_grid_size, device):
+def _prepare_chained(volumes, seg, sub_grid_size, device, on_device=False):
     import torch
     vol = np.ascontiguousarray(volumes, dtype=np.float32)
     if vol.ndim != 4 or vol.shape[0] != 4:
@@ -96,6 +100,9 @@ def _prepare_chained(volumes, seg, sub_grid_size, device):
     m = int(m.value)
     proj = torch.empty((n, 1), dtype=torch.int32, device=dev)
     _lib.check(lib.ps_knn_batch(h, p(sub_xyz), p(xyz), 1, m, n, 3, 1, p(proj), 1))
+    if on_device:  # (stream-ordered on torch's current stream, like every tensor of the caller)
+        return dict(xyz=xyz[:n], colors=colors[:n], labels=labels[:n], xyz_origin=origin[:n], sub_xyz=sub_xyz[:m], sub_colors=sub_colors[:m],
+                    sub_labels=sub_labels[:m], proj_idx=proj[:, 0])
     torch.cuda.synchronize(dev)
     return dict(xyz=xyz[:n].cpu().numpy(), colors=colors[:n].cpu().numpy(), labels=labels[:n].cpu().numpy().astype(np.uint8),
                 xyz_origin=origin[:n].cpu().numpy(), sub_xyz=sub_xyz[:m].cpu().numpy(), sub_colors=sub_colors[:m].cpu().numpy(),
