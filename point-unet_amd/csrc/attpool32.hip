@@ -22,11 +22,9 @@
 // Bound: fp32 MFMA.  Per point: (d/32) * (h/2) score MFMAs of 64 cycles per pair of points, e.g. d = 128: 128 + 64 (mlp2) + 10.
 #include "attpool.h"
 #include "mfma_tile.h"
+#include "wave_ops.h"
 
 namespace ps {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 struct Att32Args {
     const float* xyz;
@@ -39,17 +37,6 @@ struct Att32Args {
     float* agg;
     int n_total, n_cloud;
 };
-
-__device__ __forceinline__ float swap32_max(float v)
-{
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float swap32_sum(float v)
-{
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
 
 template <int D, int STAGE, int KN, int WAVES, bool SPLITN>
 __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)

@@ -18,14 +18,13 @@
 //   * weights are stored as three planes of eight bfloat16 per lane (16-byte reads, [block][chunk][plane][lane]).
 // d = 64 and 128 (levels 1-2): weights resident in LDS, a wave per tile of two points (att32b_kernel);
 // d = 256 and 512 (levels 3-4): a workgroup per tile, weight planes streamed from L2 (att32s_kernel).
+// The split, the planes and the six-product MFMA are b3_ops.h's (one definition for all bf16x3 kernels); swap32_* are wave_ops.h's.
 #include "attpool.h"
+#include "b3_ops.h"
 #include "mfma_tile.h"
+#include "wave_ops.h"
 
 namespace ps {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 struct Att32bArgs {
     const float* xyz;
@@ -39,59 +38,9 @@ struct Att32bArgs {
     int n_total, n_cloud;
 };
 
-__device__ __forceinline__ float swap32b_max(float v)
+__device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int lane)
 {
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float swap32b_sum(float v)
-{
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// three bfloat16 planes of eight fp32 values: plane word t = pieces of (x[2t], x[2t+1]), low half = the even element
-struct Planes {
-    uint4 p[3];
-};
-__device__ __forceinline__ void split_pair(float x, float y, unsigned& q1, unsigned& q2, unsigned& q3)
-{
-    const unsigned xu = __float_as_uint(x), yu = __float_as_uint(y);
-    const float xr = x - __uint_as_float(xu & 0xffff0000u), yr = y - __uint_as_float(yu & 0xffff0000u);  // exact
-    const unsigned xru = __float_as_uint(xr), yru = __float_as_uint(yr);
-    const float x3 = xr - __uint_as_float(xru & 0xffff0000u), y3 = yr - __uint_as_float(yru & 0xffff0000u);  // exact, 8 bits
-    q1 = __builtin_amdgcn_perm(yu, xu, 0x07060302u);  // [y.hi16 : x.hi16]
-    q2 = __builtin_amdgcn_perm(yru, xru, 0x07060302u);
-    q3 = __builtin_amdgcn_perm(__float_as_uint(y3), __float_as_uint(x3), 0x07060302u);
-}
-__device__ __forceinline__ Planes split8(const float (&x)[8])
-{
-    Planes r;
-    split_pair(x[0], x[1], r.p[0].x, r.p[1].x, r.p[2].x);
-    split_pair(x[2], x[3], r.p[0].y, r.p[1].y, r.p[2].y);
-    split_pair(x[4], x[5], r.p[0].z, r.p[1].z, r.p[2].z);
-    split_pair(x[6], x[7], r.p[0].w, r.p[1].w, r.p[2].w);
-    return r;
-}
-
-__device__ __forceinline__ f32x16 mfma_b(const uint4& a, const uint4& b, f32x16 acc)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-// the six kept piece products, smallest first
-__device__ __forceinline__ f32x16 mfma6(const Planes& a, const Planes& b, f32x16 acc)
-{
-    acc = mfma_b(a.p[2], b.p[0], acc);
-    acc = mfma_b(a.p[0], b.p[2], acc);
-    acc = mfma_b(a.p[1], b.p[1], acc);
-    acc = mfma_b(a.p[1], b.p[0], acc);
-    acc = mfma_b(a.p[0], b.p[1], acc);
-    acc = mfma_b(a.p[0], b.p[0], acc);
-    return acc;
-}
-__device__ __forceinline__ Planes load_planes(const uint4* img, int slot, int lane)
-{
-    Planes r;
+    B3Planes r;
     r.p[0] = img[(slot * 3 + 0) * 64 + lane];
     r.p[1] = img[(slot * 3 + 1) * 64 + lane];
     r.p[2] = img[(slot * 3 + 2) * 64 + lane];
@@ -171,7 +120,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
         const float dis = __builtin_amdgcn_sqrtf(rx * rx + ry * ry + rz * rz);
         // enc10 = [dis, rx, ry, rz, cx, cy, cz, nx | ny, nz]: the lower lane half holds K values 0..7, the upper 8..15 (10.. are zero)
         const float ev[8] = {hl ? ny : dis, hl ? nz : rx, hl ? 0.f : ry, hl ? 0.f : rz, hl ? 0.f : cx, hl ? 0.f : cy, hl ? 0.f : cz, hl ? 0.f : nx};
-        const Planes E = split8(ev);
+        const B3Planes E = b3_split8<3>(ev);
         if (hl == 0) NB[c32] = nbr;
         gstage(0, t0 + t_step);
         wave_lds_sync();
@@ -211,17 +160,17 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
                 const float4 bb = *reinterpret_cast<const float4*>(b1 + cb * 32 + g4 * 8 + hl * 4);
                 acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
             }
-            acc = mfma6(load_planes(w1, cb, lane), E, acc);
+            acc = b3_mfma6<3>(load_planes(w1, cb, lane), E, acc);
 #pragma unroll
             for (int r = 0; r < 16; ++r) f1[cb][r] = leaky02(acc[r]);
         }
         gstage(1, t0 + t_step);
-        Planes P[NQ];  // the operand planes of the tile that feeds the scores (chunk q = accumulator registers 8 (q & 1) .. of block q >> 1)
-        auto split_block = [&](const f32x16& f, Planes& lo, Planes& hi) {
+        B3Planes P[NQ];  // the operand planes of the tile that feeds the scores (chunk q = accumulator registers 8 (q & 1) .. of block q >> 1)
+        auto split_block = [&](const f32x16& f, B3Planes& lo, B3Planes& hi) {
             const float x0[8] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]};
             const float x1[8] = {f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
-            lo = split8(x0);
-            hi = split8(x1);
+            lo = b3_split8<3>(x0);
+            hi = b3_split8<3>(x1);
         };
         auto store_block = [&](const f32x16& f, int cb) {  // -> fp32 tile (value reads of the weighted sum)
 #pragma unroll
@@ -248,7 +197,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
                     acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
                 }
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) acc = mfma6(load_planes(w2, cb * NQ + q, lane), P[q], acc);
+                for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(load_planes(w2, cb * NQ + q, lane), P[q], acc);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) f2[cb][r] = leaky02(acc[r]);
             }
@@ -270,7 +219,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) acc = mfma6(P[q], load_planes(wb, cb * NQ + q, lane), acc);
+            for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(P[q], load_planes(wb, cb * NQ + q, lane), acc);
             f32x2 (&vv)[8] = v[cb & 1];
             if (cb * 32 >= H) {  // values = f_xyz (LDS tile)
                 const float* tv = TX + (cb * 32 - H + c32) + 4 * hl * PITCH;
@@ -287,7 +236,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
                 float m = fmaxf(sc[pi * PP][0], sc[pi * PP][1]);
 #pragma unroll
                 for (int j = 1; j < PP; ++j) m = fmaxf(m, fmaxf(sc[pi * PP + j][0], sc[pi * PP + j][1]));
-                m = swap32b_max(m);
+                m = swap32_max(m);
                 const f32x2 mm = {m, m};
                 f32x2 ssum2 = {0.f, 0.f}, num2 = {0.f, 0.f};
 #pragma unroll
@@ -297,8 +246,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
                     ssum2 += ex;
                     num2 = __builtin_elementwise_fma(ex, vv[pi * PP + j], num2);
                 }
-                const float ssum = swap32b_sum(ssum2[0] + ssum2[1]);
-                const float num = swap32b_sum(num2[0] + num2[1]);
+                const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
+                const float num = swap32_sum(num2[0] + num2[1]);
                 if (hl == 0 && t0 + pi < t_end) a.agg[__umul24(pp[pi], D) + (unsigned)(cb * 32 + c32)] = num * __builtin_amdgcn_rcpf(ssum);
             }
         }
@@ -371,7 +320,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         float x0[8], x1[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { x0[r] = leaky02(acc[r]); x1[r] = leaky02(acc[8 + r]); }
-        const Planes lo = split8(x0), hi = split8(x1);
+        const B3Planes lo = b3_split8<3>(x0), hi = b3_split8<3>(x1);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
             planes[((2 * cb) * 3 + pl) * 64 + lane] = lo.p[pl];
@@ -389,7 +338,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
     gstage(1, t_first);
     gstage(2, t_first);
     static_assert(NB_H == 1, "att32s: one transposed block per wave");
-    const Planes W1 = load_planes(a.w1, wave, lane);  // this wave's LocSE block: resident for the whole kernel
+    const B3Planes W1 = load_planes(a.w1, wave, lane);  // this wave's LocSE block: resident for the whole kernel
     const f32x16 seed1 = seed(a.b1, wave);
     constexpr int PD = D >= 512 ? 4 : 2;                // score-weight chunks in flight per block (measured: 2 at d = 256, 4 at d = 512)
     constexpr int PD2 = STAGE == 2 ? (D >= 512 ? 4 : 8) : 1;  // mlp2-weight chunks in flight (measured: all 8 at d = 256, 4 at d = 512)
@@ -404,11 +353,11 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         const float rx = cx - nx, ry = cy - ny, rz = cz - nz;
         const float dis = __builtin_amdgcn_sqrtf(rx * rx + ry * ry + rz * rz);
         const float ev[8] = {hl ? ny : dis, hl ? nz : rx, hl ? 0.f : ry, hl ? 0.f : rz, hl ? 0.f : cx, hl ? 0.f : cy, hl ? 0.f : cz, hl ? 0.f : nx};
-        const Planes E = split8(ev);
+        const B3Planes E = b3_split8<3>(ev);
         if (hl == 0 && wave == 0) NB[c32] = nbr;
         gstage(0, t0 + t_step);
         // the first weight chunks of the next product do not depend on anything: they travel under LocSE and its barrier
-        Planes ring[PD2], rA[PD], rB[PD];
+        B3Planes ring[PD2], rA[PD], rB[PD];
         if constexpr (STAGE == 2) {
 #pragma unroll
             for (int q = 0; q < PD2; ++q) ring[q] = load_planes(a.w2, wave * NQ + q, lane);
@@ -421,7 +370,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         }
 
         // ---- LFA mlp1 (transposed), this wave's block ----
-        emit_block(mfma6(W1, E, seed1), wave, PA, STAGE == 1);
+        emit_block(b3_mfma6<3>(W1, E, seed1), wave, PA, STAGE == 1);
         __syncthreads();
         gstage(1, t0 + t_step);
         // neighbour-row offsets and the gathers of this wave's two score blocks (they travel under the products below)
@@ -444,12 +393,12 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             for (int q0 = 0; q0 + PD2 < NQ; q0 += PD2) {
 #pragma unroll
                 for (int j = 0; j < PD2; ++j) {
-                    acc = mfma6(ring[j], load_planes(PA, q0 + j, lane), acc);
+                    acc = b3_mfma6<3>(ring[j], load_planes(PA, q0 + j, lane), acc);
                     ring[j] = load_planes(a.w2, cb * NQ + q0 + j + PD2, lane);  // refilled in place, behind its last reader
                 }
             }
 #pragma unroll
-            for (int j = 0; j < PD2; ++j) acc = mfma6(ring[j], load_planes(PA, NQ - PD2 + j, lane), acc);
+            for (int j = 0; j < PD2; ++j) acc = b3_mfma6<3>(ring[j], load_planes(PA, NQ - PD2 + j, lane), acc);
 #pragma unroll
             for (int q = 0; q < PD; ++q) {  // the score product's first chunks, under the split + barrier
                 rA[q] = load_planes(a.wb, cbA * NQ + q, lane);
@@ -470,9 +419,9 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             for (int q0 = 0; q0 + PD < NQ; q0 += PD) {
 #pragma unroll
                 for (int j = 0; j < PD; ++j) {
-                    const Planes x = load_planes(PB, q0 + j, lane);
-                    accA = mfma6(x, rA[j], accA);
-                    accB = mfma6(x, rB[j], accB);
+                    const B3Planes x = load_planes(PB, q0 + j, lane);
+                    accA = b3_mfma6<3>(x, rA[j], accA);
+                    accB = b3_mfma6<3>(x, rB[j], accB);
                     rA[j] = load_planes(a.wb, cbA * NQ + q0 + j + PD, lane);  // refilled in place, behind its last reader
                     rB[j] = load_planes(a.wb, cbB * NQ + q0 + j + PD, lane);
                 }
@@ -484,9 +433,9 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
                 for (int r = 0; r < 16; ++r) gq[i][r >> 1][r & 1] = *reinterpret_cast<const float*>(fgb + off[r] + (i * WAVES * 32 * 4 + H * 4));
 #pragma unroll
             for (int j = 0; j < PD; ++j) {
-                const Planes x = load_planes(PB, NQ - PD + j, lane);
-                accA = mfma6(x, rA[j], accA);
-                accB = mfma6(x, rB[j], accB);
+                const B3Planes x = load_planes(PB, NQ - PD + j, lane);
+                accA = b3_mfma6<3>(x, rA[j], accA);
+                accB = b3_mfma6<3>(x, rB[j], accB);
             }
         }
         // value rows of the first block (columns < H: gathered neighbour features); the second block (f_xyz columns, LDS) goes first
@@ -513,7 +462,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
                 float m = fmaxf(sc[pi * PP][0], sc[pi * PP][1]);
 #pragma unroll
                 for (int j = 1; j < PP; ++j) m = fmaxf(m, fmaxf(sc[pi * PP + j][0], sc[pi * PP + j][1]));
-                m = swap32b_max(m);
+                m = swap32_max(m);
                 const f32x2 mm = {m, m};
                 f32x2 ssum2 = {0.f, 0.f}, num2 = {0.f, 0.f};
 #pragma unroll
@@ -523,8 +472,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
                     ssum2 += ex;
                     num2 = __builtin_elementwise_fma(ex, vv[pi * PP + j], num2);
                 }
-                const float ssum = swap32b_sum(ssum2[0] + ssum2[1]);
-                const float num = swap32b_sum(num2[0] + num2[1]);
+                const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
+                const float num = swap32_sum(num2[0] + num2[1]);
                 if (hl == 0 && t0 + pi < t_end) a.agg[__umul24(pp[pi], D) + (unsigned)(cb * 32 + c32)] = num * __builtin_amdgcn_rcpf(ssum);
             }
         }
@@ -533,26 +482,6 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static inline uint16_t piece_of(float w, int plane)
-{
-    auto trunc16 = [](float x) {
-        uint32_t u;
-        __builtin_memcpy(&u, &x, 4);
-        u &= 0xffff0000u;
-        float r;
-        __builtin_memcpy(&r, &u, 4);
-        return r;
-    };
-    volatile float w1 = trunc16(w);
-    volatile float r1 = w - w1;
-    volatile float w2 = trunc16(r1);
-    volatile float w3 = r1 - w2;
-    const float pick = plane == 0 ? w1 : (plane == 1 ? w2 : w3);
-    uint32_t u;
-    __builtin_memcpy(&u, &pick, 4);
-    return (uint16_t)(u >> 16);
-}
-
 // K order of an operand that comes out of a transposed product's accumulators: chunk q, lane half g, element j
 static inline int kmap(int q, int g, int j)
 {
@@ -568,7 +497,7 @@ void pack_b3(const float* W, int cin, int cout, uint16_t* out)
             for (int pl = 0; pl < 3; ++pl)
                 for (int l = 0; l < 64; ++l)
                     for (int j = 0; j < 8; ++j)
-                        out[(((((size_t)cb * nq + q) * 3 + pl) * 64 + l) * 8) + j] = piece_of(W[(size_t)kmap(q, l >> 5, j) * cout + 32 * cb + (l & 31)], pl);
+                        out[(((((size_t)cb * nq + q) * 3 + pl) * 64 + l) * 8) + j] = b3_piece_of(W[(size_t)kmap(q, l >> 5, j) * cout + 32 * cb + (l & 31)], pl);
 }
 
 void pack_b3_locse(const float* W1, int cout, uint16_t* out)
@@ -579,7 +508,7 @@ void pack_b3_locse(const float* W1, int cout, uint16_t* out)
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
                     const int k = 8 * (l >> 5) + j;
-                    out[((((size_t)cb * 3 + pl) * 64 + l) * 8) + j] = k < 10 ? piece_of(W1[(size_t)k * cout + 32 * cb + (l & 31)], pl) : (uint16_t)0;
+                    out[((((size_t)cb * 3 + pl) * 64 + l) * 8) + j] = k < 10 ? b3_piece_of(W1[(size_t)k * cout + 32 * cb + (l & 31)], pl) : (uint16_t)0;
                 }
 }
 

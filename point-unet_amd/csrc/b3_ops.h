@@ -1,4 +1,5 @@
-// b3_ops.h -- operand helpers of the split-bf16 ("bf16x3") matrix products shared by gemm_b3.hip and attpool_gemm.hip:
+// b3_ops.h -- operand helpers of the split-bf16 ("bf16x3") matrix products, the one definition that gemm_b3.hip, attpool_gemm.hip,
+// gemm32b.hip and attpool32b.hip share (device: split, planes, MFMA; host: b3_piece_of for the weight images):
 // v_mfma_f32_32x32x16_bf16 over exact three-way bfloat16 splits of fp32 operands (P = 3: six piece products per fp32 product, fp32
 // accumulate, fp32-level error -- attpool32b.hip explains the split) or over ONE plane of round-to-nearest-even bfloat16 (P = 1: the
 // bf16-MLP mode of the training step).
@@ -11,11 +12,9 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace ps {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 __device__ __forceinline__ void b3_split_pair(float x, float y, unsigned& q1, unsigned& q2, unsigned& q3)
 {
@@ -23,13 +22,14 @@ __device__ __forceinline__ void b3_split_pair(float x, float y, unsigned& q1, un
     const float xr = x - __uint_as_float(xu & 0xffff0000u), yr = y - __uint_as_float(yu & 0xffff0000u);  // exact
     const unsigned xru = __float_as_uint(xr), yru = __float_as_uint(yr);
     const float x3 = xr - __uint_as_float(xru & 0xffff0000u), y3 = yr - __uint_as_float(yru & 0xffff0000u);  // exact, 8 bits
-    q1 = __builtin_amdgcn_perm(yu, xu, 0x07060302u);
+    q1 = __builtin_amdgcn_perm(yu, xu, 0x07060302u);  // [y.hi16 : x.hi16]
     q2 = __builtin_amdgcn_perm(yru, xru, 0x07060302u);
     q3 = __builtin_amdgcn_perm(__float_as_uint(y3), __float_as_uint(x3), 0x07060302u);
 }
 // P = 3: the exact three-way split (fp32 products on the bf16 pipe).  P = 1: ONE plane of round-to-nearest-even bfloat16 -- the bf16-MLP
 // mode of the training step (operands rounded to bfloat16, fp32 accumulation), which so runs its large products through the same tiling
 // with a sixth of the matrix work: HBM bound ([360k, 256] x [256, 256]: 0.63 ms in rowgemm_direct_bf16 before).
+// plane word t = pieces of (x[2t], x[2t+1]), low half = the even element
 template <int P>
 struct BPlanes {
     uint4 p[P];
@@ -58,10 +58,16 @@ __device__ __forceinline__ BPlanes<P> b3_split8(const float4& lo, const float4& 
     }
     return r;
 }
+template <int P>
+__device__ __forceinline__ BPlanes<P> b3_split8(const float (&x)[8])
+{
+    return b3_split8<P>(make_float4(x[0], x[1], x[2], x[3]), make_float4(x[4], x[5], x[6], x[7]));
+}
 __device__ __forceinline__ f32x16 b3_mfma(const uint4& a, const uint4& b, f32x16 acc)
 {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
+// the six kept piece products, smallest first
 template <int P>
 __device__ __forceinline__ f32x16 b3_mfma6(const BPlanes<P>& a, const BPlanes<P>& b, f32x16 acc)
 {
@@ -76,6 +82,28 @@ __device__ __forceinline__ f32x16 b3_mfma6(const BPlanes<P>& a, const BPlanes<P>
         acc = b3_mfma(a.p[0], b.p[0], acc);
     }
     return acc;
+}
+
+// Host: bfloat16 piece `plane` (0..2) of w, the same split as b3_split_pair, for the weight images packed on the host (pack_p32b,
+// pack_b3, pack_b3_locse).  The volatiles are load-bearing: do not remove them.
+inline uint16_t b3_piece_of(float w, int plane)
+{
+    auto trunc16 = [](float x) {
+        uint32_t u;
+        __builtin_memcpy(&u, &x, 4);
+        u &= 0xffff0000u;
+        float r;
+        __builtin_memcpy(&r, &u, 4);
+        return r;
+    };
+    volatile float w1 = trunc16(w);
+    volatile float r1 = w - w1;
+    volatile float w2 = trunc16(r1);
+    volatile float w3 = r1 - w2;
+    const float pick = plane == 0 ? w1 : (plane == 1 ? w2 : w3);
+    uint32_t u;
+    __builtin_memcpy(&u, &pick, 4);
+    return (uint16_t)(u >> 16);
 }
 
 // the element function of gemm_b3_pack_kernel for the batched form (PackCache): thread i of job j.

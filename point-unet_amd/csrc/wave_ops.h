@@ -41,4 +41,16 @@ __device__ __forceinline__ int wave_sum(int v)
     return (int)wave_allreduce_u32((unsigned)v, [](unsigned a, unsigned b) { return a + b; });
 }
 
+// max / sum over the two 32-lane halves only (attpool32.hip, attpool32b.hip: a column's softmax terms live in lanes l and l ^ 32)
+__device__ __forceinline__ float swap32_max(float v)
+{
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float swap32_sum(float v)
+{
+    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
+
 }  // namespace ps
