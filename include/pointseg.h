@@ -97,8 +97,9 @@ const char* ps_last_error(void);
 const char* ps_version(void);
 /* Layout revision of the structs a caller fills (ps_pyramid, ps_train_options, ps_randla_config): bumped whenever one of them grows.
  * A host built against an older header would make the library read past its struct -- compare ps_abi_version() with the
- * PS_ABI_VERSION it was compiled with before the first call (point-unet_amd/_lib.py does).  6: ps_pyramid.built, ps_train_options.act_bf16. */
-#define PS_ABI_VERSION 6
+ * PS_ABI_VERSION it was compiled with before the first call (point-unet_amd/_lib.py does).  6: ps_pyramid.built, ps_train_options.act_bf16.
+ * 7: ps_volume_sample_args. */
+#define PS_ABI_VERSION 7
 int ps_abi_version(void);
 
 /* Per-call kernel timing on the context's stream, measured with hipEvents recorded on THAT stream.
@@ -307,6 +308,73 @@ int ps_cloud_positive_counts(ps_context* ctx, const int32_t* labels, const int64
 int ps_cloud_sample(ps_context* ctx, const float* xyz, const float* modalities, int32_t C, const int32_t* labels, const int64_t* offsets,
                     int64_t n_clouds, const int64_t* positives, const int32_t* cloud_ids, int32_t B, int64_t N, uint32_t seed, float* out_xyz,
                     float* out_features, int32_t* out_labels, int32_t* out_idx);
+
+/* ---- volume -> the network's clouds, Pancreas form (csrc/volume_sample.hip) --------------------------------------------------------------
+ * The reference's slowest preparation, PointSegment/utils/dataPreparePancreas.py:34-46 (itensity_normalize_one_volume) and :132-169
+ * (sampling_convert_pc2ply: a Python list of EVERY voxel, then `tumor + random.sample(none_tumor, n_point - len(tumor))`, eight times),
+ * with the two steps that make its positive set at inference: utils/genBinaryMap.py:67-80 (probability >= threshold) and
+ * PointSegment/utils/over_sampling.py:58-65 (binary dilation, OR truth).  One call, one caller-filled struct, device pointers, no per-voxel
+ * word array: the normalised volume, per-voxel coordinates, keys or a background index list are never stored.
+ *
+ * The rule (restated in tests/volume_sample_ref.py), a pure function of (volume, positive set, N, seed, loop); v = (x * Y + y) * Z + z:
+ *     M           = the positive set: mask[v] != 0, or probs[v * probs_C + probs_channel] >= threshold compared in float32; then `dilate`
+ *                   rounds of scipy.ndimage.binary_dilation's default (6-neighbourhood, outside the array = 0); then OR truth[v] != 0
+ *     P           = |M|;  s_sel(l) = hash32(seed + 0x9E3779B9 * (2l + 1))   (ps_cloud_sample's, with the loop as the slot)
+ *     key_sel(v)  = hash32(v * 2654435761 ^ s_sel(l)) << 32 | v
+ *     row t < P   of EVERY loop: the t-th voxel of M in ascending v
+ *     row P + t   of loop l: the voxel outside M with the t-th smallest key_sel
+ * i.e. the reference's distribution -- every positive first and in voxel order, then a uniform N - P subset of the background in
+ * uniformly random order (random.sample returns selection order), NOT shuffled, so the mask's points are the prefix the pyramid's
+ * sub-sampling keeps (runPancreas.py:107, 133).  One key does both jobs: given which keys are the N - P smallest, their order is uniform.
+ *     value       = (float)(((double)raw - mean) / std), mean / std = population statistics of ALL voxels in float64 (despite its docstring
+ *                   the reference does not mask zeros).  PS_VOLUME_I16: integer sums, n * sum(x^2) - sum(x)^2 formed exactly in 128 bits
+ *                   and rounded once, so the statistics do not depend on the reduction order.  PS_VOLUME_F32: float64 sums in one fixed
+ *                   order (bit-reproducible run to run); the yardstick is the float64 expression, not the reference's float32
+ *                   accumulation of a float32 array.
+ *     xyz         = (float)c / (float)dim, one IEEE float32 division per coordinate (:165)
+ * Outputs (device, every one optional): out_mask u8[X,Y,Z] = M as 0 / 1; out_stats f64[2] = {mean, std}; out_positives i64[1] = P;
+ * out_xyz f32[loops,N,3]; out_features f32[loops,N,4] = [xyz | value] (runPancreas.py:125); out_labels i32[loops,N] = label_src[v], or
+ * 1 on M and 0 elsewhere when label_src is NULL; out_origin i32[loops,N,3] = (x, y, z) (the reference's *_xyz_origin_loop_i.npy,
+ * point2prod's xyz_origin); out_idx i32[loops,N] = v.  N == 0: mask / statistics / P only (loops is not read).
+ * Limits: X * Y * Z < 2^31, every dimension <= 65 535 (the reference stores uint16 coordinates), 1 <= loops <= PS_VOLUME_SAMPLE_MAX_LOOPS,
+ * P <= N <= X * Y * Z, loops * N < 2^31, 0 <= dilate <= PS_VOLUME_SAMPLE_MAX_DILATE.
+ * Scratch: two-call protocol -- scratch == NULL only fills scratch_bytes (<= X*Y*Z + 128 * loops * N + 2^20: one byte per voxel, the
+ * (key, voxel) pairs of the output rows with their ping-pong copy, counters); the second call takes device memory of at least that size,
+ * 256-byte aligned, which must stay valid until the stream has passed the call (and, with deferred checks, until ps_synchronize).
+ * Errors: every argument error returns PS_EINVAL before anything is enqueued, the outputs untouched.  P > N is only known on the device:
+ * PS_ESTATE, nothing written outside the buffers (the rows are then unspecified), returned by this call (one synchronisation) or, with
+ * ps_set_deferred_checks on, by the next ps_synchronize.  Otherwise asynchronous on the context's stream. */
+#define PS_VOLUME_I16 1
+#define PS_VOLUME_F32 2
+#define PS_VOLUME_SAMPLE_MAX_LOOPS 16
+#define PS_VOLUME_SAMPLE_MAX_DILATE 64
+typedef struct {
+    const void* volume;          /* [X, Y, Z] row-major (z fastest: the order of dataPreparePancreas.py:144) */
+    int32_t volume_dtype;        /* PS_VOLUME_I16 | PS_VOLUME_F32 */
+    int32_t dilate;
+    int64_t X, Y, Z;
+    const uint8_t* mask;         /* the positive set, exactly one of mask / probs: u8[X,Y,Z], != 0 is positive (the `label` of :139, 154-155) */
+    const float* probs;          /* f32[X*Y*Z, probs_C], 1 <= probs_C <= 65 535 */
+    int32_t probs_C, probs_channel;
+    float threshold;
+    int32_t loops;
+    const uint8_t* truth;        /* optional, OR-ed in after the dilation (over_sampling.py:62) */
+    const uint8_t* label_src;    /* optional: out_labels = label_src[v] */
+    int64_t N;                   /* rows per loop (reference: 8 x 180 000, :136, 28) */
+    uint32_t seed;
+    uint32_t reserved;           /* 0 */
+    uint8_t* out_mask;
+    double* out_stats;
+    int64_t* out_positives;
+    float* out_xyz;
+    float* out_features;
+    int32_t* out_labels;
+    int32_t* out_origin;
+    int32_t* out_idx;
+    void* scratch;
+    int64_t scratch_bytes;
+} ps_volume_sample_args;
+int ps_volume_sample(ps_context* ctx, ps_volume_sample_args* a);
 
 /* The op-level kernels of the training step -- forward / backward pairs of the ops above, BatchNorm in training mode, the fused and
  * recompute forms the native trainer chooses between, the deterministic scatter-adds, loss and Adam -- are declared in

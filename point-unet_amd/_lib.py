@@ -8,7 +8,8 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpointseg_hip.so")
-PS_ABI_VERSION = 6  # include/pointseg.h
+PS_ABI_VERSION = 7  # include/pointseg.h
+PS_VOLUME_I16, PS_VOLUME_F32 = 1, 2
 
 PS_MAX_LAYERS = 8
 c_f32p = ctypes.POINTER(ctypes.c_float)
@@ -55,6 +56,38 @@ class PsTrainOptions(ctypes.Structure):
         ("fused_convbn", ctypes.c_int32),
         ("overlap_wgrad", ctypes.c_int32),
         ("act_bf16", ctypes.c_int32),
+    ]
+
+
+class PsVolumeSampleArgs(ctypes.Structure):
+    _fields_ = [
+        ("volume", c_vp),
+        ("volume_dtype", ctypes.c_int32),
+        ("dilate", ctypes.c_int32),
+        ("X", ctypes.c_int64),
+        ("Y", ctypes.c_int64),
+        ("Z", ctypes.c_int64),
+        ("mask", c_vp),
+        ("probs", c_vp),
+        ("probs_C", ctypes.c_int32),
+        ("probs_channel", ctypes.c_int32),
+        ("threshold", ctypes.c_float),
+        ("loops", ctypes.c_int32),
+        ("truth", c_vp),
+        ("label_src", c_vp),
+        ("N", ctypes.c_int64),
+        ("seed", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("out_mask", c_vp),
+        ("out_stats", c_vp),
+        ("out_positives", c_vp),
+        ("out_xyz", c_vp),
+        ("out_features", c_vp),
+        ("out_labels", c_vp),
+        ("out_origin", c_vp),
+        ("out_idx", c_vp),
+        ("scratch", c_vp),
+        ("scratch_bytes", ctypes.c_int64),
     ]
 
 
@@ -121,6 +154,8 @@ PROTOTYPES = {
     "ps_cloud_positive_counts": (ctypes.c_int, [c_vp, c_vp, c_i64p, ctypes.c_int64, c_i64p]),
     "ps_cloud_sample": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_i64p, ctypes.c_int64, c_i64p, c_i32p, ctypes.c_int32, ctypes.c_int64,
                                        ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
+    # volume -> the network's clouds, Pancreas form (csrc/volume_sample.hip)
+    "ps_volume_sample": (ctypes.c_int, [c_vp, ctypes.POINTER(PsVolumeSampleArgs)]),
     "ps_op_bn_train_sums": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
     "ps_op_bn_train_apply": (ctypes.c_int, [c_vp] * 5 + [ctypes.c_int64] * 3 + [ctypes.c_float, ctypes.c_int] + [c_vp] * 4),
     "ps_op_bn_train_bwd_sums": (ctypes.c_int, [c_vp] * 7 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [c_vp] * 2),

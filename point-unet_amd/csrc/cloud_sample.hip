@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "sample_hash.h"
 #include "sortscan.h"
 
 namespace ps {
@@ -25,8 +26,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kPerThread = 16;
 constexpr int kTile = kThreads * kPerThread;  // points per workgroup of the per-point passes
-constexpr unsigned kSeedMul = 0x9E3779B9u;
-constexpr unsigned kIndexMul = 2654435761u;
 
 // per slot, device: the select's state
 struct SampleSlot {
@@ -48,14 +47,6 @@ struct SlotInfo {
     int cloud;
     unsigned pad;
 };
-
-__device__ __forceinline__ unsigned hash32(unsigned x)  // lowbias32, as ops_train.hip's dropout
-{
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ unsigned point_hash(unsigned i, unsigned s) { return hash32(i * kIndexMul ^ s); }
 
 __device__ __forceinline__ unsigned wave_sum(unsigned v)
 {
@@ -367,12 +358,6 @@ __global__ __launch_bounds__(256) void cloud_positive_count_kernel(const int32_t
 int scan_launches(size_t n) { const size_t nt = (n + 2047) / 2048; return nt > 1 ? 2 + scan_launches(nt) : 1; }
 int sort_pass_launches(size_t n) { return 2 + scan_launches(256 * ((n + 8191) / 8192)); }
 
-unsigned host_hash32(unsigned x)
-{
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
 }  // namespace
 
 }  // namespace ps
@@ -444,8 +429,8 @@ extern "C" int ps_cloud_sample(ps_context* c, const float* xyz, const float* mod
         SlotInfo& s = info[b];
         s.row0 = r0;
         s.n = (unsigned)n;
-        s.s_sel = host_hash32(seed + kSeedMul * (2u * b + 1u));
-        s.s_perm = host_hash32(seed + kSeedMul * (2u * b + 2u));
+        s.s_sel = hash32(seed + kSeedMul * (2u * b + 1u));
+        s.s_perm = hash32(seed + kSeedMul * (2u * b + 2u));
         s.p_host = (unsigned)p;
         s.cloud = cl;
         s.pad = 0;

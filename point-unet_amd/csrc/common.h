@@ -190,8 +190,9 @@ struct ps_context {
     unsigned pending_mask = 0;
     uint64_t builds = 0;          // ps_pyramid_build calls on this context so far (error messages name the failing one)
     uint64_t samples = 0;         // ps_cloud_sample calls on this context so far
+    uint64_t volume_samples = 0;  // ps_volume_sample draws on this context so far
     uint64_t flag_serial[8] = {}; // which build / sample each pending slot belongs to
-    int flag_kind[8] = {};        // what wrote the slot: 0 ps_pyramid_build (3 status words), 1 ps_cloud_sample (4 words)
+    int flag_kind[8] = {};        // what wrote the slot: 0 ps_pyramid_build (3 status words), 1 ps_cloud_sample (4 words), 2 ps_volume_sample (4)
     int flag_slot = 0;
     int sticky_rc = 0;            // a failed deferred check found while reusing its slot: reported by the next ps_synchronize
     std::string sticky_msg;

@@ -62,6 +62,12 @@ int ps_context::check_flag_slot(int s)
                               f[2], f[3]);
                 rc = PS_ESTATE;
             }
+        } else if (flag_kind[s] == 2) {  // ps_volume_sample: {P > N, P, N, 0}
+            if (f[0] != 0) {
+                ps::set_error("deferred check: volume sample #%llu of this context: the positive set holds %d voxels, more than N = %d (nothing "
+                              "was written outside the outputs; their rows are unspecified)", (unsigned long long)flag_serial[s], f[1], f[2]);
+                rc = PS_ESTATE;
+            }
         } else if (f[1] != 0) {
             ps::set_error("deferred check: pyramid build #%llu of this context: kd-tree builder queue overflow (degenerate cloud); its index "
                           "tables were filled with index 0", (unsigned long long)flag_serial[s]);

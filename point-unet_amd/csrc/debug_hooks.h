@@ -43,6 +43,8 @@ int ps_debug_set_tuning(ps_context* ctx, const char* field, double value);
 int ps_debug_get_tuning(ps_context* ctx, const char* field, double* value);
 /* The field names the two doors above know, '\n'-separated and NUL-terminated, into buf[cap]; PS_EINVAL when cap is too small.  No context. */
 int ps_debug_tuning_fields(char* buf, int cap);
+/* sizeof(ps_volume_sample_args) as the library was compiled: the ctypes mirror (point-unet_amd/_lib.py) is checked against it. */
+int ps_debug_volume_sample_args_size(void);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@
 
 using namespace ps;
 
+extern "C" int ps_debug_volume_sample_args_size(void) { return (int)sizeof(ps_volume_sample_args); }
+
 extern "C" int ps_debug_pack_weights(const float* W, int cin, int cout, int ntb, float* out)
 {
     PS_CHECK(W && out && (ntb == 1 || ntb == 2 || ntb == 4), "ps_debug_pack_weights: bad argument");

@@ -107,3 +107,150 @@ def _prepare_chained(volumes, seg, sub_grid_size, device, on_device=False):
     return dict(xyz=xyz[:n].cpu().numpy(), colors=colors[:n].cpu().numpy(), labels=labels[:n].cpu().numpy().astype(np.uint8),
                 xyz_origin=origin[:n].cpu().numpy(), sub_xyz=sub_xyz[:m].cpu().numpy(), sub_colors=sub_colors[:m].cpu().numpy(),
                 sub_labels=sub_labels[:m].cpu().numpy().reshape(-1).astype(np.uint8), proj_idx=proj[:, 0].cpu().numpy())
+
+
+# ---- Pancreas: CT volume + positive set -> the network's clouds (ps_volume_sample, csrc/volume_sample.hip) -------------------------------
+
+def _dev_tensor(a, dtype, dev):
+    import torch
+    if a is None:
+        return None
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def _volume_sample(shape, device, volume=None, mask=None, probs=None, channel=1, threshold=0.9, dilate=0, truth=None, label_src=None, n_point=0,
+                   loops=1, seed=0, want_mask=False, ctx=None):
+    """One ps_volume_sample call on device tensors (already of the wire dtypes).  Returns the dict of the outputs asked for."""
+    import torch
+    X, Y, Z = (int(s) for s in shape)
+    dev = torch.device("cuda", device)
+    ctx = ctx or runtime.default_context(device)
+    a = _lib.PsVolumeSampleArgs()
+    if volume is not None:
+        a.volume = runtime.ptr(volume)
+        a.volume_dtype = _lib.PS_VOLUME_I16 if volume.dtype == torch.int16 else _lib.PS_VOLUME_F32
+    a.X, a.Y, a.Z = X, Y, Z
+    a.mask, a.probs = runtime.ptr(mask), runtime.ptr(probs)
+    if probs is not None:
+        a.probs_C, a.probs_channel = int(probs.shape[-1]), int(channel)
+    a.threshold, a.dilate = float(threshold), int(dilate)
+    a.truth, a.label_src = runtime.ptr(truth), runtime.ptr(label_src)
+    a.loops, a.N, a.seed = int(loops), int(n_point), int(seed) & 0xFFFFFFFF
+    out = {"positives": torch.zeros(1, dtype=torch.int64, device=dev)}
+    a.out_positives = runtime.ptr(out["positives"])
+    if want_mask:
+        out["mask"] = torch.empty((X, Y, Z), dtype=torch.uint8, device=dev)
+        a.out_mask = runtime.ptr(out["mask"])
+    if volume is not None:
+        out["stats"] = torch.zeros(2, dtype=torch.float64, device=dev)
+        a.out_stats = runtime.ptr(out["stats"])
+    if n_point > 0:
+        L, N = int(loops), int(n_point)
+        out["xyz"] = torch.empty((L, N, 3), dtype=torch.float32, device=dev)
+        out["labels"] = torch.empty((L, N), dtype=torch.int32, device=dev)
+        out["xyz_origin"] = torch.empty((L, N, 3), dtype=torch.int32, device=dev)
+        out["idx"] = torch.empty((L, N), dtype=torch.int32, device=dev)
+        a.out_xyz, a.out_labels = runtime.ptr(out["xyz"]), runtime.ptr(out["labels"])
+        a.out_origin, a.out_idx = runtime.ptr(out["xyz_origin"]), runtime.ptr(out["idx"])
+        if volume is not None:
+            out["features"] = torch.empty((L, N, 4), dtype=torch.float32, device=dev)
+            a.out_features = runtime.ptr(out["features"])
+    lib = _lib.lib()
+    _lib.check(lib.ps_volume_sample(ctx.handle, ctypes.byref(a)))  # scratch == NULL: the size
+    scratch = torch.empty(int(a.scratch_bytes), dtype=torch.uint8, device=dev)  # (stream-ordered like every tensor of the caller)
+    a.scratch = runtime.ptr(scratch)
+    _lib.check(lib.ps_volume_sample(ctx.handle, ctypes.byref(a)))
+    if "features" in out:
+        out["value"] = out["features"][..., 3:]
+    return out
+
+
+def _shape3(*arrays):
+    for t in arrays:
+        if t is not None:
+            s = tuple(t.shape)[:3]
+            if len(s) != 3:
+                raise ValueError("expected a volume [X, Y, Z], got shape %s" % (tuple(t.shape),))
+            return s
+    raise ValueError("one of probs / mask is required")
+
+
+def pancreas_mask(probs=None, mask=None, threshold=0.9, dilate=0, truth=None, channel=1, device=0):
+    """The sampling mask of the Pancreas inference path, on the device: probs [X, Y, Z, C] (float32; channel `channel` >= threshold, compared
+    in float32: genSegmentation, utils/genBinaryMap.py:67-80) or a ready mask [X, Y, Z] (!= 0), then `dilate` rounds of
+    scipy.ndimage.binary_dilation's default structure, then OR truth (dilation_over_truth, PointSegment/utils/over_sampling.py:58-65).
+    numpy or torch, host or device.  Returns the uint8 volume [X, Y, Z] (0 / 1) as a CUDA tensor."""
+    import torch
+    if (probs is None) == (mask is None):
+        raise ValueError("pancreas_mask: exactly one of probs and mask")
+    dev = torch.device("cuda", device)
+    p = _dev_tensor(probs, torch.float32, dev)
+    if p is not None and p.dim() != 4:
+        raise ValueError("pancreas_mask: probs must have shape [X, Y, Z, C]")
+    m, t = _as_u8_nonzero(mask, dev), _as_u8_nonzero(truth, dev)
+    shape = _shape3(p, m)
+    if t is not None and tuple(t.shape) != shape:
+        raise ValueError("pancreas_mask: truth must have the volume's shape")
+    runtime.default_context(device).use_torch_stream()
+    return _volume_sample(shape, device, mask=m, probs=p, channel=channel, threshold=threshold, dilate=dilate, truth=t, want_mask=True)["mask"]
+
+
+def _is_bool(a):
+    return str(getattr(a, "dtype", "")) in ("bool", "torch.bool")
+
+
+def _as_u8_nonzero(a, dev):
+    """Any integer / bool volume -> device uint8 that is != 0 exactly where `a` is (a label 256 must not wrap to 0)."""
+    import torch
+    if a is None:
+        return None
+    if _is_bool(a):
+        return _dev_tensor(a, torch.bool, dev).to(torch.uint8)
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype == torch.uint8:
+        return t.to(dev).contiguous()
+    return (t.to(dev) != 0).to(torch.uint8).contiguous()
+
+
+def prepare_pancreas_volume(volume, label=None, mask=None, n_point=180000, loops=8, seed=0, probs=None, threshold=0.9, dilate=0, truth=None,
+                            channel=1, device=0):
+    """dataPreparePancreas.py's load_volume + sampling_convert_pc2ply (:34-46, 132-169) for one CT, on the device: `loops` clouds of
+    `n_point` rows -- every positive voxel first and in voxel order, then a uniform sample of the rest, not shuffled.
+
+    volume [X, Y, Z]: int16 or float32 (other dtypes are taken as float32), numpy or torch, host or device.
+    The positive set, one of: label (the training form, :52-56: positive where label > 0, and out labels = the label's uint8 value);
+    mask (the inference form, :189 "the binary of the attention network": labels 1 on the mask); probs [X, Y, Z, C] with threshold /
+    channel; the last two with `dilate` rounds and an optional `truth` OR-ed in (pancreas_mask's steps, fused into the same call).
+
+    Returns CUDA tensors with a leading `loops` axis: xyz f32 [L,N,3], features f32 [L,N,4] = [xyz | value], value f32 [L,N,1] (a view),
+    labels i32 [L,N], xyz_origin i32 [L,N,3], idx i32 [L,N] (flat voxel index), and stats f64 [2] = {mean, std}, positives i64 [1].
+    Loop l is the input of dataset.pancreas_cloud's consumers: build_pyramid(d["xyz"][l:l+1], cfg), features d["features"][l:l+1],
+    point2prod(logits, None, d["xyz_origin"][l], volume_shape=(Z, X, Y))."""
+    import torch
+    if sum(x is not None for x in (label, mask, probs)) != 1:
+        raise ValueError("prepare_pancreas_volume: exactly one of label, mask and probs gives the positive set")
+    dev = torch.device("cuda", device)
+    v = volume if isinstance(volume, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(volume))
+    v = v.to(dev).contiguous() if v.dtype in (torch.int16, torch.float32) else v.to(device=dev, dtype=torch.float32).contiguous()
+    if v.dim() != 3:
+        raise ValueError("prepare_pancreas_volume: volume must have shape [X, Y, Z]")
+    shape = tuple(v.shape)
+    m = p = lab = None
+    if label is not None:
+        lt = label if isinstance(label, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(label))
+        lab = lt.to(dev).to(torch.uint8).contiguous()  # (the reference's labels.astype(np.uint8), :152)
+        m = lab
+    elif mask is not None:
+        m = _as_u8_nonzero(mask, dev)
+    else:
+        p = _dev_tensor(probs, torch.float32, dev)
+        if p.dim() != 4:
+            raise ValueError("prepare_pancreas_volume: probs must have shape [X, Y, Z, C]")
+    t = _as_u8_nonzero(truth, dev)
+    for name, x in (("label / mask", m), ("probs", p), ("truth", t)):
+        if x is not None and tuple(x.shape)[:3] != shape:
+            raise ValueError("prepare_pancreas_volume: %s must have the volume's shape %s" % (name, shape))
+    runtime.default_context(device).use_torch_stream()
+    return _volume_sample(shape, device, volume=v, mask=m, probs=p, channel=channel, threshold=threshold, dilate=dilate, truth=t, label_src=lab,
+                          n_point=int(n_point), loops=int(loops), seed=seed)
