@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "sample_hash.h"
+#include "sample_select.h"
 #include "sortscan.h"
 
 namespace ps {
@@ -52,16 +53,6 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o);
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_inclusive(unsigned v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = (unsigned)__shfl_up((int)v, o);
-        if (lane >= o) v += u;
-    }
     return v;
 }
 
@@ -125,11 +116,9 @@ __global__ __launch_bounds__(256) void cloud_sample_hist_kernel(const int32_t* _
 __global__ __launch_bounds__(256) void cloud_sample_pick_kernel(const SlotInfo* __restrict__ info, SampleSlot* __restrict__ slots,
                                                                 int* __restrict__ status, unsigned N, int shift)
 {
-    __shared__ unsigned s_w[4];
     __shared__ unsigned s_need, s_rank;
     SampleSlot& sl = slots[blockIdx.x];
-    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
-    if (d == 0) {
+    if (threadIdx.x == 0) {
         if (shift == 24) {
             const unsigned P = sl.positives;
             const unsigned need = P > N ? 0u : N - P;
@@ -144,19 +133,10 @@ __global__ __launch_bounds__(256) void cloud_sample_pick_kernel(const SlotInfo* 
         s_need = sl.need;
         s_rank = sl.rank;
     }
-    const unsigned c = sl.hist[d];
-    sl.hist[d] = 0;
-    const unsigned inc = wave_inclusive(c, lane);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    if (s_need == 0) return;
-    unsigned below = inc - c;
-    for (int w = 0; w < wave; ++w) below += s_w[w];
-    const unsigned rank = s_rank;
-    if (c && below <= rank && rank < below + c) {  // exactly one digit
-        sl.prefix |= (unsigned)d << shift;
-        sl.rank = rank - below;
-        if (shift == 0) sl.r_eq = rank - below + 1;
+    unsigned left;
+    if (select_pick_digit(sl.hist, shift, &s_need, &s_rank, &sl.prefix, left)) {
+        sl.rank = left;
+        if (shift == 0) sl.r_eq = left + 1;
     }
 }
 
@@ -211,7 +191,7 @@ __global__ __launch_bounds__(256) void cloud_sample_compact_kernel(const int32_t
     }
     if (threadIdx.x < 64) {  // entry k = 4 j + w is in element order: exclusive scan over the 64 (round, wave) groups
         const unsigned cd = s_cd[threadIdx.x], ce = s_ce[threadIdx.x];
-        const unsigned id = wave_inclusive(cd, lane), ie = wave_inclusive(ce, lane);
+        const unsigned id = wave_inclusive_sum(cd, lane), ie = wave_inclusive_sum(ce, lane);
         s_cd[threadIdx.x] = id - cd;
         s_ce[threadIdx.x] = ie - ce;
     }
@@ -255,7 +235,7 @@ __global__ __launch_bounds__(256) void cloud_sample_tile_scan_kernel(const SlotI
     for (unsigned k0 = 0; k0 < nt; k0 += 256) {
         const unsigned k = k0 + threadIdx.x;
         const unsigned cd = k < nt ? td[k] : 0u, ce = k < nt ? te[k] : 0u;
-        const unsigned id = wave_inclusive(cd, lane), ie = wave_inclusive(ce, lane);
+        const unsigned id = wave_inclusive_sum(cd, lane), ie = wave_inclusive_sum(ce, lane);
         if (lane == 63) {
             s_w[0][wave] = id;
             s_w[1][wave] = ie;
@@ -314,18 +294,8 @@ __global__ __launch_bounds__(256) void cloud_sample_gather_kernel(const float* _
     }
     __syncthreads();
     const bool vec = ((reinterpret_cast<uintptr_t>(out_xyz) | reinterpret_cast<uintptr_t>(out_f)) & 15) == 0;
-    auto store = [&](const float* src, float* dst, unsigned count) {
-        if (vec) {
-            const unsigned n4 = count / 4;
-            for (unsigned k = threadIdx.x; k < n4; k += 256)
-                reinterpret_cast<float4*>(dst)[k] = reinterpret_cast<const float4*>(src)[k];
-            for (unsigned k = n4 * 4 + threadIdx.x; k < count; k += 256) dst[k] = src[k];
-        } else {
-            for (unsigned k = threadIdx.x; k < count; k += 256) dst[k] = src[k];
-        }
-    };
-    store(s_x, out_xyz + (size_t)t0 * 3, rows * 3);
-    store(s_f, out_f + (size_t)t0 * F, rows * F);
+    store_staged_words(s_x, out_xyz + (size_t)t0 * 3, rows * 3, vec);
+    store_staged_words(s_f, out_f + (size_t)t0 * F, rows * F, vec);
 }
 
 // positives per cloud: thread = 16 consecutive rows, one atomic per cloud run.  grid over the bank's rows.
@@ -353,10 +323,6 @@ __global__ __launch_bounds__(256) void cloud_positive_count_kernel(const int32_t
     }
     if (cnt) atomicAdd(&counts[c], cnt);
 }
-
-// launches of exclusive_scan_u32 over n words (sortscan.hip: 2048 per tile, recursive over the tile totals) and of one sort pass
-int scan_launches(size_t n) { const size_t nt = (n + 2047) / 2048; return nt > 1 ? 2 + scan_launches(nt) : 1; }
-int sort_pass_launches(size_t n) { return 2 + scan_launches(256 * ((n + 8191) / 8192)); }
 
 }  // namespace
 
@@ -480,7 +446,7 @@ extern "C" int ps_cloud_sample(ps_context* c, const float* xyz, const float* mod
         hipLaunchKernelGGL(cloud_sample_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, xyz, modalities, (int)C, labels, d_info,
                            sorted, (unsigned)N, (unsigned)total, out_xyz, out_features, out_labels, out_idx);
         PS_HIP(hipGetLastError());
-        stg.n = 1 + 8 + 3 + ((bits + 7) / 8) * sort_pass_launches(total) + 1;
+        stg.n = 1 + 8 + 3 + radix_sort_pairs_launches(total, bits) + 1;
     }
     // the device's positive counts against positives_host: a stale table is PS_ESTATE (the batch was drawn with the device's counts)
     if (c->deferred) return c->defer_status(d_status, 4 * sizeof(int), 1, c->samples++);

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "sortscan.h"
 #include "bf16_io.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -88,16 +89,6 @@ struct BkPlan {
     size_t table;  // entries (the scan runs over table + 1)
 };
 
-__device__ __forceinline__ unsigned bk_wave_inclusive_sum(unsigned v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = (unsigned)__shfl_up((int)v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // (kBkHistTiles consecutive tiles per workgroup; 4 measured slower than 1 -- 76 against 50 us at level 0: fewer, longer workgroups)
 constexpr int kBkHistTiles = 1;
 template <int TILE>
@@ -140,7 +131,7 @@ __device__ __forceinline__ unsigned bk_scan_digits(unsigned (*s)[kBkDigits], uns
     for (int w = 0; w < 4; ++w) c[w] = *reinterpret_cast<const uint2*>(&s[w][d0]);
     tot0 = c[0].x + c[1].x + c[2].x + c[3].x;
     const unsigned tot1 = c[0].y + c[1].y + c[2].y + c[3].y;
-    const unsigned inc = bk_wave_inclusive_sum(tot0 + tot1, lane);
+    const unsigned inc = wave_inclusive_sum(tot0 + tot1, lane);
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
     unsigned woff = 0;

@@ -119,13 +119,7 @@ struct TopkInsertFrom {
 template <int K>
 PS_HD void topk_insert(float (&dist)[K], int (&idx)[K], float d, int p)
 {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(PS_KNN_EXP_DISTONLY)
-    // EXPERIMENT (wrong indices, timing only): what the kernel costs when an insertion moves distances alone
-#pragma unroll
-    for (int j = K - 1; j >= 1; --j) dist[j] = __builtin_amdgcn_fmed3f(dist[j - 1], dist[j], d);
-    dist[0] = fminf(dist[0], d);
-    idx[0] = p;
-#elif defined(__HIP_DEVICE_COMPILE__) && !defined(PS_KNN_FULL_INSERT)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PS_KNN_FULL_INSERT)
     TopkInsertFrom<K, K - 1>::run(dist, idx, d, p, dist[K - 1] > d);
 #elif defined(__HIP_DEVICE_COMPILE__)
     // the list is ascending, so the new value of slot j is the MEDIAN of (dist[j-1], dist[j], d): dist[j] when d is not below it,
@@ -249,20 +243,9 @@ PS_HD bool knn_search_one(const TreeView& t, float qx, float qy, float qz, float
             // all (<= kLeafMax) point loads are issued before the first distance is needed: one memory round trip per
             // leaf instead of one per point
             float4 pv[kLeafMax];
-#ifdef PS_KNN_EXP_ONELEAFLOAD
-            // EXPERIMENT (wrong results, timing only): one record load per leaf visit instead of ten -- what the vector-memory address path costs
-            pv[0] = gload(t.pts + lf_x);
-#pragma unroll
-            for (int j = 1; j < kLeafMax; ++j) { pv[j] = pv[0]; pv[j].x += 1e-3f * j; }
-#elif defined(PS_KNN_EXP_MASKED_LEAF)
-            // EXPERIMENT: only the slots the leaf has -- a lane's record loads are one vector-memory lookup each, and a leaf holds ~7 of 10
-#pragma unroll
-            for (int j = 0; j < kLeafMax; ++j) pv[j] = lf_x + j < lf_y ? gload(t.pts + lf_x + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-#else
 #pragma unroll
             for (int j = 0; j < kLeafMax; ++j) pv[j] = gload(t.pts + lf_x + j);  // one address, ten immediate offsets: the record
             // array is padded by kLeafMax entries (TreeSetPlan::carve), slots past the leaf's end are read and ignored below
-#endif
 #pragma unroll
             for (int j = 0; j < kLeafMax; ++j) {
                 // A slot past the leaf's end gets d = FLT_MAX, which never beats the current worst.  The insertion then runs

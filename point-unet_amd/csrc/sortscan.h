@@ -12,6 +12,8 @@ namespace ps {
 size_t scan_workspace_words(size_t n);
 // out[i] = in[0] + ... + in[i-1] (mod 2^32); in and out may be the same array.  Enqueues on st, never synchronises.
 void exclusive_scan_u32(hipStream_t st, const unsigned* in, unsigned* out, size_t n, unsigned* work);
+// kernel launches exclusive_scan_u32 enqueues for n elements (for the callers' stage records)
+int scan_launches(size_t n);
 
 // workspace, in unsigned words, of radix_sort_pairs_u64 over n pairs
 size_t sort_workspace_words(size_t n);
@@ -20,5 +22,7 @@ size_t sort_workspace_words(size_t n);
 int radix_sort_pairs_u64(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, size_t n, int bits, unsigned* work);
 // the same with 32-bit keys (bits <= 32): a third less traffic per pass
 int radix_sort_pairs_u32(hipStream_t st, unsigned* k0, unsigned* k1, unsigned* v0, unsigned* v1, size_t n, int bits, unsigned* work);
+// kernel launches either sort enqueues for n pairs and `bits` key bits
+int radix_sort_pairs_launches(size_t n, int bits);
 
 }  // namespace ps

@@ -3,22 +3,13 @@
 // voxels dataPrepareBraTS keeps).  HBM-bound integer work: every pass streams its arrays once, 16 bytes per lane where the
 // layout allows, and the only cross-workgroup communication is a table of per-tile totals scanned by the next launch.
 #include "sortscan.h"
+#include "wave_ops.h"
 
 namespace ps {
 
 namespace {
 
 constexpr int kTile = 2048;  // elements per workgroup: 256 threads x 8
-
-__device__ __forceinline__ unsigned wave_inclusive_sum(unsigned v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = (unsigned)__shfl_up((int)v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
 
 // out = exclusive scan of the tile (without the tiles before it), sums[tile] = the tile's total; thread t owns eight
 // CONSECUTIVE elements (two 16-byte accesses when the tile is full)
@@ -73,6 +64,7 @@ size_t pad64(size_t n) { return (n + 63) & ~size_t(63); }
 
 constexpr int kSortTile = 8192;  // elements per workgroup of the radix passes: 256 threads x 32 (a wave owns 2048 consecutive ones)
 size_t sort_tiles_of(size_t n) { return (n + kSortTile - 1) / kSortTile; }
+int sort_passes(int bits) { return bits <= 8 ? 1 : (bits + 7) / 8; }
 
 // digit counts of one tile -> table[digit * ntiles + tile] (digit-major: its exclusive scan is, for every (digit, tile), the
 // number of keys with a smaller digit plus those with the same digit in earlier tiles = where the tile's run of that digit starts)
@@ -197,6 +189,13 @@ void exclusive_scan_u32(hipStream_t st, const unsigned* in, unsigned* out, size_
     }
 }
 
+int scan_launches(size_t n)
+{
+    if (n == 0) return 0;
+    const size_t nt = tiles_of(n);
+    return nt > 1 ? 2 + scan_launches(nt) : 1;  // the tiles, the scan of their totals, the add
+}
+
 size_t sort_workspace_words(size_t n)
 {
     const size_t table = pad64(256 * sort_tiles_of(n));
@@ -212,7 +211,7 @@ static int radix_sort_pairs(hipStream_t st, KeyT* k0, KeyT* k1, unsigned* v0, un
     unsigned* scan_work = work + pad64(table_n);
     KeyT* k[2] = {k0, k1};
     unsigned* v[2] = {v0, v1};
-    const int passes = bits <= 8 ? 1 : (bits + 7) / 8;
+    const int passes = sort_passes(bits);
     const size_t stage_bytes = (sizeof(KeyT) + sizeof(unsigned)) * kSortTile;  // the tile sorted in LDS: 64 KB (u32 keys) / 96 KB (u64)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(radix_scatter_kernel<KeyT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_bytes);
     // (a refusal shows up as a launch error, which the callers pick up with hipGetLastError)
@@ -225,6 +224,12 @@ static int radix_sort_pairs(hipStream_t st, KeyT* k0, KeyT* k1, unsigned* v0, un
         cur ^= 1;
     }
     return cur;
+}
+
+int radix_sort_pairs_launches(size_t n, int bits)
+{
+    if (n == 0) return 0;
+    return sort_passes(bits) * (2 + scan_launches(256 * sort_tiles_of(n)));  // per pass: histogram, table scan, scatter
 }
 
 int radix_sort_pairs_u64(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, size_t n, int bits, unsigned* work)

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "sample_hash.h"
+#include "sample_select.h"
 #include "sortscan.h"
 
 namespace ps {
@@ -59,16 +60,6 @@ union Bytes16 {
     uint4 q;
     uint8_t b[16];
 };
-
-__device__ __forceinline__ unsigned wave_inclusive(unsigned v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned u = (unsigned)__shfl_up((int)v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
 
 // 16 bytes of a caller's u8 volume at voxel v0 (a multiple of 16), zeros from voxel n on; one 16-byte load where the pointer allows
 __device__ __forceinline__ Bytes16 load16_u8(const uint8_t* __restrict__ p, unsigned v0, unsigned n, bool aligned)
@@ -437,10 +428,9 @@ __global__ __launch_bounds__(256) void vs_hist_kernel(const uint8_t* __restrict_
 // voxels to take and raises the status when P > N.  grid `loops`, 256 threads (thread = digit).
 __global__ __launch_bounds__(256) void vs_pick_kernel(VsState* __restrict__ st, unsigned N, int shift)
 {
-    __shared__ unsigned s_w[4];
     __shared__ unsigned s_need, s_rank;
-    const int l = blockIdx.x, d = threadIdx.x, lane = d & 63, wave = d >> 6;
-    if (d == 0) {
+    const int l = blockIdx.x;
+    if (threadIdx.x == 0) {
         const unsigned P = st->positives;
         const unsigned need = P > N ? 0u : N - P;
         if (shift == 24) {
@@ -455,19 +445,8 @@ __global__ __launch_bounds__(256) void vs_pick_kernel(VsState* __restrict__ st, 
         s_need = need;
         s_rank = st->rank[l];
     }
-    const unsigned c = st->hist[l][d];
-    st->hist[l][d] = 0;
-    const unsigned inc = wave_inclusive(c, lane);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    if (s_need == 0) return;
-    unsigned below = inc - c;
-    for (int w = 0; w < wave; ++w) below += s_w[w];
-    const unsigned rank = s_rank;
-    if (c && below <= rank && rank < below + c) {  // exactly one digit
-        st->prefix[l] |= (unsigned)d << shift;
-        st->rank[l] = rank - below;
-    }
+    unsigned left;
+    if (select_pick_digit(st->hist[l], shift, &s_need, &s_rank, &st->prefix[l], left)) st->rank[l] = left;
 }
 
 // ---- 4. compact -------------------------------------------------------------------------------------------------------------------------
@@ -587,26 +566,11 @@ __global__ __launch_bounds__(256) void vs_gather_kernel(const T* __restrict__ vo
         if (out_i) out_i[t] = (int32_t)v;
     }
     __syncthreads();
-    auto store = [&](const void* src_v, void* dst_v, unsigned count) {  // 4-byte words
-        const uint32_t* src = static_cast<const uint32_t*>(src_v);
-        uint32_t* dst = static_cast<uint32_t*>(dst_v);
-        if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            const unsigned n4 = count / 4;
-            for (unsigned k = threadIdx.x; k < n4; k += 256) reinterpret_cast<uint4*>(dst)[k] = reinterpret_cast<const uint4*>(src)[k];
-            for (unsigned k = n4 * 4 + threadIdx.x; k < count; k += 256) dst[k] = src[k];
-        } else {
-            for (unsigned k = threadIdx.x; k < count; k += 256) dst[k] = src[k];
-        }
-    };
-    if (out_xyz) store(s_x, out_xyz + (size_t)t0 * 3, rows * 3);
-    if (out_o) store(s_o, out_o + (size_t)t0 * 3, rows * 3);
+    if (out_xyz) store_staged_words(s_x, out_xyz + (size_t)t0 * 3, rows * 3);
+    if (out_o) store_staged_words(s_o, out_o + (size_t)t0 * 3, rows * 3);
 }
 
 size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-
-// launches of exclusive_scan_u32 over n words (sortscan.hip: 2048 per tile, recursive over the tile totals) and of one sort pass
-int scan_launches(size_t n) { const size_t nt = (n + 2047) / 2048; return nt > 1 ? 2 + scan_launches(nt) : 1; }
-int sort_pass_launches(size_t n) { return 2 + scan_launches(256 * ((n + 8191) / 8192)); }
 
 }  // namespace
 
@@ -731,7 +695,7 @@ extern "C" int ps_volume_sample(ps_context* c, ps_volume_sample_args* a)
                 hipLaunchKernelGGL(vs_gather_kernel<float>, ggrid, dim3(256), 0, sm, static_cast<const float*>(a->volume), m, a->label_src, sorted, n,
                                    (unsigned)total, (unsigned)a->X, (unsigned)a->Y, (unsigned)a->Z, st, a->out_xyz, a->out_features, a->out_labels,
                                    a->out_origin, a->out_idx);
-            launches += 8 + 1 + ((bits + 7) / 8) * sort_pass_launches(total) + 1;
+            launches += 8 + 1 + radix_sort_pairs_launches(total, bits) + 1;
         }
         PS_HIP(hipGetLastError());
         stg.n = launches;

@@ -1,4 +1,4 @@
-// wave_ops.h -- all-lanes reductions of a 64-lane wave without LDS traffic.
+// wave_ops.h -- all-lanes reductions of a 64-lane wave without LDS traffic, and the wave's inclusive prefix sum.
 // `x = op(x, __shfl_xor(x, o))` compiles to ds_bpermute_b32 on gfx950: an LDS-pipe round trip (~100+ cycles) per butterfly step,
 // six of them in a dependent chain per reduction.  Here the four in-row steps are DPP modifiers on the VALU instruction itself
 // (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror: each pairs complementary lane sets, which is all
@@ -39,6 +39,18 @@ __device__ __forceinline__ float wave_max(float v)
 __device__ __forceinline__ int wave_sum(int v)
 {
     return (int)wave_allreduce_u32((unsigned)v, [](unsigned a, unsigned b) { return a + b; });
+}
+
+// Inclusive prefix sum over the wave's lanes (lane = the caller's lane id).  Six ds_bpermute steps, not DPP row_shr / row_bcast: the sort
+// (sortscan.hip) and the inverse index (invidx.hip) were measured with exactly this sequence, and a DPP form has not been.
+__device__ __forceinline__ unsigned wave_inclusive_sum(unsigned v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned u = (unsigned)__shfl_up((int)v, o);
+        if (lane >= o) v += u;
+    }
+    return v;
 }
 
 // max / sum over the two 32-lane halves only (attpool32.hip, attpool32b.hip: a column's softmax terms live in lanes l and l ^ 32)

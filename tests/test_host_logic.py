@@ -318,11 +318,11 @@ def test_package_import_sets_the_pipeline_environment_contract():
 def test_the_default_library_never_reads_the_environment():
     """VERDICT r5 item 6: the A/B knobs of profiles/tools/* are ONE struct (csrc/common.h, ps::Tuning) that only a library built with
     -DPS_TUNING_ENV fills from PS_* variables, once, in ps_create.  The default build holds constants: every getenv in csrc/ sits inside an
-    #ifdef of an experiment macro, there is no function-static cache of a knob, and the shipped .so does not even contain the variables'
+    #ifdef PS_TUNING_ENV (the one macro allowed: the rejected K-NN experiments and their own macros have left csrc/), there is no function-static cache of a knob, and the shipped .so does not even contain the variables'
     names -- PS_INV_BUCKET=0 in the environment of the default build cannot change what it runs."""
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "point-unet_amd", "csrc")
-    allowed_macros = ("PS_TUNING_ENV", "PS_KNN_REFILL_EXP", "PS_KNN_PROF")
+    allowed_macros = ("PS_TUNING_ENV",)
     for name in sorted(os.listdir(csrc)):
         if not name.endswith((".hip", ".h")):
             continue
