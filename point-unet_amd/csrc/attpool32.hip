@@ -20,28 +20,18 @@
 // LDS tile pitch = H + 4 floats = 4 x odd: conflict-free for the b128 reads and writes above (MI355X_MICROARCH.md, LDS).
 //
 // Bound: fp32 MFMA.  Per point: (d/32) * (h/2) score MFMAs of 64 cycles per pair of points, e.g. d = 128: 128 + 64 (mlp2) + 10.
-#include "attpool.h"
-#include "mfma_tile.h"
-#include "wave_ops.h"
+// The tile frame -- walk, geometry prefetch, neighbour-row offsets, bias seed, tile store, pooling of a score block -- is att32_tile.h's,
+// one text shared with the split-bf16 kernels of attpool32b.hip, which are judged against this one.
+#include "att32_tile.h"
 
 namespace ps {
 
-struct Att32Args {
-    const float* xyz;
-    const int32_t* idx;
-    const int32_t* order;
-    const float* fg;
-    const float* w1; const float* b1;  // LocSE mlp1: [H/32][5][64] image
-    const float* w2; const float* b2;  // LFA mlp2:   pack_p32 image of [H, H] (stage 2)
-    const float* wb;                   // Wfc[H:, :]: pack_p32 image of [H, D]
-    float* agg;
-    int n_total, n_cloud;
-};
+struct Att32Args : Att32ArgsT<float> {};  // w1: [H/32][5][64] image (pack_p32_locse); w2, wb: pack_p32 images
 
 template <int D, int STAGE, int KN, int WAVES, bool SPLITN>
 __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)
 {
-    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN, RP = 16 / PPT;
+    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN;
     constexpr int CBH = H / 32, CBD = D / 32, NQ = H / 8;
     constexpr int W1F = CBH * 5 * 64, W2F = STAGE == 2 ? H * H : 0, WBF = H * D;
     constexpr int TILE = 32 * PITCH;
@@ -76,78 +66,25 @@ __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)
         else wave_lds_sync();
     };
 
-    // tiles walk a contiguous eighth of the points per XCD (PointWalk of attpool.hip), PPT consecutive points per tile
-    const int per_xcd = ((((a.n_total + 7) >> 3) + PPT - 1) / PPT) * PPT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int tiles_per_wg = SPLITN ? 1 : WAVES;
-    const int t_end = min(a.n_total, (xcd + 1) * per_xcd);
-    // Geometry of a tile = three dependent gathers (leaf order -> neighbour index -> coordinates): the NEXT tile's chain is issued
-    // in pieces between the phases of the current tile (gstage 0..2), so none of its latency is exposed.
-    const int t_first = xcd * per_xcd + (slot * tiles_per_wg + (SPLITN ? 0 : wave)) * PPT, t_step = slots * tiles_per_wg * PPT;
-    int n_pp[PPT], n_nl = 0;
-    float n_c[3], n_n[3];
-    // (the kernel is VALU-issue bound at d <= 128 -- one VALU instruction per SIMD every four cycles --, so the index arithmetic is
-    //  kept lean: no integer division for a single cloud, 24-bit multiplies, 32-bit element offsets from uniform bases)
-    const bool one_cloud = a.n_total == a.n_cloud;
-    auto cloud_base = [&](int row) { return one_cloud ? 0 : (row / a.n_cloud) * a.n_cloud; };
-    auto gstage = [&](int st, int t0n) {
-        if (t0n >= t_end) return;
-        if (st == 0) {
-#pragma unroll
-            for (int i = 0; i < PPT; ++i) {
-                const int t = min(t0n + i, t_end - 1);
-                n_pp[i] = a.order ? cloud_base(t) + a.order[t] : t;
-            }
-        } else if (st == 1) {
-            const unsigned p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl = a.idx[p * (unsigned)KN + (unsigned)(c32 & (KN - 1))];
-            const float* cp = a.xyz + 3u * p;
-            n_c[0] = cp[0]; n_c[1] = cp[1]; n_c[2] = cp[2];
-        } else {
-            const int p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl += cloud_base(p);
-            const float* np = a.xyz + 3u * (unsigned)n_nl;
-            n_n[0] = np[0]; n_n[1] = np[1]; n_n[2] = np[2];
-        }
-    };
-    gstage(0, t_first);
-    gstage(1, t_first);
-    gstage(2, t_first);
+    constexpr int TPW = SPLITN ? 1 : WAVES;
+    const int tiw = SPLITN ? 0 : wave;
+#include "att32_tile_walk.h"
     for (int t0 = t_first; t0 < t_end; t0 += t_step) {
-        // ---- geometry of this lane's row: (point t0 + row / KN, neighbour row % KN) ----
-        int pp[PPT];
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) pp[i] = n_pp[i];
-        const int nbr = n_nl;
-        const float cx = n_c[0], cy = n_c[1], cz = n_c[2];
-        const float nx = n_n[0], ny = n_n[1], nz = n_n[2];
-        const float rx = cx - nx, ry = cy - ny, rz = cz - nz;
-        const float dis = __builtin_amdgcn_sqrtf(rx * rx + ry * ry + rz * rz);
-        // enc10 = [dis, rx, ry, rz, cx, cy, cz, nx, ny, nz]; MFMA step s takes elements 2s (lanes 0-31) and 2s + 1 (lanes 32-63)
+#include "att32_tile_row.h"
+        // MFMA step s takes elements 2s (lanes 0-31) and 2s + 1 (lanes 32-63) of enc10
         float e[5];
-        e[0] = hl ? rx : dis; e[1] = hl ? rz : ry; e[2] = hl ? cy : cx; e[3] = hl ? nx : cz; e[4] = hl ? nz : ny;
+        e[0] = hl ? enc[1] : enc[0]; e[1] = hl ? enc[3] : enc[2]; e[2] = hl ? enc[5] : enc[4]; e[3] = hl ? enc[7] : enc[6]; e[4] = hl ? enc[9] : enc[8];
         if (hl == 0 && (!SPLITN || wave == 0)) NB[c32] = nbr;
         gstage(0, t0 + t_step);
 
         // ---- LFA mlp1 (transposed: C[channel][row]): f_xyz1 = lrelu(enc10 . W1 + b1) -> T1 ----
 #pragma unroll
         for (int cb = cb0; cb < CBH; cb += CBSTEP) {
-            f32x16 acc;  // seeded with the bias (register r of this lane = channel 32 cb + 8 (r >> 2) + 4 hl + (r & 3))
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const float4 bb = *reinterpret_cast<const float4*>(b1 + cb * 32 + g4 * 8 + hl * 4);
-                acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
-            }
+            f32x16 acc;
+            ATT32_BIAS_SEED(acc, b1, cb);
 #pragma unroll
             for (int s = 0; s < 5; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[(cb * 5 + s) * 64 + lane], e[s], acc, 0, 0, 0);
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int ch = cb * 32 + g4 * 8 + hl * 4;
-                float4 o;
-                o.x = leaky02(acc[4 * g4]); o.y = leaky02(acc[4 * g4 + 1]);
-                o.z = leaky02(acc[4 * g4 + 2]); o.w = leaky02(acc[4 * g4 + 3]);
-                *reinterpret_cast<float4*>(T1 + c32 * PITCH + ch) = o;
-            }
+            ATT32_STORE_BLOCK(T1 + c32 * PITCH, cb, leaky02, acc);
         }
         phase_sync();
         gstage(1, t0 + t_step);
@@ -158,11 +95,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)
 #pragma unroll
             for (int cb = cb0; cb < CBH; cb += CBSTEP) {
                 f32x16& acc = acc2[SPLITN ? 0 : cb];
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {  // seeded with the bias
-                    const float4 bb = *reinterpret_cast<const float4*>(b2 + cb * 32 + g4 * 8 + hl * 4);
-                    acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
-                }
+                ATT32_BIAS_SEED(acc, b2, cb);
                 const float4* wq = reinterpret_cast<const float4*>(w2) + (size_t)cb * NQ * 64 + lane;
                 const float* xr = T1 + c32 * PITCH + 4 * hl;
 #pragma unroll 8
@@ -174,54 +107,26 @@ __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw.z, bx.z, acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw.w, bx.w, acc, 0, 0, 0);
                 }
-                if constexpr (SPLITN) {
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int ch = cb * 32 + g4 * 8 + hl * 4;
-                        float4 o;
-                        o.x = leaky02(acc[4 * g4]); o.y = leaky02(acc[4 * g4 + 1]);
-                        o.z = leaky02(acc[4 * g4 + 2]); o.w = leaky02(acc[4 * g4 + 3]);
-                        *reinterpret_cast<float4*>(T2 + c32 * PITCH + ch) = o;
-                    }
-                }
+                if constexpr (SPLITN) { ATT32_STORE_BLOCK(T2 + c32 * PITCH, cb, leaky02, acc); }
             }
             if constexpr (!SPLITN) {
                 wave_lds_sync();  // every read of the mlp1 tile precedes the writes below (DS operations of a wave execute in order)
 #pragma unroll
-                for (int cb = 0; cb < CBH; ++cb)
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int ch = cb * 32 + g4 * 8 + hl * 4;
-                        float4 o;
-                        o.x = leaky02(acc2[cb][4 * g4]); o.y = leaky02(acc2[cb][4 * g4 + 1]);
-                        o.z = leaky02(acc2[cb][4 * g4 + 2]); o.w = leaky02(acc2[cb][4 * g4 + 3]);
-                        *reinterpret_cast<float4*>(T1 + c32 * PITCH + ch) = o;
-                    }
+                for (int cb = 0; cb < CBH; ++cb) { ATT32_STORE_BLOCK(T1 + c32 * PITCH, cb, leaky02, acc2[cb]); }
             }
             phase_sync();
         }
         const float* TX = T2;
 
         // ---- scores (C[row][channel]) = G[nbr] + f_xyz . Wfc[H:, :], softmax over the K rows of a point, weighted sum ----
-        // accumulator register r of this lane is row (r & 3) + 8 * (r >> 2) + 4 * hl of the tile
-        // byte offset of (that row's neighbour, this lane's column of the wave's first column block) in fg: the column blocks that
-        // follow are compile-time byte offsets of the loads (instruction immediates): no address arithmetic per gather
-        unsigned off[16];
-        {
-            const unsigned col0 = (unsigned)(cb0 * 32 + c32) * 4u;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int4 nb4 = *reinterpret_cast<const int4*>(NB + 8 * g4 + 4 * hl);
-                off[4 * g4] = __umul24(nb4.x, LDF * 4u) + col0; off[4 * g4 + 1] = __umul24(nb4.y, LDF * 4u) + col0;  // rows < 2^24 (att_pool32_fits)
-                off[4 * g4 + 2] = __umul24(nb4.z, LDF * 4u) + col0; off[4 * g4 + 3] = __umul24(nb4.w, LDF * 4u) + col0;
-            }
-        }
+        unsigned off[16];  // of this lane's column of the wave's first column block
+        ATT32_ROW_OFFSETS(off, NB, LDF, (unsigned)(cb0 * 32 + c32) * 4u);
         const char* fgb = reinterpret_cast<const char*>(a.fg);
         // The gathers of column block i + 1 (G rows for the scores, f rows for the values) are issued before the MFMAs of block i
         // and consumed after them: their latency hides behind ~2 000 cycles of matrix work.  G is ADDED after the product
         // (instead of seeding the accumulator) for the same reason.
         constexpr int NCB = CBD / CBSTEP;
-        f32x2 gq[2][8], v[2][8];  // register pairs: the softmax arithmetic below runs on v_pk_*_f32 (two scores per instruction)
+        f32x2 gq[2][8], v[2][8];
         auto gather = [&](int i, f32x2 (&gdst)[8], f32x2 (&vdst)[8]) {
             const int rel = i * CBSTEP * 32 * 4;  // compile-time (the loop below is fully unrolled)
 #pragma unroll
@@ -252,37 +157,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32_kernel(Att32Args a)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax.w, bw.w, acc, 0, 0, 0);
             }
             f32x2 (&vv)[8] = v[i & 1];
-            if (cb * 32 >= H) {  // values = f_xyz (LDS tile)
-                const float* tv = TX + (cb * 32 - H + c32) + 4 * hl * PITCH;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) vv[r >> 1][r & 1] = tv[((r & 3) + 8 * (r >> 2)) * PITCH];
-            }
-            // the Wfc[H:, :] image is pre-multiplied by log2(e) (pack_p32 call in randla.hip), the gathered G joins with the same factor:
-            // softmax(s) = exp2(s' - max s') with s' = s log2(e) -- one multiply per score less than expf
-            f32x2 sc[8];
-            const f32x2 l2e = {1.4426950408889634f, 1.4426950408889634f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sc[j] = __builtin_elementwise_fma(gq[i & 1][j], l2e, f32x2{acc[2 * j], acc[2 * j + 1]});
-            constexpr int PP = RP / 2;  // register pairs per point
-#pragma unroll
-            for (int pi = 0; pi < PPT; ++pi) {
-                float m = fmaxf(sc[pi * PP][0], sc[pi * PP][1]);
-#pragma unroll
-                for (int j = 1; j < PP; ++j) m = fmaxf(m, fmaxf(sc[pi * PP + j][0], sc[pi * PP + j][1]));
-                m = swap32_max(m);
-                const f32x2 mm = {m, m};
-                f32x2 ssum2 = {0.f, 0.f}, num2 = {0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < PP; ++j) {
-                    const f32x2 dd = sc[pi * PP + j] - mm;
-                    const f32x2 ex = {__builtin_amdgcn_exp2f(dd[0]), __builtin_amdgcn_exp2f(dd[1])};
-                    ssum2 += ex;
-                    num2 = __builtin_elementwise_fma(ex, vv[pi * PP + j], num2);
-                }
-                const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
-                const float num = swap32_sum(num2[0] + num2[1]);
-                if (hl == 0 && t0 + pi < t_end) a.agg[__umul24(pp[pi], D) + (unsigned)(cb * 32 + c32)] = num * __builtin_amdgcn_rcpf(ssum);
-            }
+            const f32x2 (&gs)[8] = gq[i & 1];
+#include "att32_tile_pool.h"
         }
         phase_sync();  // the tile and the neighbour rows are overwritten by the next tile
     }
@@ -357,17 +233,9 @@ bool att_pool32_fits(const AttStage& s)
 
 int att_pool32_stage(ps_context* c, const AttStage& s)
 {
-    Att32Args a;
-    a.xyz = s.xyz; a.idx = s.idx; a.order = s.order; a.fg = s.fg;
-    a.w1 = s.p32->w1; a.b1 = s.lfa1->bias;
-    a.w2 = s.lfa2 ? s.p32->w2 : nullptr; a.b2 = s.lfa2 ? s.lfa2->bias : nullptr;
-    a.wb = s.lfa2 ? s.p32->wb2 : s.p32->wb1;
-    a.agg = s.agg;
-    a.n_total = (int)s.n_total; a.n_cloud = (int)s.n_cloud;
     if (s.n_total <= 0) return PS_OK;
-    const int stage = s.lfa2 ? 2 : 1;
-    if (s.k == 16) return stage == 1 ? dispatch32<1, 16>(c, s.d, a) : dispatch32<2, 16>(c, s.d, a);
-    return stage == 1 ? dispatch32<1, 32>(c, s.d, a) : dispatch32<2, 32>(c, s.d, a);
+    const Att32Args a = att32_args<Att32Args>(s, s.p32->w1, s.p32->w2, s.p32->wb1, s.p32->wb2);
+    return att32_stage_k(s, [&](auto stage, auto k) { return dispatch32<stage(), k()>(c, s.d, a); });
 }
 
 }  // namespace ps

@@ -18,25 +18,15 @@
 //   * weights are stored as three planes of eight bfloat16 per lane (16-byte reads, [block][chunk][plane][lane]).
 // d = 64 and 128 (levels 1-2): weights resident in LDS, a wave per tile of two points (att32b_kernel);
 // d = 256 and 512 (levels 3-4): a workgroup per tile, weight planes streamed from L2 (att32s_kernel).
+// What does not change is att32_tile.h's, one text for the three kernels: the tile walk and the geometry prefetch, the neighbour-row
+// offsets, bias seed and tile store of a transposed block, and the pooling of a score block.
 // The split, the planes and the six-product MFMA are b3_ops.h's (one definition for all bf16x3 kernels); swap32_* are wave_ops.h's.
-#include "attpool.h"
+#include "att32_tile.h"
 #include "b3_ops.h"
-#include "mfma_tile.h"
-#include "wave_ops.h"
 
 namespace ps {
 
-struct Att32bArgs {
-    const float* xyz;
-    const int32_t* idx;
-    const int32_t* order;
-    const float* fg;
-    const uint4* w1; const float* b1;  // LocSE mlp1: pack_b3_locse image
-    const uint4* w2; const float* b2;  // LFA mlp2: pack_b3 image of [H, H] (stage 2)
-    const uint4* wb;                   // Wfc[H:, :] (times log2 e): pack_b3 image of [H, D]
-    float* agg;
-    int n_total, n_cloud;
-};
+struct Att32bArgs : Att32ArgsT<uint4> {};  // w1: pack_b3_locse image; w2, wb: pack_b3 images
 
 __device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int lane)
 {
@@ -50,7 +40,7 @@ __device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int 
 template <int D, int STAGE, int KN, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 {
-    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN, RP = 16 / PPT;
+    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN;
     constexpr int CBH = H / 32, CBD = D / 32, NQ = H / 16;
     constexpr int W1Q = CBH * 3 * 64, W2Q = STAGE == 2 ? CBH * NQ * 3 * 64 : 0, WBQ = CBD * NQ * 3 * 64;  // uint4 counts
     constexpr int TILE = 32 * PITCH;
@@ -77,65 +67,18 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
     const uint4 *w1 = Wq, *w2 = Wq + W1Q, *wb = Wq + W1Q + W2Q;
     const float *b1 = bias, *b2 = bias + H;
 
-    // tiles walk a contiguous eighth of the points per XCD, PPT consecutive points per tile (as attpool32.hip)
-    const int per_xcd = ((((a.n_total + 7) >> 3) + PPT - 1) / PPT) * PPT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int t_end = min(a.n_total, (xcd + 1) * per_xcd);
-    const int t_first = xcd * per_xcd + (slot * WAVES + wave) * PPT, t_step = slots * WAVES * PPT;
-    int n_pp[PPT], n_nl = 0;
-    float n_c[3], n_n[3];
-    const bool one_cloud = a.n_total == a.n_cloud;
-    auto cloud_base = [&](int row) { return one_cloud ? 0 : (row / a.n_cloud) * a.n_cloud; };
-    auto gstage = [&](int st, int t0n) {  // the NEXT tile's three dependent gathers, issued in pieces between the phases of this one
-        if (t0n >= t_end) return;
-        if (st == 0) {
-#pragma unroll
-            for (int i = 0; i < PPT; ++i) {
-                const int t = min(t0n + i, t_end - 1);
-                n_pp[i] = a.order ? cloud_base(t) + a.order[t] : t;
-            }
-        } else if (st == 1) {
-            const unsigned p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl = a.idx[p * (unsigned)KN + (unsigned)(c32 & (KN - 1))];
-            const float* cp = a.xyz + 3u * p;
-            n_c[0] = cp[0]; n_c[1] = cp[1]; n_c[2] = cp[2];
-        } else {
-            const int p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl += cloud_base(p);
-            const float* np = a.xyz + 3u * (unsigned)n_nl;
-            n_n[0] = np[0]; n_n[1] = np[1]; n_n[2] = np[2];
-        }
-    };
-    gstage(0, t_first);
-    gstage(1, t_first);
-    gstage(2, t_first);
+    constexpr int TPW = WAVES;
+    const int tiw = wave;
+#include "att32_tile_walk.h"
     for (int t0 = t_first; t0 < t_end; t0 += t_step) {
-        int pp[PPT];
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) pp[i] = n_pp[i];
-        const int nbr = n_nl;
-        const float cx = n_c[0], cy = n_c[1], cz = n_c[2];
-        const float nx = n_n[0], ny = n_n[1], nz = n_n[2];
-        const float rx = cx - nx, ry = cy - ny, rz = cz - nz;
-        const float dis = __builtin_amdgcn_sqrtf(rx * rx + ry * ry + rz * rz);
-        // enc10 = [dis, rx, ry, rz, cx, cy, cz, nx | ny, nz]: the lower lane half holds K values 0..7, the upper 8..15 (10.. are zero)
-        const float ev[8] = {hl ? ny : dis, hl ? nz : rx, hl ? 0.f : ry, hl ? 0.f : rz, hl ? 0.f : cx, hl ? 0.f : cy, hl ? 0.f : cz, hl ? 0.f : nx};
+#include "att32_tile_row.h"
+        const float ev[8] = ATT32_LOCSE_K16(enc);
         const B3Planes E = b3_split8<3>(ev);
         if (hl == 0) NB[c32] = nbr;
         gstage(0, t0 + t_step);
         wave_lds_sync();
-        // byte offset of (row r's neighbour, this lane's column of the first column block) in fg; the column blocks that follow are
-        // compile-time byte offsets of the loads.  accumulator register r of a score tile is row (r & 3) + 8 * (r >> 2) + 4 * hl.
-        unsigned off[16];
-        {
-            const unsigned col0 = (unsigned)c32 * 4u;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int4 nb4 = *reinterpret_cast<const int4*>(NB + 8 * g4 + 4 * hl);
-                off[4 * g4] = __umul24(nb4.x, LDF * 4u) + col0; off[4 * g4 + 1] = __umul24(nb4.y, LDF * 4u) + col0;
-                off[4 * g4 + 2] = __umul24(nb4.z, LDF * 4u) + col0; off[4 * g4 + 3] = __umul24(nb4.w, LDF * 4u) + col0;
-            }
-        }
+        unsigned off[16];  // of this lane's column of the first column block
+        ATT32_ROW_OFFSETS(off, NB, LDF, (unsigned)c32 * 4u);
         const char* fgb = reinterpret_cast<const char*>(a.fg);
         f32x2 gq[2][8], v[2][8];
         auto gather = [&](int i, f32x2 (&gdst)[8], f32x2 (&vdst)[8]) {
@@ -155,11 +98,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 #pragma unroll
         for (int cb = 0; cb < CBH; ++cb) {
             f32x16 acc;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const float4 bb = *reinterpret_cast<const float4*>(b1 + cb * 32 + g4 * 8 + hl * 4);
-                acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
-            }
+            ATT32_BIAS_SEED(acc, b1, cb);
             acc = b3_mfma6<3>(load_planes(w1, cb, lane), E, acc);
 #pragma unroll
             for (int r = 0; r < 16; ++r) f1[cb][r] = leaky02(acc[r]);
@@ -173,12 +112,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
             hi = b3_split8<3>(x1);
         };
         auto store_block = [&](const f32x16& f, int cb) {  // -> fp32 tile (value reads of the weighted sum)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                float4 o;
-                o.x = f[4 * g4]; o.y = f[4 * g4 + 1]; o.z = f[4 * g4 + 2]; o.w = f[4 * g4 + 3];
-                *reinterpret_cast<float4*>(T1 + c32 * PITCH + cb * 32 + g4 * 8 + hl * 4) = o;
-            }
+            ATT32_STORE_BLOCK(T1 + c32 * PITCH, cb, , f);
         };
 #pragma unroll
         for (int cb = 0; cb < CBH; ++cb) split_block(f1[cb], P[2 * cb], P[2 * cb + 1]);
@@ -191,11 +125,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 #pragma unroll
             for (int cb = 0; cb < CBH; ++cb) {
                 f32x16 acc;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const float4 bb = *reinterpret_cast<const float4*>(b2 + cb * 32 + g4 * 8 + hl * 4);
-                    acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
-                }
+                ATT32_BIAS_SEED(acc, b2, cb);
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(load_planes(w2, cb * NQ + q, lane), P[q], acc);
 #pragma unroll
@@ -221,35 +151,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(P[q], load_planes(wb, cb * NQ + q, lane), acc);
             f32x2 (&vv)[8] = v[cb & 1];
-            if (cb * 32 >= H) {  // values = f_xyz (LDS tile)
-                const float* tv = TX + (cb * 32 - H + c32) + 4 * hl * PITCH;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) vv[r >> 1][r & 1] = tv[((r & 3) + 8 * (r >> 2)) * PITCH];
-            }
-            f32x2 sc[8];
-            const f32x2 l2e = {1.4426950408889634f, 1.4426950408889634f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sc[j] = __builtin_elementwise_fma(gq[cb & 1][j], l2e, f32x2{acc[2 * j], acc[2 * j + 1]});
-            constexpr int PP = RP / 2;  // register pairs per point
-#pragma unroll
-            for (int pi = 0; pi < PPT; ++pi) {
-                float m = fmaxf(sc[pi * PP][0], sc[pi * PP][1]);
-#pragma unroll
-                for (int j = 1; j < PP; ++j) m = fmaxf(m, fmaxf(sc[pi * PP + j][0], sc[pi * PP + j][1]));
-                m = swap32_max(m);
-                const f32x2 mm = {m, m};
-                f32x2 ssum2 = {0.f, 0.f}, num2 = {0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < PP; ++j) {
-                    const f32x2 dd = sc[pi * PP + j] - mm;
-                    const f32x2 ex = {__builtin_amdgcn_exp2f(dd[0]), __builtin_amdgcn_exp2f(dd[1])};
-                    ssum2 += ex;
-                    num2 = __builtin_elementwise_fma(ex, vv[pi * PP + j], num2);
-                }
-                const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
-                const float num = swap32_sum(num2[0] + num2[1]);
-                if (hl == 0 && t0 + pi < t_end) a.agg[__umul24(pp[pi], D) + (unsigned)(cb * 32 + c32)] = num * __builtin_amdgcn_rcpf(ssum);
-            }
+            const f32x2 (&gs)[8] = gq[cb & 1];
+#include "att32_tile_pool.h"
         }
         wave_lds_sync();  // the tile and the neighbour rows are overwritten by the next tile
     }
@@ -263,7 +166,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 template <int D, int STAGE, int KN, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
 {
-    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN, RP = 16 / PPT;
+    constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN;
     constexpr int CBH = H / 32, CBD = D / 32, NQ = H / 16;
     constexpr int PLQ = NQ * 3 * 64;  // uint4s of one set of operand planes
     constexpr int NB_H = CBH / WAVES, NB_D = CBD / WAVES;  // blocks per wave
@@ -276,43 +179,14 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
     int* NB = reinterpret_cast<int*>(smem);
     uint4* PA = reinterpret_cast<uint4*>(smem + 32);
     uint4* PB = STAGE == 2 ? PA + PLQ : PA;
-    float* TV = reinterpret_cast<float*>(PB + PLQ);
+    float* TX = reinterpret_cast<float*>(PB + PLQ);
 
-    const int per_xcd = ((((a.n_total + 7) >> 3) + PPT - 1) / PPT) * PPT;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int t_end = min(a.n_total, (xcd + 1) * per_xcd);
-    const int t_first = xcd * per_xcd + slot * PPT, t_step = slots * PPT;
-    int n_pp[PPT], n_nl = 0;
-    float n_c[3], n_n[3];
-    const bool one_cloud = a.n_total == a.n_cloud;
-    auto cloud_base = [&](int row) { return one_cloud ? 0 : (row / a.n_cloud) * a.n_cloud; };
-    auto gstage = [&](int st, int t0n) {
-        if (t0n >= t_end) return;
-        if (st == 0) {
-#pragma unroll
-            for (int i = 0; i < PPT; ++i) {
-                const int t = min(t0n + i, t_end - 1);
-                n_pp[i] = a.order ? cloud_base(t) + a.order[t] : t;
-            }
-        } else if (st == 1) {
-            const unsigned p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl = a.idx[p * (unsigned)KN + (unsigned)(c32 & (KN - 1))];
-            const float* cp = a.xyz + 3u * p;
-            n_c[0] = cp[0]; n_c[1] = cp[1]; n_c[2] = cp[2];
-        } else {
-            const int p = PPT == 2 ? (c32 >= KN ? n_pp[PPT - 1] : n_pp[0]) : n_pp[0];
-            n_nl += cloud_base(p);
-            const float* np = a.xyz + 3u * (unsigned)n_nl;
-            n_n[0] = np[0]; n_n[1] = np[1]; n_n[2] = np[2];
-        }
-    };
-    auto seed = [&](const float* b, int cb) {
+    constexpr int TPW = 1;  // the waves of a workgroup share one tile
+    const int tiw = 0;
+#include "att32_tile_walk.h"
+    auto seed = [&](const float* b, int cb) {  // (as a lambda: written out in place this kernel compiles to other code)
         f32x16 acc;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 bb = *reinterpret_cast<const float4*>(b + cb * 32 + g4 * 8 + hl * 4);
-            acc[4 * g4] = bb.x; acc[4 * g4 + 1] = bb.y; acc[4 * g4 + 2] = bb.z; acc[4 * g4 + 3] = bb.w;
-        }
+        ATT32_BIAS_SEED(acc, b, cb);
         return acc;
     };
     // LeakyReLU of a transposed block -> its two chunks of operand planes (LDS) and, when asked, the fp32 value tile
@@ -326,17 +200,14 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             planes[((2 * cb) * 3 + pl) * 64 + lane] = lo.p[pl];
             planes[((2 * cb + 1) * 3 + pl) * 64 + lane] = hi.p[pl];
         }
-        if (values) {
+        if (values) {  // (ATT32_STORE_BLOCK from x0 | x1)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 const float* x = g4 < 2 ? x0 + 4 * g4 : x1 + 4 * (g4 - 2);
-                *reinterpret_cast<float4*>(TV + c32 * PITCH + cb * 32 + g4 * 8 + hl * 4) = make_float4(x[0], x[1], x[2], x[3]);
+                *reinterpret_cast<float4*>(TX + c32 * PITCH + cb * 32 + g4 * 8 + hl * 4) = make_float4(x[0], x[1], x[2], x[3]);
             }
         }
     };
-    gstage(0, t_first);
-    gstage(1, t_first);
-    gstage(2, t_first);
     static_assert(NB_H == 1, "att32s: one transposed block per wave");
     const B3Planes W1 = load_planes(a.w1, wave, lane);  // this wave's LocSE block: resident for the whole kernel
     const f32x16 seed1 = seed(a.b1, wave);
@@ -344,15 +215,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
     constexpr int PD2 = STAGE == 2 ? (D >= 512 ? 4 : 8) : 1;  // mlp2-weight chunks in flight (measured: all 8 at d = 256, 4 at d = 512)
     const int cbA = wave, cbB = wave + WAVES;
     for (int t0 = t_first; t0 < t_end; t0 += t_step) {
-        int pp[PPT];
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) pp[i] = n_pp[i];
-        const int nbr = n_nl;
-        const float cx = n_c[0], cy = n_c[1], cz = n_c[2];
-        const float nx = n_n[0], ny = n_n[1], nz = n_n[2];
-        const float rx = cx - nx, ry = cy - ny, rz = cz - nz;
-        const float dis = __builtin_amdgcn_sqrtf(rx * rx + ry * ry + rz * rz);
-        const float ev[8] = {hl ? ny : dis, hl ? nz : rx, hl ? 0.f : ry, hl ? 0.f : rz, hl ? 0.f : cx, hl ? 0.f : cy, hl ? 0.f : cz, hl ? 0.f : nx};
+#include "att32_tile_row.h"
+        const float ev[8] = ATT32_LOCSE_K16(enc);
         const B3Planes E = b3_split8<3>(ev);
         if (hl == 0 && wave == 0) NB[c32] = nbr;
         gstage(0, t0 + t_step);
@@ -375,15 +239,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         gstage(1, t0 + t_step);
         // neighbour-row offsets and the gathers of this wave's two score blocks (they travel under the products below)
         unsigned off[16];
-        {
-            const unsigned col0 = (unsigned)(wave * 32 + c32) * 4u;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int4 nb4 = *reinterpret_cast<const int4*>(NB + 8 * g4 + 4 * hl);
-                off[4 * g4] = __umul24(nb4.x, LDF * 4u) + col0; off[4 * g4 + 1] = __umul24(nb4.y, LDF * 4u) + col0;
-                off[4 * g4 + 2] = __umul24(nb4.z, LDF * 4u) + col0; off[4 * g4 + 3] = __umul24(nb4.w, LDF * 4u) + col0;
-            }
-        }
+        ATT32_ROW_OFFSETS(off, NB, LDF, (unsigned)(wave * 32 + c32) * 4u);
         const char* fgb = reinterpret_cast<const char*>(a.fg);
         if constexpr (STAGE == 2) {
             // ---- LFA mlp2 (transposed): weights (A) stream from L2 PD2 chunks ahead, f_xyz1's planes (B) come from LDS ----
@@ -447,35 +303,8 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             const int cb = wave + i * WAVES;
             const f32x16& acc = i == 0 ? accA : accB;
             f32x2 (&vv)[8] = v[i];
-            if (cb * 32 >= H) {  // values = f_xyz (LDS tile)
-                const float* tv = TV + (cb * 32 - H + c32) + 4 * hl * PITCH;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) vv[r >> 1][r & 1] = tv[((r & 3) + 8 * (r >> 2)) * PITCH];
-            }
-            f32x2 sc[8];
-            const f32x2 l2e = {1.4426950408889634f, 1.4426950408889634f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sc[j] = __builtin_elementwise_fma(gq[i][j], l2e, f32x2{acc[2 * j], acc[2 * j + 1]});
-            constexpr int PP = RP / 2;
-#pragma unroll
-            for (int pi = 0; pi < PPT; ++pi) {
-                float m = fmaxf(sc[pi * PP][0], sc[pi * PP][1]);
-#pragma unroll
-                for (int j = 1; j < PP; ++j) m = fmaxf(m, fmaxf(sc[pi * PP + j][0], sc[pi * PP + j][1]));
-                m = swap32_max(m);
-                const f32x2 mm = {m, m};
-                f32x2 ssum2 = {0.f, 0.f}, num2 = {0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < PP; ++j) {
-                    const f32x2 dd = sc[pi * PP + j] - mm;
-                    const f32x2 ex = {__builtin_amdgcn_exp2f(dd[0]), __builtin_amdgcn_exp2f(dd[1])};
-                    ssum2 += ex;
-                    num2 = __builtin_elementwise_fma(ex, vv[pi * PP + j], num2);
-                }
-                const float ssum = swap32_sum(ssum2[0] + ssum2[1]);
-                const float num = swap32_sum(num2[0] + num2[1]);
-                if (hl == 0 && t0 + pi < t_end) a.agg[__umul24(pp[pi], D) + (unsigned)(cb * 32 + c32)] = num * __builtin_amdgcn_rcpf(ssum);
-            }
+            const f32x2 (&gs)[8] = gq[i];
+#include "att32_tile_pool.h"
         }
         __syncthreads();  // planes, value tile and neighbour rows are overwritten by the next tile
     }
@@ -557,27 +386,12 @@ bool att_pool32b_fits(const AttStage& s)
 
 int att_pool32b_stage(ps_context* c, const AttStage& s)
 {
-    Att32bArgs a;
-    a.xyz = s.xyz; a.idx = s.idx; a.order = s.order; a.fg = s.fg;
-    a.w1 = reinterpret_cast<const uint4*>(s.p32->w1b); a.b1 = s.lfa1->bias;
-    a.w2 = s.lfa2 ? reinterpret_cast<const uint4*>(s.p32->w2b) : nullptr; a.b2 = s.lfa2 ? s.lfa2->bias : nullptr;
-    a.wb = reinterpret_cast<const uint4*>(s.lfa2 ? s.p32->wb2b : s.p32->wb1b);
-    a.agg = s.agg;
-    a.n_total = (int)s.n_total; a.n_cloud = (int)s.n_cloud;
     if (s.n_total <= 0) return PS_OK;
-    const int stage = s.lfa2 ? 2 : 1;
-#define PS_A32B(DD)                                                                                                      \
-    if (s.k == 16) return stage == 1 ? launch_att32b<DD, 1, 16>(c, a) : launch_att32b<DD, 2, 16>(c, a);                  \
-    return stage == 1 ? launch_att32b<DD, 1, 32>(c, a) : launch_att32b<DD, 2, 32>(c, a)
-    if (s.d == 64) { PS_A32B(64); }
-    if (s.d == 128) { PS_A32B(128); }
-#undef PS_A32B
-#define PS_A32S(DD)                                                                                                      \
-    if (s.k == 16) return stage == 1 ? launch_att32s<DD, 1, 16>(c, a) : launch_att32s<DD, 2, 16>(c, a);                  \
-    return stage == 1 ? launch_att32s<DD, 1, 32>(c, a) : launch_att32s<DD, 2, 32>(c, a)
-    if (s.d == 256) { PS_A32S(256); }
-    PS_A32S(512);
-#undef PS_A32S
+    const Att32bArgs a = att32_args<Att32bArgs>(s, s.p32->w1b, s.p32->w2b, s.p32->wb1b, s.p32->wb2b);
+    if (s.d == 64) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<64, stage(), k()>(c, a); });
+    if (s.d == 128) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<128, stage(), k()>(c, a); });
+    if (s.d == 256) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<256, stage(), k()>(c, a); });
+    return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<512, stage(), k()>(c, a); });
 }
 
 }  // namespace ps
