@@ -1205,6 +1205,22 @@ int wgrad_finish(ps_context* c, const WgradJob* d_jobs, int n_jobs, int64_t max_
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
+
+// RECOMP: `third` holds the scores and the kernel forms the softmax again; otherwise it holds the probabilities the forward kept
+template <bool RECOMP>
+static int softmax_pool_bwd(ps_context* c, const float* dagg, const float* fset, const float* third, int64_t R, int64_t K, int64_t d, float* dfset,
+                            float* dscores)
+{
+    if (!R) return PS_OK;
+    PS_HIP(hipSetDevice(c->device));
+    Stage st(c, "train_softpool_bwd", 1);
+    const dim3 grid(ceil_div(R * d, 256));
+    if (K == 16) hipLaunchKernelGGL((softpool_bwd_kernel<16, RECOMP>), grid, dim3(256), 0, c->stream, dagg, fset, third, R, (int)K, (int)d, dfset, dscores);
+    else if (K == 32) hipLaunchKernelGGL((softpool_bwd_kernel<32, RECOMP>), grid, dim3(256), 0, c->stream, dagg, fset, third, R, (int)K, (int)d, dfset, dscores);
+    else hipLaunchKernelGGL((softpool_bwd_kernel<0, RECOMP>), grid, dim3(256), 0, c->stream, dagg, fset, third, R, (int)K, (int)d, dfset, dscores);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
 }  // namespace ps
 
 extern "C" {
@@ -1242,37 +1258,17 @@ int ps_op_bn_train_fwd(ps_context* c, const float* x, const float* gamma, const 
     return ps_op_bn_train_fwd_ex(c, x, gamma, beta, R, C, eps, leaky, y, C, mean, invstd, var, scratch2C);
 }
 
-int ps_op_bn_train_fwd_ex(ps_context* c, const float* x, const float* gamma, const float* beta, int64_t R, int64_t C, float eps, int leaky, float* y,
-                          int64_t ldy, float* mean, float* invstd, float* var, float* scratch2C)
-{
-    PS_CHECK(c && x && gamma && beta && y && mean && invstd && var && scratch2C, "ps_op_bn_train_fwd: NULL argument");
-    PS_CHECK(R >= 1 && C >= 1 && ldy >= C, "ps_op_bn_train_fwd: empty tensor");
-    PS_HIP(hipSetDevice(c->device));
-    if (bn_slice_ok(c->tune, R, C, x, y, ldy)) {
-        Stage st1(c, "train_bn_fwd", 1);
-        hipLaunchKernelGGL(bn_slice_fwd_kernel, dim3((unsigned)(C / kBnSliceCh)), dim3(kBnSliceThreads), 0, c->stream, x, gamma, beta, (int)R, (int)C, eps, leaky, y, ldy, mean, invstd,
-                           var, scratch2C, static_cast<float*>(nullptr), static_cast<float*>(nullptr), 0.f);
-        PS_HIP(hipGetLastError());
-        return PS_OK;
-    }
-    Stage st(c, "train_bn_fwd", 3);
-    const BnFinish bn = {mean, invstd, var, nullptr, nullptr, R, eps, 0.f};
-    PS_TRY(colreduce2(c, SumSq{x}, R, (int)C, scratch2C, scratch2C + C, &bn));
-    if (bn_vec_ok(C, x, y, x, ldy))
-        hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
-                           ldy);
-    else
-        hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
-                           ldy);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
+// the two elementwise launches, float4 form where bn_vec_ok allows (the caller checks hipGetLastError).  Each is DEFINED behind its first
+// caller: kernel templates are emitted in the order of their first reference, and the device code keeps the order it had
+static void launch_bn_apply(ps_context* c, const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd, int64_t R, int64_t C,
+                            int leaky, float* y, int64_t ldy);
+static void launch_bn_bwd_apply(ps_context* c, const float* dy, int64_t lddy, const float* x, const float* gamma, const float* beta, const float* mean,
+                                const float* invstd, const float* sum_g, const float* sum_gx, int64_t R, int64_t R_total, int64_t C, int leaky, float* dx);
 
-int ps_op_bn_train_fwd_mov(ps_context* c, const float* x, const float* gamma, const float* beta, int64_t R, int64_t C, float eps, int leaky, float* y,
-                           int64_t ldy, float* mean, float* invstd, float* var, float* scratch2C, float* moving_mean, float* moving_var, float momentum)
+// moving_mean / moving_var may be NULL (ps_op_bn_train_fwd_ex: batch statistics only)
+static int bn_train_fwd(ps_context* c, const float* x, const float* gamma, const float* beta, int64_t R, int64_t C, float eps, int leaky, float* y, int64_t ldy,
+                        float* mean, float* invstd, float* var, float* scratch2C, float* moving_mean, float* moving_var, float momentum)
 {
-    PS_CHECK(c && x && gamma && beta && y && mean && invstd && var && scratch2C && moving_mean && moving_var, "ps_op_bn_train_fwd_mov: NULL argument");
-    PS_CHECK(R >= 1 && C >= 1 && ldy >= C, "ps_op_bn_train_fwd_mov: empty tensor");
     PS_HIP(hipSetDevice(c->device));
     if (bn_slice_ok(c->tune, R, C, x, y, ldy)) {
         Stage st1(c, "train_bn_fwd", 1);
@@ -1284,14 +1280,36 @@ int ps_op_bn_train_fwd_mov(ps_context* c, const float* x, const float* gamma, co
     Stage st(c, "train_bn_fwd", 3);
     const BnFinish bn = {mean, invstd, var, moving_mean, moving_var, R, eps, momentum};
     PS_TRY(colreduce2(c, SumSq{x}, R, (int)C, scratch2C, scratch2C + C, &bn));
+    launch_bn_apply(c, x, gamma, beta, mean, invstd, R, C, leaky, y, ldy);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+static void launch_bn_apply(ps_context* c, const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd, int64_t R, int64_t C,
+                            int leaky, float* y, int64_t ldy)
+{
     if (bn_vec_ok(C, x, y, x, ldy))
         hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
                            ldy);
     else
         hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
                            ldy);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+}
+
+int ps_op_bn_train_fwd_ex(ps_context* c, const float* x, const float* gamma, const float* beta, int64_t R, int64_t C, float eps, int leaky, float* y,
+                          int64_t ldy, float* mean, float* invstd, float* var, float* scratch2C)
+{
+    PS_CHECK(c && x && gamma && beta && y && mean && invstd && var && scratch2C, "ps_op_bn_train_fwd: NULL argument");
+    PS_CHECK(R >= 1 && C >= 1 && ldy >= C, "ps_op_bn_train_fwd: empty tensor");
+    return bn_train_fwd(c, x, gamma, beta, R, C, eps, leaky, y, ldy, mean, invstd, var, scratch2C, nullptr, nullptr, 0.f);
+}
+
+int ps_op_bn_train_fwd_mov(ps_context* c, const float* x, const float* gamma, const float* beta, int64_t R, int64_t C, float eps, int leaky, float* y,
+                           int64_t ldy, float* mean, float* invstd, float* var, float* scratch2C, float* moving_mean, float* moving_var, float momentum)
+{
+    PS_CHECK(c && x && gamma && beta && y && mean && invstd && var && scratch2C && moving_mean && moving_var, "ps_op_bn_train_fwd_mov: NULL argument");
+    PS_CHECK(R >= 1 && C >= 1 && ldy >= C, "ps_op_bn_train_fwd_mov: empty tensor");
+    return bn_train_fwd(c, x, gamma, beta, R, C, eps, leaky, y, ldy, mean, invstd, var, scratch2C, moving_mean, moving_var, momentum);
 }
 
 int ps_op_bn_train_bwd(ps_context* c, const float* dy, const float* x, const float* gamma, const float* beta, const float* mean, const float* invstd,
@@ -1316,14 +1334,20 @@ int ps_op_bn_train_bwd_ex(ps_context* c, const float* dy, int64_t lddy, const fl
     Stage st(c, "train_bn_bwd", 2);
     // dbeta = sum g, dgamma = sum g*xhat
     PS_TRY(colreduce2(c, BnBwdSums{dy, x, gamma, beta, mean, invstd, leaky, (int)C, lddy}, R, (int)C, dbeta, dgamma));
-    if (bn_vec_ok(C, x, dy, dx, lddy))
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, dbeta, dgamma,
-                           R * C, (int)C, 1.0f / (float)R, leaky, dx, lddy);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, dbeta, dgamma,
-                           R * C, (int)C, 1.0f / (float)R, leaky, dx, lddy);
+    launch_bn_bwd_apply(c, dy, lddy, x, gamma, beta, mean, invstd, dbeta, dgamma, R, R, C, leaky, dx);
     PS_HIP(hipGetLastError());
     return PS_OK;
+}
+
+static void launch_bn_bwd_apply(ps_context* c, const float* dy, int64_t lddy, const float* x, const float* gamma, const float* beta, const float* mean,
+                                const float* invstd, const float* sum_g, const float* sum_gx, int64_t R, int64_t R_total, int64_t C, int leaky, float* dx)
+{
+    if (bn_vec_ok(C, x, dy, dx, lddy))
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, sum_g, sum_gx,
+                           R * C, (int)C, 1.0f / (float)R_total, leaky, dx, lddy);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, sum_g, sum_gx,
+                           R * C, (int)C, 1.0f / (float)R_total, leaky, dx, lddy);
 }
 
 // ---- the same two ops split at their reduction, for BatchNorm statistics shared by several GPUs (config 4): the caller
@@ -1353,12 +1377,7 @@ int ps_op_bn_train_apply_ex(ps_context* c, const float* x, const float* gamma, c
     PS_HIP(hipSetDevice(c->device));
     Stage st(c, "train_bn_fwd", 2);
     hipLaunchKernelGGL(bn_finish_stats_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, c->stream, sums2C, sums2C + C, R_total, (int)C, eps, mean, invstd, var);
-    if (bn_vec_ok(C, x, y, x, ldy))
-        hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
-                           ldy);
-    else
-        hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, x, gamma, beta, mean, invstd, R * C, (int)C, leaky, y,
-                           ldy);
+    launch_bn_apply(c, x, gamma, beta, mean, invstd, R, C, leaky, y, ldy);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
@@ -1395,12 +1414,7 @@ int ps_op_bn_train_bwd_apply_ex(ps_context* c, const float* dy, int64_t lddy, co
     PS_CHECK(R >= 1 && C >= 1 && R_total >= R && lddy >= C, "ps_op_bn_train_bwd_apply: bad row counts");
     PS_HIP(hipSetDevice(c->device));
     Stage st(c, "train_bn_bwd", 1);
-    if (bn_vec_ok(C, x, dy, dx, lddy))
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(R * C / 4)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, sum_g, sum_gx,
-                           R * C, (int)C, 1.0f / (float)R_total, leaky, dx, lddy);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ew_grid(R * C)), dim3(256), 0, c->stream, dy, x, gamma, beta, mean, invstd, sum_g, sum_gx,
-                           R * C, (int)C, 1.0f / (float)R_total, leaky, dx, lddy);
+    launch_bn_bwd_apply(c, dy, lddy, x, gamma, beta, mean, invstd, sum_g, sum_gx, R, R_total, C, leaky, dx);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
@@ -1443,30 +1457,14 @@ int ps_op_softmax_pool_bwd(ps_context* c, const float* dagg, const float* fset, 
                            float* dscores)
 {
     PS_CHECK(c && dagg && fset && probs && dfset && dscores, "ps_op_softmax_pool_bwd: NULL argument");
-    if (!R) return PS_OK;
-    PS_HIP(hipSetDevice(c->device));
-    Stage st(c, "train_softpool_bwd", 1);
-    const dim3 grid(ceil_div(R * d, 256));
-    if (K == 16) hipLaunchKernelGGL((softpool_bwd_kernel<16, false>), grid, dim3(256), 0, c->stream, dagg, fset, probs, R, (int)K, (int)d, dfset, dscores);
-    else if (K == 32) hipLaunchKernelGGL((softpool_bwd_kernel<32, false>), grid, dim3(256), 0, c->stream, dagg, fset, probs, R, (int)K, (int)d, dfset, dscores);
-    else hipLaunchKernelGGL((softpool_bwd_kernel<0, false>), grid, dim3(256), 0, c->stream, dagg, fset, probs, R, (int)K, (int)d, dfset, dscores);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+    return softmax_pool_bwd<false>(c, dagg, fset, probs, R, K, d, dfset, dscores);
 }
 
 int ps_op_softmax_pool_bwd_scores(ps_context* c, const float* dagg, const float* fset, const float* scores, int64_t R, int64_t K, int64_t d, float* dfset,
                                   float* dscores)
 {
     PS_CHECK(c && dagg && fset && scores && dfset && dscores, "ps_op_softmax_pool_bwd_scores: NULL argument");
-    if (!R) return PS_OK;
-    PS_HIP(hipSetDevice(c->device));
-    Stage st(c, "train_softpool_bwd", 1);
-    const dim3 grid(ceil_div(R * d, 256));
-    if (K == 16) hipLaunchKernelGGL((softpool_bwd_kernel<16, true>), grid, dim3(256), 0, c->stream, dagg, fset, scores, R, (int)K, (int)d, dfset, dscores);
-    else if (K == 32) hipLaunchKernelGGL((softpool_bwd_kernel<32, true>), grid, dim3(256), 0, c->stream, dagg, fset, scores, R, (int)K, (int)d, dfset, dscores);
-    else hipLaunchKernelGGL((softpool_bwd_kernel<0, true>), grid, dim3(256), 0, c->stream, dagg, fset, scores, R, (int)K, (int)d, dfset, dscores);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+    return softmax_pool_bwd<true>(c, dagg, fset, scores, R, K, d, dfset, dscores);
 }
 
 int ps_op_random_sample_bwd(ps_context* c, const float* dout, const float* out, const float* feature, const int32_t* pool_idx, int64_t B, int64_t N,

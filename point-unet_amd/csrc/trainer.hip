@@ -170,23 +170,24 @@ struct Tn {
     bool b16 = false;  // rows STORED as bfloat16 (ps_train_options.act_bf16): only ever handed to the ops that read them that way
     std::shared_ptr<Block> own;
     bool contiguous() const { return ld == C; }
+    bool vec_ok() const { return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // float4 rows: what the row kernels ask of an operand
     int64_t numel() const { return R * C; }
     explicit operator bool() const { return p != nullptr; }
 };
 
-// ---- small kernels of the tape itself ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void tr_transpose_kernel(const float* __restrict__ src, int rows, int cols, float* __restrict__ dst)
-{
-    // dst[c, r] = src[r, c]; 32x32 tiles through LDS (weights only: at most 1.5 M elements)
-    __shared__ float tile[32][33];
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int j = ty; j < 32; j += 8)
-        if (by + j < rows && bx + tx < cols) tile[j][tx] = src[(size_t)(by + j) * cols + bx + tx];
-    __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (bx + j < cols && by + tx < rows) dst[(size_t)(bx + j) * rows + by + tx] = tile[tx][j];
-}
+// sets a field of the context -- a mode the ops read: the bf16-GEMM mode, bfloat16-stored [N*K, h] rows (ps_set_train_act_bf16), the stream -- for
+// the lifetime of the object, then puts the previous value back
+template <class T>
+struct Scoped {
+    T& field;
+    const T was;
+    Scoped(T& f, T value) : field(f), was(f) { field = value; }
+    ~Scoped() { field = was; }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+};
 
+// ---- small kernels of the tape itself ------------------------------------------------------------------------------------------------
 template <bool ADD>
 __global__ __launch_bounds__(256) void tr_copy2d_kernel(const float* __restrict__ src, int64_t lds, float* __restrict__ dst, int64_t ldd, int64_t n, int C)
 {
@@ -525,6 +526,11 @@ struct ps_trainer {
     }
     std::vector<WgradJob> wjobs;  // weight / bias gradient partials waiting for the step's one reduction launch
     std::vector<Tn> wkeep;
+    void queue_wgrad(const Tn& part, float* dst, int64_t slabs, int64_t rows, int64_t cols, bool transposed = false)
+    {
+        wjobs.push_back(WgradJob{part.p, dst, (int)slabs, (int)rows, (int)cols, transposed ? 1 : 0});
+        wkeep.push_back(part);  // (alive until the reduction launch has been enqueued)
+    }
     void finish_wgrads()
     {
         join_side();  // (the partial products may still be running on the second stream)
@@ -544,14 +550,13 @@ struct ps_trainer {
     }
 
     hipStream_t stream() const { return c->stream; }
-    // tells the storage-aware ops (ps_set_train_act_bf16) that the [N*K, h] rows of this call are bfloat16, for the lifetime of the object
-    struct ActScope {
-        ps_context* c;
-        bool was;
-        ActScope(ps_context* ctx, bool on) : c(ctx), was(ctx->train_act_bf16) { c->train_act_bf16 = on; }
-        ~ActScope() { c->train_act_bf16 = was; }
-    };
-
+    // a [C]-sized kernel of the tape: one thread per channel in blocks of 64 on the step's stream
+    template <class Kernel, class... Args>
+    void launch_c(Kernel kernel, int64_t C, Args... args)
+    {
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), args...);
+        TK_HIP(hipGetLastError());
+    }
     // ---- tensors
     Tn alloc(int64_t R, int64_t C, bool req = true)
     {
@@ -609,20 +614,6 @@ struct ps_trainer {
         Tn o = alloc(t.R, t.C, t.req);
         copy2d(t, o, false);
         return o;
-    }
-    Tn transpose(const Tn& w)  // [r, c] contiguous -> fresh [c, r]
-    {
-        Tn o = alloc(w.C, w.R, false);
-        Stage st(c, "train_copies", 1);
-        hipLaunchKernelGGL(tr_transpose_kernel, dim3(ceil_div(w.C, 32), ceil_div(w.R, 32)), dim3(256), 0, stream(), w.p, (int)w.R, (int)w.C, o.p);
-        TK_HIP(hipGetLastError());
-        return o;
-    }
-    void transpose_into(const Tn& src, float* dst)
-    {
-        Stage st(c, "train_copies", 1);
-        hipLaunchKernelGGL(tr_transpose_kernel, dim3(ceil_div(src.C, 32), ceil_div(src.R, 32)), dim3(256), 0, stream(), src.p, (int)src.R, (int)src.C, dst);
-        TK_HIP(hipGetLastError());
     }
     // a world of ONE rank is the identity: the callback is skipped (and the BatchNorm layers keep their cheaper one-rank form) unless
     // ps_trainer_set_collective asked for it with PS_COLLECTIVE_AT_WORLD_ONE -- bench.py's measurement of the host collective's floor
@@ -750,22 +741,14 @@ struct ps_trainer {
     Tn linear(const Tn& x, const Tn& W, const float* b, const Tn& gW, float* gb, bool transposed = false, const Tn* into = nullptr, bool fp32_only = false,
               bool defer_dgrad = false)
     {
-        struct Fp32Scope {  // switches the context's bf16-GEMM mode off for the lifetime of the object
-            ps_context* c;
-            bool was;
-            Fp32Scope(ps_context* ctx, bool on) : c(ctx), was(ctx->train_bf16) { if (on) c->train_bf16 = false; }
-            ~Fp32Scope() { c->train_bf16 = was; }
-        };
-        struct WtScope {  // tells ps_op_conv1x1_ex that its weight matrix is stored [cout, cin] (read through strides while packing)
-            ps_context* c;
-            WtScope(ps_context* ctx, bool on) : c(ctx) { c->conv_w_transposed = on; }
-            ~WtScope() { c->conv_w_transposed = false; }
-        };
-        Fp32Scope fwd_scope(c, fp32_only);
+        // fp32_only switches the context's bf16-GEMM mode off around this layer's products; conv_w_transposed tells ps_op_conv1x1_ex that its
+        // weight matrix is stored [cout, cin] (read through strides while packing).  Only this function sets that flag, around single
+        // calls that do not nest: it is false on entry, which is what Scoped puts back
+        Scoped<bool> fwd_scope(c->train_bf16, c->train_bf16 && !fp32_only);
         const int64_t R = x.R, cin = x.C, cout = transposed ? W.R : W.C;
         Tn y;
         {
-            WtScope wt(c, transposed);  // conv2d_transpose kernels are stored [out, in]
+            Scoped<bool> wt(c->conv_w_transposed, transposed);  // conv2d_transpose kernels are stored [out, in]
             if (!into) {
                 y = alloc(R, cout);
                 TK(ps_op_conv1x1_ex(c, x.p, x.ld, W.p, b, R, cin, cout, 0, 0, y.p, y.ld));
@@ -777,7 +760,7 @@ struct ps_trainer {
         const bool had_into = into != nullptr;
         const Tn into_t = had_into ? *into : Tn();
         record(y, [=](const Tn& dy) {
-            Fp32Scope bwd_scope(c, fp32_only);
+            Scoped<bool> bwd_scope(c->train_bf16, c->train_bf16 && !fp32_only);
             if (had_into) grad_of[into_t.id] = dy;  // d(into + x.W)/d(into) = 1: the producer of `into` (earlier on the tape) gets the same gradient
             {
                 // weight / bias gradient: per-slab partials now (plain stores), summed in slab order by the ONE wgrad_finish launch at the
@@ -786,15 +769,10 @@ struct ps_trainer {
                 Tn part = alloc(nb, cin * cout, false);
                 Tn dbp = gb ? alloc(nb, cout, false) : Tn();
                 {
-                    struct StreamScope {  // the product is enqueued on the second stream: the context's stream is what every launch below uses
-                        ps_context* c;
-                        hipStream_t was;
-                        StreamScope(ps_context* ctx, hipStream_t s) : c(ctx), was(ctx->stream) { if (s) c->stream = s; }
-                        ~StreamScope() { c->stream = was; }
-                    };
                     const bool on_side = use_side();
                     if (on_side) fork_to_side();
-                    StreamScope ss(c, on_side ? side : nullptr);
+                    // the product is enqueued on the second stream: the context's stream is what every launch below uses
+                    Scoped<hipStream_t> ss(c->stream, on_side ? side : c->stream);
                     Stage st(c, "train_wgrad", 1);
                     TK(wgrad_partial(c, x.p, x.ld, dy.p, dy.ld, R, cin, cout, part.p, gb ? dbp.p : nullptr));
                     if (on_side) {
@@ -802,18 +780,14 @@ struct ps_trainer {
                         wkeep.push_back(dy);
                     }
                 }
-                wjobs.push_back(WgradJob{part.p, gW.p, (int)nb, (int)cin, (int)cout, transposed ? 1 : 0});
-                wkeep.push_back(part);
-                if (gb) {
-                    wjobs.push_back(WgradJob{dbp.p, gb, (int)nb, 1, (int)cout, 0});
-                    wkeep.push_back(dbp);
-                }
+                queue_wgrad(part, gW.p, nb, cin, cout, transposed);
+                if (gb) queue_wgrad(dbp, gb, nb, 1, cout);
             }
             if (x.req) {
                 // dx = dy . W^T: the GEMM's [cout, cin] matrix IS the stored kernel for the transposed layers and its transpose for all others
                 auto dgrad = [=]() {
-                    Fp32Scope scope(c, fp32_only);
-                    WtScope wt(c, !transposed);
+                    Scoped<bool> scope(c->train_bf16, c->train_bf16 && !fp32_only);
+                    Scoped<bool> wt(c->conv_w_transposed, !transposed);
                     auto it = grad_of.find(x.id);
                     if (it != grad_of.end()) {
                         // x already has a gradient from another consumer: add this one in the GEMM epilogue
@@ -833,10 +807,21 @@ struct ps_trainer {
         });
         return y;
     }
+    // the layer's own kernel, bias and their gradients ([cout, cin] for the conv2d_transpose layers)
+    Tn linear(const Tn& x, const LayerP& lp, const Tn* into = nullptr, bool fp32_only = false, bool defer_dgrad = false)
+    {
+        return linear(x, Wt(lp), lp.b >= 0 ? params + lp.b : nullptr, gWt(lp), lp.b >= 0 ? grads + lp.b : nullptr, lp.kind == kDeconv, into, fp32_only, defer_dgrad);
+    }
 
     // y = act(BN_train(x)); out: optional [R, C] column block of a wider tensor (rows contiguous) that receives y
     Tn bn_act(const Tn& x_in, const LayerP& lp, bool leaky, const Tn* out = nullptr)
     {
+        if (sync_bn && coll_active()) {
+            // statistics over the rows of ALL ranks: two small all-reduces per layer (2*C floats forward, 2*C backward)
+            PendingBn p = bn_begin(x_in, lp, leaky, out);
+            allreduce(p.sums(), 2 * p.x.C, 0);
+            return bn_end(p);
+        }
         const Tn x = contig(x_in);
         const int64_t R = x.R, C = x.C;
         Tn y = out ? *out : alloc(R, C);
@@ -844,54 +829,62 @@ struct ps_trainer {
         Tn stats = alloc(5, C, false);  // mean, invstd, var, [sum x | sum x^2]
         float *mean = stats.p, *invstd = stats.p + C, *var = stats.p + 2 * C, *sums = stats.p + 3 * C;
         const float *gamma = params + lp.gamma, *beta = params + lp.beta;
-        const bool sync = sync_bn && coll_active();
-        const int64_t R_total = sync ? R * world : R;
-        if (!sync) {
-            // statistics, moving-statistics update and the apply pass: three launches
-            TK(ps_op_bn_train_fwd_mov(c, x.p, gamma, beta, R, C, kBnEps, leaky ? 1 : 0, y.p, y.ld, mean, invstd, var, sums, buffers + lp.mov_mean,
-                                      buffers + lp.mov_var, kBnMomentum));
-        } else {
-            // statistics over the rows of ALL ranks: two small all-reduces per layer (2*C floats forward, 2*C backward)
-            TK(ps_op_bn_train_sums(c, x.p, R, C, sums));
-            allreduce(sums, 2 * C, 0);
-            TK(ps_op_bn_train_apply_ex(c, x.p, gamma, beta, sums, R, R_total, C, kBnEps, leaky ? 1 : 0, y.p, y.ld, mean, invstd, var));
-        }
-        if (sync) {
-            Stage st(c, "train_bn_fwd", 1);
-            hipLaunchKernelGGL(tr_ema2_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), buffers + lp.mov_mean, buffers + lp.mov_var, mean, var, (int)C,
-                               kBnMomentum);
-            TK_HIP(hipGetLastError());
-        }
+        // statistics, moving-statistics update and the apply pass: three launches
+        TK(ps_op_bn_train_fwd_mov(c, x.p, gamma, beta, R, C, kBnEps, leaky ? 1 : 0, y.p, y.ld, mean, invstd, var, sums, buffers + lp.mov_mean, buffers + lp.mov_var,
+                                  kBnMomentum));
         float *ggamma = grads + lp.gamma, *gbeta = grads + lp.beta;
         const Tn xin = x_in;
         record(y, [=](const Tn& dy) {
             Tn dx = alloc(R, C);
-            if (!sync) {
-                TK(ps_op_bn_train_bwd_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, R, C, leaky ? 1 : 0, dx.p, ggamma, gbeta));
-            } else {
-                // local sums are this rank's dgamma / dbeta (averaged with every other gradient later); dx needs the global ones
-                TK(ps_op_bn_train_bwd_sums_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, R, C, leaky ? 1 : 0, ggamma, gbeta));
-                Tn tot = alloc(2, C, false);
-                hipLaunchKernelGGL(tr_pair_copy_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), gbeta, ggamma, (int)C, tot.p);
-                TK_HIP(hipGetLastError());
-                allreduce(tot.p, 2 * C, 0);
-                TK(ps_op_bn_train_bwd_apply_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, tot.p, tot.p + C, R, R_total, C, leaky ? 1 : 0, dx.p));
-            }
+            TK(ps_op_bn_train_bwd_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, R, C, leaky ? 1 : 0, dx.p, ggamma, gbeta));
             (void)stats;  // (mean / invstd live in it)
             accum(xin, dx);
         });
         return y;
     }
 
-    // ---- shared statistics of INDEPENDENT BatchNorm layers in one all-reduce (SyncBN, world > 1) ---------------------------------------
-    // bn_act's shared-statistics form cut in two: bn_begin leaves this rank's [sum | sum x^2] in p.sums(); whoever all-reduces them (a
-    // companion layer's call) is followed by bn_end: apply pass, moving statistics, backward closure (its own all-reduce of the 2 C
-    // backward sums -- the backward of the two layers does not run at the same time).
-    struct PendingBn {
-        Tn x, x_in, y, stats, shared;  // shared: a [2 Ca + 2 Cb] buffer two pending layers put their sums into (kept alive by both)
+    // ---- BatchNorm statistics shared by the ranks (SyncBN, world > 1) -------------------------------------------------------------------
+    // One layer between its halves: x [R, C] contiguous; stats points at mean[C] | invstd[C] | var[C] and keeps their block alive.  The three
+    // parts below are what a layer on its own (bn_end) and the residual pair (res_pair_sync) are made of; the all-reduces between them are
+    // the caller's, which is where the two differ.
+    struct BnLayer {
+        Tn x, stats;
         const LayerP* lp = nullptr;
-        float* ext = nullptr;          // this layer's 2 C sums inside `shared`
-        bool leaky = false, open = false;
+        bool leaky = false;
+    };
+    // forward finish: statistics from the sums of all ranks' rows, the apply pass, the moving statistics
+    void sync_bn_finish(const BnLayer& l, const float* sums, const Tn& y)
+    {
+        const int64_t R = l.x.R, C = l.x.C;
+        float *mean = l.stats.p, *invstd = mean + C, *var = mean + 2 * C;
+        TK(ps_op_bn_train_apply_ex(c, l.x.p, params + l.lp->gamma, params + l.lp->beta, sums, R, R * world, C, kBnEps, l.leaky ? 1 : 0, y.p, y.ld, mean, invstd, var));
+        Stage st(c, "train_bn_fwd", 1);
+        launch_c(tr_ema2_kernel, C, buffers + l.lp->mov_mean, buffers + l.lp->mov_var, mean, var, (int)C, kBnMomentum);
+    }
+    // backward, first half: the local sums are this rank's dgamma / dbeta (averaged with every other gradient later); dx needs the global
+    // ones: tot [2 C] receives the copy [dbeta | dgamma] that the caller all-reduces
+    void sync_bn_bwd_sums(const BnLayer& l, const Tn& dy, float* tot)
+    {
+        const int64_t C = l.x.C;
+        float *ggamma = grads + l.lp->gamma, *gbeta = grads + l.lp->beta;
+        TK(ps_op_bn_train_bwd_sums_ex(c, dy.p, dy.ld, l.x.p, params + l.lp->gamma, params + l.lp->beta, l.stats.p, l.stats.p + C, l.x.R, C, l.leaky ? 1 : 0, ggamma, gbeta));
+        launch_c(tr_pair_copy_kernel, C, gbeta, ggamma, (int)C, tot);
+    }
+    // backward, second half: dx from the all-reduced tot
+    void sync_bn_bwd_apply(const BnLayer& l, const Tn& dy, const float* tot, const Tn& dx)
+    {
+        const int64_t R = l.x.R, C = l.x.C;
+        TK(ps_op_bn_train_bwd_apply_ex(c, dy.p, dy.ld, l.x.p, params + l.lp->gamma, params + l.lp->beta, l.stats.p, l.stats.p + C, tot, tot + C, R, R * world, C,
+                                       l.leaky ? 1 : 0, dx.p));
+    }
+
+    // A layer cut in two, so that INDEPENDENT layers can share an all-reduce: bn_begin leaves this rank's [sum | sum x^2] in p.sums(); whoever
+    // all-reduces them (bn_act for a layer on its own, a companion layer's call otherwise) is followed by bn_end: apply pass, moving
+    // statistics, backward closure (its own all-reduce of the 2 C backward sums -- the backward of two layers does not run at the same time).
+    struct PendingBn : BnLayer {  // (stats: 5 C -- mean | invstd | var | [sum x | sum x^2])
+        Tn x_in, y, shared;  // shared: a [2 Ca + 2 Cb] buffer two pending layers put their sums into (kept alive by both)
+        float* ext = nullptr;  // this layer's 2 C sums inside `shared`
+        bool open = false;
         float* sums() const { return ext ? ext : stats.p + 3 * x.C; }
     };
     PendingBn bn_begin(const Tn& x_in, const LayerP& lp, bool leaky, const Tn* out = nullptr, const Tn* shared = nullptr, int64_t shared_off = 0)
@@ -914,29 +907,16 @@ struct ps_trainer {
     }
     Tn bn_end(PendingBn& p)
     {
-        const LayerP& lp = *p.lp;
-        const Tn x = p.x, xin = p.x_in, y = p.y, stats = p.stats;
-        const int64_t R = x.R, C = x.C, R_total = R * world;
-        const bool leaky = p.leaky;
-        float *mean = stats.p, *invstd = stats.p + C, *var = stats.p + 2 * C;
-        const float *gamma = params + lp.gamma, *beta = params + lp.beta;
-        TK(ps_op_bn_train_apply_ex(c, x.p, gamma, beta, p.sums(), R, R_total, C, kBnEps, leaky ? 1 : 0, y.p, y.ld, mean, invstd, var));
-        {
-            Stage st(c, "train_bn_fwd", 1);
-            hipLaunchKernelGGL(tr_ema2_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), buffers + lp.mov_mean, buffers + lp.mov_var, mean, var, (int)C,
-                               kBnMomentum);
-            TK_HIP(hipGetLastError());
-        }
-        float *ggamma = grads + lp.gamma, *gbeta = grads + lp.beta;
+        const BnLayer l = p;
+        const Tn xin = p.x_in, y = p.y;
+        sync_bn_finish(l, p.sums(), y);
         record(y, [=](const Tn& dy) {
-            Tn dx = alloc(R, C);
-            TK(ps_op_bn_train_bwd_sums_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, R, C, leaky ? 1 : 0, ggamma, gbeta));
+            const int64_t C = l.x.C;
+            Tn dx = alloc(l.x.R, C);
             Tn tot = alloc(2, C, false);
-            hipLaunchKernelGGL(tr_pair_copy_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), gbeta, ggamma, (int)C, tot.p);
-            TK_HIP(hipGetLastError());
+            sync_bn_bwd_sums(l, dy, tot.p);
             allreduce(tot.p, 2 * C, 0);
-            TK(ps_op_bn_train_bwd_apply_ex(c, dy.p, dy.ld, x.p, gamma, beta, mean, invstd, tot.p, tot.p + C, R, R_total, C, leaky ? 1 : 0, dx.p));
-            (void)stats;
+            sync_bn_bwd_apply(l, dy, tot.p, dx);
             accum(xin, dx);
         });
         p.open = false;
@@ -950,51 +930,66 @@ struct ps_trainer {
     Tn res_pair_sync(const Tn& xa_in, const LayerP& la, const Tn& xb_in, const LayerP& lb)
     {
         const Tn xa = contig(xa_in), xb = contig(xb_in);
-        const int64_t R = xa.R, C = xa.C, R_total = R * world;
+        const int64_t R = xa.R, C = xa.C;
         if (xb.R != R || xb.C != C) {
             ps::set_error("trainer: res_pair_sync: the two branches differ in shape");
             throw TrainError{PS_ESTATE};
         }
         Tn st = alloc(10, C, false);  // per branch: mean | invstd | var, then the four sums [sum a | sum a^2 | sum b | sum b^2] contiguously
-        float *mean_a = st.p, *invstd_a = st.p + C, *var_a = st.p + 2 * C, *mean_b = st.p + 3 * C, *invstd_b = st.p + 4 * C, *var_b = st.p + 5 * C;
+        Tn st_b = st;
+        st_b.p = st.p + 3 * C;
+        const BnLayer a{xa, st, &la, false}, b{xb, st_b, &lb, false};
         float* sums = st.p + 6 * C;
-        const float *ga = params + la.gamma, *ba = params + la.beta, *gb = params + lb.gamma, *bb = params + lb.beta;
         TK(ps_op_bn_train_sums(c, xa.p, R, C, sums));
         TK(ps_op_bn_train_sums(c, xb.p, R, C, sums + 2 * C));
         allreduce(sums, 4 * C, 0);
         Tn ya = alloc(R, C), yb = alloc(R, C);
-        TK(ps_op_bn_train_apply_ex(c, xa.p, ga, ba, sums, R, R_total, C, kBnEps, 0, ya.p, ya.ld, mean_a, invstd_a, var_a));
-        TK(ps_op_bn_train_apply_ex(c, xb.p, gb, bb, sums + 2 * C, R, R_total, C, kBnEps, 0, yb.p, yb.ld, mean_b, invstd_b, var_b));
-        {
-            Stage stg(c, "train_bn_fwd", 2);
-            hipLaunchKernelGGL(tr_ema2_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), buffers + la.mov_mean, buffers + la.mov_var, mean_a, var_a, (int)C, kBnMomentum);
-            hipLaunchKernelGGL(tr_ema2_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), buffers + lb.mov_mean, buffers + lb.mov_var, mean_b, var_b, (int)C, kBnMomentum);
-            TK_HIP(hipGetLastError());
-        }
+        sync_bn_finish(a, sums, ya);
+        sync_bn_finish(b, sums + 2 * C, yb);
         Tn y = alloc(R, C);
         y.req = true;
         TK(ps_op_add_lrelu(c, ya.p, yb.p, y.numel(), y.p));
-        float *gga = grads + la.gamma, *gba = grads + la.beta, *ggb = grads + lb.gamma, *gbb = grads + lb.beta;
         record(y, [=](const Tn& dy_in) {
             const Tn dy = contig(dy_in);
             Tn ds = alloc(R, C);
             TK(ps_op_add_lrelu_bwd(c, dy.p, y.p, y.numel(), ds.p));
-            // this rank's dgamma / dbeta of both layers (averaged with every other gradient later); dx needs the global sums
-            TK(ps_op_bn_train_bwd_sums_ex(c, ds.p, ds.ld, xa.p, ga, ba, mean_a, invstd_a, R, C, 0, gga, gba));
-            TK(ps_op_bn_train_bwd_sums_ex(c, ds.p, ds.ld, xb.p, gb, bb, mean_b, invstd_b, R, C, 0, ggb, gbb));
             Tn tot = alloc(4, C, false);
-            hipLaunchKernelGGL(tr_pair_copy_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), gba, gga, (int)C, tot.p);
-            hipLaunchKernelGGL(tr_pair_copy_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, stream(), gbb, ggb, (int)C, tot.p + 2 * C);
-            TK_HIP(hipGetLastError());
+            sync_bn_bwd_sums(a, ds, tot.p);
+            sync_bn_bwd_sums(b, ds, tot.p + 2 * C);
             allreduce(tot.p, 4 * C, 0);
             Tn dxa = alloc(R, C), dxb = alloc(R, C);
-            TK(ps_op_bn_train_bwd_apply_ex(c, ds.p, ds.ld, xa.p, ga, ba, mean_a, invstd_a, tot.p, tot.p + C, R, R_total, C, 0, dxa.p));
-            TK(ps_op_bn_train_bwd_apply_ex(c, ds.p, ds.ld, xb.p, gb, bb, mean_b, invstd_b, tot.p + 2 * C, tot.p + 3 * C, R, R_total, C, 0, dxb.p));
-            (void)st; (void)ya; (void)yb;
+            sync_bn_bwd_apply(a, ds, tot.p, dxa);
+            sync_bn_bwd_apply(b, ds, tot.p + 2 * C, dxb);
+            (void)ya; (void)yb;  // (held until here, as they always were: the step's pool footprint stays what it was)
             accum(xa_in, dxa);
             accum(xb_in, dxb);
         });
         return y;
+    }
+
+    // ---- both ends of the BatchNorm of the recompute-form layers (locse_bn_act, conv_bn_fused, conv_bn_rect) ------------------------------
+    // forward: float64 sums of y (at s64) and y^2 (at s64 + sq_off) over this rank's rows -- all-reduced here, n_reduce doubles, when the
+    // statistics are shared -- to a fresh [4, C] block mean | var | invstd | scale, and the moving statistics
+    Tn recomp_stats(const char* stage, double* s64, int64_t n_reduce, int64_t sq_off, int64_t R_total, const LayerP& lp)
+    {
+        const int64_t C = lp.cout;
+        if (sync_bn && coll_active()) allreduce(s64, n_reduce, 1);
+        Tn st4 = alloc(4, C, false);
+        Stage st(c, stage, 1);
+        launch_c(tr_locse_stats_kernel, C, s64, (double)R_total, params + lp.gamma, (int)C, kBnEps, st4.p, buffers + lp.mov_mean, buffers + lp.mov_var, kBnMomentum,
+                 (int)sq_off);
+        return st4;
+    }
+    // backward: acc = S1[C] | S2[C] | ... (this rank's sums) -> dbeta = S1, dgamma = S2 and tot = S1 | S2, summed over the ranks when shared
+    Tn recomp_bwd_sums(const char* stage, const float* acc, int64_t C, float* ggamma, float* gbeta)
+    {
+        Tn tot = alloc(2, C, false);
+        {
+            Stage st(c, stage, 1);
+            launch_c(tr_locse_local_kernel, C, acc, (int)C, ggamma, gbeta, tot.p);
+        }
+        if (sync_bn && coll_active()) allreduce(tot.p, 2 * C, 0);
+        return tot;
     }
 
     // f_xyz = LeakyReLU(BN_train(relative_pos_encoding(xyz, idx) . W + b)) -> [B*N*K, h] (out: optional column block), with nothing but
@@ -1013,28 +1008,19 @@ struct ps_trainer {
         TK(ps_op_locse_train_sums(c, xyz, idx, B, N, K, W, b, h, s64));
         if (n_comp) {
             Stage st(c, "train_bn_fwd", 1);
-            hipLaunchKernelGGL(tr_f2d_kernel, dim3(ceil_div(n_comp, 64)), dim3(64), 0, stream(), companion->sums(), (int)n_comp, s64 + 2 * h);
-            TK_HIP(hipGetLastError());
+            launch_c(tr_f2d_kernel, n_comp, companion->sums(), (int)n_comp, s64 + 2 * h);
         }
-        if (sync) allreduce(s64, 2 * h + n_comp, 1);
+        Tn st4 = recomp_stats("train_locse_fwd", s64, 2 * h + n_comp, h, R_total, lp);  // mean | var | invstd | scale
+        float *mean = st4.p, *invstd = st4.p + 2 * h, *scale = st4.p + 3 * h;
         if (n_comp) {
             Stage st(c, "train_bn_fwd", 1);
-            hipLaunchKernelGGL(tr_d2f_kernel, dim3(ceil_div(n_comp, 64)), dim3(64), 0, stream(), s64 + 2 * h, (int)n_comp, companion->sums());
-            TK_HIP(hipGetLastError());
-        }
-        Tn st4 = alloc(4, h, false);  // mean | var | invstd | scale
-        float *mean = st4.p, *invstd = st4.p + 2 * h, *scale = st4.p + 3 * h;
-        {
-            Stage st(c, "train_locse_fwd", 1);
-            hipLaunchKernelGGL(tr_locse_stats_kernel, dim3(ceil_div(h, 64)), dim3(64), 0, stream(), s64, (double)R_total, gamma, (int)h, kBnEps, st4.p,
-                               buffers + lp.mov_mean, buffers + lp.mov_var, kBnMomentum, (int)h);
-            TK_HIP(hipGetLastError());
+            launch_c(tr_d2f_kernel, n_comp, s64 + 2 * h, (int)n_comp, companion->sums());
         }
         Tn y = out ? *out : alloc(R, h);
         y.req = true;
         y.b16 = act16;
         {
-            ActScope as(c, act16);
+            Scoped<bool> as(c->train_act_bf16, act16);
             TK(ps_op_locse_train_apply(c, xyz, idx, B, N, K, W, b, h, mean, scale, beta, y.p, y.ld));
         }
         float *gW = grads + lp.w, *gb = grads + lp.b, *ggamma = grads + lp.gamma, *gbeta = grads + lp.beta;
@@ -1045,17 +1031,12 @@ struct ps_trainer {
                 throw TrainError{PS_ESTATE};
             }
             {
-                ActScope as(c, act16);
+                Scoped<bool> as(c->train_act_bf16, act16);
                 TK(ps_op_locse_train_bwd(c, xyz, idx, B, N, K, W, b, h, scale, beta, mean, invstd, dz.p, dz.ld, acc.p));
             }
-            Tn tot = alloc(2, h, false);
-            Stage st(c, "train_locse_bwd", 2);
-            hipLaunchKernelGGL(tr_locse_local_kernel, dim3(ceil_div(h, 64)), dim3(64), 0, stream(), acc.p, (int)h, ggamma, gbeta, tot.p);
-            TK_HIP(hipGetLastError());
-            if (sync) allreduce(tot.p, 2 * h, 0);
-            hipLaunchKernelGGL(tr_locse_wgrad_kernel, dim3(ceil_div(h, 64)), dim3(64), 0, stream(), acc.p, tot.p, gamma, invstd, (int)h, (float)R,
-                               1.0f / (float)R_total, gW, gb);
-            TK_HIP(hipGetLastError());
+            Tn tot = recomp_bwd_sums("train_locse_bwd", acc.p, h, ggamma, gbeta);
+            Stage st(c, "train_locse_bwd", 1);
+            launch_c(tr_locse_wgrad_kernel, h, acc.p, tot.p, gamma, invstd, (int)h, (float)R, 1.0f / (float)R_total, gW, gb);
             (void)st4;
         });
         return y;
@@ -1071,40 +1052,32 @@ struct ps_trainer {
         //  8-channel layer stays fp32 in both forms)
         const int max_c = c->tune.convbn_max_c;  // 64 (A/B knob of the experiments in DESIGN.md)
         if (lp.cout > max_c) return false;
-        return x.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x.p) & 15) == 0;  // (a column block of a concat buffer is fine)
+        return x.vec_ok();  // (a column block of a concat buffer is fine)
     }
     Tn conv_bn_fused(const Tn& x, const LayerP& lp, bool defer_dgrad, const Tn* out = nullptr)
     {
         const int64_t R = x.R, h = lp.cout, CP = h < 16 ? 16 : h;
-        const bool sync = sync_bn && coll_active();
-        const int64_t R_total = sync ? R * world : R;
-        const float *W = params + lp.w, *b = params + lp.b, *gamma = params + lp.gamma, *beta = params + lp.beta;
+        const int64_t R_total = sync_bn && coll_active() ? R * world : R;
+        const float *W = params + lp.w, *b = params + lp.b, *beta = params + lp.beta;
         Tn sums = alloc(1, 6 * CP, false);  // 3 CP doubles: sum y | sum y^2 | sum x
         double* s64 = reinterpret_cast<double*>(sums.p);
         const bool act16 = x.b16;  // (bfloat16 rows in, bfloat16 rows out)
         {
-            ActScope as(c, act16);
+            Scoped<bool> as(c->train_act_bf16, act16);
             TK(ps_op_conv_bn_train_sums(c, x.p, x.ld, W, b, R, h, s64));
         }
-        if (sync) allreduce(s64, 2 * CP, 1);
-        Tn st4 = alloc(4, h, false);  // mean | var | invstd | scale
+        Tn st4 = recomp_stats("train_convbn_fwd", s64, 2 * CP, CP, R_total, lp);  // mean | var | invstd | scale
         float *mean = st4.p, *invstd = st4.p + 2 * h, *scale = st4.p + 3 * h;
-        {
-            Stage st(c, "train_convbn_fwd", 1);
-            hipLaunchKernelGGL(tr_locse_stats_kernel, dim3(ceil_div(h, 64)), dim3(64), 0, stream(), s64, (double)R_total, gamma, (int)h, kBnEps, st4.p,
-                               buffers + lp.mov_mean, buffers + lp.mov_var, kBnMomentum, (int)CP);
-            TK_HIP(hipGetLastError());
-        }
         Tn z = out ? *out : alloc(R, h);
         z.req = true;
         z.b16 = act16;
         {
-            ActScope as(c, act16);
+            Scoped<bool> as(c->train_act_bf16, act16);
             TK(ps_op_conv_bn_train_apply(c, x.p, x.ld, W, b, R, h, mean, scale, beta, z.p, z.ld));
         }
         float *gW = grads + lp.w, *gb = grads + lp.b, *ggamma = grads + lp.gamma, *gbeta = grads + lp.beta;
         record(z, [=](const Tn& dz_in) {
-            const bool dz_ok = dz_in.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(dz_in.p) & 15) == 0;
+            const bool dz_ok = dz_in.vec_ok();
             if (dz_in.b16 != act16 || (act16 && !dz_ok)) {  // (bfloat16 rows in and out: so are the gradient rows dz and dx)
                 ps::set_error("trainer: conv_bn_fused: gradient rows in the wrong storage format");
                 throw TrainError{PS_ESTATE};
@@ -1112,16 +1085,10 @@ struct ps_trainer {
             const Tn dz = dz_ok ? dz_in : contig(dz_in);
             Tn acc = alloc(1, 3 * h, false);
             {
-                ActScope as(c, act16);
+                Scoped<bool> as(c->train_act_bf16, act16);
                 TK(ps_op_conv_bn_train_bwd_sums2(c, x.p, x.ld, W, b, R, h, mean, invstd, scale, beta, dz.p, dz.ld, acc.p));
             }
-            Tn tot = alloc(2, h, false);
-            {
-                Stage st(c, "train_convbn_bwd", 1);
-                hipLaunchKernelGGL(tr_locse_local_kernel, dim3(ceil_div(h, 64)), dim3(64), 0, stream(), acc.p, (int)h, ggamma, gbeta, tot.p);
-                TK_HIP(hipGetLastError());
-            }
-            if (sync) allreduce(tot.p, 2 * h, 0);
+            Tn tot = recomp_bwd_sums("train_convbn_bwd", acc.p, h, ggamma, gbeta);
             auto apply = [=]() {
                 auto it = grad_of.find(x.id);
                 const bool add = it != grad_of.end();
@@ -1132,7 +1099,7 @@ struct ps_trainer {
                     throw TrainError{PS_ESTATE};
                 }
                 {
-                    ActScope as(c, act16);
+                    Scoped<bool> as(c->train_act_bf16, act16);
                     TK(ps_op_conv_bn_train_bwd_apply_w(c, x.p, x.ld, W, b, R, h, mean, invstd, scale, beta, tot.p, 1.0f / (float)R_total, dz.p, dz.ld, add ? 1 : 0,
                                                        dx.p, dx.ld, gW, gb));
                 }
@@ -1159,7 +1126,7 @@ struct ps_trainer {
         if (!opt.fused_convbn || lp.kind == kDeconv || lp.b < 0 || lp.gamma < 0 || !ps_op_convbn_train_supported(lp.cin, lp.cout)) return false;
         const int max_w = c->tune.convbn_rect_max;  // (A/B knob: cin * cout)
         if (lp.cin * lp.cout > max_w) return false;
-        return x.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x.p) & 15) == 0;
+        return x.vec_ok();
     }
     // addend (optional): z = LeakyReLU(BN(x . W + b) + addend) -- the residual sum of dilated_res_block in the pass that writes the second
     // summand (ps_op_convbn_train_apply_add); `leaky` must be false then.  Its backward first forms ds = dz lrelu'(z), which is the
@@ -1169,21 +1136,13 @@ struct ps_trainer {
         const bool fused_add = addend_in != nullptr;
         const Tn addend = fused_add ? *addend_in : Tn();
         const int64_t R = x.R, ci = lp.cin, co = lp.cout;
-        const bool sync = sync_bn && coll_active();
-        const int64_t R_total = sync ? R * world : R;
-        const float *W = params + lp.w, *b = params + lp.b, *gamma = params + lp.gamma, *beta = params + lp.beta;
+        const int64_t R_total = sync_bn && coll_active() ? R * world : R;
+        const float *W = params + lp.w, *b = params + lp.b, *beta = params + lp.beta;
         Tn sums = alloc(1, 4 * co, false);  // 2 cout doubles: sum y | sum y^2
         double* s64 = reinterpret_cast<double*>(sums.p);
         TK(ps_op_convbn_train_sums(c, x.p, x.ld, W, b, R, ci, co, s64));
-        if (sync) allreduce(s64, 2 * co, 1);
-        Tn st4 = alloc(4, co, false);  // mean | var | invstd | scale
+        Tn st4 = recomp_stats("train_convbn_fwd", s64, 2 * co, co, R_total, lp);  // mean | var | invstd | scale
         float *mean = st4.p, *invstd = st4.p + 2 * co, *scale = st4.p + 3 * co;
-        {
-            Stage st(c, "train_convbn_fwd", 1);
-            hipLaunchKernelGGL(tr_locse_stats_kernel, dim3(ceil_div(co, 64)), dim3(64), 0, stream(), s64, (double)R_total, gamma, (int)co, kBnEps, st4.p,
-                               buffers + lp.mov_mean, buffers + lp.mov_var, kBnMomentum, (int)co);
-            TK_HIP(hipGetLastError());
-        }
         Tn z = alloc(R, co);
         if (fused_add)
             TK(ps_op_convbn_train_apply_add(c, x.p, x.ld, W, b, R, ci, co, mean, scale, beta, addend.p, addend.ld, z.p, z.ld));
@@ -1207,22 +1166,16 @@ struct ps_trainer {
                 }
                 dz_in = ds;
             }
-            const bool dz_ok = dz_in.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(dz_in.p) & 15) == 0;
+            const bool dz_ok = dz_in.vec_ok();
             const Tn dz = dz_ok ? dz_in : contig(dz_in);
             Tn acc = alloc(1, 2 * co, false);
             TK(ps_op_convbn_train_bwd_sums(c, x.p, x.ld, W, b, R, ci, co, mean, invstd, scale, beta, leaky ? 1 : 0, dz.p, dz.ld, acc.p));
-            Tn tot = alloc(2, co, false);
-            {
-                Stage st(c, "train_convbn_bwd", 1);
-                hipLaunchKernelGGL(tr_locse_local_kernel, dim3(ceil_div(co, 64)), dim3(64), 0, stream(), acc.p, (int)co, ggamma, gbeta, tot.p);
-                TK_HIP(hipGetLastError());
-            }
-            if (sync) allreduce(tot.p, 2 * co, 0);
+            Tn tot = recomp_bwd_sums("train_convbn_bwd", acc.p, co, ggamma, gbeta);
             Tn dx;
             int add = 0;
             if (x.req) {
                 auto it = grad_of.find(x.id);
-                add = it != grad_of.end() && it->second.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(it->second.p) & 15) == 0 ? 1 : 0;
+                add = it != grad_of.end() && it->second.vec_ok() ? 1 : 0;
                 dx = add ? it->second : alloc(R, ci);
             }
             TK(ps_op_convbn_train_bwd_apply(c, x.p, x.ld, W, b, R, ci, co, mean, invstd, scale, beta, leaky ? 1 : 0, tot.p, 1.0f / (float)R_total, dz.p, dz.ld, add,
@@ -1231,6 +1184,23 @@ struct ps_trainer {
             (void)st4;
         });
         return z;
+    }
+
+    // the gradient of a gathered source x [B*N, d] from the gradient rows of its gather (rows [B*rows_per_cloud, d], row stride ldr).
+    // Deterministic: the fixed-order gather-reduction over the table's inverse index -- the FIRST gradient of x is written (every row, empty
+    // segments as zeros: no zero-filled buffer to add into), later ones are accumulated; otherwise a float-atomic scatter-add
+    void gathered_grad(const Tn& x, const int32_t* idx, int64_t B, int64_t N, int64_t rows_per_cloud, const float* rows, int64_t ldr, int64_t d)
+    {
+        if (opt.deterministic) {
+            const bool fresh = !grad_of.count(x.id);
+            Tn dst = fresh ? alloc(x.R, x.C) : accum_buffer(x);
+            const Inv& iv = inverse(idx, B, N, rows_per_cloud);
+            reduce_rows(iv, rows, ldr, d, dst.p, dst.ld, fresh ? 0 : 1);
+            if (fresh) grad_of[x.id] = dst;
+        } else {
+            Tn dst = accum_buffer(x);
+            TK(ps_op_scatter_add_rows_ex(c, rows, ldr, idx, B, N, rows_per_cloud, d, dst.p));
+        }
     }
 
     // x [B*N, d], idx [B, M, K] -> [B*M*K, d]; out: optional column block of a wider tensor that receives the rows
@@ -1243,25 +1213,12 @@ struct ps_trainer {
         TK(ps_op_gather_neighbour_ex(c, x.p, idx, B, N, M, K, d, o.p, o.ld));
         const Tn xin = x_in;
         record(o, [=](const Tn& dy) {
-            if (opt.deterministic && !grad_of.count(xin.id)) {
-                // first gradient of x: the gather-reduction writes every row (empty segments as zeros): no zero-filled buffer to add into
-                Tn fresh = alloc(xin.R, xin.C);
-                const Inv& iv = inverse(idx, B, N, M * K);
-                reduce_rows(iv, dy.p, dy.ld, d, fresh.p, fresh.ld, 0);
-                grad_of[xin.id] = fresh;
-                return;
-            }
-            Tn buf = accum_buffer(xin);
-            if (!buf.contiguous()) {
+            auto have = grad_of.find(xin.id);
+            if (have != grad_of.end() && !have->second.contiguous()) {
                 ps::set_error("trainer: scatter-add into a strided gradient");
                 throw TrainError{PS_ESTATE};
             }
-            if (opt.deterministic) {
-                const Inv& iv = inverse(idx, B, N, M * K);
-                reduce_rows(iv, dy.p, dy.ld, d, buf.p, buf.ld, 1);
-            } else {
-                TK(ps_op_scatter_add_rows_ex(c, dy.p, dy.ld, idx, B, N, M * K, d, buf.p));
-            }
+            gathered_grad(xin, idx, B, N, M * K, dy.p, dy.ld, d);
         });
         return o;
     }
@@ -1334,8 +1291,7 @@ struct ps_trainer {
                 Stage st(c, "train_wgrad", 1);
                 TK(wgrad_partial(c, fset.p, fset.ld, ds.p, ds.ld, RK, d, d, part.p, nullptr));
             }
-            wjobs.push_back(WgradJob{part.p, gW.p, (int)nb, (int)d, (int)d, 0});
-            wkeep.push_back(part);
+            queue_wgrad(part, gW.p, nb, d, d);
         });
         return agg;
     }
@@ -1353,9 +1309,8 @@ struct ps_trainer {
     bool att_gemm_split_ok(const Tn& f_src, const int32_t* idx, const Tn& f_xyz, int64_t B, int64_t M, int64_t K) const
     {
         const int64_t d = 2 * f_src.C, rows = B * M * K;
-        auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
         return opt.fused_att && att_gemm_on && c->train_b3 && ps_op_att_pool_gemm_supported(K, d) && d <= 256 /* (the split-source kernels) */ && rows >= 16384 && rows < (1ll << 31) && d % 128 == 0 &&
-               f_src.ld % 4 == 0 && f_xyz.ld % 4 == 0 && f_xyz.C == f_src.C && al(f_src.p) && al(f_xyz.p) && al(idx) && f_src.R / B * f_src.ld < (1ll << 31);
+               f_src.vec_ok() && f_xyz.vec_ok() && f_xyz.C == f_src.C && (reinterpret_cast<uintptr_t>(idx) & 15) == 0 && f_src.R / B * f_src.ld < (1ll << 31);
     }
     Tn attpool_gemm_split(const Tn& f_src_in, const int32_t* idx, int64_t B, int64_t M, int64_t K, const Tn& f_xyz, const Tn& W, const Tn& gW)
     {
@@ -1371,16 +1326,7 @@ struct ps_trainer {
             Tn rows = alloc(RK, h, false), ds = alloc(RK, d, false);
             TK(ps_op_att_pool_gemm_bwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.p, dfx.ld, add_in_place ? 1 : 0,
                                              ds.p, ds.ld));
-            if (opt.deterministic) {
-                const bool fresh_src = !grad_of.count(f_src.id);  // (first gradient of f_src: written, not added into zeros)
-                Tn dsrc = fresh_src ? alloc(f_src.R, f_src.C) : accum_buffer(f_src);
-                const Inv& iv = inverse(idx, B, N, M * K);
-                reduce_rows(iv, rows.p, h, h, dsrc.p, dsrc.ld, fresh_src ? 0 : 1);
-                if (fresh_src) grad_of[f_src.id] = dsrc;
-            } else {
-                Tn dsrc = accum_buffer(f_src);
-                TK(ps_op_scatter_add_rows_ex(c, rows.p, h, idx, B, N, M * K, h, dsrc.p));
-            }
+            gathered_grad(f_src, idx, B, N, M * K, rows.p, h, h);
             const int64_t nb = wgrad_split_slabs(c, f_src.p, f_src.ld, idx, f_xyz.p, f_xyz.ld, ds.p, ds.ld, RK, d, d);
             if (nb <= 0) {
                 ps::set_error("trainer: the split-source weight gradient does not apply (rows %lld, d %lld)", (long long)RK, (long long)d);
@@ -1391,8 +1337,7 @@ struct ps_trainer {
                 Stage st(c, "train_wgrad", 1);
                 TK(wgrad_b3_partial_split(c, f_src.p, f_src.ld, idx, N, M * K, f_xyz.p, f_xyz.ld, ds.p, ds.ld, RK, d, d, part.p));
             }
-            wjobs.push_back(WgradJob{part.p, gW.p, (int)nb, (int)d, (int)d, 0});
-            wkeep.push_back(part);
+            queue_wgrad(part, gW.p, nb, d, d);
             if (!add_in_place) accum(f_xyz, dfx);
             run_deferred(f_xyz.id);
         });
@@ -1407,7 +1352,7 @@ struct ps_trainer {
         Tn agg = alloc(B * M, d);
         const bool act16 = f_xyz.b16;  // (the f_xyz half as bfloat16 rows)
         {
-            ActScope as(c, act16);
+            Scoped<bool> as(c->train_act_bf16, act16);
             // d = 128 in the bf16-MLP mode: the forward on the frame of the large GEMMs (attpool_gemm.hip: scores in accumulator tiles,
             // the bfloat16 rows of f_xyz ARE operand fragments) -- 0.37 -> 0.2x ms per pooling; the backward stays with the per-point
             // kernel, which owns the weight gradient
@@ -1419,7 +1364,7 @@ struct ps_trainer {
                 TK(ps_op_att_pool_train_fwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, K, d, agg.p));
         }
         record(agg, [=](const Tn& dy_in) {
-            ActScope as(c, act16);
+            Scoped<bool> as(c->train_act_bf16, act16);
             const Tn dy = contig(dy_in);
             // f_xyz usually has a gradient already (the h -> h convolution's input gradient ran first): the kernel adds into it instead of
             // writing a second tensor that an axpy pass then folds in (4 passes over [N*K, h] -> 2)
@@ -1427,21 +1372,14 @@ struct ps_trainer {
             const bool add_in_place = have != grad_of.end() && have->second.C == h && have->second.R == B * M * K && have->second.b16 == act16;
             Tn dfx = add_in_place ? have->second : alloc(B * M * K, h);
             if (!add_in_place) dfx.b16 = act16;  // (the gradient rows of the bfloat16-stored half are bfloat16 as well)
-            struct Flag {
-                ps_context* c;
-                Flag(ps_context* ctx, bool on) : c(ctx) { c->att_df_accum = on; }
-                ~Flag() { c->att_df_accum = false; }
-            } flag(c, add_in_place);
-            const bool fresh_src = opt.deterministic && !grad_of.count(f_src.id);  // (first gradient of f_src: written, not added into zeros)
-            Tn dsrc = fresh_src ? alloc(f_src.R, f_src.C) : accum_buffer(f_src);  // the gathered half's gradient is added in place
+            Scoped<bool> flag(c->att_df_accum, add_in_place);  // (set nowhere else, and this closure does not nest: false on entry)
             if (opt.deterministic) {
-                // ... as plain rows first, then summed per source row in ascending row order (no float atomics)
+                // the gathered half's gradient as plain rows first, then summed per source row in ascending row order (no float atomics)
                 Tn rows = alloc(B * M * K, h, false);
                 TK(ps_op_att_pool_train_bwd_split_rows(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.p, dfx.ld, gW.p));
-                const Inv& iv = inverse(idx, B, N, M * K);
-                reduce_rows(iv, rows.p, h, h, dsrc.p, dsrc.ld, fresh_src ? 0 : 1);
-                if (fresh_src) grad_of[f_src.id] = dsrc;
+                gathered_grad(f_src, idx, B, N, M * K, rows.p, h, h);
             } else {
+                Tn dsrc = accum_buffer(f_src);  // the gathered half's gradient is added in place
                 TK(ps_op_att_pool_train_bwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, dsrc.p, dsrc.ld, dfx.p, dfx.ld, gW.p));
             }
             if (!add_in_place) accum(f_xyz, dfx);
@@ -1478,15 +1416,8 @@ struct ps_trainer {
                                ((reinterpret_cast<uintptr_t>(dy.p) | reinterpret_cast<uintptr_t>(out.p) | reinterpret_cast<uintptr_t>(x.p)) & 15) == 0;
             Tn buf = fresh ? alloc(xin.R, xin.C) : accum_buffer(xin);
             if (fresh) grad_of[xin.id] = buf;
-            struct Flag {
-                ps_context* c;
-                Flag(ps_context* ctx, bool on) : c(ctx) { c->pool_bwd_overwrite = on; }
-                ~Flag()
-                {
-                    c->pool_bwd_overwrite = false;
-                    c->walk_order = nullptr;
-                }
-            } flag(c, fresh);
+            Scoped<bool> flag(c->pool_bwd_overwrite, fresh);  // (set nowhere else: false on entry)
+            Scoped<const int32_t*> walk(c->walk_order, nullptr);  // the hint set below never outlives this op: NULL again behind it
             if (by_inverse && buf.contiguous()) {
                 const Inv& iv = inverse(neigh, B, N, N * K);  // (shared with the level's gathers: the pooling rows are a prefix of every segment)
                 c->walk_order = iv.order;  // (the level's leaf order: the kernel walks its destinations in it, XCD by XCD)
@@ -1552,8 +1483,7 @@ struct ps_trainer {
         if (bn && !out && !fp32_only && !defer_dgrad && convbn_rect_ok(x, lp)) return conv_bn_rect(x, lp, act);
         // (the square layers on [N] rows -- mlp1, att_pooling's mlp: 16 -> 16, 32 -> 32, 64 -> 64 -- measured no gain in the recompute form:
         //  43.9 / 43.8 ms without, 44.5 / 43.9 ms with; they keep the GEMM + BatchNorm kernels)
-        Tn y = linear(x, Wt(lp), lp.b >= 0 ? params + lp.b : nullptr, gWt(lp), lp.b >= 0 ? grads + lp.b : nullptr, lp.kind == kDeconv, nullptr, fp32_only,
-                      defer_dgrad);
+        Tn y = linear(x, lp, nullptr, fp32_only, defer_dgrad);
         if (bn) y = bn_act(y, lp, act, out);
         return y;
     }
@@ -1583,8 +1513,7 @@ struct ps_trainer {
         Tn agg;
         if (opt.fused_att && ps_op_att_pool_train_supported(K, fcat.C)) {
             agg = attpool(fcat, W, gW, K);  // levels whose [N*K, d] tensors are large: one kernel per direction
-        } else if (opt.fused_att && att_gemm_on && att_gemm_pays(K, fcat.C) && fcat.ld % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(fcat.p) & 15) == 0) {
+        } else if (opt.fused_att && att_gemm_on && att_gemm_pays(K, fcat.C) && fcat.vec_ok()) {
             agg = attpool_gemm(fcat, W, gW, K);  // the wide levels: scores in registers on the frame of the large GEMMs
         } else {
             Tn s = linear(fcat, W, nullptr, gW, nullptr);
@@ -1601,7 +1530,7 @@ struct ps_trainer {
         Tn x = external(const_cast<float*>(features), B * pyr->n[0], cfg.in_channels, false);
         begin_section("fc0");
         const LayerP& fc0 = layer("fc0");
-        Tn f = linear(x, P(fc0.w, fc0.cin, fc0.cout), params + fc0.b, G(fc0.w, fc0.cin, fc0.cout), grads + fc0.b);
+        Tn f = linear(x, fc0);
         f = bn_act(f, fc0, true);
         std::vector<Tn> enc;
         for (int i = 0; i < L; ++i) {
@@ -1620,8 +1549,7 @@ struct ps_trainer {
             PendingBn pend1;
             Tn f_pc, pair_sums;
             if (sync_merge && l_mlp1.gamma >= 0 && lfa1.gamma >= 0 && !convbn_rect_ok(feature, l_mlp1)) {
-                Tn x1 = linear(feature, Wt(l_mlp1), l_mlp1.b >= 0 ? params + l_mlp1.b : nullptr, gWt(l_mlp1), l_mlp1.b >= 0 ? grads + l_mlp1.b : nullptr,
-                               l_mlp1.kind == kDeconv);
+                Tn x1 = linear(feature, l_mlp1);
                 if (!locse_fused) pair_sums = alloc(1, 2 * l_mlp1.cout + 2 * hloc, false);  // (op-by-op LocSE: both layers' float sums side by side)
                 pend1 = bn_begin(x1, l_mlp1, true, nullptr, locse_fused ? nullptr : &pair_sums, 0);
                 f_pc = pend1.y;  // (shape, pitch and address are final; the values arrive with bn_end, before the first reader is enqueued)
@@ -1637,8 +1565,7 @@ struct ps_trainer {
             auto locse = [&](const Tn* out) -> Tn {
                 if (!locse_fused && pend1.open) {
                     // the op-by-op form of the pair: both layers' sums in ONE float all-reduce
-                    Tn xr = linear(rel, Wt(lfa1), lfa1.b >= 0 ? params + lfa1.b : nullptr, gWt(lfa1), lfa1.b >= 0 ? grads + lfa1.b : nullptr, lfa1.kind == kDeconv,
-                                   nullptr, /*fp32_only*/ true);
+                    Tn xr = linear(rel, lfa1, nullptr, /*fp32_only*/ true);
                     PendingBn p2 = bn_begin(xr, lfa1, true, out, &pair_sums, 2 * l_mlp1.cout);
                     allreduce(pair_sums.p, 2 * l_mlp1.cout + 2 * hloc, 0);
                     bn_end(pend1);
@@ -1704,17 +1631,14 @@ struct ps_trainer {
             const LayerP& sl = layer(n + "shortcut");
             if (sync_merge && l_mlp2.gamma >= 0 && sl.gamma >= 0 && l_mlp2.cout == sl.cout) {
                 // shared statistics: mlp2 and the shortcut as one pair -- one all-reduce per direction for both (res_pair_sync)
-                auto lin = [&](const Tn& x, const LayerP& lp) {
-                    return linear(x, Wt(lp), lp.b >= 0 ? params + lp.b : nullptr, gWt(lp), lp.b >= 0 ? grads + lp.b : nullptr, lp.kind == kDeconv);
-                };
-                Tn xa = lin(f_agg2, l_mlp2);
-                Tn xb = lin(feature, sl);
+                Tn xa = linear(f_agg2, l_mlp2);
+                Tn xb = linear(feature, sl);
                 f_enc = res_pair_sync(xa, l_mlp2, xb, sl);
             } else {
                 Tn a = conv(f_agg2, n + "mlp2", true, false);
                 // the residual sum + LeakyReLU inside the shortcut's apply pass where that layer runs in the recompute form (levels 0-1)
                 const bool fuse = c->tune.train_fuse_residual;  // (A/B knob)
-                if (fuse && sl.gamma >= 0 && convbn_rect_ok(feature, sl) && a.contiguous() && a.ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.p) & 15) == 0 && a.req) {
+                if (fuse && sl.gamma >= 0 && convbn_rect_ok(feature, sl) && a.contiguous() && a.vec_ok() && a.req) {
                     f_enc = conv_bn_rect(feature, sl, false, &a);
                 } else {
                     Tn b = conv(feature, n + "shortcut", true, false);
@@ -1843,7 +1767,7 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
     const bool bf16 = t->opt.mlp_bf16 != 0;
     const bool was_bf16 = c->train_bf16;
     // (ps_set_train_act_bf16 is a public setter of the op-level surface: a flag left on by an op-level caller of a shared context must not
-    //  reach the ops this step calls outside an ActScope -- the row reductions and the split-source pooling read it directly)
+    //  reach the ops this step calls outside a Scoped setting of it --the row reductions and the split-source pooling read it directly)
     const bool was_act_bf16 = c->train_act_bf16;
     c->train_act_bf16 = false;
     int rc = PS_OK;
@@ -1927,20 +1851,12 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
     t->wkeep.clear();
     t->inv_cache.clear();
     if (rc != PS_OK) return rc;
-    if (!optimise) {
-        try {
+    try {
+        if (!optimise) {
             t->finish_profile();
-        } catch (const TrainError& e) {
-            return e.rc;
+            return PS_OK;
         }
-        return PS_OK;
-    }
-    try {
         t->mark("grad all-reduce");
-    } catch (const TrainError& e) {
-        return e.rc;
-    }
-    try {
         if (t->coll_active()) {
             // gradient synchronisation of config 4: ONE all-reduce of the flat fp32 gradient buffer, then the mean over the ranks
             t->allreduce(t->grads, t->n_params, 0);
@@ -1950,22 +1866,14 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
                 TK_HIP(hipGetLastError());
             }
         }
-    } catch (const TrainError& e) {
-        return e.rc;
-    }
-    t->step += 1;
-    try {
+        t->step += 1;
         t->mark("adam");
-    } catch (const TrainError& e) {
-        return e.rc;
-    }
-    const int arc = ps_op_adam(c, t->params, t->grads, t->adam_m, t->adam_v, t->n_params, t->opt.learning_rate, 0.9f, 0.999f, 1e-8f, t->step);
-    try {
+        const int arc = ps_op_adam(c, t->params, t->grads, t->adam_m, t->adam_v, t->n_params, t->opt.learning_rate, 0.9f, 0.999f, 1e-8f, t->step);
         t->finish_profile();
+        return arc;
     } catch (const TrainError& e) {
         return e.rc;
     }
-    return arc;
 }
 
 }  // namespace ps

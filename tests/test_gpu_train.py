@@ -10,7 +10,7 @@ import netcase
 pytestmark = pytest.mark.gpu
 
 
-def _setup(cfg, xyz, feats, seed=3, lr=1e-3, keep_prob=1.0, labels=None, sync_bn=False, oracle_pyramid=True, mlp_dtype="fp32"):
+def _setup(cfg, xyz, feats, seed=3, lr=1e-3, keep_prob=1.0, labels=None, sync_bn=False, oracle_pyramid=True, mlp_dtype="fp32", **trainer_kw):
     import torch
     from oracle import bindings as ob
     from oracle import randla_oracle as ro
@@ -22,7 +22,7 @@ def _setup(cfg, xyz, feats, seed=3, lr=1e-3, keep_prob=1.0, labels=None, sync_bn
     if labels is None:
         labels = rng.integers(0, cfg.num_classes, xyz.shape[:2]).astype(np.int32)
     cw = np.linspace(1.0, 2.0, cfg.num_classes).astype(np.float32)
-    tr = Trainer(cfg, params=params, learning_rate=lr, class_weights=cw, keep_prob=keep_prob, sync_bn=sync_bn, mlp_dtype=mlp_dtype)
+    tr = Trainer(cfg, params=params, learning_rate=lr, class_weights=cw, keep_prob=keep_prob, sync_bn=sync_bn, mlp_dtype=mlp_dtype, **trainer_kw)
     pyr = build_pyramid(torch.from_numpy(xyz).cuda(), cfg)
     host_pyr = None
     if oracle_pyramid:
@@ -42,22 +42,26 @@ def syncbn_labels(cfg, xyz):
     return np.random.default_rng(11).integers(0, cfg.num_classes, xyz.shape[:2]).astype(np.int32)
 
 
-@pytest.mark.parametrize("world,merged", [(2, True), (8, True), (2, False)], ids=["2", "8", "2-unmerged"])
-def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world, merged):
+@pytest.mark.parametrize("world,merged,op_by_op", [(2, True, False), (8, True, False), (2, False, False), (2, True, True)],
+                         ids=["2", "8", "2-unmerged", "2-opbyop"])
+def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world, merged, op_by_op):
     """BASELINE configs[3] semantics: `world` ranks with one cloud each and shared BatchNorm statistics take the same
     optimisation step as one rank with the batch of `world` clouds -- at 2 and at the 8 ranks of the node configs[3] names.  The ranks are
     processes on this one GPU joined by gloo (the collective is backend-agnostic; RCCL carries it on the 8-GPU node).  Also asserted at
     that world size: the number of all-reduce calls a step makes (ps_trainer_collective_stats) -- one for the flat gradient buffer plus
     two per BatchNorm layer with shared statistics (89 for the five-layer network's 44 layers) MINUS the merged ones: the independent
     pairs share a call (mlp2 || shortcut in both directions, mlp1 || LocSE-mlp1 forward: 15 calls less, 74) --, exactly one with per-GPU
-    statistics.  Unmerged (the worker sets train_merge_syncbn = 0 on its context before its trainer is created): the same step, 89 calls."""
+    statistics.  Unmerged (the worker sets train_merge_syncbn = 0 on its context before its trainer is created): the same step, 89 calls.
+    Op by op (fused_locse=False on the one-rank trainer and on the workers): the LocSE convolution as GEMM + BatchNorm, whose sums share
+    ONE float all-reduce with mlp1's -- the pair saves the same forward call per level as the fused form, so 74 again."""
     import os
     import subprocess
     import sys
     import torch
     cfg, xyz, feats = syncbn_case(world)
     labels = syncbn_labels(cfg, xyz)
-    tr, pyr, params, _, cw, _ = _setup(cfg, xyz, feats, labels=labels, oracle_pyramid=False)
+    trainer_kw = {"fused_locse": False} if op_by_op else {}
+    tr, pyr, params, _, cw, _ = _setup(cfg, xyz, feats, labels=labels, oracle_pyramid=False, **trainer_kw)
     loss = tr.train_step(pyr, torch.from_numpy(feats).cuda(), torch.from_numpy(labels).cuda())
     torch.cuda.synchronize()
     want_grad, want_flat, want_loss = tr.grad.cpu().numpy(), tr.flat.cpu().numpy(), float(loss)
@@ -71,9 +75,10 @@ def test_sync_bn_ranks_equal_one_rank_with_the_batch(tmp_path, world, merged):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     procs = []
+    flags = ([] if merged else ["--unmerged"]) + (["--op-by-op"] if op_by_op else [])
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, worker, out] + ([] if merged else ["--unmerged"]), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+        procs.append(subprocess.Popen([sys.executable, worker, out] + flags, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     logs = [p.communicate(timeout=900)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n".join(l[-2000:] for l in logs)
     got = [np.load(out + ".rank%d.npz" % r) for r in range(world)]
