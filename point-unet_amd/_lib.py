@@ -1,6 +1,7 @@
 """ctypes binding of libpointseg_hip.so -- the only door between the Python host code and the HIP kernels.
 
-The signatures below are include/pointseg.h verbatim.  The library is built in-tree by compile_op.sh
+The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
+(PREPARE_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -10,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpointseg_hip.so")
 PS_ABI_VERSION = 7  # include/pointseg.h
 PS_VOLUME_I16, PS_VOLUME_F32 = 1, 2
+PS_VOLUME_U8 = 3  # include/pointseg_prepare.h
 
 PS_MAX_LAYERS = 8
 c_f32p = ctypes.POINTER(ctypes.c_float)
@@ -259,6 +261,12 @@ PROTOTYPES = {
     "ps_randla_train_step": (ctypes.c_int, [c_vp, ctypes.POINTER(PsPyramid), c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
+# every symbol include/pointseg_prepare.h declares (dataset preparation in front of the entry points above; csrc/resample.hip)
+PREPARE_PROTOTYPES = {
+    "ps_volume_zoom": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32] + [ctypes.c_int64] * 3 + [ctypes.c_int32] + [ctypes.c_int64] * 3
+                       + [ctypes.c_uint32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -278,7 +286,7 @@ def lib():
         except Exception:  # pragma: no cover
             pass
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -5,6 +5,9 @@ pipeline of PointSegment/utils/dataPrepareBraTS.py (load_volume :31-72, convert_
     prepare_brats_volume                      + DataProcessing.grid_sub_sampling(sub_grid_size) and the 1-NN projection of the
                                               full cloud onto the sub-cloud (the reference asks sklearn's KDTree; here the
                                               exact HIP KNN -- equal distances, possibly a different index among exact ties)
+    resample_pancreas_ct ps_volume_zoom       the spline zooms, flip, crop and HU clip of PointSegment/utils/cvt_CT_down.py:79-104 and
+    zoom_volume                               cvt_CT.py:79-105 on a raw Pancreas CT + label (scipy.ndimage.zoom, order 3 / 0)
+    prepare_pancreas_volume, pancreas_mask    ps_volume_sample: the resampled CT + positive set -> the network's clouds
 """
 import ctypes
 
@@ -254,3 +257,127 @@ def prepare_pancreas_volume(volume, label=None, mask=None, n_point=180000, loops
     runtime.default_context(device).use_torch_stream()
     return _volume_sample(shape, device, volume=v, mask=m, probs=p, channel=channel, threshold=threshold, dilate=dilate, truth=t, label_src=lab,
                           n_point=int(n_point), loops=int(loops), seed=seed)
+
+
+# ---- Pancreas: raw CT -> the resampled volume prepare_pancreas_volume starts from (ps_volume_zoom, csrc/resample.hip) --------------------
+
+_ZOOM_DTYPES = {"torch.int16": _lib.PS_VOLUME_I16, "torch.float32": _lib.PS_VOLUME_F32, "torch.uint8": _lib.PS_VOLUME_U8}
+
+
+def _zoom_input(volume, dev, who):
+    import torch
+    t = volume if isinstance(volume, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(volume))
+    if str(t.dtype) not in _ZOOM_DTYPES:
+        raise ValueError("%s: dtype %s is none of int16, uint8, float32" % (who, t.dtype))
+    if t.dim() != 3:
+        raise ValueError("%s: expected a 3-D volume, got shape %s" % (who, tuple(t.shape)))
+    return t.to(dev).contiguous()
+
+
+def _zoom_shape(shape, zoom):
+    z = (zoom,) * 3 if np.isscalar(zoom) else tuple(zoom)
+    if len(z) != 3:
+        raise ValueError("zoom must be a scalar or three factors")
+    return tuple(int(round(n * float(f))) for n, f in zip(shape, z))  # scipy's own expression: Python's round, half to even
+
+
+def _zoom_dev(v, out_shape, order, flip_mask, clip, device):
+    """One ps_volume_zoom call on a contiguous device tensor."""
+    import torch
+    ctx = runtime.default_context(device)
+    ctx.use_torch_stream()
+    out = torch.empty(out_shape, dtype=v.dtype, device=v.device)
+    lo, hi = (0.0, 0.0) if clip is None else (float(clip[0]), float(clip[1]))
+    need = ctypes.c_int64(0)
+    lib = _lib.lib()
+    args = [ctx.handle, runtime.ptr(v), _ZOOM_DTYPES[str(v.dtype)], *(int(s) for s in v.shape), int(order), *(int(s) for s in out_shape), int(flip_mask),
+            int(clip is not None), lo, hi, runtime.ptr(out)]
+    _lib.check(lib.ps_volume_zoom(*args, None, ctypes.byref(need)))  # scratch == NULL: the size
+    scratch = torch.empty(int(need.value), dtype=torch.uint8, device=v.device)  # (stream-ordered like every tensor of the caller)
+    _lib.check(lib.ps_volume_zoom(*args, runtime.ptr(scratch), ctypes.byref(need)))
+    return out
+
+
+def _flip_mask(flip):
+    axes = (flip,) if np.isscalar(flip) else tuple(flip)
+    mask = 0
+    for a in axes:
+        if int(a) not in (0, 1, 2):
+            raise ValueError("flip axes must be 0, 1 or 2, got %r" % (a,))
+        mask |= 1 << int(a)
+    return mask
+
+
+def zoom_volume(volume, zoom, order=3, flip=(), clip=None, device=0):
+    """scipy.ndimage.zoom(volume, zoom, order=order) with scipy's defaults (mode='constant', cval=0, prefilter=True, grid_mode=False), on
+    the device: volume [n0, n1, n2] int16, uint8 or float32, numpy or torch, host or device; zoom a scalar or three factors; order 0 or 3.
+    flip: axes read reversed (np.flip(volume, flip) in front of the zoom); clip = (lo, hi): np.clip behind it.  The output shape is
+    scipy's, int(round(n * zoom)) per axis.  Returns a CUDA tensor of the input's dtype.  The rule, with the plane of zeros scipy leaves
+    where j * (n - 1) / (m - 1) rounds above n - 1, is stated in include/pointseg_prepare.h."""
+    import torch
+    if order not in (0, 3):
+        raise ValueError("zoom_volume: order must be 0 or 3")
+    v = _zoom_input(volume, torch.device("cuda", device), "zoom_volume")
+    shape = _zoom_shape(v.shape, zoom)
+    if min(shape) < 1:
+        raise ValueError("zoom_volume: zoom %r of shape %s leaves an empty volume %s" % (zoom, tuple(v.shape), shape))
+    return _zoom_dev(v, shape, order, _flip_mask(flip), clip, device)
+
+
+def resample_pancreas_ct(ct, seg=None, spacing_z=1.0, slice_thickness=1, down_scale=0.5, lower=-100, upper=240, flip_y=False, crop=None, device=0):
+    """The resampling of one NIH Pancreas-CT case, on the device, step by step as the reference's two scripts do it:
+    flip_y=False, crop=None is PointSegment/utils/cvt_CT_down.py:79-104; flip_y=True with crop is cvt_CT.py:79-105.
+
+        1. spacing_z != slice_thickness: zoom by (spacing_z / slice_thickness, 1, 1), order 3 on the CT (rounded to int16 again, as
+           scipy returns the input's dtype), order 0 on seg                                             (:80, 82)
+        2. flip_y: np.flip(ct, 1) -- the CT alone, "the dataset mismatch between label and data"         (cvt_CT.py:85)
+        3. crop = ((s0, e0), (s1, e1), (s2, e2)), inclusive ends, clamped to the volume, CT and seg      (cvt_CT.py:88-94)
+        4. down_scale != 1: zoom by down_scale on every axis, order 3 / order 0                          (:97-99 / :98-100)
+        5. clip the CT to [lower, upper]                                                                 (:103-104 / :104-105)
+
+    The flip is an index map of step 4's read (the crop box is mirrored to match) and the clip follows step 4's rounding, so both are
+    exact.  ct: int16 (other dtypes are taken as int16, as sitk.ReadImage(..., sitkInt16) does), seg: uint8 or None; numpy or torch,
+    host or device.  Axis order: the arrays are SimpleITK's, [z, y, x]; spacing_z is ct.GetSpacing()[-1].  The NIfTI the scripts write
+    from them and dataPreparePancreas.py then reads with nibabel is the transposed view [x, y, z].
+
+    Returns {"ct": int16 [z, y, x], "seg": uint8 [z, y, x] or None, "spacing_scale": (int(1 / down_scale), int(1 / down_scale),
+    slice_thickness / down_scale)} (the factors the scripts scale the x, y spacing by and the new z spacing, cvt_CT_down.py:148), the arrays as CUDA tensors.  They hand over
+    to the sampling without leaving HBM:
+
+        out = resample_pancreas_ct(ct, seg, spacing_z=2.5)
+        clouds = prepare_pancreas_volume(out["ct"].permute(2, 1, 0).contiguous(), label=out["seg"].permute(2, 1, 0).contiguous())
+    """
+    import torch
+    dev = torch.device("cuda", device)
+    c = ct if isinstance(ct, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ct))
+    c = _zoom_input(c.to(dev).to(torch.int16), dev, "resample_pancreas_ct")
+    s = None
+    if seg is not None:
+        s = seg if isinstance(seg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(seg))
+        s = _zoom_input(s.to(dev).to(torch.uint8), dev, "resample_pancreas_ct")
+        if tuple(s.shape) != tuple(c.shape):
+            raise ValueError("resample_pancreas_ct: seg must have the CT's shape")
+    if spacing_z != slice_thickness:
+        z = (spacing_z / slice_thickness, 1, 1)
+        shape = _zoom_shape(c.shape, z)
+        c = _zoom_dev(c, shape, 3, 0, None, device)
+        if s is not None:
+            s = _zoom_dev(s, shape, 0, 0, None, device)
+    flip = 2 if flip_y else 0
+    if crop is not None:
+        box = [(max(0, int(a)), min(n - 1, int(b)) + 1) for n, (a, b) in zip(c.shape, crop)]
+        if s is not None:
+            s = s[box[0][0]:box[0][1], box[1][0]:box[1][1], box[2][0]:box[2][1]].contiguous()
+        if flip_y:  # flip(ct, 1)[:, a:b] read through the flip is ct[:, n - b:n - a]
+            n1 = c.shape[1]
+            box[1] = (n1 - box[1][1], n1 - box[1][0])
+        c = c[box[0][0]:box[0][1], box[1][0]:box[1][1], box[2][0]:box[2][1]].contiguous()
+    clip = (lower, upper)
+    if down_scale != 1:
+        shape = _zoom_shape(c.shape, down_scale)
+        c = _zoom_dev(c, shape, 3, flip, clip, device)
+        if s is not None:
+            s = _zoom_dev(s, shape, 0, 0, None, device)
+    else:  # (no zoom left to carry the flip and the clip: an order-0 pass at the same shape is the copy that applies them)
+        c = _zoom_dev(c, tuple(c.shape), 0, flip, clip, device)
+    return {"ct": c, "seg": s, "spacing_scale": (int(1 / down_scale), int(1 / down_scale), slice_thickness / down_scale)}
