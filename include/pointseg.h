@@ -215,7 +215,10 @@ int ps_randla_tap(ps_randla* net, int which, float* host_out, int64_t count);
  * Off by default. */
 int ps_randla_keep_taps(ps_randla* net, int on);
 
-/* ---- op-by-op surface (Network.* static methods, RandLANet.py:337-401); device pointers --------------- */
+/* ---- op-by-op surface (Network.* static methods, RandLANet.py:337-401); device pointers ---------------
+ * Shapes: B, M >= 0 (an empty call returns PS_OK and writes nothing); N, K, d >= 1; N, M, K, d and M * K below 2^31 (the kernels
+ * take the per-cloud sizes as int).  A NULL pointer or a shape outside these returns PS_EINVAL before anything is enqueued, the
+ * output untouched. */
 /* gather_neighbour: pc f32[B,N,d], idx i32[B,M,K] -> out f32[B,M,K,d] */
 int ps_op_gather_neighbour(ps_context* ctx, const float* pc, const int32_t* idx, int64_t B, int64_t N,
                            int64_t M, int64_t K, int64_t d, float* out);
@@ -233,7 +236,8 @@ int ps_op_nearest_interpolation(ps_context* ctx, const float* feature, const int
 int ps_op_conv1x1(ps_context* ctx, const float* x, const float* w, const float* b, int64_t R, int64_t cin,
                   int64_t cout, int leaky, float* y);
 /* att_pooling up to (not including) its trailing conv2d: fset f32[R,K,d], wfc f32[d,d] ->
- * agg f32[R,d] = sum_K fset * softmax_K(fset . wfc) */
+ * agg f32[R,d] = sum_K fset * softmax_K(fset . wfc).  1 <= K <= 32, d >= 1, 0 <= R < 2^31 and K * d * 4 <= 160 KB (a row's
+ * neighbourhood sits in the LDS; the limit itself -- K = 32, d = 1280 -- launches on gfx950); anything else is PS_EINVAL. */
 int ps_op_att_pool(ps_context* ctx, const float* fset, const float* wfc, int64_t R, int64_t K, int64_t d,
                    float* agg);
 

@@ -35,6 +35,9 @@ __global__ __launch_bounds__(256) void gather_rows4_kernel(const float* __restri
     *reinterpret_cast<float4*>(out + row * ldo + 4 * q) = *reinterpret_cast<const float4*>(pc + (b * n_cloud + idx[row]) * (size_t)(4 * d4) + 4 * q);
 }
 
+// the kernels of this file take their per-cloud sizes as `int`
+static bool fits_int(int64_t v) { return v <= 0x7fffffffll; }
+
 static void launch_gather_rows(ps_context* c, const float* pc, const int32_t* idx, float* out, size_t rows, int rows_per_cloud, int n_cloud, int d, int ldo)
 {
     if ((d & 3) == 0 && (ldo & 3) == 0 && ((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(out)) & 15) == 0)
@@ -282,6 +285,7 @@ extern "C" int ps_op_gather_neighbour_ex(ps_context* c, const float* pc, const i
 {
     PS_CHECK(c && pc && idx && out, "ps_op_gather_neighbour: NULL argument");
     PS_CHECK(B >= 0 && N >= 1 && M >= 0 && K >= 1 && d >= 1 && ldo >= d, "ps_op_gather_neighbour: bad shape");
+    PS_CHECK(fits_int(N) && fits_int(K) && fits_int(M) && fits_int(M * K) && fits_int(ldo), "ps_op_gather_neighbour: N, M * K and ldo must stay below 2^31");
     const size_t rows = (size_t)B * M * K;
     if (!rows) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
@@ -300,6 +304,8 @@ extern "C" int ps_op_gather_neighbour(ps_context* c, const float* pc, const int3
 extern "C" int ps_op_relative_pos_encoding(ps_context* c, const float* xyz, const int32_t* idx, int64_t B, int64_t N, int64_t K, float* out)
 {
     PS_CHECK(c && xyz && idx && out, "ps_op_relative_pos_encoding: NULL argument");
+    PS_CHECK(B >= 0 && N >= 1 && K >= 1, "ps_op_relative_pos_encoding: bad shape");
+    PS_CHECK(fits_int(N) && fits_int(K), "ps_op_relative_pos_encoding: N and K must stay below 2^31");
     const size_t total = (size_t)B * N * K;
     if (!total) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
@@ -313,6 +319,8 @@ extern "C" int ps_op_random_sample(ps_context* c, const float* feature, const in
                                    int64_t d, float* out)
 {
     PS_CHECK(c && feature && pool_idx && out, "ps_op_random_sample: NULL argument");
+    PS_CHECK(B >= 0 && N >= 1 && M >= 0 && K >= 1 && d >= 1, "ps_op_random_sample: bad shape");
+    PS_CHECK(fits_int(N) && fits_int(M) && fits_int(K) && fits_int(d), "ps_op_random_sample: N, M, K and d must stay below 2^31");
     const size_t rows = (size_t)B * M;
     if (!rows) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
@@ -330,6 +338,8 @@ extern "C" int ps_op_random_sample_ties(ps_context* c, const float* feature, con
                                         float* out, uint8_t* ties)
 {
     PS_CHECK(c && feature && pool_idx && out && ties, "ps_op_random_sample_ties: NULL argument");
+    PS_CHECK(B >= 0 && N >= 1 && M >= 0 && K >= 1 && d >= 1, "ps_op_random_sample_ties: bad shape");
+    PS_CHECK(fits_int(N) && fits_int(M) && fits_int(d), "ps_op_random_sample_ties: N, M and d must stay below 2^31");
     PS_CHECK(d % 4 == 0 && K <= 255 && (reinterpret_cast<uintptr_t>(feature) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(ties) & 3) == 0 && B * std::max(N, M) < (1ll << 31),
              "ps_op_random_sample_ties: d must be a multiple of 4, K <= 255, buffers 16-byte aligned");
@@ -343,6 +353,8 @@ extern "C" int ps_op_nearest_interpolation(ps_context* c, const float* feature, 
                                            float* out)
 {
     PS_CHECK(c && feature && interp_idx && out, "ps_op_nearest_interpolation: NULL argument");
+    PS_CHECK(B >= 0 && N >= 1 && M >= 0 && d >= 1, "ps_op_nearest_interpolation: bad shape");
+    PS_CHECK(fits_int(N) && fits_int(M) && fits_int(d), "ps_op_nearest_interpolation: N, M and d must stay below 2^31");
     const size_t rows = (size_t)B * M;
     if (!rows) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
@@ -500,7 +512,7 @@ extern "C" int ps_op_conv1x1(ps_context* c, const float* x, const float* w, cons
 extern "C" int ps_op_att_pool(ps_context* c, const float* fset, const float* wfc, int64_t R, int64_t K, int64_t d, float* agg)
 {
     PS_CHECK(c && fset && wfc && agg, "ps_op_att_pool: NULL argument");
-    PS_CHECK(K >= 1 && K <= 32 && d >= 1, "ps_op_att_pool: K must be in 1..32");
+    PS_CHECK(K >= 1 && K <= 32 && d >= 1 && R >= 0 && fits_int(R), "ps_op_att_pool: K must be in 1..32, d >= 1, 0 <= R < 2^31");
     if (!R) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
     const size_t smem = (size_t)K * d * sizeof(float);

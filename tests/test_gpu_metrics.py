@@ -244,3 +244,53 @@ def test_validate_undefined_iou_is_nan(M):
     cm = np.array([[5, 0, 0], [1, 3, 0], [0, 0, 0]])
     s = M.scores_from_confusion(cm)
     assert math.isnan(s["iou"][2]) and s["mean_iou"] == pytest.approx((5 / 6 + 3 / 4) / 2) and s["accuracy"] == 8 / 9
+
+
+# ---- edges of the two post-processing kernels: C = 1, C = 32, an unaligned C = 4 base, NaN and +inf rows ---------------------------------
+def _edge_rows(rng, n, C):
+    """rows with NaN (np.argmax: the first NaN wins, whatever else the row holds), +inf, -inf, ties and a NaN in every position"""
+    v = rng.standard_normal((n, C)).astype(np.float32)
+    v[rng.random((n, C)) < 0.05] = np.nan
+    v[rng.random((n, C)) < 0.03] = np.inf
+    v[rng.random((n, C)) < 0.03] = -np.inf
+    v[::9] = v[::9, :1]                      # all equal: class 0
+    for c in range(C):                       # a lone NaN in column c; a NaN after a +inf; a NaN before it
+        v[100 + 3 * c] = rng.standard_normal(C)
+        v[100 + 3 * c, c] = np.nan
+        v[101 + 3 * c] = np.inf
+        v[101 + 3 * c, c] = np.nan
+        v[102 + 3 * c] = np.nan
+        v[102 + 3 * c, c] = np.inf
+    return v
+
+
+@pytest.mark.parametrize("C,off", [(1, 0), (32, 0), (4, 0), (4, 1), (5, 1)])
+def test_probs_to_labels_edges(M, C, off):
+    """probs_to_labels4_kernel for C = 4 on a 16-byte aligned base, probs_to_labels_kernel for every other C and for C = 4 one float into
+    its buffer; V = 2051 voxels (a partial last block); a table of C distinct entries."""
+    rng = np.random.default_rng(C + off)
+    V = 2051
+    v = _edge_rows(rng, V, C)
+    assert np.isnan(v).any(1).sum() > 100 and np.isinf(v).any()
+    table = [(7 * c + 3) % 256 for c in range(C)]
+    buf = torch.zeros(V * C + 8, device="cuda")
+    vol = buf[off:off + V * C].view(V, C)
+    vol.copy_(torch.from_numpy(v))
+    assert vol.data_ptr() % 16 == 4 * off
+    got = M.probs_to_labels(vol, table).cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        want = np.array(table, np.uint8)[np.argmax(v, 1)]
+    assert got.shape == (V,) and np.array_equal(got, want)
+    assert len(np.unique(want)) == C
+
+
+@pytest.mark.parametrize("C", [1, 32])
+def test_confusion_edges(M, C):
+    """confusion_kernel at one class and at the 32-class limit, rows with NaN / +-inf, labels outside [0, C) skipped."""
+    rng = np.random.default_rng(C)
+    n = 5003
+    logits = _edge_rows(rng, n, C)
+    labels = rng.integers(-1, C + 1, n).astype(np.int32)
+    cm = M.confusion(torch.from_numpy(logits).cuda(), torch.from_numpy(labels).cuda(), C).cpu().numpy()
+    assert np.array_equal(cm, _np_confusion(logits, labels, C))
+    assert cm.sum() == ((labels >= 0) & (labels < C)).sum() and (C == 1 or np.count_nonzero(cm) > C)
