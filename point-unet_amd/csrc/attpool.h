@@ -44,6 +44,10 @@ int att_pool32_stage(ps_context* c, const AttStage& s);
 bool att_pool32b_fits(const AttStage& s);
 int att_pool32b_stage(ps_context* c, const AttStage& s);
 
+// the 32x32 forms when they fit (the split-bf16 one first, when the context asks for it), otherwise att_pool16_stage
 int att_pool_stage(ps_context* c, const AttStage& s);
+// the 16x16x4 kernels of attpool.hip: the direct formulation when wfull is set (d <= 32), otherwise the pre-product kernel att_kernel --
+// what a level too large for the 32x32 forms (2^24 rows, 4 GiB of fg) runs
+int att_pool16_stage(ps_context* c, const AttStage& s);
 
 }  // namespace ps

@@ -561,6 +561,11 @@ int att_pool_stage(ps_context* c, const AttStage& s)
 {
     if (c->att_bf16x3 && att_pool32b_fits(s)) return att_pool32b_stage(c, s);
     if (att_pool32_fits(s)) return att_pool32_stage(c, s);
+    return att_pool16_stage(c, s);
+}
+
+int att_pool16_stage(ps_context* c, const AttStage& s)
+{
     AttArgs a;
     a.xyz = s.xyz; a.idx = s.idx; a.order = s.order; a.fg = s.fg;
     a.w1p = s.lfa1->wp; a.b1 = s.lfa1->bias;

@@ -35,6 +35,45 @@ int ps_debug_gemm32(ps_context* ctx, int split_bf16, const float* x1, int ld1, i
  * [nq k / sk, nq (k + 1) / sk), pd chunks in flight.  Host only: no GPU work. */
 int ps_debug_gemm32_plan(ps_context* ctx, int split_bf16, int64_t R, int cin, int cout, int* out4);
 
+/* A chain of 1..4 dense layers over R rows, act_l = act([act_{l-1} | extra_l] . W_l + b_l), act_{-1} = [x1[g1] | x2[g2]] (csrc/rowgemm.h: rowchain).
+ * W [cin, cout] and bias [cout] (NULL: zeros): HOST.  x1 / x2 / g1 / g2 / y / extra: DEVICE pointers (NULL: absent; g*m / g*n: batched gather, row r
+ * reads x[(r / gm) * gn + g[r]] when gm != 0).  y: optional store of the layer's rows, row stride ldy.  extra (layers > 0): plain rows of c_extra
+ * channels appended after the previous activations; extra_gather only exists to be refused. */
+typedef struct ps_debug_chain_layer {
+    const float* W;
+    const float* bias;
+    int cin, cout, leaky;
+    float* y;
+    int ldy;
+    const float* extra;
+    int ld_extra, c_extra;
+    const int32_t* extra_gather;
+} ps_debug_chain_layer;
+typedef struct ps_debug_chain_desc {
+    int n_layers;
+    ps_debug_chain_layer layer[4];
+    const float* x1; const int32_t* g1; int ld1, c1, g1m, g1n;
+    const float* x2; const int32_t* g2; int ld2, c2, g2m, g2n;
+    int64_t R;
+} ps_debug_chain_desc;
+/* Runs the chain with freshly packed weights (pack_weights + zero-padded bias, and the k-permuted image when cin % 16 == 0, as ps_randla_set_weights
+ * packs every layer); needs a GPU.  form 0: rowchain() as the network calls it, with a weight-image cache; 1: regchain with the image re-ordered
+ * inside the kernel (no cache); 2: rowchain_lds (the LDS-staged kernel); 3: layer by layer through rowgemm (16x16x4 kernels; un-stored rows go to
+ * scratch).  Returns PS_EINVAL, with a message, when the chain does not fit the form. */
+int ps_debug_chain(ps_context* ctx, const ps_debug_chain_desc* d, int form);
+/* The launch rowchain() makes for the same description: out4 = {form (0: the chain fits neither kernel, 1: regchain_kernel, 2: rowchain_kernel),
+ * workgroups, dynamic LDS bytes, rowchain_kernel's float4 input staging (log2 of the float4s per row; 0 = scalar staging)}.  A workgroup is four
+ * waves that each take one 16-row tile per round: past workgroups * 64 rows a wave walks to a second tile.  Host only: reads the channel counts
+ * and the alignment of the pointers, never what they point to; W / bias may be NULL. */
+int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4);
+/* One attentive-pooling stage (1 or 2) of encoder level `level` of a live network with its weights set, on the network's own packed images
+ * (log2(e) scaling and weight halves included); AttStage is filled as ps_randla_forward fills it.  xyz f32[n_total, 3], idx i32[n_total, K]
+ * (cloud-local), order i32[n_total] or NULL, fg f32[n_total, d/2 + d] = [f | G] for d >= 64 and f32[n_total, d/2] = f below, agg f32[n_total, d]:
+ * DEVICE pointers.  form 0: att_pool_stage (the product's dispatch), 1: att_pool32b_stage (split-bf16 32x32), 2: att_pool32_stage (fp32 32x32),
+ * 3: att_pool16_stage (16x16x4: the direct kernel at d <= 32, att_kernel above).  PS_EINVAL when the level does not fit the form. */
+int ps_debug_att_stage(ps_randla* net, int level, int stage, int form, const float* xyz, const int32_t* idx, const int32_t* order, const float* fg,
+                       int64_t n_total, int64_t n_cloud, float* agg);
+
 /* The experiment knobs of one context (csrc/common.h, struct ps::Tuning), by C++ field name ("inv_bucket", "gemm32b_rw", ...).  Set accepts
  * exactly the values the kernels are compiled for (the rules of the -DPS_TUNING_ENV build, without its clamping) and refuses anything else,
  * and unknown names, with PS_EINVAL.  Kernel dispatch reads the knobs per call; the native trainer reads its train_* knobs (and

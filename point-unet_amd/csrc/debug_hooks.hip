@@ -1,6 +1,7 @@
 // debug_hooks.hip -- the TEST-ONLY library libpointseg_debug.so (declarations: debug_hooks.h): doors used by the test-suite to
 // exercise the product's OWN host logic without a GPU -- the kd-tree construction rules (kdtree_host.hip) and the per-query
-// search routine that the HIP kernel instantiates (kdtree.h, __host__ __device__) -- and to read a device-built tree back.
+// search routine that the HIP kernel instantiates (kdtree.h, __host__ __device__) --, to read a device-built tree back, and to launch
+// kernel forms of the forward on their own (one dense layer, a layer chain, an attention stage) that the network picks by shape.
 // Built next to the product library and linked against it; nothing in the product library or the Python package refers to it
 // (tests/conftest.py binds it) -- it is not a CPU fallback.  The two pure-host doors (ps_debug_knn_host, ps_debug_kdtree_host) live
 // in debug_host.hip, which is also built on its own under the host sanitizers (`make asan-host`).
@@ -12,6 +13,8 @@
 #include "kdtree_host.h"
 #include "rowgemm.h"
 #include "attpool.h"
+#include "debug_hooks.h"
+#include "randla_net.h"
 
 using namespace ps;
 
@@ -74,6 +77,192 @@ extern "C" int ps_debug_gemm32_plan(ps_context* c, int split_bf16, int64_t R, in
     out4[2] = p.sk;
     out4[3] = p.pd;
     return PS_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------
+// layer chains on their own (rowgemm.h: rowchain / regchain / rowchain_lds / rowgemm)
+// --------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ChainBuild {
+    PackedLinear L[kChainMaxSteps];
+    ChainStep steps[kChainMaxSteps];
+    RowSrc s1, s2;
+    int n = 0;
+};
+
+// the description as ChainStep / RowSrc: the geometry emit() of ps_randla_set_weights gives a layer; the image pointers stay `image` (any non-null
+// pointer: the fits / plan functions only test them) until ps_debug_chain has packed them
+int chain_describe(const ps_debug_chain_desc* d, ChainBuild& b, const float* image)
+{
+    PS_CHECK(d && d->n_layers >= 1 && d->n_layers <= kChainMaxSteps, "ps_debug_chain: 1..%d layers", kChainMaxSteps);
+    PS_CHECK(d->R >= 0 && d->c1 > 0 && d->c2 >= 0 && d->ld1 >= d->c1 && (d->c2 == 0 || d->ld2 >= d->c2), "ps_debug_chain: bad row sources");
+    b.n = d->n_layers;
+    b.s1.x = d->x1; b.s1.gather = d->g1; b.s1.ld = d->ld1; b.s1.c = d->c1; b.s1.gm = d->g1 ? d->g1m : 0; b.s1.gn = d->g1 ? d->g1n : 0;
+    if (d->c2) {
+        b.s2.x = d->x2; b.s2.gather = d->g2; b.s2.ld = d->ld2; b.s2.c = d->c2; b.s2.gm = d->g2 ? d->g2m : 0; b.s2.gn = d->g2 ? d->g2n : 0;
+    }
+    for (int i = 0; i < b.n; ++i) {
+        const ps_debug_chain_layer& y = d->layer[i];
+        PS_CHECK(y.cin > 0 && y.cout > 0 && y.cin <= 4096 && y.cout <= 4096, "ps_debug_chain: layer %d: bad channel counts", i);
+        PS_CHECK(!y.y || y.ldy >= y.cout, "ps_debug_chain: layer %d: ldy below cout", i);
+        PS_CHECK(!y.extra || (i > 0 && y.c_extra > 0 && y.ld_extra >= y.c_extra), "ps_debug_chain: layer %d: bad extra source", i);
+        PackedLinear& L = b.L[i];
+        L = PackedLinear();
+        L.cin = y.cin; L.cout = y.cout; L.leaky = y.leaky;
+        L.ks = (y.cin + 3) / 4;
+        L.ntb = choose_ntb(y.cout);
+        L.cblocks = (y.cout + 16 * L.ntb - 1) / (16 * L.ntb);
+        L.wp = image; L.bias = image;
+        ChainStep& st = b.steps[i];
+        st = ChainStep();
+        st.L = &L; st.y = y.y; st.ldy = y.ldy;
+        if (y.extra) {
+            st.extra.x = y.extra; st.extra.ld = y.ld_extra; st.extra.c = y.c_extra; st.extra.gather = y.extra_gather;
+        }
+    }
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4)
+{
+    PS_CHECK(d && out4 && d->R >= 1, "ps_debug_chain_plan: bad argument");
+    static const float nothing = 0.f;
+    ChainBuild b;
+    PS_TRY(chain_describe(d, b, &nothing));
+    const ChainPlan p = rowchain_plan(b.steps, b.n, b.s1, b.s2, d->R);
+    out4[0] = p.form;
+    out4[1] = p.form ? p.blocks : 0;
+    out4[2] = p.form ? (int)p.lds_bytes : 0;
+    out4[3] = p.fast_in;
+    return PS_OK;
+}
+
+extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int form)
+{
+    PS_CHECK(c && d && form >= 0 && form <= 3, "ps_debug_chain: bad argument");
+    ChainBuild b;
+    PS_TRY(chain_describe(d, b, nullptr));
+    PS_CHECK(d->x1 && (d->c2 == 0 || d->x2), "ps_debug_chain: NULL row source");
+    for (int i = 0; i < b.n; ++i) PS_CHECK(d->layer[i].W, "ps_debug_chain: layer %d has no weights", i);
+    if (form == 3) {  // (the chain forms refuse these in their fits tests; layer by layer they would show only after the first layers ran)
+        int cur = d->c1 + d->c2;
+        for (int i = 0; i < b.n; ++i) {
+            const ps_debug_chain_layer& y = d->layer[i];
+            PS_CHECK(!(y.extra && y.extra_gather), "ps_debug_chain: layer %d: the extra rows of a chain are plain rows", i);
+            cur += y.extra ? y.c_extra : 0;
+            PS_CHECK(cur == y.cin, "ps_debug_chain: layer %d expects %d channels, the chain gives %d", i, y.cin, cur);
+            cur = y.cout;
+        }
+    }
+    if (d->R == 0) return PS_OK;
+    PS_HIP(hipSetDevice(c->device));
+    // pack: wp + zero-padded bias (+ the k-permuted image) per layer, one upload; form 3 keeps its un-stored rows behind them
+    std::vector<float> host;
+    size_t wp_off[kChainMaxSteps], b_off[kChainMaxSteps], wq_off[kChainMaxSteps], tmp_off[kChainMaxSteps];
+    auto grow = [&](size_t floats) {
+        const size_t off = (host.size() + 63) & ~size_t(63);
+        host.resize(off + floats);
+        return off;
+    };
+    for (int i = 0; i < b.n; ++i) {
+        const ps_debug_chain_layer& y = d->layer[i];
+        PackedLinear& L = b.L[i];
+        wp_off[i] = grow(L.packed_floats());
+        pack_weights(y.W, y.cin, y.cout, L.ntb, host.data() + wp_off[i]);
+        b_off[i] = grow((size_t)L.cout_pad());
+        for (int k = 0; k < L.cout_pad(); ++k) host[b_off[i] + k] = (y.bias && k < y.cout) ? y.bias[k] : 0.f;
+        wq_off[i] = 0;
+        // (no w32 / w32b / wb image on purpose: form 3 then stays on the 16x16x4 kernels of rowgemm.hip -- the direct-load one for 16-byte aligned
+        //  rows of 16-multiple widths, the generic LDS one otherwise -- and never moves to gemm32, which has its own door)
+        if (y.cin % 16 == 0) {
+            wq_off[i] = grow(L.kperm_floats());
+            pack_weights_kperm(y.W, y.cin, y.cout, L.ntb, host.data() + wq_off[i]);
+        }
+    }
+    size_t total = (host.size() + 63) & ~size_t(63);
+    for (int i = 0; i < b.n; ++i) {
+        tmp_off[i] = total;
+        if (form == 3 && !d->layer[i].y) total += ((size_t)d->R * d->layer[i].cout + 63) & ~size_t(63);
+    }
+    float* dev = nullptr;
+    PS_HIP(hipMalloc(reinterpret_cast<void**>(&dev), total * sizeof(float)));
+    int rc = PS_OK;
+    if (hipMemcpyAsync(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        set_error("ps_debug_chain: upload failed");
+        rc = PS_EHIP;
+    }
+    for (int i = 0; i < b.n; ++i) {
+        b.L[i].wp = dev + wp_off[i];
+        b.L[i].bias = dev + b_off[i];
+        b.L[i].wq = wq_off[i] ? dev + wq_off[i] : nullptr;
+    }
+    if (rc == PS_OK) {
+        if (form == 0) {
+            ChainCache cache;
+            if (rowchain_fits(b.steps, b.n, b.s1, b.s2)) rc = rowchain(c, b.steps, b.n, b.s1, b.s2, d->R, &cache);
+            else { set_error("ps_debug_chain: the chain fits neither chain kernel (channels above %d, mismatched, or a gathered extra)", kChainMaxC); rc = PS_EINVAL; }
+            (void)hipStreamSynchronize(c->stream);
+            cache.clear();
+        } else if (form == 1) {
+            if (regchain_fits(b.steps, b.n, b.s1, b.s2)) rc = regchain(c, b.steps, b.n, b.s1, b.s2, d->R, nullptr);
+            else { set_error("ps_debug_chain: not one of regchain's compiled chain shapes"); rc = PS_EINVAL; }
+        } else if (form == 2) {
+            if (rowchain_lds_plan(b.steps, b.n, b.s1, b.s2, d->R).form == 2) rc = rowchain_lds(c, b.steps, b.n, b.s1, b.s2, d->R);
+            else { set_error("ps_debug_chain: the chain does not fit the LDS-staged kernel (channels above %d, mismatched, or a gathered extra)", kChainMaxC); rc = PS_EINVAL; }
+        } else {
+            RowSrc in1 = b.s1, in2 = b.s2;
+            for (int i = 0; i < b.n && rc == PS_OK; ++i) {
+                const ChainStep& st = b.steps[i];
+                if (i > 0) {
+                    in2 = RowSrc();
+                    if (st.extra.x) in2 = st.extra;
+                }
+                float* out = st.y ? st.y : dev + tmp_off[i];
+                const int ldo = st.y ? st.ldy : b.L[i].cout;
+                rc = rowgemm(c, b.L[i], in1, in2, d->R, out, ldo);
+                in1 = RowSrc();
+                in1.x = out; in1.ld = ldo; in1.c = b.L[i].cout;
+            }
+        }
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(dev);
+    return rc;
+}
+
+// --------------------------------------------------------------------------------------------------------
+// one attentive-pooling stage of a live network (randla_net.h), through each of its stage functions (attpool.h)
+// --------------------------------------------------------------------------------------------------------
+extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form, const float* xyz, const int32_t* idx, const int32_t* order,
+                                  const float* fg, int64_t n_total, int64_t n_cloud, float* agg)
+{
+    PS_CHECK(net && xyz && idx && fg && agg, "ps_debug_att_stage: NULL argument");
+    PS_CHECK(net->have_weights, "ps_debug_att_stage: weights not set");
+    PS_CHECK(level >= 0 && level < net->cfg.num_layers && (stage == 1 || stage == 2) && form >= 0 && form <= 3, "ps_debug_att_stage: bad level / stage / form");
+    PS_CHECK(n_total >= 0 && n_cloud >= 1 && n_total % n_cloud == 0, "ps_debug_att_stage: n_total must be a whole number of clouds");
+    ps_context* c = net->ctx;
+    PS_HIP(hipSetDevice(c->device));
+    const EncLevel& e = net->enc[level];
+    const int d = e.d, h = d / 2;
+    const bool use_g = d >= 64;
+    AttStage s;
+    s.xyz = xyz; s.idx = idx; s.order = order; s.fg = fg; s.lfa1 = &e.lfa1; s.agg = agg;
+    s.n_total = n_total; s.n_cloud = n_cloud; s.d = d; s.k = net->cfg.k_n; s.ldf = use_g ? h + d : h;
+    s.p32 = e.has_p32 ? &e.p32 : nullptr;
+    s.lfa2 = stage == 2 ? &e.lfa2 : nullptr;
+    s.wbot = use_g ? (stage == 1 ? &e.bot1 : &e.bot2) : nullptr;
+    s.wfull = use_g ? nullptr : (stage == 1 ? &e.full1 : &e.full2);
+    int rc = PS_EINVAL;
+    if (form == 0) rc = att_pool_stage(c, s);
+    else if (form == 1 && att_pool32b_fits(s)) rc = att_pool32b_stage(c, s);
+    else if (form == 2 && att_pool32_fits(s)) rc = att_pool32_stage(c, s);
+    else if (form == 3) rc = att_pool16_stage(c, s);
+    else set_error("ps_debug_att_stage: the level (d = %d, %lld rows) does not fit the 32x32 form %d", d, (long long)n_total, form);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
 }
 
 // --------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 // the head (fc1, fc2, fc, :146-151; dropout is the identity in inference) are one chain over the level-0 rows.
 #include "attpool.h"
 #include "common.h"
+#include "randla_net.h"
 #include "rowgemm.h"
 
 #include <memory>
@@ -103,38 +104,9 @@ int pool_max(ps_context* c, const float* feat, const int32_t* idx, const int32_t
     return PS_OK;
 }
 
-struct LayerSpec {
-    int cin, cout, leaky;
-    size_t w_off, b_off;  // offsets into the host blob (floats)
-};
-
-struct EncLevel {
-    PackedLinear mlp1, top1, lfa1, bot1, full1, att1mlp, lfa2, top2, bot2, full2, att2mlp, mlp2sc;
-    Att32Weights p32;  // d >= 64: weight images of the 32x32x2 attentive-pooling kernels
-    bool has_p32 = false;
-    int d_in, d;
-};
-
 }  // namespace ps
 
 using namespace ps;
-
-struct ps_randla {
-    ps_context* ctx = nullptr;
-    ps_randla_config cfg;
-    std::vector<LayerSpec> specs;  // blob order
-    int64_t blob_floats = 0;
-    bool have_weights = false;
-    DevBuf wbuf;
-    ChainCache chains;  // re-ordered weight images of the register-resident layer chains (regchain.hip)
-    PackedLinear fc0, decoder0, fc1, fc2, fc;
-    std::vector<EncLevel> enc;
-    std::vector<PackedLinear> dec;
-    // taps of the last forward (device pointers into ctx->net_arena) and their sizes
-    struct Tap { int which; const float* p; int64_t count; };
-    std::vector<Tap> taps;
-    bool keep_taps = false;  // ps_randla_keep_taps: also store the rows only ps_randla_tap reads (last decoder step)
-};
 
 namespace {
 

@@ -278,6 +278,23 @@ bool regchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const 
     return rc_build(steps, n_steps, s1, s2, a, lds);
 }
 
+static int rc_blocks(int64_t R, size_t lds_bytes)
+{
+    const int64_t tiles = (R + 15) / 16;
+    const int per_cu = std::max(1, std::min(4, (int)(160 * 1024 / std::max<size_t>(lds_bytes, 1))));  // weights staged once per workgroup
+    return (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * per_cu));
+}
+
+ChainPlan regchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R)
+{
+    ChainPlan p;
+    RcArgs a;
+    if (!rc_build(steps, n_steps, s1, s2, a, p.lds_bytes)) return ChainPlan();
+    p.form = 1;
+    p.blocks = rc_blocks(R, p.lds_bytes);
+    return p;
+}
+
 template <class S>
 static int rc_launch(ps_context* c, const RcArgs& a, size_t lds_bytes, int blocks)
 {
@@ -315,9 +332,7 @@ int regchain(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s
         a.image = hit->img.as<float>();
         a.image_floats = (int)(lds_bytes / sizeof(float));
     }
-    const int tiles = (int)((R + 15) / 16);
-    const int per_cu = std::max(1, std::min(4, (int)(160 * 1024 / std::max<size_t>(lds_bytes, 1))));  // weights staged once per workgroup
-    const int blocks = std::max(1, std::min((tiles + 3) / 4, 256 * per_cu));
+    const int blocks = rc_blocks(R, lds_bytes);
     if (rc_matches<RcFc0>(a)) PS_TRY(rc_launch<RcFc0>(c, a, lds_bytes, blocks));
     else if (rc_matches<RcEnc0>(a)) PS_TRY(rc_launch<RcEnc0>(c, a, lds_bytes, blocks));
     else if (rc_matches<RcOne0>(a)) PS_TRY(rc_launch<RcOne0>(c, a, lds_bytes, blocks));

@@ -112,6 +112,20 @@ struct ChainCache {
     }
 };
 int regchain(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R, ChainCache* cache);
+// the LDS-staged form (rowchain_kernel, rowgemm.hip) of any chain within kChainMaxC: what rowchain() falls back to when the shape is not one of
+// regchain's
+int rowchain_lds(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R);
+// The launch regchain() / rowchain_lds() / rowchain() make for R rows of a chain: the launchers call these, and so does the test door
+// ps_debug_chain_plan (debug_hooks.h).  Host only.
+struct ChainPlan {
+    int form = 0;          // 0: the chain does not fit this form, 1: regchain_kernel, 2: rowchain_kernel
+    int blocks = 0;        // workgroups (each of four waves walking 16-row tiles)
+    size_t lds_bytes = 0;  // dynamic LDS per workgroup
+    int fast_in = 0;       // rowchain_kernel only: log2(float4s per input row) when the float4 staging applies, else 0 (scalar staging)
+};
+ChainPlan regchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R);
+ChainPlan rowchain_lds_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R);
+ChainPlan rowchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R);  // the one rowchain() takes
 int rowchain(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R, ChainCache* cache = nullptr);
 
 // gemm_b3.hip: large fp32 products of the training step on bf16 MFMA over exact three-way splits

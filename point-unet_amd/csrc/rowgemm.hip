@@ -639,7 +639,7 @@ __global__ __launch_bounds__(256) void rowchain_kernel(ChainArgs a)
 }
 
 // (the network's own chain shapes run in regchain.hip, 1.2-2.4x faster than the LDS-staged rowchain_kernel below, which stays as the
-//  form for every other shape; both are parity-tested)
+//  form for every other shape; both are tested on their own through ps_debug_chain, debug_hooks.h)
 
 static bool lds_chain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2);
 
@@ -663,47 +663,82 @@ static bool lds_chain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1
     return true;
 }
 
+// the weight image's layout in LDS, the float4 staging rule and the launch size of rowchain_lds (a: optional, receives the layout)
+static ChainPlan lds_chain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R, ChainArgs* a)
+{
+    ChainPlan p;
+    if (!lds_chain_fits(steps, n_steps, s1, s2)) return p;
+    int off = 0;
+    for (int i = 0; i < n_steps; ++i) {
+        const PackedLinear& L = *steps[i].L;
+        const int w_floats = (int)L.packed_floats(), b_floats = L.cout_pad();
+        if (a) { a->l[i].w_off = off; a->l[i].w_floats = w_floats; }
+        off += (w_floats + 3) & ~3;
+        if (a) { a->l[i].b_off = off; a->l[i].b_floats = b_floats; }
+        off += (b_floats + 3) & ~3;
+    }
+    if (a) a->tile_off = off;
+    {
+        const int cin0 = s1.c + s2.c, q = cin0 / 4;
+        const bool pow2 = cin0 % 4 == 0 && q >= 2 && (q & (q - 1)) == 0;
+        const bool al = s1.c % 4 == 0 && s2.c % 4 == 0 && s1.ld % 4 == 0 && (s2.c == 0 || s2.ld % 4 == 0) && aligned16(s1.x) && (s2.c == 0 || aligned16(s2.x));
+        if (pow2 && al)
+            while ((1 << p.fast_in) < q) ++p.fast_in;
+    }
+    p.lds_bytes = sizeof(float) * ((size_t)off + 4 * 2 * 16 * kChainPitch);
+    if (p.lds_bytes > 160 * 1024) return p;  // (form 0: the weights of the chain do not fit the LDS)
+    p.form = 2;
+    // few, long-lived workgroups: the weight image is loaded once per workgroup
+    const int64_t tiles = (R + 15) / 16;
+    const int per_cu = std::max(1, (int)(160 * 1024 / p.lds_bytes));
+    p.blocks = (int)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * std::min(per_cu, 4)));
+    return p;
+}
+
+ChainPlan rowchain_lds_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R)
+{
+    return lds_chain_plan(steps, n_steps, s1, s2, R, nullptr);
+}
+
+ChainPlan rowchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R)
+{
+    const ChainPlan p = regchain_plan(steps, n_steps, s1, s2, R);
+    return p.form ? p : rowchain_lds_plan(steps, n_steps, s1, s2, R);
+}
+
 int rowchain(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R, ChainCache* cache)
 {
     if (R <= 0) return PS_OK;
     if (regchain_fits(steps, n_steps, s1, s2)) return regchain(c, steps, n_steps, s1, s2, R, cache);
-    PS_CHECK(lds_chain_fits(steps, n_steps, s1, s2), "rowchain: the layer chain does not fit (channels above %d or mismatched)", kChainMaxC);
+    return rowchain_lds(c, steps, n_steps, s1, s2, R);
+}
+
+int rowchain_lds(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, int64_t R)
+{
+    if (R <= 0) return PS_OK;
     PS_CHECK(R < (int64_t)1 << 31, "rowchain: too many rows");
     ChainArgs a = {};
+    const ChainPlan plan = lds_chain_plan(steps, n_steps, s1, s2, R, &a);  // (lds_bytes stays 0 when lds_chain_fits refuses the chain)
+    PS_CHECK(plan.lds_bytes, "rowchain: the layer chain does not fit (channels above %d or mismatched)", kChainMaxC);
+    PS_CHECK(plan.form == 2, "rowchain: weights of the chain do not fit the LDS (%zu bytes)", plan.lds_bytes);
     a.x1 = s1.x; a.g1 = s1.gather; a.ld1 = s1.ld; a.c1 = s1.c; a.g1m = s1.gm; a.g1n = s1.gn;
     a.x2 = s2.x; a.g2 = s2.gather; a.ld2 = s2.ld; a.c2 = s2.c; a.g2m = s2.gm; a.g2n = s2.gn;
     a.n = n_steps;
     a.R = (int)R;
-    int off = 0;
     for (int i = 0; i < n_steps; ++i) {
         const PackedLinear& L = *steps[i].L;
         ChainArgs::Lyr& y = a.l[i];
         y.wp = L.wp; y.bias = L.bias; y.y = steps[i].y; y.ldy = steps[i].ldy;
         y.ex = steps[i].extra.x; y.ldex = steps[i].extra.ld; y.cex = steps[i].extra.x ? steps[i].extra.c : 0;
         y.cout = L.cout; y.ks = L.ks; y.ntb = L.ntb; y.cblocks = L.cblocks; y.leaky = L.leaky;
-        y.w_off = off; y.w_floats = (int)L.packed_floats(); off += (y.w_floats + 3) & ~3;
-        y.b_off = off; y.b_floats = L.cout_pad(); off += (y.b_floats + 3) & ~3;
     }
-    a.tile_off = off;
-    {
-        const int cin0 = s1.c + s2.c, q = cin0 / 4;
-        const bool pow2 = cin0 % 4 == 0 && q >= 2 && (q & (q - 1)) == 0;
-        const bool al = s1.c % 4 == 0 && s2.c % 4 == 0 && s1.ld % 4 == 0 && (s2.c == 0 || s2.ld % 4 == 0) && aligned16(s1.x) && (s2.c == 0 || aligned16(s2.x));
-        a.fast_in = 0;
-        if (pow2 && al)
-            while ((1 << a.fast_in) < q) ++a.fast_in;
-    }
-    const size_t lds_bytes = sizeof(float) * ((size_t)off + 4 * 2 * 16 * kChainPitch);
-    PS_CHECK(lds_bytes <= 160 * 1024, "rowchain: weights of the chain do not fit the LDS (%zu bytes)", lds_bytes);
+    a.fast_in = plan.fast_in;
+    const size_t lds_bytes = plan.lds_bytes;
     if (lds_bytes > c->chain_lds_attr) {  // (per context = per device)
         PS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rowchain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         c->chain_lds_attr = lds_bytes;
     }
-    // few, long-lived workgroups: the weight image is loaded once per workgroup
-    const int tiles = (int)((R + 15) / 16);
-    const int per_cu = std::max(1, (int)(160 * 1024 / lds_bytes));
-    const int blocks = std::max(1, std::min((tiles + 3) / 4, 256 * std::min(per_cu, 4)));
-    hipLaunchKernelGGL(rowchain_kernel, dim3(blocks), dim3(256), lds_bytes, c->stream, a);
+    hipLaunchKernelGGL(rowchain_kernel, dim3(plan.blocks), dim3(256), lds_bytes, c->stream, a);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
