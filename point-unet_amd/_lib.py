@@ -1,7 +1,7 @@
 """ctypes binding of libpointseg_hip.so -- the only door between the Python host code and the HIP kernels.
 
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
-(PREPARE_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(PREPARE_PROTOTYPES) and include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -267,6 +267,17 @@ PREPARE_PROTOTYPES = {
                        + [ctypes.c_uint32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_i64p]),
 }
 
+# every symbol include/pointseg_postprocess.h declares (the clean-up of a predicted label volume; csrc/postprocess.hip)
+PS_MORPH_DILATE, PS_MORPH_ERODE, PS_MORPH_CLOSE, PS_MORPH_OPEN = 1, 2, 3, 4
+PS_KEEP_ABOVE, PS_KEEP_LARGEST_TWO, PS_KEEP_OVERLAP = 1, 2, 3
+POSTPROCESS_PROTOTYPES = {
+    "ps_label_components": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.c_int32, ctypes.c_int32] + [c_vp] * 5 + [c_i64p]),
+    "ps_binary_morph": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.c_int32] * 3 + [c_vp, c_vp, c_i64p]),
+    "ps_keep_components": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp, c_vp, c_i64p]),
+    "ps_fill_holes": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 3 + [c_vp, c_vp, c_i64p]),
+    "ps_brats_postprocess": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.c_int64, c_vp, c_vp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -286,7 +297,7 @@ def lib():
         except Exception:  # pragma: no cover
             pass
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
