@@ -31,13 +31,6 @@
 
 namespace ps {
 
-__device__ __forceinline__ float round_bf16(float x)
-{
-    unsigned u = __float_as_uint(x);
-    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even (finite inputs)
-    return __uint_as_float(u & 0xffff0000u);
-}
-
 template <int D>
 struct AttTrainGeom {
     static constexpr int PW = D + 16 + (D % 32 == 16 ? 16 : 0);  // weight pitch = 16 (mod 32): conflict-free B-fragment reads

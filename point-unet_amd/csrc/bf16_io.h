@@ -9,6 +9,14 @@ namespace ps {
 typedef __bf16 io_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float io_f32x2 __attribute__((ext_vector_type(2)));
 
+// the bfloat16 nearest to x as an fp32: the operand rounding of the bf16-MLP mode (ps_set_train_gemm_bf16)
+__device__ __forceinline__ float round_bf16(float x)
+{
+    unsigned u = __float_as_uint(x);
+    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even (finite inputs)
+    return __uint_as_float(u & 0xffff0000u);
+}
+
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi)  // (low half = lo)
 {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(io_f32x2{lo, hi}, io_bf16x2));

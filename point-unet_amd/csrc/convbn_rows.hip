@@ -12,9 +12,8 @@
 //                           merged per workgroup and then across workgroups in a fixed order)               2 reads + 1 write (+ 1 read)
 //   6-7 passes over [rows, 8] tensors against 15 op by op (convolution 2, statistics 1, normalise 2, BatchNorm backward 2 + 3, input
 //   gradient 3, weight gradient 2).  Deterministic: fixed grid, fixed reduction order, no atomics.
-#include "common.h"
+#include "convbn_tile.h"
 #include "reduce_partials.h"
-#include "bf16_io.h"
 
 namespace ps {
 
@@ -100,7 +99,7 @@ struct CbCols {
     }
 };
 
-// workgroup sum of NV per-thread values in a fixed order: xor butterfly inside the wave, the four waves in order through LDS
+// workgroup sum of NV per-thread values in a fixed order: xor butterfly inside the wave, the four waves in order through LDS (convbn_tile.h)
 template <class T, int NV>
 __device__ __forceinline__ void cb_block_reduce(T (&v)[NV], T* red /* [waves][NV] */, T* dst /* this workgroup's partial [NV] */)
 {
@@ -112,12 +111,7 @@ __device__ __forceinline__ void cb_block_reduce(T (&v)[NV], T* red /* [waves][NV
         for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
         if (lane == 0) red[wave * NV + i] = s;
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NV; i += kCbThreads) {
-        T s = 0;
-        for (int w = 0; w < kCbThreads / 64; ++w) s += red[w * NV + i];
-        dst[i] = s;
-    }
+    wg_merge<T, kCbThreads / 64>(red, NV, dst);
 }
 
 // ---- forward: statistics.  partial layout per workgroup (doubles): sy[CP] | sq[CP] | sx[CP], CP = 16 (the layout of smallconv_train.hip)
@@ -255,14 +249,21 @@ __global__ __launch_bounds__(kCbThreads) void cb_bwd_apply_kernel(CbArgs a)
     cb_block_reduce<float, NV>(acc, red, static_cast<float*>(a.part) + (size_t)blockIdx.x * NV);
 }
 
+// what every entry starts from
+static CbArgs cb_args(const ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R)
+{
+    CbArgs a = {};
+    a.x_bf16 = convbn_rows_bf16(c) ? 1 : 0;
+    a.x = x; a.ldx = (int)ldx; a.w = w; a.b = b; a.R = R;
+    return a;
+}
+
 static int cb_blocks(int64_t R) { return (int)std::max<int64_t>(1, std::min<int64_t>((R + kCbThreads - 1) / kCbThreads, kCbBlocks)); }
 
 // entry points for smallconv_train.hip's dispatch (C = 8 only)
 int convbn_rows_sums(ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R, double* sums)
 {
-    CbArgs a = {};
-    a.x_bf16 = c->train_act_bf16 && c->train_bf16 ? 1 : 0;  // (x, apply's out and the gradient rows dz / dx as bfloat16: ps_set_train_act_bf16)
-    a.x = x; a.ldx = (int)ldx; a.w = w; a.b = b; a.R = R;
+    CbArgs a = cb_args(c, x, ldx, w, b, R);
     const int blocks = cb_blocks(R);
     PS_TRY(c->red_ws.reserve(sizeof(double) * (size_t)blocks * 48 + 256));
     a.part = c->red_ws.as<void>();
@@ -276,9 +277,8 @@ int convbn_rows_sums(ps_context* c, const float* x, int64_t ldx, const float* w,
 int convbn_rows_apply(ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R, const float* mean, const float* scale,
                       const float* beta, float* out, int64_t ldo)
 {
-    CbArgs a = {};
-    a.x_bf16 = c->train_act_bf16 && c->train_bf16 ? 1 : 0;  // (x, apply's out and the gradient rows dz / dx as bfloat16: ps_set_train_act_bf16)
-    a.x = x; a.ldx = (int)ldx; a.w = w; a.b = b; a.R = R; a.mean = mean; a.scale = scale; a.beta = beta; a.out = out; a.ldo = (int)ldo;
+    CbArgs a = cb_args(c, x, ldx, w, b, R);
+    a.mean = mean; a.scale = scale; a.beta = beta; a.out = out; a.ldo = (int)ldo;
     if (a.x_bf16) hipLaunchKernelGGL((cb_apply_kernel<8, true>), dim3(cb_blocks(R)), dim3(kCbThreads), 0, c->stream, a);
     else hipLaunchKernelGGL((cb_apply_kernel<8, false>), dim3(cb_blocks(R)), dim3(kCbThreads), 0, c->stream, a);
     PS_HIP(hipGetLastError());
@@ -288,9 +288,8 @@ int convbn_rows_apply(ps_context* c, const float* x, int64_t ldx, const float* w
 int convbn_rows_bwd_sums(ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R, const float* mean, const float* invstd,
                          const float* scale, const float* beta, const float* dz, int64_t lddz, float* s12)
 {
-    CbArgs a = {};
-    a.x_bf16 = c->train_act_bf16 && c->train_bf16 ? 1 : 0;  // (x, apply's out and the gradient rows dz / dx as bfloat16: ps_set_train_act_bf16)
-    a.x = x; a.ldx = (int)ldx; a.w = w; a.b = b; a.R = R; a.mean = mean; a.invstd = invstd; a.scale = scale; a.beta = beta; a.dz = dz; a.lddz = (int)lddz;
+    CbArgs a = cb_args(c, x, ldx, w, b, R);
+    a.mean = mean; a.invstd = invstd; a.scale = scale; a.beta = beta; a.dz = dz; a.lddz = (int)lddz;
     const int blocks = cb_blocks(R);
     PS_TRY(c->red_ws.reserve(sizeof(float) * (size_t)blocks * 16 + 256));
     a.part = c->red_ws.as<void>();
@@ -305,9 +304,8 @@ int convbn_rows_bwd_apply(ps_context* c, const float* x, int64_t ldx, const floa
                           const float* scale, const float* beta, const float* s12, float inv_rows, const float* dz, int64_t lddz, int accumulate, float* dx,
                           int64_t lddx, float* dw, float* db)
 {
-    CbArgs a = {};
-    a.x_bf16 = c->train_act_bf16 && c->train_bf16 ? 1 : 0;  // (x, apply's out and the gradient rows dz / dx as bfloat16: ps_set_train_act_bf16)
-    a.x = x; a.ldx = (int)ldx; a.w = w; a.b = b; a.R = R; a.mean = mean; a.invstd = invstd; a.scale = scale; a.beta = beta; a.s12 = s12;
+    CbArgs a = cb_args(c, x, ldx, w, b, R);
+    a.mean = mean; a.invstd = invstd; a.scale = scale; a.beta = beta; a.s12 = s12;
     a.inv_rows = inv_rows; a.dz = dz; a.lddz = (int)lddz; a.out = dx; a.ldo = (int)lddx; a.accum = accumulate ? 1 : 0;
     const int blocks = cb_blocks(R);
     PS_TRY(c->red_ws.reserve(sizeof(float) * (size_t)blocks * 72 + 256));

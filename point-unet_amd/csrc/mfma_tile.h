@@ -77,7 +77,8 @@ __device__ __forceinline__ float xor_max_lds(float v)
     v = fmaxf(v, __shfl_xor(v, 16));
     return fmaxf(v, __shfl_xor(v, 32));
 }
-__device__ __forceinline__ float xor_sum_lds(float v)
+template <class T>  // float or double
+__device__ __forceinline__ T xor_sum_lds(T v)
 {
     v += __shfl_xor(v, 16);
     return v + __shfl_xor(v, 32);

@@ -8,6 +8,7 @@
 
 #include <hip/hip_fp16.h>
 #include "rowgemm.h"
+#include "bf16_io.h"
 
 namespace ps {
 
@@ -375,14 +376,9 @@ __global__ __launch_bounds__(256) void tinyconv_kernel(const float* __restrict__
 {
     __shared__ __attribute__((aligned(16))) float W[CIN * COUT];
     __shared__ float Bv[COUT];
-    auto rb = [&](float v) {
-        unsigned u = __float_as_uint(v);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return __uint_as_float(u & 0xffff0000u);
-    };
     for (int i = threadIdx.x; i < CIN * COUT; i += 256) {  // W[k][n]; wt: the matrix is stored [n][k]
         const float v = wt ? w[(i % COUT) * CIN + i / COUT] : w[i];
-        W[i] = bf16 ? rb(v) : v;
+        W[i] = bf16 ? round_bf16(v) : v;
     }
     if ((int)threadIdx.x < COUT) Bv[threadIdx.x] = b ? b[threadIdx.x] : 0.f;
     __syncthreads();
@@ -395,7 +391,7 @@ __global__ __launch_bounds__(256) void tinyconv_kernel(const float* __restrict__
         }
         if (bf16) {
 #pragma unroll
-            for (int k = 0; k < CIN; ++k) xv[k] = rb(xv[k]);
+            for (int k = 0; k < CIN; ++k) xv[k] = round_bf16(xv[k]);
         }
         float acc[COUT];
 #pragma unroll

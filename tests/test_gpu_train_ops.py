@@ -666,6 +666,87 @@ def test_conv_bn_train_backward_against_float64_autograd(C):
     assert _rel_close(_host(dw2), ref["dw"], 1e-4, np.abs(ref["dw"]).max() + 0 * ref["dw"])[0]
 
 
+def _off_grid(a, how, fill):
+    """A device copy of the [R, C] array `a` (or, a = None, `fill` everywhere) as a view the 16-byte paths cannot take: rows of pitch C + 1
+    ("pitch") or a base one float past an aligned address ("offset").  Returns (view, pitch, the elements around it that nothing may write)."""
+    import torch
+    R, C = fill.shape if a is None else a.shape
+    if how == "pitch":
+        buf = torch.full((R, C + 1), 7.75, device="cuda")
+        view, ld, guard = buf[:, :C], C + 1, buf[:, C]
+    else:
+        buf = torch.full((1 + R * C,), 7.75, device="cuda")
+        view, ld, guard = buf[1:].view(R, C), C, buf[:1]
+    view.copy_(_dev(fill if a is None else a))
+    assert view.data_ptr() % 16 != 0 or ld % 4 != 0
+    return view, ld, guard
+
+
+@pytest.mark.parametrize("C", [16, 64])
+def test_conv_bn_train_rows_off_the_16_byte_grid_against_float64_autograd(C):
+    """The second data path of the square kernels (csrc/smallconv_train.hip, a.vec == 0): dz or out / dx rows that are not 16-byte aligned or
+    whose pitch is no multiple of 4 travel as 4-byte accesses in the accumulator layout -- loads of dz, direct stores of z and dx, `*dst + acc`
+    for accumulate.  _apply, _bwd_sums, _bwd_sums2, _bwd_apply (fresh and accumulated) and _bwd_apply_w against float64 autograd with the bars
+    of test_conv_bn_train_backward_against_float64_autograd; R = 37 is three tiles, the last one ragged, and fewer tiles than waves.  The
+    floats between and in front of the rows keep their value."""
+    import torch
+    _lib, L, h = _env()
+    R = 37
+    CP = max(C, 16)
+    rng = np.random.default_rng(100 + C)
+    x = rng.standard_normal((R, C)).astype(np.float32)
+    w = (rng.standard_normal((C, C)) / np.sqrt(C)).astype(np.float32)
+    b = rng.standard_normal(C).astype(np.float32)
+    gamma = (rng.random(C) + 0.5).astype(np.float32)
+    beta = rng.standard_normal(C).astype(np.float32)
+    pre = _conv_bn64(x, w, b, gamma, beta, 1, None)
+    dz = _away_from_kink(rng.standard_normal((R, C)).astype(np.float32), pre["z"], 1)
+    ref = _conv_bn64(x, w, b, gamma, beta, 1, dz)
+    old = rng.standard_normal((R, C)).astype(np.float32)
+    invstd = (1.0 / np.sqrt(ref["var"] + _f32(BN_EPS))).astype(np.float32)
+    scale = (gamma * invstd).astype(np.float32)
+    X, W, Bb, Bt, Mn, Is, Sc = (_dev(a) for a in (x, w, b, beta, ref["mean"].astype(np.float32), invstd, scale))
+    gscale = np.abs(dz).sum(0) * 6
+    dx_bar = np.abs(ref["dx"]).max() + 0 * ref["dx"]
+    dw_bar = np.abs(ref["dw"]).max() + 0 * ref["dw"]
+    for how in ("pitch", "offset"):
+        DZ, lddz, dz_guard = _off_grid(dz, how, None)
+        out, ldo, out_guard = _off_grid(None, how, np.full((R, C), 5.0, np.float32))
+        _lib.check(L.ps_op_conv_bn_train_apply(h, _p(X), C, _p(W), _p(Bb), R, C, _p(Mn), _p(Sc), _p(Bt), _p(out), ldo))
+        assert _rel_close(_host(out), ref["out"], 1e-4, np.abs(ref["out"]).max(0) + 1e-6)[0], how
+        bs = torch.empty(3 * CP + 2 * CP * CP, device="cuda")
+        _lib.check(L.ps_op_conv_bn_train_bwd_sums(h, _p(X), C, _p(W), _p(Bb), R, C, _p(Mn), _p(Is), _p(Sc), _p(Bt), _p(DZ), lddz, _p(bs)))
+        bsh = _host(bs).astype(np.float64)
+        S1, S2 = bsh[:C], bsh[CP:CP + C]
+        A = bsh[3 * CP:3 * CP + CP * CP].reshape(CP, CP)[:C, :C]
+        Gm = bsh[3 * CP + CP * CP:].reshape(CP, CP)[:C, :C]
+        assert _rel_close(S1, ref["dbeta"], 1e-5, gscale)[0] and _rel_close(S2, ref["dgamma"], 1e-5, gscale)[0], how
+        dw = gamma * invstd * (A - np.outer(x.astype(np.float64).sum(0), S1) / R - Gm * S2 / R)
+        assert _rel_close(dw, ref["dw"], 1e-4, dw_bar)[0], how
+        s12 = torch.empty(3 * C, device="cuda")
+        _lib.check(L.ps_op_conv_bn_train_bwd_sums2(h, _p(X), C, _p(W), _p(Bb), R, C, _p(Mn), _p(Is), _p(Sc), _p(Bt), _p(DZ), lddz, _p(s12)))
+        s12h = _host(s12).astype(np.float64)
+        assert _rel_close(s12h[:C], ref["dbeta"], 1e-5, gscale)[0] and _rel_close(s12h[C:2 * C], ref["dgamma"], 1e-5, gscale)[0], how
+        m1 = np.zeros(CP, np.float32)
+        m2 = np.zeros(CP, np.float32)
+        m1[:C], m2[:C] = S1 / R, S2 / R
+        M1, M2 = _dev(m1), _dev(m2)
+        dw2, db2 = torch.empty(C, C, device="cuda"), torch.empty(C, device="cuda")
+        for accumulate in (0, 1):
+            want = ref["dx"] + (old.astype(np.float64) if accumulate else 0.0)
+            dx, lddx, dx_guard = _off_grid(old, how, None)
+            _lib.check(L.ps_op_conv_bn_train_bwd_apply(h, _p(X), C, _p(W), _p(Bb), R, C, _p(Mn), _p(Is), _p(Sc), _p(Bt), _p(M1), _p(M2), _p(DZ), lddz,
+                                                       accumulate, _p(dx), lddx))
+            assert _rel_close(_host(dx), want, 1e-4, dx_bar)[0], (how, accumulate)
+            dxw, lddxw, dxw_guard = _off_grid(old, how, None)
+            _lib.check(L.ps_op_conv_bn_train_bwd_apply_w(h, _p(X), C, _p(W), _p(Bb), R, C, _p(Mn), _p(Is), _p(Sc), _p(Bt), _p(s12), 1.0 / R, _p(DZ), lddz,
+                                                         accumulate, _p(dxw), lddxw, _p(dw2), _p(db2)))
+            assert _rel_close(_host(dxw), want, 1e-4, dx_bar)[0], (how, accumulate)
+            assert _rel_close(_host(dw2), ref["dw"], 1e-4, dw_bar)[0], (how, accumulate)
+            for guard in (dz_guard, out_guard, dx_guard, dxw_guard):
+                assert float(np.abs(_host(guard) - 7.75).max()) == 0.0, (how, accumulate)
+
+
 def test_conv_bn_train_refuses_what_it_is_not_compiled_for():
     """_supported(C) is false outside {8, 16, 32, 64}; for such a C, and for rows that are not 16-byte aligned, every entry returns an
     error with ps_last_error set and writes nothing."""
