@@ -1,7 +1,8 @@
 """ctypes binding of libpointseg_hip.so -- the only door between the Python host code and the HIP kernels.
 
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
-(PREPARE_PROTOTYPES) and include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES) and include/pointseg_saliency.h
+(SALIENCY_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -278,6 +279,22 @@ POSTPROCESS_PROTOTYPES = {
     "ps_brats_postprocess": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [ctypes.c_int64, c_vp, c_vp, c_i64p]),
 }
 
+
+class PsSaliencyTaps(ctypes.Structure):
+    _fields_ = [("down4", c_vp), ("c345", c_vp), ("sa", c_vp), ("c12", c_vp)]
+
+
+# every symbol include/pointseg_saliency.h declares (the saliency attention network and its window average; csrc/conv3d.hip, csrc/saliency.hip)
+SALIENCY_PROTOTYPES = {
+    "ps_conv3d": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 6 + [ctypes.c_int32, c_vp, c_vp] + [ctypes.c_int32] * 3 + [ctypes.c_int64]
+                  + [ctypes.c_int32] * 2 + [c_vp]),
+    "ps_instance_norm_relu": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 3 + [c_vp, c_vp, ctypes.c_float, c_vp, c_vp, c_i64p]),
+    "ps_saliency_weight_count": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "ps_saliency_forward": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 6 + [c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.POINTER(PsSaliencyTaps), c_vp, c_i64p]),
+    "ps_saliency_accumulate": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 10 + [c_vp, c_vp]),
+    "ps_saliency_finish": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 4 + [c_vp]),
+}
+
 _lib = None
 
 
@@ -297,7 +314,8 @@ def lib():
         except Exception:  # pragma: no cover
             pass
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items()):
+        for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
+                                  + list(SALIENCY_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -15,6 +15,7 @@
 
 #include "../../include/pointseg_postprocess.h"
 #include "common.h"
+#include "scratch.h"
 #include "sortscan.h"
 
 namespace ps {
@@ -48,9 +49,6 @@ struct CcStat {
     int count;                       // voxels the apply kernel counted (the chain's whole / enhancing counts)
     unsigned long long best1, best2;  // PS_KEEP_LARGEST_TWO: (size << 32) | ~root of the largest and of the second largest
 };
-
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
 
 __device__ __forceinline__ bool pp_neighbour(int e0, int e1, int e2, int conn)
 {
@@ -383,26 +381,6 @@ int check_dims(const char* who, int64_t d0, int64_t d1, int64_t d2, PpDims* d)
 int check_connectivity(const char* who, int32_t connectivity)
 {
     PS_CHECK(connectivity >= 1 && connectivity <= 3, "%s: connectivity = %d, must be 1, 2 or 3", who, (int)connectivity);
-    return PS_OK;
-}
-
-// the scratch of one call, carved in a fixed order; the sizing call walks the same code with base == nullptr
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count)
-    {
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += pad256(count * sizeof(T));
-        return r;
-    }
-};
-
-int check_scratch(const char* who, const void* scratch, const int64_t* scratch_bytes, size_t need)
-{
-    PS_CHECK(*scratch_bytes >= (int64_t)need, "%s: *scratch_bytes = %lld, this call needs %lld", who, (long long)*scratch_bytes, (long long)need);
-    PS_CHECK((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "%s: scratch must be 256-byte aligned", who);
     return PS_OK;
 }
 

@@ -1,0 +1,36 @@
+// saliency.h -- what conv3d.hip and saliency.hip share: the implicit-GEMM 3-D convolution with its strided forms (the network writes
+// every concat part straight into the concat's buffer, so a tensor has a channel pitch), include/pointseg_saliency.h.
+#pragma once
+
+#include "../../include/pointseg_saliency.h"
+#include "common.h"
+
+namespace ps {
+
+// One convolution.  The input is the channel concat of x (C1 channels, pitch ldx) and x2 (C2, pitch ldx2; nullptr with C2 == 0) at
+// [B, Ds, Hs, Ws], up-sampled `up` times by repetition; the output voxel row has pitch ldy.  w: [taps][C1 + C2][cout], w_bstride floats
+// further for each sample (0: one kernel for all -- the channel attention folds its per-sample scale into C345_conv's kernel).
+struct Conv3dArgs {
+    const float* x;
+    const float* x2;
+    const float* w;
+    const float* bias;
+    float* y;
+    int B, Ds, Hs, Ws, C1, C2, ldx, ldx2, up;
+    int kd, kh, kw, cout, stride, dil, ldy;
+    int64_t w_bstride;
+    // derived by conv3d_plan
+    int D, H, W, Do, Ho, Wo, pd, ph, pw;
+};
+
+inline int same_out(int in, int stride) { return (in + stride - 1) / stride; }
+inline int same_pad_before(int in, int k, int stride, int dil)
+{
+    const int total = (same_out(in, stride) - 1) * stride + (k - 1) * dil + 1 - in;
+    return (total > 0 ? total : 0) / 2;
+}
+
+void conv3d_plan(Conv3dArgs& a);                   // fills the derived fields
+void conv3d_launch(hipStream_t sm, const Conv3dArgs& a);  // (a planned; every limit checked by the caller)
+
+}  // namespace ps
