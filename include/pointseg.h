@@ -120,7 +120,10 @@ int ps_timing_end(ps_context* ctx, ps_timing_row* rows, int cap, int* n_rows);
 /* Exact K nearest neighbours, squared L2 in fp32, ascending, equal-distance ties broken exactly as the
  * reference's nanoflann 1.2.3 kd-tree (leaf 10) visits them.  support f32[B,n_support,3],
  * queries f32[B,n_queries,3], out int32[B,n_queries,K].  dim must be 3.  If n_support < K the trailing
- * K-n_support slots of every row are written as 0 (the reference returns np.zeros there, knn.pyx:93). */
+ * K-n_support slots of every row are written as 0 (the reference returns np.zeros there, knn.pyx:93).
+ * K is one of the compiled list sizes 1..16, 20, 24, 32, 48, 64 (PS_KNN_KS, csrc/kdtree.h); any other K returns PS_EINVAL before
+ * anything is enqueued, out_idx untouched, and ps_last_error() lists the sizes.  The same holds for ps_pyramid_build, which then
+ * leaves every table as it was and ps_pyramid.built = 0. */
 int ps_knn_batch(ps_context* ctx, const float* support, const float* queries, int64_t B, int64_t n_support,
                  int64_t n_queries, int64_t dim, int64_t K, int32_t* out_idx, int device_ptrs);
 /* Same with the reference's wire type (`long* batch_indices`, knn_.h:15-17). */

@@ -9,7 +9,7 @@
 extern "C" {
 #endif
 /* The product's own kd-tree construction + the per-query search routine the HIP kernel instantiates, run on the
- * host.  K in {1,5,7,16,32}. */
+ * host.  K: every size the kernels are compiled for (PS_KNN_KS, csrc/kdtree.h); any other returns PS_EINVAL, out_idx untouched. */
 int ps_debug_knn_host(const float* support, const float* queries, int64_t B, int64_t n_support,
                       int64_t n_queries, int64_t K, int32_t* out_idx);
 /* vind i32[n], nodes i32[2n,4], pts f32[n,4], root_depth i32[2], bbox f32[6] (layout: csrc/kdtree.h). */

@@ -34,12 +34,10 @@ extern "C" int ps_debug_knn_host(const float* support, const float* queries, int
         const float* q = queries + b * n2 * 3;
         int32_t* o = out + b * n2 * K;
         switch (K) {
-            case 1: search_all<1>(v, q, n2, o); break;
-            case 5: search_all<5>(v, q, n2, o); break;
-            case 7: search_all<7>(v, q, n2, o); break;
-            case 16: search_all<16>(v, q, n2, o); break;
-            case 32: search_all<32>(v, q, n2, o); break;
-            default: set_error("ps_debug_knn_host: K=%lld not instantiated (1,5,7,16,32)", (long long)K); return PS_EINVAL;
+#define PS_KCASE(k) case k: search_all<k>(v, q, n2, o); break;
+            PS_KNN_KS(PS_KCASE)  // every size the kernels are compiled for (kdtree.h)
+#undef PS_KCASE
+            default: set_error("ps_debug_knn_host: K=%lld is not a compiled size (" PS_KNN_KS_TEXT ")", (long long)K); return PS_EINVAL;
         }
     }
     return PS_OK;

@@ -37,6 +37,18 @@ struct float4 { float x, y, z, w; };
 
 #include "gmem.h"
 
+// The compiled list sizes K, ONE list: knn.hip instantiates knn_kernel<K> for every size of PS_KNN_KS and knn_pair_kernel<K> (the
+// pyramid's search) for every size of PS_KNN_PAIR_KS, debug_host.hip instantiates the host door of the same routine for PS_KNN_KS, and
+// tests/test_knn_size_coverage.py holds the tests' K lists to it.  PS_KNN_KS_TEXT is the list as the refusals print it.
+#ifdef PS_KNN_FEW_K
+#define PS_KNN_PAIR_KS(X) X(16) X(32)
+#else
+#define PS_KNN_PAIR_KS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(20) X(24) X(32) X(48) X(64)
+#endif
+#define PS_KNN_KS(X) X(1) PS_KNN_PAIR_KS(X)
+#define PS_KNN_K_TEXT(k) " " #k
+#define PS_KNN_KS_TEXT "compiled sizes:" PS_KNN_KS(PS_KNN_K_TEXT)
+
 namespace ps {
 
 constexpr int kLeafMax = 10;   // KDTreeTableAdaptor(npts, dim, points, 10)  knn_.cxx:116
@@ -44,6 +56,17 @@ constexpr int kStackMax = 64;  // deferred far-children per query; builders repo
 constexpr int kRefIdBits = 26;  // node ids < 2^26  =>  n < 2^25 points per tree
 constexpr int kRefIdMask = (1 << kRefIdBits) - 1;
 constexpr int kMaxTreePoints = 1 << 25;
+
+inline bool knn_k_compiled(int64_t K)
+{
+    switch (K) {
+#define PS_KCASE(k) case k:
+        PS_KNN_KS(PS_KCASE)
+#undef PS_KCASE
+        return true;
+        default: return false;
+    }
+}
 
 // Produced by the builder (on the device in production): root id, depth, root bounding box.
 struct TreeMeta {

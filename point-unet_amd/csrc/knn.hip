@@ -254,23 +254,17 @@ __global__ void widen_kernel(const int32_t* __restrict__ in, int64_t* __restrict
 // One workgroup per kKnnThreads queries of the largest job, rounded up to a multiple of 8: the XCD remap in knn_body covers [0, grid.x) exactly.
 static dim3 knn_grid(int max_nq, int n_jobs) { return dim3((ceil_div(max_nq, kKnnThreads) + 7) & ~7, n_jobs); }
 
-// the compiled K of the pyramid's pair kernel; the plain kernel also has K = 1
-#ifdef PS_KNN_FEW_K
-#define PS_KNN_PAIR_KS(X) X(16) X(32)
-#else
-#define PS_KNN_PAIR_KS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(20) X(24) X(32) X(48) X(64)
-#endif
-
+// (the compiled K: PS_KNN_KS / PS_KNN_PAIR_KS of kdtree.h -- the pair kernel has every size but K = 1)
 static int launch_knn(ps_context* c, const KnnJob* d_jobs, int n_jobs, int max_nq, int K)
 {
     const dim3 grid = knn_grid(max_nq, n_jobs);
     if (grid.x == 0 || n_jobs == 0) return PS_OK;
     switch (K) {
 #define PS_KCASE(k) case k: hipLaunchKernelGGL(knn_kernel<k>, grid, dim3(kKnnThreads), 0, c->stream, d_jobs); break;
-        PS_KCASE(1) PS_KNN_PAIR_KS(PS_KCASE)
+        PS_KNN_KS(PS_KCASE)
 #undef PS_KCASE
         default:
-            set_error("ps_knn: K=%d is not a compiled size (1..16, 20, 24, 32, 48, 64)", K);
+            set_error("ps_knn: K=%d is not a compiled size (" PS_KNN_KS_TEXT ")", K);
             return PS_EINVAL;
     }
     PS_HIP(hipGetLastError());
@@ -287,14 +281,12 @@ static int launch_knn_pair(ps_context* c, const KnnJob* d_jobs, int n_first, int
         PS_KNN_PAIR_KS(PS_KCASE)
 #undef PS_KCASE
         default:
-            set_error("ps_pyramid_build: K=%d is not a compiled size (1..16, 20, 24, 32, 48, 64)", K);
+            set_error("ps_pyramid_build: K=%d is not a compiled size (" PS_KNN_KS_TEXT ")", K);
             return PS_EINVAL;
     }
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
-#undef PS_KNN_PAIR_KS
-
 }  // namespace ps
 
 using namespace ps;
@@ -307,9 +299,12 @@ static int knn_batch_impl(ps_context* c, const float* support, const float* quer
 {
     PS_CHECK(c != nullptr, "ps_knn_batch: ctx is NULL");
     PS_CHECK(dim == 3, "ps_knn_batch: dim must be 3 (got %lld)", (long long)dim);
-    PS_CHECK(B >= 0 && n1 >= 0 && n2 >= 0 && K >= 1, "ps_knn_batch: negative size or K < 1");
+    PS_CHECK(B >= 0 && n1 >= 0 && n2 >= 0, "ps_knn_batch: negative size");
     PS_CHECK(n1 < kMaxTreePoints, "ps_knn_batch: n_support too large (limit 2^25 points per cloud)");
     PS_CHECK(out32 != nullptr || out64 != nullptr, "ps_knn_batch: out_idx is NULL");
+    // (K < 1 included; refused here, before anything is staged or built: launch_knn's own refusal would come behind the copies and the
+    // tree build)
+    PS_CHECK(knn_k_compiled(K), "ps_knn: K=%lld is not a compiled size (" PS_KNN_KS_TEXT ")", (long long)K);
     if (B == 0 || n2 == 0) return PS_OK;
     PS_CHECK(support != nullptr || n1 == 0, "ps_knn_batch: support is NULL");
     PS_CHECK(queries != nullptr, "ps_knn_batch: queries is NULL");
@@ -420,6 +415,8 @@ extern "C" int ps_pyramid_build(ps_context* c, const float* xyz0, int64_t B, int
         PS_CHECK(n[i + 1] >= 1, "ps_pyramid_build: level %d would be empty", i + 1);
     }
     pyr->built = 0;
+    // (refused here, before the trees are built and xyz[] is written: launch_knn_pair's own refusal would come behind all of that)
+    PS_CHECK(knn_k_compiled(K), "ps_pyramid_build: K=%d is not a compiled size (" PS_KNN_KS_TEXT ")", (int)K);
     pyr->num_layers = L;
     pyr->K = K;
     pyr->B = B;

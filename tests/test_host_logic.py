@@ -7,8 +7,12 @@ import os
 import numpy as np
 import pytest
 
+import knn_cases
 import netcase
 from conftest import brats_cloud, uniform_cloud
+
+# every K the search is compiled for: PS_KNN_KS of csrc/kdtree.h (tests/test_knn_size_coverage.py holds this list to the header)
+COMPILED_KS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 32, 48, 64]
 
 
 def _host_knn(dbg, lib, s, q, K):
@@ -36,6 +40,34 @@ def test_search_routine_upsampling_and_small(dbg, lib, oracle):
         q = rng.random((n, 3), dtype=np.float32)
         for K in (1, 5, 16):
             assert np.array_equal(_host_knn(dbg, lib, q[None], q[None], K), oracle.knn_batch(q[None], q[None], K)), (n, K)
+
+
+@pytest.mark.parametrize("K", COMPILED_KS)
+def test_search_routine_matches_oracle_at_every_compiled_k(dbg, lib, oracle, K):
+    """The portable topk_insert<K> and knn_search_one<K> of csrc/kdtree.h, index for index against the oracle at EVERY compiled list
+    size: a tie-free cloud, a lattice (equal distances everywhere: the order among equals is the insertion's `stored > d` rule), a
+    cloud of 8-fold duplicates (distance-0 ties longer than a small K), the deep tree of the geometric line, and clouds of
+    1, K-1, K, K+1 points (lists that never fill: the slots past n stay 0, as the oracle's np.zeros rows do)."""
+    for kind in knn_cases.SELF_KINDS + ("line",):
+        p = knn_cases.cloud(kind)
+        assert np.array_equal(_host_knn(dbg, lib, p[None], p[None], K), knn_cases.oracle_self(oracle, kind, K)), kind
+    s, q = knn_cases.foreign()
+    assert np.array_equal(_host_knn(dbg, lib, s[:, :500], q[:, :300], K), oracle.knn_batch(s[:, :500], q[:, :300], K))
+    for n in sorted({1, K - 1, K, K + 1} - {0}):
+        p = knn_cases.tiny(n)
+        got = _host_knn(dbg, lib, p[None], p[None], K)
+        assert np.array_equal(got, oracle.knn_batch(p[None], p[None], K)), n
+        assert not got[:, :, n:].any(), n
+
+
+@pytest.mark.parametrize("K", [0, 17, 33, 65])
+def test_search_door_refuses_an_uncompiled_k(dbg, lib, K):
+    p = knn_cases.tiny(40)
+    out = np.full((1, 40, max(K, 1)), -7, np.int32)
+    assert dbg.ps_debug_knn_host(p.ctypes.data, p.ctypes.data, 1, 40, 40, K, out.ctypes.data) == 1
+    msg = lib.ps_last_error().decode()
+    assert "K=%d" % K in msg and [int(t) for t in msg.split("compiled sizes:")[1].rstrip(")").split()] == COMPILED_KS, msg
+    assert (out == -7).all()
 
 
 def test_tree_layout_against_oracle_tree(dbg, lib, oracle):
