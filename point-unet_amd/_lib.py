@@ -1,8 +1,8 @@
 """ctypes binding of libpointseg_hip.so -- the only door between the Python host code and the HIP kernels.
 
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
-(PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES) and include/pointseg_saliency.h
-(SALIENCY_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES), include/pointseg_saliency.h
+(SALIENCY_PROTOTYPES) and include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -295,6 +295,14 @@ SALIENCY_PROTOTYPES = {
     "ps_saliency_finish": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 4 + [c_vp]),
 }
 
+# every symbol include/pointseg_saliency_train.h declares (the gradients of ps_conv3d and ps_instance_norm_relu; csrc/conv3d_train.hip)
+_CONV_GEOMETRY = [ctypes.c_int64] * 6 + [ctypes.c_int32] * 4 + [ctypes.c_int64] + [ctypes.c_int32] * 2  # B Ds Hs Ws C1 C2 up kd kh kw C_out stride dilation
+SALIENCY_TRAIN_PROTOTYPES = {
+    "ps_conv3d_bwd_data": (ctypes.c_int, [c_vp, c_vp, c_vp] + _CONV_GEOMETRY + [c_vp, c_vp, c_vp, c_i64p]),
+    "ps_conv3d_bwd_weight": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp] + _CONV_GEOMETRY + [c_vp, c_vp, c_vp, c_i64p]),
+    "ps_instance_norm_relu_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -315,7 +323,7 @@ def lib():
             pass
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
-                                  + list(SALIENCY_PROTOTYPES.items())):
+                                  + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

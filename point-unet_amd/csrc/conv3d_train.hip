@@ -1,0 +1,613 @@
+// conv3d_train.hip -- the gradients of conv3d.hip's convolution and of saliency.hip's instance norm + ReLU
+// (include/pointseg_saliency_train.h), with the forward's guarantees: exact fp32 operands on v_mfma_f32_16x16x4_f32
+// (mfma_tile.h's fragment maps), float64 fixed-order statistics, no float atomic, two runs give the same bytes.
+//
+// Data gradient: a gather, the forward's implicit GEMM with the roles turned.  Rows are the voxels i of the virtual (concatenated,
+// up-sampled) input, columns its channels, k = tap * C_out + co;  A[i, k] = dy[o, co] with o = (i + pad - t * dilation) / stride where that
+// is a whole number inside the output (0 elsewhere; never materialised), B[k, ci] = w[t, ci, co] -- a transposed copy of the kernel in
+// scratch, the one thing that is repacked.  With up == 1 the tile is written straight into dx / dx2 (the columns split at C1); with
+// up > 1 it goes to scratch and a second kernel adds each source voxel's up^3 virtual voxels in one fixed order.
+// Weight gradient: dw[(t, ci), co] = sum over voxels of in[v, (t, ci)] . dy[v, co] -- rows (t, ci) plus ONE more row of ones, whose
+// product is the bias gradient; the reduction over the output voxels is cut into slabs of 4096 per sample, a workgroup writes its slab's
+// [rows, columns] tile to scratch, and reduce_partials.h adds the slabs in one fixed order in float64.  `in` is fetched as the forward
+// fetches it (concat, / up, 0 in the padding).
+// Rounding (both): a chunk of 32 k is summed in a fresh accumulator and then added to the running one, as in conv3d.hip.
+// The data gradient is a kernel of its own and not conv3d_kernel behind a flipped kernel: its fetch would have to branch on its caller
+// (a negative tap step, the stride's parity test, the split result), and the forward has to stay byte for byte what it is.
+#include "../../include/pointseg_saliency_train.h"
+#include "mfma_tile.h"
+#include "reduce_partials.h"
+#include "saliency.h"
+#include "scratch.h"
+
+namespace ps {
+
+namespace {
+
+constexpr int kKC = 32;        // K chunk
+constexpr int kAP = kKC + 2;   // row-major A tile pitch, as conv3d.hip
+constexpr int kBP = 80;        // k-major tile pitch for up to 64 columns: the four k rows of a fragment read start 16 banks apart
+constexpr int kWSlab = 4096;   // output voxels per workgroup of the weight gradient
+constexpr int kNSlab = 4096;   // voxels per workgroup of the norm's statistics passes
+
+// One K chunk of a wave's RT x NT tiles: the chunk's 8 k-steps in a fresh accumulator, then added to the running one (conv3d.hip's
+// rounding).  a0: this lane's A element of row tile 0, k-step 0 (row tiles a_rt floats apart, k-steps a_s); b0: the same in the k-major B tile.
+template <int RT, int NT>
+__device__ __forceinline__ void chunk_mma(const float* a0, int a_rt, int a_s, const float* b0, f32x4 (&acc)[RT][NT])
+{
+    f32x4 part[RT][NT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) part[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < kKC / 4; ++s) {
+        float av[RT], bv[NT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) av[rt] = a0[rt * a_rt + s * a_s];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) bv[j] = b0[s * 4 * kBP + j * 16];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) part[rt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt], bv[j], part[rt][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[rt][j] += part[rt][j];
+}
+
+// ---- data gradient -----------------------------------------------------------------------------------------------------------------------------
+
+struct BwdDataArgs {
+    const float* dy;  // [B, Do, Ho, Wo, cout]
+    const float* wt;  // [taps][cout][cin], the transposed kernel
+    float* out0;      // columns below `split`, pitch ld0
+    float* out1;      // the others, pitch ld1
+    int ld0, ld1, split;
+    int obase;        // out0's first column
+    int c0, ncols;    // the columns (channels of the virtual input) this call computes: [c0, c0 + ncols)
+    int B, D, H, W, Do, Ho, Wo, cin, cout;
+    int kd, kh, kw, stride, dil, pd, ph, pw;
+};
+
+template <int RT, int NT>
+__global__ __launch_bounds__(256) void conv3d_bwd_data_kernel(BwdDataArgs a)
+{
+    constexpr int M = 64 * RT, N = 16 * NT;
+    constexpr int AI = M / 8;
+    constexpr int BI = kKC * N / 256;
+    constexpr int BKS = 256 / N;
+    __shared__ float As[M * kAP];
+    __shared__ float Bs[kKC * kBP];
+    __shared__ int4 rows[M];  // the row's voxel plus the padding (z, y, x) and whether the row exists
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int b = blockIdx.z, n0 = blockIdx.y * N, m0 = blockIdx.x * M;
+    const int V = a.D * a.H * a.W, Vo = a.Do * a.Ho * a.Wo;
+    for (int r = t; r < M; r += 256) {
+        const int v = m0 + r;
+        int4 ri = {0, 0, 0, 0};
+        if (v < V) ri = {v / (a.W * a.H) + a.pd, v / a.W % a.H + a.ph, v % a.W + a.pw, 1};
+        rows[r] = ri;
+    }
+    __syncthreads();
+
+    const int Ktot = a.kd * a.kh * a.kw * a.cout;
+    const int nchunks = (Ktot + kKC - 1) / kKC;
+    const int akk = t & 31, arow = t >> 5;
+    const int bcol = t % N, bk = t / N;
+    const float* dyb = a.dy + (size_t)b * Vo * a.cout;
+    const float* wb = a.wt + a.c0;
+    const bool s2 = a.stride == 2;
+
+    float areg[AI], breg[BI];
+    auto fetch = [&](int chunk) {
+        const int k = chunk * kKC + akk;
+        const bool kin = k < Ktot;
+        const int tap = kin ? k / a.cout : 0, co = kin ? k - tap * a.cout : 0;
+        const int dx = (tap % a.kw) * a.dil, dy = (tap / a.kw % a.kh) * a.dil, dz = (tap / (a.kw * a.kh)) * a.dil;
+#pragma unroll
+        for (int i = 0; i < AI; ++i) {
+            const int4 ri = rows[arow + 8 * i];
+            int z = ri.x - dz, y = ri.y - dy, x = ri.z - dx;  // o * stride
+            bool ok = kin && ri.w && (z | y | x) >= 0;
+            if (s2) {
+                ok = ok && ((z | y | x) & 1) == 0;
+                z >>= 1, y >>= 1, x >>= 1;
+            }
+            ok = ok && z < a.Do && y < a.Ho && x < a.Wo;
+            if (!ok) z = y = x = 0;
+            areg[i] = ok ? dyb[(size_t)((z * a.Ho + y) * a.Wo + x) * a.cout + co] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < BI; ++i) {
+            const int kb = chunk * kKC + bk + BKS * i;
+            breg[i] = (kb < Ktot && n0 + bcol < a.ncols) ? wb[(size_t)kb * a.cin + n0 + bcol] : 0.f;
+        }
+    };
+
+    f32x4 acc[RT][NT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    fetch(0);
+    const float* a0 = As + (wave * RT * 16 + (lane & 15)) * kAP + (lane >> 4);
+    const float* b0 = Bs + (lane >> 4) * kBP + (lane & 15);
+#pragma unroll 1
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+#pragma unroll
+        for (int i = 0; i < AI; ++i) As[(arow + 8 * i) * kAP + akk] = areg[i];
+#pragma unroll
+        for (int i = 0; i < BI; ++i) Bs[(bk + BKS * i) * kBP + bcol] = breg[i];
+        __syncthreads();
+        if (chunk + 1 < nchunks) fetch(chunk + 1);
+        chunk_mma<RT, NT>(a0, 16 * kAP, 4, b0, acc);
+        __syncthreads();
+    }
+
+    // C[i][j]: lane = j + 16 * (i / 4), reg = i % 4
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int lc = n0 + j * 16 + (lane & 15);
+        if (lc >= a.ncols) continue;
+        const int col = a.c0 + lc;
+        const bool first = col < a.split;
+        float* o = first ? a.out0 + (col - a.obase) : a.out1 + (col - a.split);
+        const int ld = first ? a.ld0 : a.ld1;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int v = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
+                if (v < V) o[((size_t)b * V + v) * ld] = acc[rt][j][r];
+            }
+    }
+}
+
+template <int RT, int NT>
+void launch_data(hipStream_t sm, const BwdDataArgs& a)
+{
+    const dim3 grid((unsigned)ceil_div((int64_t)a.D * a.H * a.W, 64 * RT), (unsigned)ceil_div(a.ncols, 16 * NT), (unsigned)a.B);
+    hipLaunchKernelGGL((conv3d_bwd_data_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
+}
+
+// wt[(tap * cout + co) * cin + ci] = w[(tap * cin + ci) * cout + co]
+__global__ __launch_bounds__(256) void transpose_kernel_kernel(const float* __restrict__ w, unsigned total, int cin, int cout, float* __restrict__ wt)
+{
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= total) return;
+    const unsigned ci = e % cin, r = e / cin, co = r % cout, tap = r / cout;
+    wt[e] = w[((size_t)tap * cin + ci) * cout + co];
+}
+
+// grid (ceil(Vs * ncols / 256), B): a source voxel's gradient = the sum of g over its up^3 virtual voxels, (dz, dy, dx) ascending
+__global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restrict__ g, int ncols, int c0, int Ds, int Hs, int Ws, int up, int C1, int C2,
+                                                           float* __restrict__ dx, float* __restrict__ dx2)
+{
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    const unsigned Vs = (unsigned)(Ds * Hs * Ws);
+    if (e >= Vs * (unsigned)ncols) return;
+    const unsigned c = e % ncols, s = e / ncols;
+    const int sx = s % Ws, sy = s / Ws % Hs, sz = s / (Ws * Hs);
+    const int H = Hs * up, W = Ws * up;
+    const float* gb = g + (size_t)blockIdx.y * Vs * up * up * up * ncols + c;
+    float sum = 0.f;
+    for (int dz = 0; dz < up; ++dz)
+        for (int dy = 0; dy < up; ++dy)
+            for (int dxx = 0; dxx < up; ++dxx)
+                sum += gb[(size_t)(((sz * up + dz) * H + sy * up + dy) * W + sx * up + dxx) * ncols];
+    const int col = c0 + (int)c;
+    const size_t row = (size_t)blockIdx.y * Vs + s;
+    if (col < C1) dx[row * C1 + col] = sum;
+    else dx2[row * C2 + (col - C1)] = sum;
+}
+
+// ---- weight and bias gradient ------------------------------------------------------------------------------------------------------------------
+
+struct BwdWeightArgs {
+    const float* x;
+    const float* x2;
+    const float* dy;
+    float* part;       // [B * slabs][nrows][cout]
+    int r0, nrows;     // the rows this call computes: [r0, r0 + nrows) of the Ktot kernel rows (tap, ci) and the row of ones (the bias) behind them
+    int Ktot, slabs, mtiles;
+    int B, Ds, Hs, Ws, C1, C2, up, D, H, W, Do, Ho, Wo, cout;
+    int kd, kh, kw, stride, dil, pd, ph, pw;
+};
+
+// grid (mtiles * B * slabs, column tiles).  Both tiles are k-major in LDS (k = a voxel of the slab): thread t fetches rows t % 64 (+ 64)
+// -- adjacent lanes adjacent input channels -- of the voxels t / 64 + 4 i, whose input corners come from LDS.
+template <int RT, int NT>
+__global__ __launch_bounds__(256) void conv3d_bwd_weight_kernel(BwdWeightArgs a)
+{
+    constexpr int M = 64 * RT, N = 16 * NT;
+    constexpr int PA = M + 16;  // 16 (mod 32) floats
+    constexpr int BI = kKC * N / 256;
+    constexpr int BKS = 256 / N;
+    __shared__ float As[kKC * PA];
+    __shared__ float Bs[kKC * kBP];
+    __shared__ int4 vox[2][kKC];  // the input corner of the voxel's receptive field (z, y, x) and whether the voxel exists
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int mt = blockIdx.x % a.mtiles, pidx = blockIdx.x / a.mtiles;
+    const int b = pidx / a.slabs, slab = pidx - b * a.slabs;
+    const int m0 = mt * M, n0 = blockIdx.y * N;
+    const int Vo = a.Do * a.Ho * a.Wo;
+    const int v0 = slab * kWSlab, v1 = min(Vo, v0 + kWSlab);
+    const int nchunks = (v1 - v0 + kKC - 1) / kKC;
+    const int cin = a.C1 + a.C2;
+    const size_t xs = (size_t)a.Ds * a.Hs * a.Ws;
+    const float* dyb = a.dy + (size_t)b * Vo * a.cout;
+
+    // this thread's rows: kind 0 = none, 1 = a kernel row, 2 = the row of ones
+    int kind[RT], rdz[RT], rdy[RT], rdx[RT], rld[RT];
+    const float* rsrc[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int lr = m0 + rt * 64 + lane, row = a.r0 + lr;
+        kind[rt] = lr >= a.nrows ? 0 : (row < a.Ktot ? 1 : 2);
+        const int tap = kind[rt] == 1 ? row / cin : 0, ci = kind[rt] == 1 ? row - tap * cin : 0;
+        rdx[rt] = (tap % a.kw) * a.dil, rdy[rt] = (tap / a.kw % a.kh) * a.dil, rdz[rt] = (tap / (a.kw * a.kh)) * a.dil;
+        const bool second = ci >= a.C1;
+        rsrc[rt] = second ? a.x2 + (size_t)b * xs * a.C2 + (ci - a.C1) : a.x + (size_t)b * xs * a.C1 + ci;
+        rld[rt] = second ? a.C2 : a.C1;
+    }
+    const int bcol = t % N, bk = t / N;
+
+    auto put_vox = [&](int chunk) {
+        if (t < kKC) {
+            const int v = v0 + chunk * kKC + t;
+            int4 vi = {0, 0, 0, 0};
+            if (v < v1) vi = {v / (a.Wo * a.Ho) * a.stride - a.pd, v / a.Wo % a.Ho * a.stride - a.ph, v % a.Wo * a.stride - a.pw, 1};
+            vox[chunk & 1][t] = vi;
+        }
+    };
+
+    float areg[RT][8], breg[BI];
+    auto fetch = [&](int chunk) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int4 vi = vox[chunk & 1][wave + 4 * i];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                int z = vi.x + rdz[rt], y = vi.y + rdy[rt], x = vi.z + rdx[rt];
+                const bool ok = kind[rt] == 1 && vi.w && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+                if (!ok) z = y = x = 0;
+                if (a.up > 1) {
+                    z = (int)((unsigned)z / (unsigned)a.up);
+                    y = (int)((unsigned)y / (unsigned)a.up);
+                    x = (int)((unsigned)x / (unsigned)a.up);
+                }
+                const float one = (kind[rt] == 2 && vi.w) ? 1.f : 0.f;
+                areg[rt][i] = ok ? rsrc[rt][(size_t)((z * a.Hs + y) * a.Ws + x) * rld[rt]] : one;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < BI; ++i) {
+            const int v = v0 + chunk * kKC + bk + BKS * i;
+            breg[i] = (v < v1 && n0 + bcol < a.cout) ? dyb[(size_t)v * a.cout + n0 + bcol] : 0.f;
+        }
+    };
+
+    f32x4 acc[RT][NT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    put_vox(0);
+    __syncthreads();
+    fetch(0);
+    // A[i][k]: lane = i + 16 * k, B[k][j]: lane = j + 16 * k -- both read row (lane / 16) of the k-step, column lane % 16 of their tile
+    const float* a0 = As + (lane >> 4) * PA + wave * RT * 16 + (lane & 15);
+    const float* b0 = Bs + (lane >> 4) * kBP + (lane & 15);
+#pragma unroll 1
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) As[(wave + 4 * i) * PA + rt * 64 + lane] = areg[rt][i];
+#pragma unroll
+        for (int i = 0; i < BI; ++i) Bs[(bk + BKS * i) * kBP + bcol] = breg[i];
+        if (chunk + 1 < nchunks) put_vox(chunk + 1);
+        __syncthreads();
+        if (chunk + 1 < nchunks) fetch(chunk + 1);
+        chunk_mma<RT, NT>(a0, 16, 4 * PA, b0, acc);
+        __syncthreads();
+    }
+
+    float* pb = a.part + (size_t)pidx * a.nrows * a.cout;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int col = n0 + j * 16 + (lane & 15);
+        if (col >= a.cout) continue;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int lr = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
+                if (lr < a.nrows) pb[(size_t)lr * a.cout + col] = acc[rt][j][r];
+            }
+    }
+}
+
+template <int RT, int NT>
+void launch_weight(hipStream_t sm, BwdWeightArgs& a)
+{
+    a.mtiles = ceil_div(a.nrows, 64 * RT);
+    const dim3 grid((unsigned)((int64_t)a.mtiles * a.B * a.slabs), (unsigned)ceil_div(a.cout, 16 * NT));
+    hipLaunchKernelGGL((conv3d_bwd_weight_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
+}
+
+// ---- instance norm + ReLU ------------------------------------------------------------------------------------------------------------------------
+
+// grid (slabs, B, channel tiles of 64), the layout of saliency.hip's statistics pass.  SECOND == false: (sum x, sum x^2);
+// SECOND == true: (sum g, sum g xhat) with g = dy where y > 0 and xhat = (x - mean) * rstd from stat[b * C + c]
+template <bool SECOND>
+__global__ __launch_bounds__(256) void in_bwd_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy, int V, int C,
+                                                          int cshift, const double2* __restrict__ stat, double* __restrict__ part)
+{
+    __shared__ double ss[256], sq[256];
+    const int t = threadIdx.x, cw = 1 << cshift;
+    const int c = blockIdx.z * 64 + (t & (cw - 1)), rl = t >> cshift, nrl = 256 >> cshift;
+    const int b = blockIdx.y, v0 = blockIdx.x * kNSlab, v1 = min(V, v0 + kNSlab);
+    double s = 0.0, q = 0.0;
+    if (c < C) {
+        const size_t base = ((size_t)b * V) * C + c;
+        double2 st = {0.0, 0.0};
+        if (SECOND) st = stat[b * C + c];
+        for (int v = v0 + rl; v < v1; v += nrl) {
+            const size_t e = base + (size_t)v * C;
+            const double f = (double)x[e];
+            if (SECOND) {
+                const double g = y[e] > 0.f ? (double)dy[e] : 0.0;
+                s += g;
+                q += g * ((f - st.x) * st.y);
+            } else {
+                s += f;
+                q += f * f;
+            }
+        }
+    }
+    ss[t] = s;
+    sq[t] = q;
+    __syncthreads();
+    if (t < cw && c < C) {
+        double S = 0.0, Q = 0.0;
+        for (int j = 0; j < nrl; ++j) {
+            S += ss[j * cw + t];
+            Q += sq[j * cw + t];
+        }
+        double* o = part + (((size_t)blockIdx.x * gridDim.y + b) * C + c) * 2;
+        o[0] = S;
+        o[1] = Q;
+    }
+}
+
+// tot[(b * C + c) * 2 + {0, 1}] -> stat[b * C + c] = (mean, 1 / sqrt(var + eps)), the biased variance of tf.nn.moments
+__global__ __launch_bounds__(256) void in_bwd_stat_kernel(const double* __restrict__ tot, int V, int BC, float eps, double2* __restrict__ stat)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= BC) return;
+    const double mean = tot[2 * i] / V;
+    double var = tot[2 * i + 1] / V - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    stat[i] = make_double2(mean, 1.0 / sqrt(var + (double)eps));
+}
+
+// grid (ceil(V * C / 256), B): dx = gamma * rstd * (g - mean(g) - xhat * mean(g xhat)); every element reads its own dy before it writes dx
+__global__ __launch_bounds__(256) void in_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* dy, int V, int C,
+                                                        const double2* __restrict__ stat, const double* __restrict__ tot2, const float* __restrict__ gamma,
+                                                        float* dx)
+{
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= (unsigned)V * (unsigned)C) return;
+    const unsigned c = e % (unsigned)C;
+    const size_t i = (size_t)blockIdx.y * V * C + e;
+    const int bc = blockIdx.y * C + c;
+    const double2 st = stat[bc];
+    const double mg = tot2[2 * bc] / V, mgx = tot2[2 * bc + 1] / V;
+    const double g = y[i] > 0.f ? (double)dy[i] : 0.0;
+    const double xh = ((double)x[i] - st.x) * st.y;
+    dx[i] = (float)((double)gamma[c] * st.y * (g - mg - xh * mgx));
+}
+
+// dbeta[c] = sum over b of tot2[b][c][0], dgamma[c] = sum over b of tot2[b][c][1], b ascending
+__global__ __launch_bounds__(256) void in_bwd_params_kernel(const double* __restrict__ tot2, int B, int C, float* __restrict__ dgamma, float* __restrict__ dbeta)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double sb = 0.0, sg = 0.0;
+    for (int b = 0; b < B; ++b) {
+        sb += tot2[((size_t)b * C + c) * 2];
+        sg += tot2[((size_t)b * C + c) * 2 + 1];
+    }
+    if (dbeta) dbeta[c] = (float)sb;
+    if (dgamma) dgamma[c] = (float)sg;
+}
+
+int cshift_for(int C)
+{
+    int s = 0;
+    while ((1 << s) < C && s < 6) ++s;
+    return s;
+}
+
+// ---- the argument checks the two convolution entries share -------------------------------------------------------------------------------------
+
+int conv_geometry_ok(const char* who, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw,
+                     int64_t C_out, int32_t stride, int32_t dilation)
+{
+    const int64_t lim = 1ll << 31;
+    auto kext = [](int k) { return k == 1 || k == 3 || k == 9; };
+    PS_CHECK(kext(kd) && kext(kh) && kext(kw), "%s: kernel %d x %d x %d, every extent must be 1, 3 or 9", who, (int)kd, (int)kh, (int)kw);
+    PS_CHECK(stride == 1 || stride == 2, "%s: stride = %d, must be 1 or 2", who, (int)stride);
+    PS_CHECK(dilation == 1 || dilation == 3 || dilation == 5 || dilation == 7, "%s: dilation = %d, must be 1, 3, 5 or 7", who, (int)dilation);
+    PS_CHECK(up >= 1 && up <= 8, "%s: up = %d, must be in [1, 8]", who, (int)up);
+    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
+    PS_CHECK(C1 >= 1 && C2 >= 0 && C1 + C2 <= 384, "%s: C1 = %lld, C2 = %lld (C1 >= 1, C2 >= 0, C1 + C2 <= 384)", who, (long long)C1, (long long)C2);
+    PS_CHECK(C_out >= 1 && C_out <= 256, "%s: C_out = %lld, must be in [1, 256]", who, (long long)C_out);
+    PS_CHECK(Ds >= 1 && Hs >= 1 && Ws >= 1 && Ds < lim && Hs < lim && Ws < lim && Ds * up * Hs * up < lim && Ds * up * Hs * up * Ws * up < lim
+                 && Ds * Hs * Ws * (C1 > C2 ? C1 : C2) < lim && Ds * up * Hs * up * Ws * up * C_out < lim,
+             "%s: input %lld x %lld x %lld (every extent >= 1, every tensor below 2^31 elements per sample)", who, (long long)Ds, (long long)Hs,
+             (long long)Ws);
+    return PS_OK;
+}
+
+}  // namespace
+
+}  // namespace ps
+
+extern "C" int ps_conv3d_bwd_data(ps_context* c, const void* dy, const void* w, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2, int32_t up,
+                                  int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* dx, void* dx2, void* scratch,
+                                  int64_t* scratch_bytes)
+{
+    using namespace ps;
+    static const char* who = "ps_conv3d_bwd_data";
+    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
+    PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
+    const int cin = (int)(C1 + C2), taps = kd * kh * kw;
+    const int D = (int)Ds * up, H = (int)Hs * up, W = (int)Ws * up;
+    Carver cv{static_cast<char*>(scratch)};
+    float* wt = cv.take<float>((size_t)taps * cin * C_out);
+    float* g = up > 1 ? cv.take<float>((size_t)B * D * H * W * cin) : nullptr;
+    if (!scratch) {
+        *scratch_bytes = (int64_t)cv.off;
+        return PS_OK;
+    }
+    PS_CHECK(dy && w, "%s: NULL dy or w (they may be NULL only in the call that sizes the scratch)", who);
+    PS_CHECK(C2 > 0 || !dx2, "%s: dx2 must be NULL when C2 == 0", who);
+    PS_CHECK(dx || dx2, "%s: every result is NULL", who);
+    PS_CHECK(dx != dy && dx2 != dy, "%s: dx and dx2 must not overlap dy", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
+
+    BwdDataArgs a = {};
+    a.dy = static_cast<const float*>(dy);
+    a.wt = wt;
+    a.c0 = dx ? 0 : (int)C1;
+    a.ncols = (dx2 ? cin : (int)C1) - a.c0;
+    if (up > 1) a.out0 = g, a.out1 = nullptr, a.ld0 = a.ncols, a.ld1 = 0, a.split = cin, a.obase = a.c0;
+    else a.out0 = static_cast<float*>(dx), a.out1 = static_cast<float*>(dx2), a.ld0 = (int)C1, a.ld1 = (int)C2, a.split = (int)C1, a.obase = 0;
+    a.B = (int)B, a.D = D, a.H = H, a.W = W, a.cin = cin, a.cout = (int)C_out;
+    a.Do = same_out(D, stride), a.Ho = same_out(H, stride), a.Wo = same_out(W, stride);
+    a.kd = kd, a.kh = kh, a.kw = kw, a.stride = stride, a.dil = dilation;
+    a.pd = same_pad_before(D, kd, stride, dilation), a.ph = same_pad_before(H, kh, stride, dilation), a.pw = same_pad_before(W, kw, stride, dilation);
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    Stage stg(c, "conv3d_bwd_data", 3);
+    const unsigned wn = (unsigned)((size_t)taps * cin * C_out);
+    hipLaunchKernelGGL(transpose_kernel_kernel, dim3(blocks256(wn)), dim3(256), 0, sm, static_cast<const float*>(w), wn, cin, (int)C_out, wt);
+    // the forward's forms: 16 * NT columns per workgroup, 128 rows where there are enough voxels to fill the device with them
+    const bool wide = (int64_t)D * H * W >= 2048;
+    if (a.ncols <= 16) wide ? launch_data<2, 1>(sm, a) : launch_data<1, 1>(sm, a);
+    else if (a.ncols <= 32) wide ? launch_data<2, 2>(sm, a) : launch_data<1, 2>(sm, a);
+    else wide ? launch_data<2, 4>(sm, a) : launch_data<1, 4>(sm, a);
+    if (up > 1)
+        hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks256((size_t)Ds * Hs * Ws * a.ncols), (unsigned)B), dim3(256), 0, sm, g, a.ncols, a.c0, (int)Ds, (int)Hs,
+                           (int)Ws, (int)up, (int)C1, (int)C2, static_cast<float*>(dx), static_cast<float*>(dx2));
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+extern "C" int ps_conv3d_bwd_weight(ps_context* c, const void* x, const void* x2, const void* dy, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1,
+                                    int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* dw,
+                                    void* dbias, void* scratch, int64_t* scratch_bytes)
+{
+    using namespace ps;
+    static const char* who = "ps_conv3d_bwd_weight";
+    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
+    PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
+    Conv3dArgs f = {};
+    f.B = (int)B, f.Ds = (int)Ds, f.Hs = (int)Hs, f.Ws = (int)Ws, f.C1 = (int)C1, f.C2 = (int)C2, f.up = up;
+    f.kd = kd, f.kh = kh, f.kw = kw, f.cout = (int)C_out, f.stride = stride, f.dil = dilation;
+    conv3d_plan(f);
+    const int Ktot = kd * kh * kw * (int)(C1 + C2);
+    const int slabs = ceil_div((int64_t)f.Do * f.Ho * f.Wo, kWSlab);
+    const int64_t n_part = B * slabs;
+    PS_CHECK(n_part * ceil_div(Ktot + 1, 64) < (1ll << 31), "%s: B = %lld times %d slabs of %d output voxels are more workgroups than one launch holds", who,
+             (long long)B, slabs, kWSlab);
+    Carver cv{static_cast<char*>(scratch)};
+    float* part = cv.take<float>((size_t)n_part * (Ktot + 1) * C_out);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)cv.off;
+        return PS_OK;
+    }
+    PS_CHECK(x && dy, "%s: NULL x or dy (they may be NULL only in the call that sizes the scratch)", who);
+    PS_CHECK((C2 == 0) == (x2 == nullptr), "%s: x2 must be given exactly when C2 > 0", who);
+    PS_CHECK(dw || dbias, "%s: every result is NULL", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
+
+    BwdWeightArgs a = {};
+    a.x = static_cast<const float*>(x), a.x2 = static_cast<const float*>(x2), a.dy = static_cast<const float*>(dy), a.part = part;
+    a.r0 = dw ? 0 : Ktot;
+    a.nrows = (dbias ? Ktot + 1 : Ktot) - a.r0;
+    a.Ktot = Ktot, a.slabs = slabs;
+    a.B = f.B, a.Ds = f.Ds, a.Hs = f.Hs, a.Ws = f.Ws, a.C1 = f.C1, a.C2 = f.C2, a.up = up, a.D = f.D, a.H = f.H, a.W = f.W, a.Do = f.Do, a.Ho = f.Ho, a.Wo = f.Wo;
+    a.cout = f.cout, a.kd = kd, a.kh = kh, a.kw = kw, a.stride = stride, a.dil = dilation, a.pd = f.pd, a.ph = f.ph, a.pw = f.pw;
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    Stage stg(c, "conv3d_bwd_weight", 2);
+    const bool tall = a.nrows > 64;
+    if (a.cout <= 16) tall ? launch_weight<2, 1>(sm, a) : launch_weight<1, 1>(sm, a);
+    else if (a.cout <= 32) tall ? launch_weight<2, 2>(sm, a) : launch_weight<1, 2>(sm, a);
+    else tall ? launch_weight<2, 4>(sm, a) : launch_weight<1, 4>(sm, a);
+    const int nv = a.nrows * a.cout, n0 = dw ? Ktot * a.cout : 0;
+    hipLaunchKernelGGL((reduce_partials2_kernel<float, double>), dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, (int)n_part, nv, n0,
+                       static_cast<float*>(dw), static_cast<float*>(dbias));
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+extern "C" int ps_instance_norm_relu_bwd(ps_context* c, const void* x, const void* y, const void* dy, int64_t B, int64_t V, int64_t C, const void* gamma, float eps,
+                                         void* dx, void* dgamma, void* dbeta, void* scratch, int64_t* scratch_bytes)
+{
+    using namespace ps;
+    static const char* who = "ps_instance_norm_relu_bwd";
+    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
+    PS_CHECK(B >= 1 && B <= 65535 && V >= 1 && C >= 1 && C <= 1024 && V < (1ll << 31) && V * C < (1ll << 31),
+             "%s: B = %lld, V = %lld, C = %lld (1 <= B <= 65535, 1 <= C <= 1024, V >= 1, V * C < 2^31)", who, (long long)B, (long long)V, (long long)C);
+    PS_CHECK(eps > 0.f, "%s: eps = %g, must be > 0", who, (double)eps);
+    const int slabs = ceil_div(V, kNSlab), nv = (int)(B * C * 2);
+    Carver cv{static_cast<char*>(scratch)};
+    double* part = cv.take<double>((size_t)slabs * nv);
+    double* tot = cv.take<double>((size_t)nv);
+    double2* stat = cv.take<double2>((size_t)B * C);
+    double* tot2 = cv.take<double>((size_t)nv);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)cv.off;
+        return PS_OK;
+    }
+    PS_CHECK(x && y && dy && gamma, "%s: NULL x, y, dy or gamma (they may be NULL only in the call that sizes the scratch)", who);
+    PS_CHECK(dx || dgamma || dbeta, "%s: every result is NULL", who);
+    PS_CHECK(dx != x && dx != y, "%s: dx must not overlap x or y (it may be dy)", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    Stage stg(c, "instance_norm_relu_bwd", 7);
+    const float *xf = static_cast<const float*>(x), *yf = static_cast<const float*>(y), *dyf = static_cast<const float*>(dy);
+    const int nB = (int)B, nV = (int)V, nC = (int)C;
+    const dim3 sgrid((unsigned)slabs, (unsigned)nB, (unsigned)ceil_div(nC, 64));
+    hipLaunchKernelGGL(in_bwd_sums_kernel<false>, sgrid, dim3(256), 0, sm, xf, yf, dyf, nV, nC, cshift_for(nC), stat, part);
+    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, tot);
+    hipLaunchKernelGGL(in_bwd_stat_kernel, dim3(blocks256((size_t)nB * nC)), dim3(256), 0, sm, tot, nV, nB * nC, eps, stat);
+    hipLaunchKernelGGL(in_bwd_sums_kernel<true>, sgrid, dim3(256), 0, sm, xf, yf, dyf, nV, nC, cshift_for(nC), stat, part);
+    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, tot2);
+    if (dx)
+        hipLaunchKernelGGL(in_bwd_dx_kernel, dim3(blocks256((size_t)nV * nC), (unsigned)nB), dim3(256), 0, sm, xf, yf, dyf, nV, nC, stat, tot2,
+                           static_cast<const float*>(gamma), static_cast<float*>(dx));
+    if (dgamma || dbeta)
+        hipLaunchKernelGGL(in_bwd_params_kernel, dim3(blocks256((size_t)nC)), dim3(256), 0, sm, tot2, nB, nC, static_cast<float*>(dgamma),
+                           static_cast<float*>(dbeta));
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}

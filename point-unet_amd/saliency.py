@@ -1,6 +1,7 @@
 """The saliency attention map in front of prepare.pancreas_mask: the reference's SaliencyAttention network (`unet3d_attention`,
 SaliencyAttention/model.py:176-314 with attention.py:79-174) run patch by patch over a volume (`overlapping_inference`,
-SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  Inference only.
+SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  The network runs for inference only; the gradients of its convolution and
+of its instance norm + ReLU (include/pointseg_saliency_train.h, csrc/conv3d_train.hip) stand at the end of this module, op by op.
 
 Parameters are a dict of TensorFlow-named arrays in TensorFlow layout under the `unet3d_attention/` scope: `<layer>/kernel`
 [kd, kh, kw, in, out] (dense layers: [in, out]), `<layer>/bias`, `<layer>/ins_norm/gamma`, `<layer>/ins_norm/beta`, with <layer> the
@@ -277,3 +278,148 @@ def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118)):
                                                       runtime.ptr(total), runtime.ptr(count)))
     _lib.check(lib.ps_saliency_finish(ctx.handle, runtime.ptr(total), runtime.ptr(count), D, H, W, K, runtime.ptr(total)))
     return total
+
+
+# ---- the gradients of the two op wrappers (include/pointseg_saliency_train.h, csrc/conv3d_train.hip) ---------------------------------------------
+
+def _two_call(name, dev, call):
+    """The two-call scratch protocol: call(None, byref(need)) sizes (it looks at the shapes alone), then the same call runs on the
+    cached buffer."""
+    need = ctypes.c_int64(0)
+    _lib.check(call(None, ctypes.byref(need)))
+    buf = _scratch_for((name, dev.index), need.value, dev)
+    _lib.check(call(runtime.ptr(buf), ctypes.byref(need)))
+
+
+def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x2", "w", "bias")):
+    """The gradients of conv3d(x, w, bias, stride, dilation, x2, up) for the output gradient dy: a dict with the entries of `need` --
+    "x" [like x], "x2" [like x2; only with x2], "w" [like w], "bias" [C_out].  Arguments are checked as conv3d checks them."""
+    who = "conv3d_backward"
+    x = _f32(x, who, "x", 5)
+    w = _f32(w, who, "w", 5)
+    dy = _f32(dy, who, "dy", 5)
+    B, Ds, Hs, Ws, C1 = x.shape
+    C2 = 0
+    if x2 is not None:
+        x2 = _f32(x2, who, "x2", 5)
+        if x2.shape[:4] != x.shape[:4]:
+            raise ValueError("conv3d_backward: x2 must have x's batch and extents")
+        C2 = x2.shape[4]
+    if w.shape[3] != C1 + C2:
+        raise ValueError("conv3d_backward: w has %d input channels, the input %d" % (w.shape[3], C1 + C2))
+    want = (B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4])
+    if tuple(dy.shape) != want:
+        raise ValueError("conv3d_backward: dy has shape %s, the convolution's output %s" % (tuple(dy.shape), want))
+    need = set(need)
+    if not need or need - {"x", "x2", "w", "bias"}:
+        raise ValueError("conv3d_backward: need must name some of x, x2, w, bias")
+    if x2 is None:
+        need.discard("x2")
+        if not need:
+            raise ValueError("conv3d_backward: the gradient of x2 was asked for and there is no x2")
+    out = {}
+    ctx = runtime.default_context(x.device.index)
+    ctx.use_torch_stream()
+    geometry = (B, Ds, Hs, Ws, C1, C2, up, w.shape[0], w.shape[1], w.shape[2], w.shape[4], stride, dilation)
+    if need & {"x", "x2"}:
+        dx = torch.empty_like(x) if "x" in need else None
+        dx2 = torch.empty_like(x2) if "x2" in need else None
+        fn = _lib.lib().ps_conv3d_bwd_data
+        _two_call("ps_conv3d_bwd_data", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(dy), runtime.ptr(w), *geometry, runtime.ptr(dx),
+                                                                        runtime.ptr(dx2), scratch, n))
+        if dx is not None:
+            out["x"] = dx
+        if dx2 is not None:
+            out["x2"] = dx2
+    if need & {"w", "bias"}:
+        dw = torch.empty_like(w) if "w" in need else None
+        db = torch.empty((w.shape[4],), dtype=torch.float32, device=x.device) if "bias" in need else None
+        fn = _lib.lib().ps_conv3d_bwd_weight
+        _two_call("ps_conv3d_bwd_weight", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(x2), runtime.ptr(dy), *geometry,
+                                                                          runtime.ptr(dw), runtime.ptr(db), scratch, n))
+        if dw is not None:
+            out["w"] = dw
+        if db is not None:
+            out["bias"] = db
+    return out
+
+
+def _norm_backward(dy, x, y, gamma, eps, need):
+    who = "instance_norm_relu_backward"
+    x, y, dy = _f32(x, who, "x"), _f32(y, who, "y"), _f32(dy, who, "dy")
+    gamma = _f32(gamma, who, "gamma", 1)
+    if x.dim() < 2 or y.shape != x.shape or dy.shape != x.shape:
+        raise ValueError("instance_norm_relu_backward: x, y and dy must be [B, ..., C] of one shape")
+    B, C = x.shape[0], x.shape[-1]
+    V = x.numel() // (B * C)
+    if gamma.shape[0] != C:
+        raise ValueError("instance_norm_relu_backward: gamma must have C values")
+    if not any(need):
+        raise ValueError("instance_norm_relu_backward: no gradient asked for")
+    dx = torch.empty_like(x) if need[0] else None
+    dgamma = torch.empty_like(gamma) if need[1] else None
+    dbeta = torch.empty_like(gamma) if need[2] else None
+    ctx = runtime.default_context(x.device.index)
+    ctx.use_torch_stream()
+    fn = _lib.lib().ps_instance_norm_relu_bwd
+    _two_call("ps_instance_norm_relu_bwd", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(y), runtime.ptr(dy), B, V, C,
+                                                                           runtime.ptr(gamma), eps, runtime.ptr(dx), runtime.ptr(dgamma), runtime.ptr(dbeta),
+                                                                           scratch, n))
+    return dx, dgamma, dbeta
+
+
+def instance_norm_relu_backward(dy, x, y, gamma, eps=EPS):
+    """The gradients of y = instance_norm_relu(x, gamma, beta, eps) for the output gradient dy: (dx, dgamma, dbeta).  y is only the ReLU's
+    mask (y > 0)."""
+    return _norm_backward(dy, x, y, gamma, eps, (True, True, True))
+
+
+class Conv3dFunction(torch.autograd.Function):
+    """conv3d with its gradients: forward ps_conv3d, backward ps_conv3d_bwd_data and ps_conv3d_bwd_weight.  Saves x, x2 and w."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, dilation, x2, up):
+        ctx.save_for_backward(x, x2, w)
+        ctx.geometry = (stride, dilation, up)
+        return conv3d(x, w, bias, stride, dilation, x2, up)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, x2, w = ctx.saved_tensors
+        stride, dilation, up = ctx.geometry
+        wanted = ctx.needs_input_grad
+        need = [name for name, i in (("x", 0), ("w", 1), ("bias", 2), ("x2", 5)) if wanted[i] and (name != "x2" or x2 is not None)]
+        g = conv3d_backward(dy, x, w, stride, dilation, x2, up, need) if need else {}
+        return g.get("x"), g.get("w"), g.get("bias"), None, None, g.get("x2"), None
+
+
+class InstanceNormReluFunction(torch.autograd.Function):
+    """instance_norm_relu with its gradients: forward ps_instance_norm_relu, backward ps_instance_norm_relu_bwd.  Saves x, y and gamma."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        y = instance_norm_relu(x, gamma, beta, eps)
+        ctx.save_for_backward(x, y, gamma)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, y, gamma = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad[:3])
+        if not any(need):
+            return None, None, None, None
+        dx, dgamma, dbeta = _norm_backward(dy, x, y, gamma, ctx.eps, need)
+        return dx, dgamma, dbeta, None
+
+
+def differentiable_conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
+    """conv3d, recorded by torch.autograd."""
+    return Conv3dFunction.apply(x, w, bias, stride, dilation, x2, up)
+
+
+def differentiable_instance_norm_relu(x, gamma, beta, eps=EPS):
+    """instance_norm_relu, recorded by torch.autograd."""
+    return InstanceNormReluFunction.apply(x, gamma, beta, eps)
