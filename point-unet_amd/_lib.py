@@ -303,6 +303,17 @@ SALIENCY_TRAIN_PROTOTYPES = {
     "ps_instance_norm_relu_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64p]),
 }
 
+# every symbol include/pointseg_saliency_attention.h declares (the channel attention, the spatial gate and softmax + Dice, each with its
+# gradient; csrc/saliency_train.hip)
+SALIENCY_ATTENTION_PROTOTYPES = {
+    "ps_channel_attention": (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int64] * 4 + [c_vp] * 8 + [c_vp, c_i64p]),
+    "ps_channel_attention_bwd": (ctypes.c_int, [c_vp] * 8 + [ctypes.c_int64] * 4 + [c_vp] * 5 + [c_vp, c_i64p]),
+    "ps_spatial_gate": (ctypes.c_int, [c_vp] * 5 + [ctypes.c_int64] * 3 + [c_vp, c_vp]),
+    "ps_spatial_gate_bwd": (ctypes.c_int, [c_vp] * 4 + [ctypes.c_int64] * 3 + [c_vp, c_vp]),
+    "ps_softmax_dice_loss": (ctypes.c_int, [c_vp] * 4 + [ctypes.c_int64] * 3 + [c_vp, c_vp, c_vp, c_i64p]),
+    "ps_softmax_dice_loss_bwd": (ctypes.c_int, [c_vp] * 6 + [ctypes.c_int64] * 3 + [c_vp]),
+}
+
 _lib = None
 
 
@@ -323,7 +334,8 @@ def lib():
             pass
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
-                                  + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())):
+                                  + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())
+                                  + list(SALIENCY_ATTENTION_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,7 +1,7 @@
 """The saliency attention map in front of prepare.pancreas_mask: the reference's SaliencyAttention network (`unet3d_attention`,
 SaliencyAttention/model.py:176-314 with attention.py:79-174) run patch by patch over a volume (`overlapping_inference`,
-SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  The network runs for inference only; the gradients of its convolution and
-of its instance norm + ReLU (include/pointseg_saliency_train.h, csrc/conv3d_train.hip) stand at the end of this module, op by op.
+SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  SaliencyNet runs it for inference behind one call; the gradients of its
+ops (include/pointseg_saliency_train.h, include/pointseg_saliency_attention.h) stand behind it, op by op, and TrainableSaliencyNet composes the graph from them.
 
 Parameters are a dict of TensorFlow-named arrays in TensorFlow layout under the `unet3d_attention/` scope: `<layer>/kernel`
 [kd, kh, kw, in, out] (dense layers: [in, out]), `<layer>/bias`, `<layer>/ins_norm/gamma`, `<layer>/ins_norm/beta`, with <layer> the
@@ -423,3 +423,291 @@ def differentiable_conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
 def differentiable_instance_norm_relu(x, gamma, beta, eps=EPS):
     """instance_norm_relu, recorded by torch.autograd."""
     return InstanceNormReluFunction.apply(x, gamma, beta, eps)
+
+
+# ---- the channel attention, the spatial gate and softmax + Dice (include/pointseg_saliency_attention.h, csrc/saliency_train.hip) ------------------
+
+def _rows(x, who, name):
+    """x [B, ..., C] -> (contiguous x, B, V, C)."""
+    x = _f32(x, who, name)
+    if x.dim() < 2:
+        raise ValueError("%s: %s must be [B, ..., C]" % (who, name))
+    B, C = x.shape[0], x.shape[-1]
+    return x, B, x.numel() // max(B * C, 1), C
+
+
+def _ctx_for(t):
+    ctx = runtime.default_context(t.device.index)
+    ctx.use_torch_stream()
+    return ctx
+
+
+def channel_attention(x, w1, b1, w2, b2, want_y=True):
+    """ChannelWiseAttention3D (attention.py:166-174): x [B, ..., C], w1 [C, Ch], b1 [Ch], w2 [Ch, C], b2 [C] -> (y, mean, hidden, scale) with
+    y = x * scale (None without want_y), mean [B, C], hidden [B, Ch], scale [B, C]: what channel_attention_backward takes."""
+    who = "channel_attention"
+    x, B, V, C = _rows(x, who, "x")
+    w1, b1, w2, b2 = _f32(w1, who, "w1", 2), _f32(b1, who, "b1", 1), _f32(w2, who, "w2", 2), _f32(b2, who, "b2", 1)
+    Ch = w1.shape[1]
+    if w1.shape[0] != C or tuple(w2.shape) != (Ch, C) or b1.shape[0] != Ch or b2.shape[0] != C:
+        raise ValueError("channel_attention: w1 %s, b1 %s, w2 %s, b2 %s do not fit C = %d" % (tuple(w1.shape), tuple(b1.shape), tuple(w2.shape), tuple(b2.shape), C))
+    mean, scale = (torch.empty((B, C), dtype=torch.float32, device=x.device) for _ in range(2))
+    hidden = torch.empty((B, Ch), dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x) if want_y else None
+    ctx = _ctx_for(x)
+    fn = _lib.lib().ps_channel_attention
+    _two_call("ps_channel_attention", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), B, V, C, Ch, runtime.ptr(w1), runtime.ptr(b1), runtime.ptr(w2),
+                                                                      runtime.ptr(b2), runtime.ptr(mean), runtime.ptr(hidden), runtime.ptr(scale), runtime.ptr(y),
+                                                                      scratch, n))
+    return y, mean, hidden, scale
+
+
+def channel_attention_backward(dy, x, mean, hidden, scale, w1, w2, need=("x", "w1", "b1", "w2", "b2")):
+    """The gradients of channel_attention for the output gradient dy: a dict with the entries of `need`."""
+    who = "channel_attention_backward"
+    x, B, V, C = _rows(x, who, "x")
+    dy = _f32(dy, who, "dy")
+    w1, w2 = _f32(w1, who, "w1", 2), _f32(w2, who, "w2", 2)
+    mean, hidden, scale = _f32(mean, who, "mean", 2), _f32(hidden, who, "hidden", 2), _f32(scale, who, "scale", 2)
+    Ch = w1.shape[1]
+    if dy.shape != x.shape or w1.shape[0] != C or tuple(w2.shape) != (Ch, C) or tuple(mean.shape) != (B, C) or tuple(scale.shape) != (B, C) \
+            or tuple(hidden.shape) != (B, Ch):
+        raise ValueError("channel_attention_backward: the shapes do not fit x %s" % (tuple(x.shape),))
+    need = set(need)
+    if not need or need - {"x", "w1", "b1", "w2", "b2"}:
+        raise ValueError("channel_attention_backward: need must name some of x, w1, b1, w2, b2")
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    out = {"x": torch.empty_like(x) if "x" in need else None, "w1": new(C, Ch) if "w1" in need else None, "b1": new(Ch) if "b1" in need else None,
+           "w2": new(Ch, C) if "w2" in need else None, "b2": new(C) if "b2" in need else None}
+    ctx = _ctx_for(x)
+    fn = _lib.lib().ps_channel_attention_bwd
+    _two_call("ps_channel_attention_bwd", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(dy), runtime.ptr(mean), runtime.ptr(hidden),
+                                                                          runtime.ptr(scale), runtime.ptr(w1), runtime.ptr(w2), B, V, C, Ch,
+                                                                          *(runtime.ptr(out[k]) for k in ("x", "w1", "b1", "w2", "b2")), scratch, n))
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def spatial_gate(a1, a2, a3, f):
+    """attention.py:148-152 and model.py:295: a1, a2, a3 [B, ...] (or [B, ..., 1]), f [B, ..., C] -> (y = f * sa, sa = sigmoid(a1 + a2 + a3))."""
+    who = "spatial_gate"
+    f, B, V, C = _rows(f, who, "f")
+    a1, a2, a3 = _f32(a1, who, "a1"), _f32(a2, who, "a2"), _f32(a3, who, "a3")
+    if not a1.numel() == a2.numel() == a3.numel() == B * V:
+        raise ValueError("spatial_gate: a1, a2 and a3 must have one value per voxel of f %s" % (tuple(f.shape),))
+    sa = torch.empty(f.shape[:-1], dtype=torch.float32, device=f.device)
+    y = torch.empty_like(f)
+    _lib.check(_lib.lib().ps_spatial_gate(_ctx_for(f).handle, runtime.ptr(a1), runtime.ptr(a2), runtime.ptr(a3), runtime.ptr(f), B, V, C, runtime.ptr(sa),
+                                          runtime.ptr(y)))
+    return y, sa
+
+
+def spatial_gate_backward(dy, f, sa, need=("f", "a")):
+    """The gradients of spatial_gate: {"f": dy * sa, "a": the gradient of each of a1, a2, a3 (one tensor, sa's shape)}; f is the value before the gate."""
+    who = "spatial_gate_backward"
+    f, B, V, C = _rows(f, who, "f")
+    dy, sa = _f32(dy, who, "dy"), _f32(sa, who, "sa")
+    if dy.shape != f.shape or sa.numel() != B * V:
+        raise ValueError("spatial_gate_backward: dy %s and sa %s do not fit f %s" % (tuple(dy.shape), tuple(sa.shape), tuple(f.shape)))
+    need = set(need)
+    if not need or need - {"f", "a"}:
+        raise ValueError("spatial_gate_backward: need must name some of f, a")
+    df = torch.empty_like(f) if "f" in need else None
+    da = torch.empty_like(sa) if "a" in need else None
+    _lib.check(_lib.lib().ps_spatial_gate_bwd(_ctx_for(f).handle, runtime.ptr(dy), runtime.ptr(f), runtime.ptr(sa), B, V, C, runtime.ptr(df), runtime.ptr(da)))
+    return {k: v for k, v in (("f", df), ("a", da)) if v is not None}
+
+
+def _loss_args(who, logits, labels, weight):
+    logits, B, V, C = _rows(logits, who, "logits")
+    if not isinstance(labels, torch.Tensor) or labels.device != logits.device or labels.dtype != torch.int32:
+        raise ValueError("%s: labels must be an int32 tensor on the logits' device" % who)
+    if labels.numel() != B * V:
+        raise ValueError("%s: labels must have one value per voxel of logits %s" % (who, tuple(logits.shape)))
+    if weight is not None:
+        weight = _f32(weight, who, "weight")
+        if weight.numel() != B * V:
+            raise ValueError("%s: weight must have one value per voxel of logits %s" % (who, tuple(logits.shape)))
+    return logits, labels.contiguous(), weight, B, V, C
+
+
+def softmax_dice_loss(logits, labels, weight=None):
+    """Loss / dice of model.py:491-548, 592-618 (weight_map branch, no mixup): logits [B, ..., C], labels [B, ...] int32, weight [B, ...] or
+    None (ones) -> (loss, a 0-dim device tensor; sums [B, C, 3] float64, what softmax_dice_loss_backward takes)."""
+    who = "softmax_dice_loss"
+    logits, labels, weight, B, V, C = _loss_args(who, logits, labels, weight)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    sums = torch.empty((B, C, 3), dtype=torch.float64, device=logits.device)
+    ctx = _ctx_for(logits)
+    fn = _lib.lib().ps_softmax_dice_loss
+    _two_call("ps_softmax_dice_loss", logits.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight), B, V, C,
+                                                                           runtime.ptr(loss), runtime.ptr(sums), scratch, n))
+    return loss, sums
+
+
+def softmax_dice_loss_backward(logits, labels, weight, sums, dloss=None):
+    """d loss / d logits times dloss (a device tensor of one float32, handed over as a pointer; None: 1)."""
+    who = "softmax_dice_loss_backward"
+    logits, labels, weight, B, V, C = _loss_args(who, logits, labels, weight)
+    if not isinstance(sums, torch.Tensor) or sums.device != logits.device or sums.dtype != torch.float64 or tuple(sums.shape) != (B, C, 3):
+        raise ValueError("softmax_dice_loss_backward: sums must be the forward's [B, C, 3] float64 tensor")
+    if dloss is not None:
+        dloss = _f32(dloss, who, "dloss")
+        if dloss.numel() != 1:
+            raise ValueError("softmax_dice_loss_backward: dloss must hold one value")
+    dlogits = torch.empty_like(logits)
+    _lib.check(_lib.lib().ps_softmax_dice_loss_bwd(_ctx_for(logits).handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight),
+                                                   runtime.ptr(sums.contiguous()), runtime.ptr(dloss), B, V, C, runtime.ptr(dlogits)))
+    return dlogits
+
+
+class ChannelAttentionFunction(torch.autograd.Function):
+    """channel_attention with its gradients.  Saves x, the two kernels and the forward's mean, hidden and scale."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        y, mean, hidden, scale = channel_attention(x, w1, b1, w2, b2)
+        ctx.save_for_backward(x, w1, w2, mean, hidden, scale)
+        ctx.mark_non_differentiable(hidden)
+        return y, hidden
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _dhidden):
+        x, w1, w2, mean, hidden, scale = ctx.saved_tensors
+        need = [n for n, wanted in zip(("x", "w1", "b1", "w2", "b2"), ctx.needs_input_grad) if wanted]
+        g = channel_attention_backward(dy, x, mean, hidden, scale, w1, w2, need) if need else {}
+        return tuple(g.get(n) for n in ("x", "w1", "b1", "w2", "b2"))
+
+
+class SpatialGateFunction(torch.autograd.Function):
+    """spatial_gate with its gradients.  Saves f (before the gate) and sa."""
+
+    @staticmethod
+    def forward(ctx, a1, a2, a3, f):
+        y, sa = spatial_gate(a1, a2, a3, f)
+        ctx.save_for_backward(f, sa)
+        ctx.shapes = (a1.shape, a2.shape, a3.shape)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        f, sa = ctx.saved_tensors
+        wanted = ctx.needs_input_grad
+        need = (["a"] if any(wanted[:3]) else []) + (["f"] if wanted[3] else [])
+        g = spatial_gate_backward(dy, f, sa, need) if need else {}
+        da = g.get("a")
+        return tuple(da.reshape(s) if da is not None and w else None for s, w in zip(ctx.shapes, wanted[:3])) + (g.get("f"),)
+
+
+class SoftmaxDiceLossFunction(torch.autograd.Function):
+    """softmax_dice_loss with its gradient.  Saves the logits, the labels, the weight and the forward's sums; the upstream gradient stays on
+    the device."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight):
+        loss, sums = softmax_dice_loss(logits, labels, weight)
+        ctx.save_for_backward(logits, labels, weight, sums)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        logits, labels, weight, sums = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return softmax_dice_loss_backward(logits, labels, weight, sums, dloss.to(torch.float32)), None, None
+
+
+def differentiable_channel_attention(x, w1, b1, w2, b2, with_hidden=False):
+    """channel_attention's y, recorded by torch.autograd (with_hidden: (y, hidden), hidden detached -- the dense ReLU's mask)."""
+    y, hidden = ChannelAttentionFunction.apply(x, w1, b1, w2, b2)
+    return (y, hidden) if with_hidden else y
+
+
+def differentiable_spatial_gate(a1, a2, a3, f):
+    """spatial_gate's y, recorded by torch.autograd."""
+    return SpatialGateFunction.apply(a1, a2, a3, f)
+
+
+def differentiable_softmax_dice_loss(logits, labels, weight=None):
+    """softmax_dice_loss's loss (0-dim, on the device), recorded by torch.autograd."""
+    return SoftmaxDiceLossFunction.apply(logits, labels, weight)
+
+
+class TrainableSaliencyNet(torch.nn.Module):
+    """unet3d_attention (model.py:176-314) composed from the differentiable ops above: one torch.nn.Parameter per entry of param_shapes,
+    under the same name, so torch.autograd and a torch optimiser train it on this package's kernels.  params: the TF-named dict."""
+
+    def __init__(self, params, in_channels, num_classes=2, device=0):
+        super().__init__()
+        self.in_channels, self.num_classes = int(in_channels), int(num_classes)
+        self.device = torch.device("cuda", device)
+        flat = flatten_params(params, self.in_channels, self.num_classes)  # (checks the names and the shapes)
+        for name, a in unflatten_params(flat, self.in_channels, self.num_classes).items():
+            self.register_parameter(name, torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(a)).to(self.device)))
+
+    def logits(self, x, masks=None):
+        """The logits [B, D, H, W, num_classes] of a patch [B, D, H, W, C_in] (extents multiples of 16).  masks: a dict that receives, per
+        layer name, the ReLU's mask of this forward (y > 0; the channel attention's hidden layer under its dense_1 name)."""
+        x = _f32(x, "TrainableSaliencyNet", "x", 5)
+        if x.shape[4] != self.in_channels or any(n % 16 or n < 16 for n in x.shape[1:4]):
+            raise ValueError("TrainableSaliencyNet: x must be [B, D, H, W, %d] with extents that are multiples of 16, got %s" % (self.in_channels, tuple(x.shape)))
+        P = dict(self.named_parameters())
+
+        def conv(name, t, stride=1, dilation=1, norm=True, x2=None, up=1):
+            n = SCOPE + name
+            y = differentiable_conv3d(t, P[n + "/kernel"], P.get(n + "/bias"), stride, dilation, x2, up)
+            if not norm:
+                return y
+            y = differentiable_instance_norm_relu(y, P[n + "/ins_norm/gamma"], P[n + "/ins_norm/beta"])
+            if masks is not None:
+                masks[name] = y.detach() > 0
+            return y
+
+        def cfe(prefix, t):  # CFE3D, model.py:154-174: the four branches meet in a torch.cat (reduced resolution)
+            return torch.cat([conv(prefix + "_cfe0", t)] + [conv("%s_cfe%d_dilation" % (prefix, r), t, dilation=d) for r, d in ((1, 3), (2, 5), (3, 7))], -1)
+
+        layer = conv("init_conv", x)
+        down = []
+        for d in range(5):
+            l_in = layer
+            for i in range(2):
+                layer = conv("down%d_conv_%d" % (d, i), layer)
+            layer = l_in + layer
+            down.append(layer)
+            if d != 4:
+                layer = conv("stride2conv%d" % d, layer, stride=2)
+        C1 = conv("C1_conv", down[0])
+        C2 = conv("C2_conv", down[1])
+        C3 = cfe("C3_cfe", down[2])
+        C4 = conv("up_conv1_C4_cfe_up2", cfe("C4_cfe", down[3]), up=2)
+        C5 = conv("up_conv1_C5_cfe_up4", cfe("C5_cfe", down[4]), up=4)
+        ca = SCOPE + _CA
+        C345, hidden = differentiable_channel_attention(torch.cat([C3, C4, C5], -1), P[ca + "_dense_1/kernel"], P[ca + "_dense_1/bias"],
+                                                        P[ca + "_dense_2/kernel"], P[ca + "_dense_2/bias"], with_hidden=True)
+        if masks is not None:
+            masks[_CA + "_dense_1"] = hidden > 0
+        C345 = conv("up_conv1_C345_up4", conv("C345_conv", C345), up=4)
+        a = [conv("spatial_attention_%d_conv2" % i, conv("spatial_attention_%d_conv1" % i, C345)) for i in (1, 2, 3)]
+        C12 = conv("C12_conv", C1, x2=conv("up_conv1_C2_up2", C2, up=2))
+        C12 = differentiable_spatial_gate(a[0], a[1], a[2], C12)
+        return conv("final", C12, norm=False, x2=C345)
+
+    def loss(self, x, labels, weight=None, masks=None):
+        """The reference's training loss (train.py:83-110 without the regulariser, which reference_optimizer carries as weight decay)."""
+        return differentiable_softmax_dice_loss(self.logits(x, masks), labels, weight)
+
+    def export(self):
+        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes."""
+        return {name: p.detach().cpu().numpy() for name, p in self.named_parameters()}
+
+
+def reference_optimizer(net, lr=0.01):
+    """train.py:50-56, 102-107: tf.train.MomentumOptimizer(lr, 0.9) on the loss plus tensorpack's l2_regularizer(1e-5) of every `kernel`
+    variable (the two dense kernels included).  The regulariser is tf.nn.l2_loss, whose gradient is 1e-5 * w: torch's weight_decay; and
+    TensorFlow's accum = 0.9 * accum + g, var -= lr * accum is torch.optim.SGD's momentum rule.  Biases, gammas and betas do not decay."""
+    named = list(net.named_parameters())
+    decay = [p for n, p in named if n.endswith("/kernel")]
+    rest = [p for n, p in named if not n.endswith("/kernel")]
+    return torch.optim.SGD([{"params": decay, "weight_decay": 1e-5}, {"params": rest, "weight_decay": 0.0}], lr=lr, momentum=0.9)
