@@ -377,6 +377,9 @@ bool wgrad_b3_split_fits(const Tuning& tn, int64_t R, int64_t cin, int64_t cout,
     return wgrad_b3_fits(tn, R, cin, cout, xr, ldxr, dy, lddy, /*one_plane: the split form's own floor*/ true) && xl && xidx && ldxl % 4 == 0 && (reinterpret_cast<uintptr_t>(xl) & 15) == 0 && (cin / 2) % 4 == 0;
 }
 
+// (the floor wgrad_b3_fits applies to the split form: the one-plane floor, or the experiment knob)
+int64_t wgrad_b3_split_min_rows(const Tuning& tn) { return tn.wgrad_b3_min_rows > 0 ? tn.wgrad_b3_min_rows : 16384; }
+
 int wgrad_b3_partial_split(ps_context* c, const float* xl, int64_t ldxl, const int32_t* xidx, int64_t n_src, int64_t rows_per_cloud, const float* xr, int64_t ldxr,
                            const float* dy, int64_t lddy, int64_t R, int64_t cin, int64_t cout, float* part)
 {

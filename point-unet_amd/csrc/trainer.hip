@@ -1309,7 +1309,10 @@ struct ps_trainer {
     bool att_gemm_split_ok(const Tn& f_src, const int32_t* idx, const Tn& f_xyz, int64_t B, int64_t M, int64_t K) const
     {
         const int64_t d = 2 * f_src.C, rows = B * M * K;
+        // (the backward's weight gradient exists in the split-source form only: a row floor moved out of reach -- wgrad_b3_min_rows -- must
+        //  send the level to the materialised pooling here, not fail the step there)
         return opt.fused_att && att_gemm_on && c->train_b3 && ps_op_att_pool_gemm_supported(K, d) && d <= 256 /* (the split-source kernels) */ && rows >= 16384 && rows < (1ll << 31) && d % 128 == 0 &&
+               rows >= ps::wgrad_b3_split_min_rows(c->tune) &&
                f_src.vec_ok() && f_xyz.vec_ok() && f_xyz.C == f_src.C && (reinterpret_cast<uintptr_t>(idx) & 15) == 0 && f_src.R / B * f_src.ld < (1ll << 31);
     }
     Tn attpool_gemm_split(const Tn& f_src_in, const int32_t* idx, int64_t B, int64_t M, int64_t K, const Tn& f_xyz, const Tn& W, const Tn& gW)
