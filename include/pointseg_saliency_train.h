@@ -1,5 +1,5 @@
 /* include/pointseg_saliency_train.h -- the gradients of the two layers that hold almost all of the saliency attention network's
- * arithmetic: the 3-D convolution (data, weight and bias gradient) and instance norm + ReLU (csrc/conv3d_train.hip).  Same conventions as
+ * arithmetic: the 3-D convolution (data, weight and bias gradient) and instance norm + ReLU (csrc/conv3d_train.hip, csrc/saliency_train.hip).  Same conventions as
  * pointseg_saliency.h (status codes, ps_last_error, caller-owned device buffers, the context's stream, the two-call scratch protocol);
  * kept out of it because a host that only runs the network never needs them.  All citations are relative to the reference repository root.
  *

@@ -295,7 +295,7 @@ SALIENCY_PROTOTYPES = {
     "ps_saliency_finish": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 4 + [c_vp]),
 }
 
-# every symbol include/pointseg_saliency_train.h declares (the gradients of ps_conv3d and ps_instance_norm_relu; csrc/conv3d_train.hip)
+# every symbol include/pointseg_saliency_train.h declares (the gradients of ps_conv3d and ps_instance_norm_relu; csrc/conv3d_train.hip, csrc/saliency_train.hip)
 _CONV_GEOMETRY = [ctypes.c_int64] * 6 + [ctypes.c_int32] * 4 + [ctypes.c_int64] + [ctypes.c_int32] * 2  # B Ds Hs Ws C1 C2 up kd kh kw C_out stride dilation
 SALIENCY_TRAIN_PROTOTYPES = {
     "ps_conv3d_bwd_data": (ctypes.c_int, [c_vp, c_vp, c_vp] + _CONV_GEOMETRY + [c_vp, c_vp, c_vp, c_i64p]),

@@ -1,6 +1,6 @@
-// conv3d_train.hip -- the gradients of conv3d.hip's convolution and of saliency.hip's instance norm + ReLU
-// (include/pointseg_saliency_train.h), with the forward's guarantees: exact fp32 operands on v_mfma_f32_16x16x4_f32
-// (mfma_tile.h's fragment maps), float64 fixed-order statistics, no float atomic, two runs give the same bytes.
+// conv3d_train.hip -- the gradients of conv3d.hip's convolution (include/pointseg_saliency_train.h; the instance norm's
+// gradient is saliency_train.hip's), with the forward's guarantees: exact fp32 operands on v_mfma_f32_16x16x4_f32 (mfma_tile.h's fragment
+// maps), float64 fixed-order slab sums, no float atomic, two runs give the same bytes.
 //
 // Data gradient: a gather, the forward's implicit GEMM with the roles turned.  Rows are the voxels i of the virtual (concatenated,
 // up-sampled) input, columns its channels, k = tap * C_out + co;  A[i, k] = dy[o, co] with o = (i + pad - t * dilation) / stride where that
@@ -28,7 +28,6 @@ constexpr int kKC = 32;        // K chunk
 constexpr int kAP = kKC + 2;   // row-major A tile pitch, as conv3d.hip
 constexpr int kBP = 80;        // k-major tile pitch for up to 64 columns: the four k rows of a fragment read start 16 banks apart
 constexpr int kWSlab = 4096;   // output voxels per workgroup of the weight gradient
-constexpr int kNSlab = 4096;   // voxels per workgroup of the norm's statistics passes
 
 // One K chunk of a wave's RT x NT tiles: the chunk's 8 k-steps in a fresh accumulator, then added to the running one (conv3d.hip's
 // rounding).  a0: this lane's A element of row tile 0, k-step 0 (row tiles a_rt floats apart, k-steps a_s); b0: the same in the k-major B tile.
@@ -343,100 +342,6 @@ void launch_weight(hipStream_t sm, BwdWeightArgs& a)
     hipLaunchKernelGGL((conv3d_bwd_weight_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
 }
 
-// ---- instance norm + ReLU ------------------------------------------------------------------------------------------------------------------------
-
-// grid (slabs, B, channel tiles of 64), the layout of saliency.hip's statistics pass.  SECOND == false: (sum x, sum x^2);
-// SECOND == true: (sum g, sum g xhat) with g = dy where y > 0 and xhat = (x - mean) * rstd from stat[b * C + c]
-template <bool SECOND>
-__global__ __launch_bounds__(256) void in_bwd_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy, int V, int C,
-                                                          int cshift, const double2* __restrict__ stat, double* __restrict__ part)
-{
-    __shared__ double ss[256], sq[256];
-    const int t = threadIdx.x, cw = 1 << cshift;
-    const int c = blockIdx.z * 64 + (t & (cw - 1)), rl = t >> cshift, nrl = 256 >> cshift;
-    const int b = blockIdx.y, v0 = blockIdx.x * kNSlab, v1 = min(V, v0 + kNSlab);
-    double s = 0.0, q = 0.0;
-    if (c < C) {
-        const size_t base = ((size_t)b * V) * C + c;
-        double2 st = {0.0, 0.0};
-        if (SECOND) st = stat[b * C + c];
-        for (int v = v0 + rl; v < v1; v += nrl) {
-            const size_t e = base + (size_t)v * C;
-            const double f = (double)x[e];
-            if (SECOND) {
-                const double g = y[e] > 0.f ? (double)dy[e] : 0.0;
-                s += g;
-                q += g * ((f - st.x) * st.y);
-            } else {
-                s += f;
-                q += f * f;
-            }
-        }
-    }
-    ss[t] = s;
-    sq[t] = q;
-    __syncthreads();
-    if (t < cw && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int j = 0; j < nrl; ++j) {
-            S += ss[j * cw + t];
-            Q += sq[j * cw + t];
-        }
-        double* o = part + (((size_t)blockIdx.x * gridDim.y + b) * C + c) * 2;
-        o[0] = S;
-        o[1] = Q;
-    }
-}
-
-// tot[(b * C + c) * 2 + {0, 1}] -> stat[b * C + c] = (mean, 1 / sqrt(var + eps)), the biased variance of tf.nn.moments
-__global__ __launch_bounds__(256) void in_bwd_stat_kernel(const double* __restrict__ tot, int V, int BC, float eps, double2* __restrict__ stat)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= BC) return;
-    const double mean = tot[2 * i] / V;
-    double var = tot[2 * i + 1] / V - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    stat[i] = make_double2(mean, 1.0 / sqrt(var + (double)eps));
-}
-
-// grid (ceil(V * C / 256), B): dx = gamma * rstd * (g - mean(g) - xhat * mean(g xhat)); every element reads its own dy before it writes dx
-__global__ __launch_bounds__(256) void in_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* dy, int V, int C,
-                                                        const double2* __restrict__ stat, const double* __restrict__ tot2, const float* __restrict__ gamma,
-                                                        float* dx)
-{
-    const unsigned e = blockIdx.x * 256u + threadIdx.x;
-    if (e >= (unsigned)V * (unsigned)C) return;
-    const unsigned c = e % (unsigned)C;
-    const size_t i = (size_t)blockIdx.y * V * C + e;
-    const int bc = blockIdx.y * C + c;
-    const double2 st = stat[bc];
-    const double mg = tot2[2 * bc] / V, mgx = tot2[2 * bc + 1] / V;
-    const double g = y[i] > 0.f ? (double)dy[i] : 0.0;
-    const double xh = ((double)x[i] - st.x) * st.y;
-    dx[i] = (float)((double)gamma[c] * st.y * (g - mg - xh * mgx));
-}
-
-// dbeta[c] = sum over b of tot2[b][c][0], dgamma[c] = sum over b of tot2[b][c][1], b ascending
-__global__ __launch_bounds__(256) void in_bwd_params_kernel(const double* __restrict__ tot2, int B, int C, float* __restrict__ dgamma, float* __restrict__ dbeta)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    double sb = 0.0, sg = 0.0;
-    for (int b = 0; b < B; ++b) {
-        sb += tot2[((size_t)b * C + c) * 2];
-        sg += tot2[((size_t)b * C + c) * 2 + 1];
-    }
-    if (dbeta) dbeta[c] = (float)sb;
-    if (dgamma) dgamma[c] = (float)sg;
-}
-
-int cshift_for(int C)
-{
-    int s = 0;
-    while ((1 << s) < C && s < 6) ++s;
-    return s;
-}
-
 // ---- the argument checks the two convolution entries share -------------------------------------------------------------------------------------
 
 int conv_geometry_ok(const char* who, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw,
@@ -562,52 +467,6 @@ extern "C" int ps_conv3d_bwd_weight(ps_context* c, const void* x, const void* x2
     const int nv = a.nrows * a.cout, n0 = dw ? Ktot * a.cout : 0;
     hipLaunchKernelGGL((reduce_partials2_kernel<float, double>), dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, (int)n_part, nv, n0,
                        static_cast<float*>(dw), static_cast<float*>(dbias));
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
-extern "C" int ps_instance_norm_relu_bwd(ps_context* c, const void* x, const void* y, const void* dy, int64_t B, int64_t V, int64_t C, const void* gamma, float eps,
-                                         void* dx, void* dgamma, void* dbeta, void* scratch, int64_t* scratch_bytes)
-{
-    using namespace ps;
-    static const char* who = "ps_instance_norm_relu_bwd";
-    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
-    PS_CHECK(B >= 1 && B <= 65535 && V >= 1 && C >= 1 && C <= 1024 && V < (1ll << 31) && V * C < (1ll << 31),
-             "%s: B = %lld, V = %lld, C = %lld (1 <= B <= 65535, 1 <= C <= 1024, V >= 1, V * C < 2^31)", who, (long long)B, (long long)V, (long long)C);
-    PS_CHECK(eps > 0.f, "%s: eps = %g, must be > 0", who, (double)eps);
-    const int slabs = ceil_div(V, kNSlab), nv = (int)(B * C * 2);
-    Carver cv{static_cast<char*>(scratch)};
-    double* part = cv.take<double>((size_t)slabs * nv);
-    double* tot = cv.take<double>((size_t)nv);
-    double2* stat = cv.take<double2>((size_t)B * C);
-    double* tot2 = cv.take<double>((size_t)nv);
-    if (!scratch) {
-        *scratch_bytes = (int64_t)cv.off;
-        return PS_OK;
-    }
-    PS_CHECK(x && y && dy && gamma, "%s: NULL x, y, dy or gamma (they may be NULL only in the call that sizes the scratch)", who);
-    PS_CHECK(dx || dgamma || dbeta, "%s: every result is NULL", who);
-    PS_CHECK(dx != x && dx != y, "%s: dx must not overlap x or y (it may be dy)", who);
-    PS_CHECK(c, "%s: NULL context", who);
-    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
-
-    PS_HIP(hipSetDevice(c->device));
-    hipStream_t sm = c->stream;
-    Stage stg(c, "instance_norm_relu_bwd", 7);
-    const float *xf = static_cast<const float*>(x), *yf = static_cast<const float*>(y), *dyf = static_cast<const float*>(dy);
-    const int nB = (int)B, nV = (int)V, nC = (int)C;
-    const dim3 sgrid((unsigned)slabs, (unsigned)nB, (unsigned)ceil_div(nC, 64));
-    hipLaunchKernelGGL(in_bwd_sums_kernel<false>, sgrid, dim3(256), 0, sm, xf, yf, dyf, nV, nC, cshift_for(nC), stat, part);
-    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, tot);
-    hipLaunchKernelGGL(in_bwd_stat_kernel, dim3(blocks256((size_t)nB * nC)), dim3(256), 0, sm, tot, nV, nB * nC, eps, stat);
-    hipLaunchKernelGGL(in_bwd_sums_kernel<true>, sgrid, dim3(256), 0, sm, xf, yf, dyf, nV, nC, cshift_for(nC), stat, part);
-    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, tot2);
-    if (dx)
-        hipLaunchKernelGGL(in_bwd_dx_kernel, dim3(blocks256((size_t)nV * nC), (unsigned)nB), dim3(256), 0, sm, xf, yf, dyf, nV, nC, stat, tot2,
-                           static_cast<const float*>(gamma), static_cast<float*>(dx));
-    if (dgamma || dbeta)
-        hipLaunchKernelGGL(in_bwd_params_kernel, dim3(blocks256((size_t)nC)), dim3(256), 0, sm, tot2, nB, nC, static_cast<float*>(dgamma),
-                           static_cast<float*>(dbeta));
     PS_HIP(hipGetLastError());
     return PS_OK;
 }

@@ -1,66 +1,31 @@
 // saliency.hip -- the saliency attention network around conv3d.hip (include/pointseg_saliency.h): instance norm + ReLU,
 // the channel and the spatial attention, softmax, the graph of unet3d_attention behind one call, and the window average.
 //
-// Instance norm: per (sample, channel) sum and sum of squares in float64 -- a workgroup adds a slab of 4096 voxels, its threads in a fixed
-// order, reduce_partials.h adds the slabs in a fixed order -- so two runs give the same bytes and E[x^2] - E[x]^2 keeps 53 bits under a mean
-// that dwarfs the deviation.  The apply pass is in place and carries the residual add of a Unet3dBlock.
+// Instance norm: per (sample, channel) sum and sum of squares in float64 by saliency_kit.h's slab-sum frame -- a workgroup adds a slab of
+// 4096 voxels, its threads in a fixed order, reduce_partials.h adds the slabs in a fixed order -- so two runs give the same bytes and
+// E[x^2] - E[x]^2 keeps 53 bits under a mean that dwarfs the deviation.  The apply pass is in place and carries the residual add of a
+// Unet3dBlock.  The channel attention's dense part, the spatial gate and the softmax are the kit's too: saliency_train.hip's ops run the same code.
 // Concats are never copied: a convolution writes its channels into the concat's buffer (channel pitch ldy), the norm and the next
 // convolution read them there (ldx).  The channel attention's per-sample scale goes into C345_conv's kernel, not over the 384-channel tensor.
 #include <algorithm>
 
-#include "reduce_partials.h"
 #include "saliency.h"
-#include "scratch.h"
+#include "saliency_kit.h"
 
 namespace ps {
 
 namespace {
 
-constexpr int kSlab = 4096;  // voxels per workgroup of the statistics pass
-
 // ---- instance norm + ReLU ----------------------------------------------------------------------------------------------------------------------
 
-// grid (slabs, B, channel tiles of 64).  cw = the power of two >= min(C, 64): thread t adds channel t % cw of the rows t / cw, t / cw + 256 / cw, ...
-__global__ __launch_bounds__(256) void in_stats_kernel(const float* __restrict__ x, int ld, int V, int C, int cshift, double* __restrict__ part)
-{
-    __shared__ double ss[256], sq[256];
-    const int t = threadIdx.x, cw = 1 << cshift;
-    const int c = blockIdx.z * 64 + (t & (cw - 1)), rl = t >> cshift, nrl = 256 >> cshift;
-    const int b = blockIdx.y, v0 = blockIdx.x * kSlab, v1 = min(V, v0 + kSlab);
-    double s = 0.0, q = 0.0;
-    if (c < C) {
-        const float* p = x + ((size_t)b * V) * ld + c;
-        for (int v = v0 + rl; v < v1; v += nrl) {
-            const double f = (double)p[(size_t)v * ld];
-            s += f;
-            q += f * f;
-        }
-    }
-    ss[t] = s;
-    sq[t] = q;
-    __syncthreads();
-    if (t < cw && c < C) {
-        double S = 0.0, Q = 0.0;
-        for (int j = 0; j < nrl; ++j) {
-            S += ss[j * cw + t];
-            Q += sq[j * cw + t];
-        }
-        double* o = part + (((size_t)blockIdx.x * gridDim.y + b) * C + c) * 2;
-        o[0] = S;
-        o[1] = Q;
-    }
-}
-
-// tot[(b * C + c) * 2 + {0, 1}] -> coef[b * C + c] = (mean, gamma / sqrt(var + eps)), the biased variance of tf.nn.moments
+// tot[(b * C + c) * 2 + {0, 1}] -> coef[b * C + c] = (mean, gamma / sqrt(var + eps))
 __global__ __launch_bounds__(256) void in_coef_kernel(const double* __restrict__ tot, int V, int C, int BC, const float* __restrict__ gamma, float eps,
                                                       float2* __restrict__ coef)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= BC) return;
-    const double mean = tot[2 * i] / V;
-    double var = tot[2 * i + 1] / V - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    coef[i] = make_float2((float)mean, (float)((double)gamma[i % C] / sqrt(var + (double)eps)));
+    const double2 m = moments(tot, i, V, eps);
+    coef[i] = make_float2((float)m.x, (float)((double)gamma[i % C] / m.y));
 }
 
 // grid (ceil(V * C / 256), B): y = max(0, (x - mean) * scale + beta) [+ res]
@@ -83,24 +48,10 @@ struct NormWs {
     float2* coef;  // [B][C]
 };
 
-int cshift_for(int C)
-{
-    int s = 0;
-    while ((1 << s) < C && s < 6) ++s;
-    return s;
-}
-
-void stats_run(hipStream_t sm, const float* x, int ldx, int B, int V, int C, const NormWs& ws)
-{
-    const int slabs = ceil_div(V, kSlab), nv = B * C * 2;
-    hipLaunchKernelGGL(in_stats_kernel, dim3((unsigned)slabs, (unsigned)B, (unsigned)ceil_div(C, 64)), dim3(256), 0, sm, x, ldx, V, C, cshift_for(C), ws.part);
-    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, ws.part, slabs, nv, ws.tot);
-}
-
 void norm_run(hipStream_t sm, const float* x, int ldx, float* y, int ldy, const float* res, int ldres, int B, int V, int C, const float* gamma,
               const float* beta, float eps, const NormWs& ws)
 {
-    stats_run(sm, x, ldx, B, V, C, ws);
+    stats_run(sm, x, ldx, B, V, C, ws.part, ws.tot);
     hipLaunchKernelGGL(in_coef_kernel, dim3(blocks256((size_t)B * C)), dim3(256), 0, sm, ws.tot, V, C, B * C, gamma, eps, ws.coef);
     hipLaunchKernelGGL(in_apply_kernel, dim3(blocks256((size_t)V * C), (unsigned)B), dim3(256), 0, sm, x, ldx, y, ldy, res, ldres, V, C, ws.coef, beta);
 }
@@ -111,69 +62,28 @@ size_t norm_part_count(int B, int V, int C) { return (size_t)ceil_div(V, kSlab) 
 
 constexpr int kCA = 384, kCAh = 96, kC345 = 64;
 
-// ChannelWiseAttention3D (attention.py:166-174), one workgroup per sample: mean over the voxels (from the statistics pass's sums), dense
-// 384 -> 96 ReLU, dense 96 -> 384 sigmoid; the scale lands in this sample's copy of C345_conv's [384, 64] kernel.
+// ChannelWiseAttention3D (attention.py:166-174), one workgroup per sample: the kit's dense part on the statistics pass's sums; the scale
+// lands in this sample's copy of C345_conv's [384, 64] kernel.
 __global__ __launch_bounds__(256) void ca_fold_kernel(const double* __restrict__ tot, int V, const float* __restrict__ w1, const float* __restrict__ b1,
                                                       const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ wc,
                                                       float* __restrict__ wfold)
 {
     __shared__ float mean[kCA], h[kCAh], s[kCA];
     const int t = threadIdx.x, b = blockIdx.x;
-    for (int c = t; c < kCA; c += 256) mean[c] = (float)(tot[((size_t)b * kCA + c) * 2] / V);
-    __syncthreads();
-    if (t < kCAh) {
-        double acc = (double)b1[t];
-        for (int i = 0; i < kCA; ++i) acc += (double)mean[i] * (double)w1[i * kCAh + t];
-        h[t] = fmaxf((float)acc, 0.f);
-    }
-    __syncthreads();
-    for (int c = t; c < kCA; c += 256) {
-        double acc = (double)b2[c];
-        for (int i = 0; i < kCAh; ++i) acc += (double)h[i] * (double)w2[i * kCA + c];
-        s[c] = (float)(1.0 / (1.0 + exp(-acc)));
-    }
-    __syncthreads();
+    ca_dense(tot + (size_t)b * kCA * 2, 2, V, kCA, kCAh, w1, b1, w2, b2, mean, h, s);
     for (int e = t; e < kCA * kC345; e += 256) wfold[(size_t)b * kCA * kC345 + e] = s[e / kC345] * wc[e];
 }
 
-// SpatialAttention3D's tail (attention.py:148-152) and model.py:295: sa = sigmoid(a1 + a2 + a3); the C channels of `f` (pitch ld) times sa
-__global__ __launch_bounds__(256) void sa_mul_kernel(const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ a3, int V, int cshiftC,
-                                                     float* __restrict__ sa, float* __restrict__ f, int ld)
-{
-    const unsigned e = blockIdx.x * 256u + threadIdx.x;
-    const unsigned v = e >> cshiftC, c = e & ((1u << cshiftC) - 1u);
-    if (v >= (unsigned)V) return;
-    const size_t row = (size_t)blockIdx.y * V + v;
-    const float z = (a1[row] + a2[row]) + a3[row];
-    const float g = 1.f / (1.f + expf(-z));
-    if (c == 0) sa[row] = g;
-    f[row * ld + c] *= g;
-}
-
-constexpr int kMaxClasses = 16;
-
+// one thread per voxel: probs = softmax(logits)
+template <int MODE>
 __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ logits, size_t rows, int C, float* __restrict__ probs)
 {
     const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
-    float v[kMaxClasses];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c)
-        if (c < C) {
-            v[c] = logits[r * C + c];
-            m = fmaxf(m, v[c]);
-        }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c)
-        if (c < C) {
-            v[c] = expf(v[c] - m);
-            s += v[c];
-        }
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c)
-        if (c < C) probs[r * C + c] = v[c] / s;
+    Row<MODE> v;
+    row_load<MODE>(logits + r * C, C, v);
+    row_softmax<MODE>(C, v);
+    row_store<MODE>(probs + r * C, C, v);
 }
 
 // dst[r, 0:C] (dense) = src[r, 0:C] (pitch ld): the taps
@@ -277,8 +187,7 @@ extern "C" int ps_instance_norm_relu(ps_context* c, const void* x, int64_t B, in
     using namespace ps;
     static const char* who = "ps_instance_norm_relu";
     PS_CHECK(scratch_bytes && (c || !scratch), "%s: NULL argument", who);
-    PS_CHECK(B >= 1 && B <= 65535 && V >= 1 && C >= 1 && C <= 1024 && V < (1ll << 31) && V * C < (1ll << 31),
-             "%s: B = %lld, V = %lld, C = %lld (1 <= B <= 65535, 1 <= C <= 1024, V >= 1, V * C < 2^31)", who, (long long)B, (long long)V, (long long)C);
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, 1024, kLimitVC));
     PS_CHECK(eps > 0.f, "%s: eps = %g, must be > 0", who, (double)eps);
     Carver cv{static_cast<char*>(scratch)};
     NormWs ws;
@@ -409,7 +318,7 @@ extern "C" int ps_saliency_forward(ps_context* c, const void* x, int64_t B, int6
     layer(net.up4, cfe4, 128, 3, 2, 1, 1, cat345 + 128, kCA);
     layer(net.up5, cfe5, 128, 4, 4, 1, 1, cat345 + 256, kCA);
     // the channel attention into C345_conv's kernel, C345_conv, up to full resolution (model.py:255-271)
-    stats_run(sm, cat345, kCA, nB, Vl[2], kCA, ws);
+    stats_run(sm, cat345, kCA, nB, Vl[2], kCA, ws.part, ws.tot);
     hipLaunchKernelGGL(ca_fold_kernel, dim3((unsigned)nB), dim3(256), 0, sm, ws.tot, Vl[2], wt + net.L[net.d1].w, wt + net.L[net.d1].b, wt + net.L[net.d2].w,
                        wt + net.L[net.d2].b, wt + net.L[net.c345].w, wfold);
     layer(net.c345, cat345, kCA, 2, 1, 1, 1, c345q, kC345, nullptr, 0, wfold, (int64_t)kCA * kC345);
@@ -425,13 +334,19 @@ extern "C" int ps_saliency_forward(ps_context* c, const void* x, int64_t B, int6
     layer(net.upc2, c2, 64, 1, 2, 1, 1, cat12 + 64, 128);
     layer(net.c12, cat12, 128, 0, 1, 1, 1, fuse, 128);
     float* sa = att + BV0 * 3;
-    hipLaunchKernelGGL(sa_mul_kernel, dim3(blocks256((size_t)Vl[0] * 64), (unsigned)nB), dim3(256), 0, sm, att, att + BV0, att + BV0 * 2, Vl[0], 6, sa, fuse, 128);
+    PS_TRY(gate_run(sm, att, att + BV0, att + BV0 * 2, fuse, 128, nB, Vl[0], 64, sa, fuse, 128));
     if (taps && taps->sa) PS_HIP(hipMemcpyAsync(taps->sa, sa, BV0 * sizeof(float), hipMemcpyDeviceToDevice, sm));
     if (taps && taps->c12)
         hipLaunchKernelGGL(copy_rows_kernel, dim3(blocks256(BV0 * 64)), dim3(256), 0, sm, fuse, 128, BV0, 64, static_cast<float*>(taps->c12));
     // the logits and their softmax (model.py:298-307, train.py:116)
     layer(net.fin, fuse, 128, 0, 1, 1, 1, lg, K);
-    if (probs) hipLaunchKernelGGL(softmax_kernel, dim3(blocks256(BV0)), dim3(256), 0, sm, lg, BV0, K, static_cast<float*>(probs));
+    if (probs) {
+        float* pr = static_cast<float*>(probs);
+        const int mode = dice_mode(K, lg, pr);
+        if (mode == 2) hipLaunchKernelGGL(softmax_kernel<2>, dim3(blocks256(BV0)), dim3(256), 0, sm, lg, BV0, K, pr);
+        else if (mode == 4) hipLaunchKernelGGL(softmax_kernel<4>, dim3(blocks256(BV0)), dim3(256), 0, sm, lg, BV0, K, pr);
+        else hipLaunchKernelGGL(softmax_kernel<1>, dim3(blocks256(BV0)), dim3(256), 0, sm, lg, BV0, K, pr);
+    }
     PS_HIP(hipGetLastError());
     return PS_OK;
 }

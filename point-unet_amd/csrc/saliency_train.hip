@@ -1,143 +1,106 @@
-// saliency_train.hip -- the channel attention, the spatial gate and softmax + weighted Dice of the saliency attention network, each with its
-// gradient (include/pointseg_saliency_attention.h).  Beside conv3d_train.hip these are the ops a training step of
-// unet3d_attention still lacked; saliency.hip's forward keeps its own fused forms of the first two and is not touched.
+// saliency_train.hip -- the gradients of saliency.hip's ops: instance norm + ReLU (include/pointseg_saliency_train.h), and the
+// channel attention, the spatial gate and softmax + weighted Dice, each with the forward a training step records
+// (include/pointseg_saliency_attention.h).  The convolution's gradients are conv3d_train.hip's.  What these ops share with
+// saliency.hip's fused forward -- the slab sums, the moments, the channel attention's dense part, the gate, the softmax -- is saliency_kit.h's.
 //
 // All of them are memory-bound: a pass reads or writes each large tensor once, 16 bytes per lane along the channel axis where C % 4 == 0
 // and the tensors are 16-byte aligned (VEC = 4), a float at a time elsewhere (VEC = 1) -- the same values either way, a lane adds its own
-// channels only.  Every sum over voxels is a float64 partial per (slab of 4096 voxels, sample), the threads of a slab added in a fixed
-// order, the slabs by reduce_partials.h: no float atomic, two runs give the same bytes.
-#include <cstdint>
-
+// channels only.  Every sum over voxels goes through the kit's slab-sum frame (the loss keeps its own wave-butterfly form).
 #include "../../include/pointseg_saliency_attention.h"
-#include "reduce_partials.h"
-#include "scratch.h"
+#include "../../include/pointseg_saliency_train.h"
+#include "saliency_kit.h"
 
 namespace ps {
 
 namespace {
 
-constexpr int kSlab = 4096;  // voxels per workgroup of a reduction pass
-constexpr int kMaxC = 1024, kMaxCh = 256, kMaxClasses = 16;
+constexpr int kMaxC = 1024, kMaxCh = 256;
 
-template <int VEC>
-struct Vec;
-template <>
-struct Vec<1> {
-    float v[1];
+// ---- instance norm + ReLU ------------------------------------------------------------------------------------------------------------------------
+
+// (sum g, sum g xhat) with g = dy where y > 0 and xhat = (x - mean) * rstd from stat[b * C + c]
+struct NormBwdSums {
+    static constexpr int kUnroll = 4;
+    const float* __restrict__ x;
+    const float* __restrict__ y;
+    const float* __restrict__ dy;
+    const double2* __restrict__ stat;
+    __device__ __forceinline__ void operator()(int bc, size_t e, double (&d)[2]) const
+    {
+        const double2 st = stat[bc];
+        const double f = (double)x[e], g = y[e] > 0.f ? (double)dy[e] : 0.0;
+        d[0] = g;
+        d[1] = g * ((f - st.x) * st.y);
+    }
 };
-template <>
-struct alignas(16) Vec<4> {
-    float v[4];
-};
 
-template <int VEC>
-__device__ __forceinline__ Vec<VEC> vload(const float* p)
+// tot[(b * C + c) * 2 + {0, 1}] -> stat[b * C + c] = (mean, 1 / sqrt(var + eps))
+__global__ __launch_bounds__(256) void in_bwd_stat_kernel(const double* __restrict__ tot, int V, int BC, float eps, double2* __restrict__ stat)
 {
-    return *reinterpret_cast<const Vec<VEC>*>(p);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= BC) return;
+    const double2 m = moments(tot, i, V, eps);
+    stat[i] = make_double2(m.x, 1.0 / m.y);
 }
 
-template <int VEC>
-__device__ __forceinline__ void vstore(float* p, const Vec<VEC>& a)
+// grid (ceil(V * C / 256), B): dx = gamma * rstd * (g - mean(g) - xhat * mean(g xhat)); every element reads its own dy before it writes dx
+__global__ __launch_bounds__(256) void in_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* dy, int V, int C,
+                                                        const double2* __restrict__ stat, const double* __restrict__ tot2, const float* __restrict__ gamma,
+                                                        float* dx)
 {
-    *reinterpret_cast<Vec<VEC>*>(p) = a;
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= (unsigned)V * (unsigned)C) return;
+    const unsigned c = e % (unsigned)C;
+    const size_t i = (size_t)blockIdx.y * V * C + e;
+    const int bc = blockIdx.y * C + c;
+    const double2 st = stat[bc];
+    const double mg = tot2[2 * bc] / V, mgx = tot2[2 * bc + 1] / V;
+    const double g = y[i] > 0.f ? (double)dy[i] : 0.0;
+    const double xh = ((double)x[i] - st.x) * st.y;
+    dx[i] = (float)((double)gamma[c] * st.y * (g - mg - xh * mgx));
 }
 
-// ---- sum over the voxels of a [* m], per (slab, sample, channel) -------------------------------------------------------------------------------
-
-// grid (slabs, B, lane tiles).  A row of the workgroup is cw = 1 << cshift lanes of VEC channels each; thread t adds the rows t / cw,
-// t / cw + 256 / cw, ... of its slab, then the first cw threads add the 256 / cw row sums of their channels, ascending.
-template <int VEC, bool MUL>
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a, const float* __restrict__ m, int V, int C, int cshift, double* __restrict__ part)
+// dbeta[c] = sum over b of tot2[b][c][0], dgamma[c] = sum over b of tot2[b][c][1], b ascending
+__global__ __launch_bounds__(256) void in_bwd_params_kernel(const double* __restrict__ tot2, int B, int C, float* __restrict__ dgamma, float* __restrict__ dbeta)
 {
-    __shared__ double ss[VEC][256];
-    const int t = threadIdx.x, cw = 1 << cshift;
-    const int c = (blockIdx.z * cw + (t & (cw - 1))) * VEC, rl = t >> cshift, nrl = 256 >> cshift;
-    const int b = blockIdx.y, v0 = blockIdx.x * kSlab, v1 = min(V, v0 + kSlab);
-    double s[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) s[k] = 0.0;
-    if (c < C) {
-        const size_t base = (size_t)b * V * C + c;
-#pragma unroll 4
-        for (int v = v0 + rl; v < v1; v += nrl) {
-            const Vec<VEC> f = vload<VEC>(a + base + (size_t)v * C);
-            if (MUL) {
-                const Vec<VEC> g = vload<VEC>(m + base + (size_t)v * C);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) s[k] += (double)f.v[k] * (double)g.v[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) s[k] += (double)f.v[k];
-            }
-        }
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double sb = 0.0, sg = 0.0;
+    for (int b = 0; b < B; ++b) {
+        sb += tot2[((size_t)b * C + c) * 2];
+        sg += tot2[((size_t)b * C + c) * 2 + 1];
     }
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) ss[k][t] = s[k];
-    __syncthreads();
-    if (t < cw && c < C) {
-        double* o = part + ((size_t)blockIdx.x * gridDim.y + b) * C + c;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            double S = 0.0;
-            for (int j = 0; j < nrl; ++j) S += ss[k][j * cw + t];
-            o[k] = S;
-        }
-    }
-}
-
-int lane_shift(int groups, int max_shift)
-{
-    int s = 0;
-    while ((1 << s) < groups && s < max_shift) ++s;
-    return s;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// part [slabs][B][C] and tot [B][C]: tot[b, c] = sum over v of a[b, v, c] (* m[b, v, c])
-void colsum_run(hipStream_t sm, const float* a, const float* m, int B, int V, int C, double* part, double* tot)
-{
-    const int slabs = ceil_div(V, kSlab), nv = B * C;
-    const bool vec = C % 4 == 0 && aligned16(a) && aligned16(m);
-    // 8 lanes of 16 bytes (a 128-byte line) or 64 lanes of 4 per row of the workgroup
-    const int groups = vec ? C / 4 : C, cshift = lane_shift(groups, vec ? 3 : 6);
-    const dim3 grid((unsigned)slabs, (unsigned)B, (unsigned)ceil_div(groups, 1 << cshift));
-    if (vec) {
-        if (m) hipLaunchKernelGGL((colsum_kernel<4, true>), grid, dim3(256), 0, sm, a, m, V, C, cshift, part);
-        else hipLaunchKernelGGL((colsum_kernel<4, false>), grid, dim3(256), 0, sm, a, m, V, C, cshift, part);
-    } else {
-        if (m) hipLaunchKernelGGL((colsum_kernel<1, true>), grid, dim3(256), 0, sm, a, m, V, C, cshift, part);
-        else hipLaunchKernelGGL((colsum_kernel<1, false>), grid, dim3(256), 0, sm, a, m, V, C, cshift, part);
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, tot);
+    if (dbeta) dbeta[c] = (float)sb;
+    if (dgamma) dgamma[c] = (float)sg;
 }
 
 // ---- channel attention -------------------------------------------------------------------------------------------------------------------------
 
-// One workgroup per sample; saliency.hip's ca_fold_kernel with the widths as arguments and the three vectors kept.
+// part [slabs][B][C] and tot [B][C]: tot[b, c] = sum over v of a[b, v, c] (* m[b, v, c])
+void colsum_run(hipStream_t sm, const float* a, const float* m, int B, int V, int C, double* part, double* tot)
+{
+    if (C % 4 == 0 && aligned16(a) && aligned16(m)) {
+        if (m) slab_sum_run<4, 1>(sm, ColumnSum<4, true>{a, m}, C, B, V, C, part, tot);
+        else slab_sum_run<4, 1>(sm, ColumnSum<4, false>{a, m}, C, B, V, C, part, tot);
+    } else {
+        if (m) slab_sum_run<1, 1>(sm, ColumnSum<1, true>{a, m}, C, B, V, C, part, tot);
+        else slab_sum_run<1, 1>(sm, ColumnSum<1, false>{a, m}, C, B, V, C, part, tot);
+    }
+}
+
+// One workgroup per sample: the kit's dense part, the three vectors kept for the gradient.
 __global__ __launch_bounds__(256) void ca_dense_kernel(const double* __restrict__ tot, int V, int C, int Ch, const float* __restrict__ w1,
                                                        const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
                                                        float* __restrict__ mean_out, float* __restrict__ hidden_out, float* __restrict__ scale_out)
 {
-    __shared__ float mean[kMaxC], h[kMaxCh];
+    __shared__ float mean[kMaxC], h[kMaxCh], s[kMaxC];
     const int t = threadIdx.x, b = blockIdx.x;
+    ca_dense(tot + (size_t)b * C, 1, V, C, Ch, w1, b1, w2, b2, mean, h, s);
     for (int c = t; c < C; c += 256) {
-        mean[c] = (float)(tot[(size_t)b * C + c] / V);
         mean_out[(size_t)b * C + c] = mean[c];
+        scale_out[(size_t)b * C + c] = s[c];
     }
-    __syncthreads();
-    for (int i = t; i < Ch; i += 256) {
-        double acc = (double)b1[i];
-        for (int c = 0; c < C; ++c) acc += (double)mean[c] * (double)w1[(size_t)c * Ch + i];
-        h[i] = fmaxf((float)acc, 0.f);
-        hidden_out[(size_t)b * Ch + i] = h[i];
-    }
-    __syncthreads();
-    for (int c = t; c < C; c += 256) {
-        double acc = (double)b2[c];
-        for (int i = 0; i < Ch; ++i) acc += (double)h[i] * (double)w2[(size_t)i * C + c];
-        scale_out[(size_t)b * C + c] = (float)(1.0 / (1.0 + exp(-acc)));
-    }
+    for (int i = t; i < Ch; i += 256) hidden_out[(size_t)b * Ch + i] = h[i];
 }
 
 // grid (ceil(V * C / VEC / 256), B): y = x * scale [+ add], scale and add per (sample, channel).  Every lane reads its own x before it
@@ -232,25 +195,6 @@ __global__ __launch_bounds__(256) void ca_bwd_dense_kernel(const double* __restr
 
 // ---- spatial gate ------------------------------------------------------------------------------------------------------------------------------
 
-// one lane per (row, VEC channels) of the B * V rows; as saliency.hip's sa_mul_kernel every lane of a row computes the row's sigmoid
-template <int VEC>
-__global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ a3, const float* f,
-                                                   unsigned rows, int C, float* __restrict__ sa, float* y)
-{
-    const unsigned e = blockIdx.x * 256u + threadIdx.x, groups = (unsigned)C / VEC;
-    const unsigned row = e / groups, cg = e - row * groups;
-    if (row >= rows) return;
-    const float z = (a1[row] + a2[row]) + a3[row];
-    const float g = 1.f / (1.f + expf(-z));
-    if (cg == 0) sa[row] = g;
-    const size_t i = (size_t)row * C + (size_t)cg * VEC;
-    const Vec<VEC> v = vload<VEC>(f + i);
-    Vec<VEC> o;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) o.v[k] = v.v[k] * g;
-    vstore<VEC>(y + i, o);
-}
-
 // A row is 1 << lshift lanes (a power of two up to 64, so a row never straddles a wave); lane l adds the channel groups l, l + lanes, ...
 // in float64, the lanes meet in a butterfly: the order depends on C (and the alignment's VEC) alone.  df = dy * sa on the way.
 template <int VEC>
@@ -283,69 +227,6 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* dy, const fl
 }
 
 // ---- softmax + weighted Dice -------------------------------------------------------------------------------------------------------------------
-
-// How a voxel's C logits are moved.  MODE 2: C == 2, one 8-byte access; MODE 4: C % 4 == 0, 16-byte accesses; MODE 1: floats.
-template <int MODE>
-struct Row {
-    static constexpr int NC = MODE == 2 ? 2 : kMaxClasses;
-    float v[NC];
-};
-
-template <int MODE>
-__device__ __forceinline__ void row_load(const float* p, int C, Row<MODE>& r)
-{
-    if (MODE == 2) {
-        const float2 a = *reinterpret_cast<const float2*>(p);
-        r.v[0] = a.x, r.v[1] = a.y;
-    } else if (MODE == 4) {
-#pragma unroll
-        for (int q = 0; q < Row<MODE>::NC / 4; ++q)
-            if (q * 4 < C) {
-                const float4 a = *reinterpret_cast<const float4*>(p + q * 4);
-                r.v[q * 4] = a.x, r.v[q * 4 + 1] = a.y, r.v[q * 4 + 2] = a.z, r.v[q * 4 + 3] = a.w;
-            }
-    } else {
-#pragma unroll
-        for (int c = 0; c < Row<MODE>::NC; ++c)
-            if (c < C) r.v[c] = p[c];
-    }
-}
-
-template <int MODE>
-__device__ __forceinline__ void row_store(float* p, int C, const Row<MODE>& r)
-{
-    if (MODE == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(r.v[0], r.v[1]);
-    } else if (MODE == 4) {
-#pragma unroll
-        for (int q = 0; q < Row<MODE>::NC / 4; ++q)
-            if (q * 4 < C) *reinterpret_cast<float4*>(p + q * 4) = make_float4(r.v[q * 4], r.v[q * 4 + 1], r.v[q * 4 + 2], r.v[q * 4 + 3]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < Row<MODE>::NC; ++c)
-            if (c < C) p[c] = r.v[c];
-    }
-}
-
-// saliency.hip's softmax_kernel on a row in registers
-template <int MODE>
-__device__ __forceinline__ void row_softmax(int C, Row<MODE>& r)
-{
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < Row<MODE>::NC; ++c)
-        if (c < C) m = fmaxf(m, r.v[c]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < Row<MODE>::NC; ++c)
-        if (c < C) {
-            r.v[c] = expf(r.v[c] - m);
-            s += r.v[c];
-        }
-#pragma unroll
-    for (int c = 0; c < Row<MODE>::NC; ++c)
-        if (c < C) r.v[c] = r.v[c] / s;
-}
 
 __device__ __forceinline__ double wave_sum(double a)
 {
@@ -449,43 +330,51 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* logits, cons
     row_store<MODE>(dlogits + row * C, C, p);
 }
 
-int dice_mode(int C, const void* a, const void* b)
-{
-    if (C == 2 && (reinterpret_cast<uintptr_t>(a) & 7) == 0 && (reinterpret_cast<uintptr_t>(b) & 7) == 0) return 2;
-    if (C % 4 == 0 && aligned16(a) && aligned16(b)) return 4;
-    return 1;
-}
-
-// ---- the argument checks -----------------------------------------------------------------------------------------------------------------------
-
-int ca_shape_ok(const char* who, int64_t B, int64_t V, int64_t C, int64_t Ch)
-{
-    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
-    PS_CHECK(C >= 1 && C <= kMaxC, "%s: C = %lld, must be in [1, %d]", who, (long long)C, kMaxC);
-    PS_CHECK(Ch >= 1 && Ch <= kMaxCh, "%s: Ch = %lld, must be in [1, %d]", who, (long long)Ch, kMaxCh);
-    PS_CHECK(V >= 1 && V < (1ll << 31) && V * C < (1ll << 31), "%s: V = %lld (V >= 1, V * C < 2^31)", who, (long long)V);
-    return PS_OK;
-}
-
-int gate_shape_ok(const char* who, int64_t B, int64_t V, int64_t C)
-{
-    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
-    PS_CHECK(C >= 1 && C <= kMaxC, "%s: C = %lld, must be in [1, %d]", who, (long long)C, kMaxC);
-    PS_CHECK(V >= 1 && V < (1ll << 31) && B * V * C < (1ll << 31), "%s: V = %lld (V >= 1, B * V * C < 2^31)", who, (long long)V);
-    return PS_OK;
-}
-
-int dice_shape_ok(const char* who, int64_t B, int64_t V, int64_t C)
-{
-    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
-    PS_CHECK(C >= 2 && C <= kMaxClasses, "%s: C = %lld, must be in [2, %d]", who, (long long)C, kMaxClasses);
-    PS_CHECK(V >= 1 && V < (1ll << 31), "%s: V = %lld, must be in [1, 2^31)", who, (long long)V);
-    return PS_OK;
-}
-
 }  // namespace
 
 }  // namespace ps
+
+extern "C" int ps_instance_norm_relu_bwd(ps_context* c, const void* x, const void* y, const void* dy, int64_t B, int64_t V, int64_t C, const void* gamma, float eps,
+                                         void* dx, void* dgamma, void* dbeta, void* scratch, int64_t* scratch_bytes)
+{
+    using namespace ps;
+    static const char* who = "ps_instance_norm_relu_bwd";
+    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, kMaxC, kLimitVC));
+    PS_CHECK(eps > 0.f, "%s: eps = %g, must be > 0", who, (double)eps);
+    const int slabs = ceil_div(V, kSlab), nv = (int)(B * C * 2);
+    Carver cv{static_cast<char*>(scratch)};
+    double* part = cv.take<double>((size_t)slabs * nv);
+    double* tot = cv.take<double>((size_t)nv);
+    double2* stat = cv.take<double2>((size_t)B * C);
+    double* tot2 = cv.take<double>((size_t)nv);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)cv.off;
+        return PS_OK;
+    }
+    PS_CHECK(x && y && dy && gamma, "%s: NULL x, y, dy or gamma (they may be NULL only in the call that sizes the scratch)", who);
+    PS_CHECK(dx || dgamma || dbeta, "%s: every result is NULL", who);
+    PS_CHECK(dx != x && dx != y, "%s: dx must not overlap x or y (it may be dy)", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    Stage stg(c, "instance_norm_relu_bwd", 7);
+    const float *xf = static_cast<const float*>(x), *yf = static_cast<const float*>(y), *dyf = static_cast<const float*>(dy);
+    const int nB = (int)B, nV = (int)V, nC = (int)C;
+    stats_run(sm, xf, nC, nB, nV, nC, part, tot);
+    hipLaunchKernelGGL(in_bwd_stat_kernel, dim3(blocks256((size_t)nB * nC)), dim3(256), 0, sm, tot, nV, nB * nC, eps, stat);
+    slab_sum_run<1, 2>(sm, NormBwdSums{xf, yf, dyf, stat}, nC, nB, nV, nC, part, tot2);
+    if (dx)
+        hipLaunchKernelGGL(in_bwd_dx_kernel, dim3(blocks256((size_t)nV * nC), (unsigned)nB), dim3(256), 0, sm, xf, yf, dyf, nV, nC, stat, tot2,
+                           static_cast<const float*>(gamma), static_cast<float*>(dx));
+    if (dgamma || dbeta)
+        hipLaunchKernelGGL(in_bwd_params_kernel, dim3(blocks256((size_t)nC)), dim3(256), 0, sm, tot2, nB, nC, static_cast<float*>(dgamma),
+                           static_cast<float*>(dbeta));
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
 
 extern "C" int ps_channel_attention(ps_context* c, const void* x, int64_t B, int64_t V, int64_t C, int64_t Ch, const void* w1, const void* b1, const void* w2,
                                     const void* b2, void* mean, void* hidden, void* scale, void* y, void* scratch, int64_t* scratch_bytes)
@@ -493,7 +382,8 @@ extern "C" int ps_channel_attention(ps_context* c, const void* x, int64_t B, int
     using namespace ps;
     static const char* who = "ps_channel_attention";
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
-    PS_TRY(ca_shape_ok(who, B, V, C, Ch));
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, kMaxC, kLimitVC));
+    PS_CHECK(Ch >= 1 && Ch <= kMaxCh, "%s: Ch = %lld, must be in [1, %d]", who, (long long)Ch, kMaxCh);
     Carver cv{static_cast<char*>(scratch)};
     double* part = cv.take<double>((size_t)ceil_div(V, kSlab) * B * C);
     double* tot = cv.take<double>((size_t)B * C);
@@ -526,7 +416,8 @@ extern "C" int ps_channel_attention_bwd(ps_context* c, const void* x, const void
     using namespace ps;
     static const char* who = "ps_channel_attention_bwd";
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
-    PS_TRY(ca_shape_ok(who, B, V, C, Ch));
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, kMaxC, kLimitVC));
+    PS_CHECK(Ch >= 1 && Ch <= kMaxCh, "%s: Ch = %lld, must be in [1, %d]", who, (long long)Ch, kMaxCh);
     Carver cv{static_cast<char*>(scratch)};
     double* part = cv.take<double>((size_t)ceil_div(V, kSlab) * B * C);
     double* ds = cv.take<double>((size_t)B * C);
@@ -561,21 +452,15 @@ extern "C" int ps_spatial_gate(ps_context* c, const void* a1, const void* a2, co
 {
     using namespace ps;
     static const char* who = "ps_spatial_gate";
-    PS_TRY(gate_shape_ok(who, B, V, C));
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, kMaxC, kLimitBVC));
     PS_CHECK(a1 && a2 && a3 && f && sa && y, "%s: NULL a1, a2, a3, f, sa or y", who);
     PS_CHECK(c, "%s: NULL context", who);
 
     PS_HIP(hipSetDevice(c->device));
     Stage stg(c, "spatial_gate", 1);
-    const unsigned rows = (unsigned)(B * V);
-    const bool vec = C % 4 == 0 && aligned16(f) && aligned16(y);
-    const dim3 grid(blocks256((size_t)rows * C / (vec ? 4 : 1)));
-    if (vec)
-        hipLaunchKernelGGL(gate_kernel<4>, grid, dim3(256), 0, c->stream, static_cast<const float*>(a1), static_cast<const float*>(a2),
-                           static_cast<const float*>(a3), static_cast<const float*>(f), rows, (int)C, static_cast<float*>(sa), static_cast<float*>(y));
-    else
-        hipLaunchKernelGGL(gate_kernel<1>, grid, dim3(256), 0, c->stream, static_cast<const float*>(a1), static_cast<const float*>(a2),
-                           static_cast<const float*>(a3), static_cast<const float*>(f), rows, (int)C, static_cast<float*>(sa), static_cast<float*>(y));
+    // dense rows: the B * V voxels as one sample
+    PS_TRY(gate_run(c->stream, static_cast<const float*>(a1), static_cast<const float*>(a2), static_cast<const float*>(a3), static_cast<const float*>(f), (int)C,
+                    1, (int)(B * V), (int)C, static_cast<float*>(sa), static_cast<float*>(y), (int)C));
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
@@ -584,7 +469,7 @@ extern "C" int ps_spatial_gate_bwd(ps_context* c, const void* dy, const void* f,
 {
     using namespace ps;
     static const char* who = "ps_spatial_gate_bwd";
-    PS_TRY(gate_shape_ok(who, B, V, C));
+    PS_TRY(rows_shape_ok(who, B, V, C, 1, kMaxC, kLimitBVC));
     PS_CHECK(dy && f && sa, "%s: NULL dy, f or sa", who);
     PS_CHECK(df || da, "%s: every result is NULL", who);
     PS_CHECK(df != f, "%s: df must not overlap f (it may be dy)", who);
@@ -612,7 +497,7 @@ extern "C" int ps_softmax_dice_loss(ps_context* c, const void* logits, const voi
     using namespace ps;
     static const char* who = "ps_softmax_dice_loss";
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
-    PS_TRY(dice_shape_ok(who, B, V, C));
+    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
     const int slabs = ceil_div(V, kSlab), nv = (int)(B * C * 3);
     Carver cv{static_cast<char*>(scratch)};
     double* part = cv.take<double>((size_t)slabs * nv);
@@ -646,7 +531,7 @@ extern "C" int ps_softmax_dice_loss_bwd(ps_context* c, const void* logits, const
 {
     using namespace ps;
     static const char* who = "ps_softmax_dice_loss_bwd";
-    PS_TRY(dice_shape_ok(who, B, V, C));
+    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
     PS_CHECK(logits && labels && sums, "%s: NULL logits, labels or sums (weight and dloss may be NULL)", who);
     PS_CHECK(dlogits, "%s: NULL dlogits", who);
     PS_CHECK(c, "%s: NULL context", who);

@@ -125,14 +125,28 @@ def _scratch_for(key, need, dev):
     return buf
 
 
+def _ctx_for(t):
+    ctx = runtime.default_context(t.device.index)
+    ctx.use_torch_stream()
+    return ctx
+
+
+def _two_call(name, dev, call):
+    """The two-call scratch protocol: call(None, byref(need)) sizes (it looks at the shapes alone), then the same call runs on the
+    cached buffer.  Returns the size."""
+    need = ctypes.c_int64(0)
+    _lib.check(call(None, ctypes.byref(need)))
+    buf = _scratch_for((name, dev.index), need.value, dev)
+    _lib.check(call(runtime.ptr(buf), ctypes.byref(need)))
+    return need.value
+
+
 def _same_out(n, stride):
     return -(-n // stride)
 
 
-def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
-    """tf.layers.conv3d(x, padding="SAME") without activation: x [B, D, H, W, C1] (and x2 [B, D, H, W, C2], concatenated behind it on the
-    channel axis; both up-sampled `up` times by repetition first), w [kd, kh, kw, C1 + C2, C_out], bias [C_out] or None.  CUDA float32."""
-    who = "conv3d"
+def _conv_args(who, x, w, x2, up, stride):
+    """What conv3d and conv3d_backward check alike: (x, w, x2, the geometry's (B, Ds, Hs, Ws, C1, C2), the output's shape)."""
     x = _f32(x, who, "x", 5)
     w = _f32(w, who, "w", 5)
     B, Ds, Hs, Ws, C1 = x.shape
@@ -140,20 +154,25 @@ def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
     if x2 is not None:
         x2 = _f32(x2, who, "x2", 5)
         if x2.shape[:4] != x.shape[:4]:
-            raise ValueError("conv3d: x2 must have x's batch and extents")
+            raise ValueError("%s: x2 must have x's batch and extents" % who)
         C2 = x2.shape[4]
     if w.shape[3] != C1 + C2:
-        raise ValueError("conv3d: w has %d input channels, the input %d" % (w.shape[3], C1 + C2))
+        raise ValueError("%s: w has %d input channels, the input %d" % (who, w.shape[3], C1 + C2))
+    return x, w, x2, (B, Ds, Hs, Ws, C1, C2), (B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4])
+
+
+def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
+    """tf.layers.conv3d(x, padding="SAME") without activation: x [B, D, H, W, C1] (and x2 [B, D, H, W, C2], concatenated behind it on the
+    channel axis; both up-sampled `up` times by repetition first), w [kd, kh, kw, C1 + C2, C_out], bias [C_out] or None.  CUDA float32."""
+    who = "conv3d"
+    x, w, x2, dims, out_shape = _conv_args(who, x, w, x2, up, stride)
     if bias is not None:
         bias = _f32(bias, who, "bias", 1)
         if bias.shape[0] != w.shape[4]:
             raise ValueError("conv3d: bias must have C_out values")
-    y = torch.empty((B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4]), dtype=torch.float32,
-                    device=x.device)
-    ctx = runtime.default_context(x.device.index)
-    ctx.use_torch_stream()
-    _lib.check(_lib.lib().ps_conv3d(ctx.handle, runtime.ptr(x), runtime.ptr(x2), B, Ds, Hs, Ws, C1, C2, up, runtime.ptr(w), runtime.ptr(bias), w.shape[0],
-                                    w.shape[1], w.shape[2], w.shape[4], stride, dilation, runtime.ptr(y)))
+    y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().ps_conv3d(_ctx_for(x).handle, runtime.ptr(x), runtime.ptr(x2), *dims, up, runtime.ptr(w), runtime.ptr(bias), w.shape[0], w.shape[1],
+                                    w.shape[2], w.shape[4], stride, dilation, runtime.ptr(y)))
     return y
 
 
@@ -169,13 +188,10 @@ def instance_norm_relu(x, gamma, beta, eps=EPS):
     if gamma.shape[0] != C or beta.shape[0] != C:
         raise ValueError("instance_norm_relu: gamma and beta must have C values")
     y = torch.empty_like(x)
-    ctx = runtime.default_context(x.device.index)
-    ctx.use_torch_stream()
+    ctx = _ctx_for(x)
     fn = _lib.lib().ps_instance_norm_relu
-    need = ctypes.c_int64(0)
-    _lib.check(fn(ctx.handle, None, B, V, C, None, None, eps, None, None, ctypes.byref(need)))
-    buf = _scratch_for(("ps_instance_norm_relu", x.device.index), need.value, x.device)
-    _lib.check(fn(ctx.handle, runtime.ptr(x), B, V, C, runtime.ptr(gamma), runtime.ptr(beta), eps, runtime.ptr(y), runtime.ptr(buf), ctypes.byref(need)))
+    _two_call("ps_instance_norm_relu", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), B, V, C, runtime.ptr(gamma), runtime.ptr(beta), eps,
+                                                                       runtime.ptr(y), scratch, n))
     return y
 
 
@@ -215,16 +231,11 @@ class SaliencyNet:
             out["sa"] = torch.empty((B, D, H, W), dtype=torch.float32, device=x.device)
             out["c12"] = torch.empty((B, D, H, W, 64), dtype=torch.float32, device=x.device)
             tp = _lib.PsSaliencyTaps(*(runtime.ptr(out[k]) for k in ("down4", "c345", "sa", "c12")))
-        ctx = runtime.default_context(x.device.index)
-        ctx.use_torch_stream()
+        ctx = _ctx_for(x)
         fn = _lib.lib().ps_saliency_forward
-        need = ctypes.c_int64(0)
-        n = self.weights.numel()
-        _lib.check(fn(ctx.handle, None, B, D, H, W, self.in_channels, K, None, n, None, None, None, None, ctypes.byref(need)))
-        buf = _scratch_for(("ps_saliency_forward", x.device.index), need.value, x.device)
-        self.scratch_bytes = need.value
-        _lib.check(fn(ctx.handle, runtime.ptr(x), B, D, H, W, self.in_channels, K, runtime.ptr(self.weights), n, runtime.ptr(logits), runtime.ptr(probs),
-                      ctypes.byref(tp) if tp is not None else None, runtime.ptr(buf), ctypes.byref(need)))
+        self.scratch_bytes = _two_call("ps_saliency_forward", x.device, lambda scratch, n: fn(
+            ctx.handle, runtime.ptr(x), B, D, H, W, self.in_channels, K, runtime.ptr(self.weights), self.weights.numel(), runtime.ptr(logits), runtime.ptr(probs),
+            ctypes.byref(tp) if tp is not None else None, scratch, n))
         return out
 
     def forward(self, patch):
@@ -264,7 +275,7 @@ def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118)):
     total = torch.zeros((D, H, W, K), dtype=torch.float32, device=v.device)
     count = torch.zeros((D, H, W), dtype=torch.int32, device=v.device)
     crop = torch.empty((1,) + tuple(patch) + (C,), dtype=torch.float32, device=v.device)
-    ctx = runtime.default_context(v.device.index)
+    ctx = _ctx_for(v)
     lib = _lib.lib()
     for o0 in window_origins(D, patch[0], steps[0]):
         for o1 in window_origins(H, patch[1], steps[1]):
@@ -280,34 +291,14 @@ def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118)):
     return total
 
 
-# ---- the gradients of the two op wrappers (include/pointseg_saliency_train.h, csrc/conv3d_train.hip) ---------------------------------------------
-
-def _two_call(name, dev, call):
-    """The two-call scratch protocol: call(None, byref(need)) sizes (it looks at the shapes alone), then the same call runs on the
-    cached buffer."""
-    need = ctypes.c_int64(0)
-    _lib.check(call(None, ctypes.byref(need)))
-    buf = _scratch_for((name, dev.index), need.value, dev)
-    _lib.check(call(runtime.ptr(buf), ctypes.byref(need)))
-
+# ---- the gradients of the two op wrappers (include/pointseg_saliency_train.h, csrc/conv3d_train.hip, csrc/saliency_train.hip) ---------------------------------------------
 
 def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x2", "w", "bias")):
     """The gradients of conv3d(x, w, bias, stride, dilation, x2, up) for the output gradient dy: a dict with the entries of `need` --
     "x" [like x], "x2" [like x2; only with x2], "w" [like w], "bias" [C_out].  Arguments are checked as conv3d checks them."""
     who = "conv3d_backward"
-    x = _f32(x, who, "x", 5)
-    w = _f32(w, who, "w", 5)
+    x, w, x2, dims, want = _conv_args(who, x, w, x2, up, stride)
     dy = _f32(dy, who, "dy", 5)
-    B, Ds, Hs, Ws, C1 = x.shape
-    C2 = 0
-    if x2 is not None:
-        x2 = _f32(x2, who, "x2", 5)
-        if x2.shape[:4] != x.shape[:4]:
-            raise ValueError("conv3d_backward: x2 must have x's batch and extents")
-        C2 = x2.shape[4]
-    if w.shape[3] != C1 + C2:
-        raise ValueError("conv3d_backward: w has %d input channels, the input %d" % (w.shape[3], C1 + C2))
-    want = (B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4])
     if tuple(dy.shape) != want:
         raise ValueError("conv3d_backward: dy has shape %s, the convolution's output %s" % (tuple(dy.shape), want))
     need = set(need)
@@ -318,9 +309,8 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
         if not need:
             raise ValueError("conv3d_backward: the gradient of x2 was asked for and there is no x2")
     out = {}
-    ctx = runtime.default_context(x.device.index)
-    ctx.use_torch_stream()
-    geometry = (B, Ds, Hs, Ws, C1, C2, up, w.shape[0], w.shape[1], w.shape[2], w.shape[4], stride, dilation)
+    ctx = _ctx_for(x)
+    geometry = dims + (up, w.shape[0], w.shape[1], w.shape[2], w.shape[4], stride, dilation)
     if need & {"x", "x2"}:
         dx = torch.empty_like(x) if "x" in need else None
         dx2 = torch.empty_like(x2) if "x2" in need else None
@@ -359,8 +349,7 @@ def _norm_backward(dy, x, y, gamma, eps, need):
     dx = torch.empty_like(x) if need[0] else None
     dgamma = torch.empty_like(gamma) if need[1] else None
     dbeta = torch.empty_like(gamma) if need[2] else None
-    ctx = runtime.default_context(x.device.index)
-    ctx.use_torch_stream()
+    ctx = _ctx_for(x)
     fn = _lib.lib().ps_instance_norm_relu_bwd
     _two_call("ps_instance_norm_relu_bwd", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(y), runtime.ptr(dy), B, V, C,
                                                                            runtime.ptr(gamma), eps, runtime.ptr(dx), runtime.ptr(dgamma), runtime.ptr(dbeta),
@@ -434,12 +423,6 @@ def _rows(x, who, name):
         raise ValueError("%s: %s must be [B, ..., C]" % (who, name))
     B, C = x.shape[0], x.shape[-1]
     return x, B, x.numel() // max(B * C, 1), C
-
-
-def _ctx_for(t):
-    ctx = runtime.default_context(t.device.index)
-    ctx.use_torch_stream()
-    return ctx
 
 
 def channel_attention(x, w1, b1, w2, b2, want_y=True):

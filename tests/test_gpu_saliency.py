@@ -189,6 +189,23 @@ def test_network_batch_of_two_equals_two_single_runs():
     assert torch.equal(both[0:1], la) and torch.equal(both[1:2], lb)
 
 
+@pytest.mark.parametrize("classes", [3, 4])
+def test_network_softmax_load_forms(classes):
+    """The forward's softmax moves a voxel's logits as floats (3 classes) or in 16-byte accesses (4); two classes, everywhere else in this
+    file, take the 8-byte form.  The probabilities against the host's softmax of the device's own logits."""
+    from point_unet_amd import _lib
+    sal = _sal()
+    params = sal.init_params(1, classes, seed=31)
+    net = sal.SaliencyNet(params, 1, classes)
+    assert _lib.lib().ps_saliency_weight_count(1, classes) == sum(int(np.prod(s)) for s in sal.param_shapes(1, classes).values()) == net.weights.numel()
+    x = torch.from_numpy(np.random.default_rng(32).standard_normal((1, 16, 16, 16, 1)).astype(np.float32)).cuda()
+    out = net.forward_taps(x)
+    logits = out["logits"].cpu().numpy()
+    assert logits.shape == (1, 16, 16, 16, classes) and logits.dtype == np.float32
+    _bar(out["probs"].cpu().numpy(), ref.softmax(logits.astype(np.float64)), ref.softmax(logits), "softmax of %d classes" % classes)
+    assert torch.equal(net.probs(x), out["probs"])
+
+
 # ---- 8., 9. the window average -----------------------------------------------------------------------------------------------------------------
 
 PATCH, STEPS = (16, 32, 32), (12, 24, 24)
