@@ -2,7 +2,8 @@
 
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
 (PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES), include/pointseg_saliency.h
-(SALIENCY_PROTOTYPES) and include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
+(SALIENCY_ATTENTION_PROTOTYPES) and include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -314,6 +315,19 @@ SALIENCY_ATTENTION_PROTOTYPES = {
     "ps_softmax_dice_loss_bwd": (ctypes.c_int, [c_vp] * 6 + [ctypes.c_int64] * 3 + [c_vp]),
 }
 
+# every symbol include/pointseg_saliency_data.h declares (volumes prepared and kept on the device, training patches drawn from them;
+# csrc/saliency_data.hip)
+PS_PATCH_RANDOM, PS_PATCH_ALL_POSITIVE, PS_PATCH_ONE_POSITIVE = 0, 1, 2
+PS_PATCH_MAX_B, PS_PATCH_MAX_T, PS_PATCH_MAX_C = 64, 16, 16
+SALIENCY_DATA_PROTOTYPES = {
+    "ps_saliency_brats_measure": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32] + [ctypes.c_int64] * 3 + [ctypes.c_int32, c_i64p, ctypes.POINTER(ctypes.c_double)]),
+    "ps_saliency_brats_apply": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int32] + [ctypes.c_int64] * 3 + [ctypes.c_int32, c_i64p, ctypes.POINTER(ctypes.c_double)]
+                                + [c_vp] * 3),
+    "ps_saliency_pancreas_prepare": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32, ctypes.c_int64] + [c_vp] * 4),
+    "ps_patch_sample": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i64p, ctypes.c_int64, ctypes.c_int32, c_i32p,
+                                       ctypes.c_int32, ctypes.c_int32, c_i64p, ctypes.c_uint32, ctypes.c_int32] + [c_vp] * 4),
+}
+
 _lib = None
 
 
@@ -335,7 +349,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
                                   + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())
-                                  + list(SALIENCY_ATTENTION_PROTOTYPES.items())):
+                                  + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,628 @@
+// saliency_data.hip -- the saliency network's data on the device (include/pointseg_saliency_data.h): the preparation of a volume
+// (crop_brain_region / load_pancreas_img, SaliencyAttention/utils.py:30-78, 313-388) and training batches of patches drawn from resident
+// volumes (sampler3d and BatchData's reject loop, SaliencyAttention/data_sampler.py:77-88, 169-214) by the rule the header states and
+// tests/saliency_data_ref.py restates in numpy.
+//
+// Preparation, BraTS form: an integer min / max pass for the box of raw[0] != 0, then -- the box still on the device -- the two-pass
+// statistics of every modality inside it: a float64 partial per (slab of 4096 crop voxels, modality), the threads of a slab added in a
+// fixed order, the slabs by reduce_partials.h.  One copy brings the box and the sums to the host; the apply pass takes them back as arguments.
+//
+// Sampler: the host derives every candidate's centre and window (hashes of the seed: no device state) into one table, uploaded together
+// with the zeroed counts.  Launch 1 counts the labels > 0 of the windows the mode can ask for, a row's bytes read as the aligned 4-byte
+// words that cover it (the row starts at an arbitrary byte); integer atomics, so two runs agree.  Launch 2 writes the batch: every
+// workgroup derives all slots' tries from the counts, then fills 16-byte pieces of the outputs -- a piece inside the copied box is loaded
+// at the alignment its source address has (16, 8 or 4 bytes; labels and weights 4 or 1), a piece outside is the fill hash.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "reduce_partials.h"
+#include "sample_hash.h"
+#include "scratch.h"
+#include "wave_ops.h"
+
+#include "../../include/pointseg_saliency_data.h"
+
+namespace ps {
+
+namespace {
+
+constexpr int kCropSlab = 4096;     // crop voxels per workgroup of a statistics pass
+constexpr unsigned kAxisMul = 0x85EBCA6Bu;  // h_a = hash32(s(b, t) + kAxisMul * (a + 1)); a = 3: the fill's seed
+
+// ---- preparation ---------------------------------------------------------------------------------------------------------------------------
+
+struct CropBox {
+    int lo[3], ext[3];  // first voxel and extents (0: raw[0] is all zero)
+};
+
+// the raw min / max of raw[0] != 0 (as the box pass left them) grown by the margin and clamped
+__device__ __forceinline__ CropBox crop_box(const int* __restrict__ mm, int margin, int D, int H, int W)
+{
+    const int dims[3] = {D, H, W};
+    CropBox b;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int mn = mm[a], mx = mm[3 + a];
+        if (mx < mn) {
+            b.lo[a] = 0;
+            b.ext[a] = 0;
+        } else {
+            const int l = max(mn - margin, 0), h = min(mx + margin, dims[a] - 1);
+            b.lo[a] = l;
+            b.ext[a] = h - l + 1;
+        }
+    }
+    return b;
+}
+
+// crop-linear index -> the voxel's index in the uncropped volume
+__device__ __forceinline__ size_t crop_source(const CropBox& b, unsigned i, int H, int W)
+{
+    const unsigned x = i % (unsigned)b.ext[2], r = i / (unsigned)b.ext[2];
+    const unsigned y = r % (unsigned)b.ext[1], z = r / (unsigned)b.ext[1];
+    return ((size_t)(b.lo[0] + z) * H + (b.lo[1] + y)) * W + (b.lo[2] + x);
+}
+
+__global__ __launch_bounds__(256) void brats_box_kernel(const float* __restrict__ raw0, unsigned nvox, int H, int W, int* __restrict__ mm)
+{
+    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {-1, -1, -1};
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nvox; i += gridDim.x * 256u) {
+        if (raw0[i] == 0.f) continue;
+        const int x = (int)(i % (unsigned)W), r = (int)(i / (unsigned)W);
+        const int p[3] = {r / H, r % H, x};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = min(mn[a], p[a]);
+            mx[a] = max(mx[a], p[a]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int lo = (int)wave_allreduce_u32((unsigned)mn[a], [](unsigned p, unsigned q) { return (unsigned)min((int)p, (int)q); });
+        const int hi = (int)wave_allreduce_u32((unsigned)mx[a], [](unsigned p, unsigned q) { return (unsigned)max((int)p, (int)q); });
+        if ((threadIdx.x & 63) == 0) {
+            if (lo != INT_MAX) atomicMin(&mm[a], lo);
+            if (hi >= 0) atomicMax(&mm[3 + a], hi);
+        }
+    }
+}
+
+// the 256 values of a workgroup added in one fixed tree; the sum is in thread 0
+__device__ __forceinline__ double block_sum_fixed(double v, double* ss)
+{
+    ss[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) ss[threadIdx.x] += ss[threadIdx.x + s];
+        __syncthreads();
+    }
+    return ss[0];
+}
+
+// DEV = false: part[slab][c][2] = (sum, count) of the voxels > 0; DEV = true: part[slab][c] = sum of (v - mean)^2, mean from tot.
+// grid (slabs of the UNCROPPED volume, C): slabs past the crop write zeros.
+template <bool DEV>
+__global__ __launch_bounds__(256) void brats_stats_kernel(const float* __restrict__ raw, size_t nvox, int D, int H, int W, int margin,
+                                                          const int* __restrict__ mm, const double* __restrict__ tot, double* __restrict__ part)
+{
+    __shared__ double ss[256];
+    const CropBox b = crop_box(mm, margin, D, H, W);
+    const unsigned ncrop = (unsigned)b.ext[0] * (unsigned)b.ext[1] * (unsigned)b.ext[2];
+    const int c = blockIdx.y, C = gridDim.y;
+    const float* v = raw + (size_t)c * nvox;
+    const double mean = DEV ? tot[2 * c] / tot[2 * c + 1] : 0.0;
+    double s = 0.0, n = 0.0;
+    const unsigned i0 = blockIdx.x * (unsigned)kCropSlab;
+    for (int u = 0; u < kCropSlab / 256; ++u) {
+        const unsigned i = i0 + u * 256u + threadIdx.x;
+        if (i >= ncrop) break;
+        const float f = v[crop_source(b, i, H, W)];
+        if (f > 0.f) {
+            if (DEV) {
+                const double d = (double)f - mean;
+                s += d * d;
+            } else {
+                s += (double)f;
+                n += 1.0;
+            }
+        }
+    }
+    s = block_sum_fixed(s, ss);
+    if (DEV) {
+        if (threadIdx.x == 0) part[(size_t)blockIdx.x * C + c] = s;
+    } else {
+        __syncthreads();
+        n = block_sum_fixed(n, ss);
+        if (threadIdx.x == 0) {
+            part[((size_t)blockIdx.x * C + c) * 2] = s;
+            part[((size_t)blockIdx.x * C + c) * 2 + 1] = n;
+        }
+    }
+}
+
+struct ApplyArgs {
+    double mean[PS_PATCH_MAX_C], sd[PS_PATCH_MAX_C];
+    CropBox box;
+};
+
+// one thread per crop voxel: C normalised values (channels-last), the label, the weight
+__global__ __launch_bounds__(256) void brats_apply_kernel(const float* __restrict__ raw, const int32_t* __restrict__ seg, size_t nvox, int H, int W, int C,
+                                                          int num_class, ApplyArgs a, unsigned ncrop, float* __restrict__ image,
+                                                          uint8_t* __restrict__ label, uint8_t* __restrict__ weight)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= ncrop) return;
+    const size_t src = crop_source(a.box, i, H, W);
+    float* o = image + (size_t)i * C;
+    for (int c = 0; c < C; ++c) {
+        const float f = raw[(size_t)c * nvox + src];
+        o[c] = f == 0.f ? 0.f : (float)(((double)f - a.mean[c]) / a.sd[c]);
+    }
+    weight[i] = raw[src] > 0.f ? 1 : 0;
+    int l = seg ? seg[src] : 0;
+    if (num_class == 4) l = l == 4 ? 3 : l;
+    else l = (l == 4 || l == 2) ? 1 : l;
+    label[i] = (uint8_t)l;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void pancreas_prepare_kernel(const T* __restrict__ ct, size_t n, const uint8_t* __restrict__ label,
+                                                               float* __restrict__ image, uint8_t* __restrict__ out_label, uint8_t* __restrict__ weight)
+{
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        image[i] = (float)(((double)ct[i] + 100.0) / 340.0);
+        out_label[i] = label ? label[i] : 0;
+        weight[i] = 1;
+    }
+}
+
+// ---- the sampler ---------------------------------------------------------------------------------------------------------------------------
+
+// candidate (slot b, try t), host-filled: the window of the rule, as the kernels need it
+struct PatchCand {
+    const float* img;
+    const uint8_t* lab;
+    const uint8_t* wgt;
+    int dim[3];   // the volume's extents
+    int c[3];     // the centre
+    int src[3];   // c - r0: the box's first voxel in the volume
+    int lo[3];    // out / 2 - r0: the box's first voxel in the patch
+    int n[3];     // r0 + r1: the box's extents (0 is possible: a patch of extent 1 centred on `in`)
+    unsigned s_fill;
+    int vol;
+    int count;    // its index in the counts, -1: never asked for
+    int pad;
+};
+
+struct PatchShape {
+    int P[3], C, B, T, mode;
+};
+
+// labels > 0 in bytes [a, a + len) of a volume [base, end): through the aligned words that lie inside the volume, bytes at its two ends
+__device__ __forceinline__ unsigned count_word(uintptr_t q, uintptr_t a, uintptr_t a_end, uintptr_t base, uintptr_t end)
+{
+    const uintptr_t f = a > q ? a : q, l = a_end < q + 4 ? a_end : q + 4;
+    if (f >= l) return 0;
+    if (q >= base && q + 4 <= end) {
+        const unsigned lo = (unsigned)(f - q), hi = (unsigned)(l - q);
+        unsigned m = hi == 4 ? ~0u : (1u << (8 * hi)) - 1u;
+        m &= ~((1u << (8 * lo)) - 1u);
+        const unsigned x = *reinterpret_cast<const unsigned*>(q) & m;
+        return (unsigned)__popc((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u);
+    }
+    unsigned n = 0;
+    for (uintptr_t p = f; p < l; ++p) n += *reinterpret_cast<const uint8_t*>(p) != 0;
+    return n;
+}
+
+// Launch 1.  grid (blocks of 2048 words, windows); a window's rows are kdw words each (the most a row of P2 bytes can touch).
+__global__ __launch_bounds__(256) void patch_count_kernel(const PatchCand* __restrict__ cands, const int* __restrict__ win, unsigned* __restrict__ counts,
+                                                          unsigned kdw)
+{
+    const PatchCand& cd = cands[win[blockIdx.y]];
+    const unsigned rows = (unsigned)cd.n[0] * (unsigned)cd.n[1], total = rows * kdw;
+    const unsigned i0 = blockIdx.x * 2048u;
+    if (i0 >= total || cd.n[2] == 0) return;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(cd.lab);
+    const uintptr_t end = base + (size_t)cd.dim[0] * cd.dim[1] * cd.dim[2];
+    unsigned n = 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const unsigned i = i0 + u * 256u + threadIdx.x;
+        if (i < total) {
+            const unsigned row = i / kdw, k = i - row * kdw;
+            const unsigned y = row % (unsigned)cd.n[1], z = row / (unsigned)cd.n[1];
+            const uintptr_t a = base + ((size_t)(cd.src[0] + z) * cd.dim[1] + (cd.src[1] + y)) * cd.dim[2] + cd.src[2];
+            n += count_word((a & ~(uintptr_t)3) + 4 * (uintptr_t)k, a, a + cd.n[2], base, end);
+        }
+    }
+    n = (unsigned)wave_sum((int)n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counts[cd.count], n);
+}
+
+// The rule's choice of try for slot b (thread-serial; the same in every workgroup).  any_earlier: some slot b' < B - 1 has pos(b', 0) > 0.
+__device__ __forceinline__ int choose_try(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts, const PatchShape& sh, int b,
+                                          bool any_earlier, int& ok)
+{
+    ok = 1;
+    if (sh.mode == PS_PATCH_RANDOM) return 0;
+    if (sh.mode == PS_PATCH_ONE_POSITIVE && (b < sh.B - 1 || any_earlier)) return 0;
+    for (int t = 0; t < sh.T; ++t)
+        if (counts[cands[b * sh.T + t].count] > 0) return t;
+    ok = 0;
+    return sh.T - 1;
+}
+
+__device__ __forceinline__ float fill_value(unsigned j, unsigned s_fill) { return (float)(point_hash(j, s_fill) >> 8) * 0x1p-24f; }
+
+// element j of a slot's [P0, P1, P2, C] patch
+__device__ __forceinline__ float image_element(const PatchCand& cd, const PatchShape& sh, unsigned j)
+{
+    const unsigned c = j % (unsigned)sh.C, v = j / (unsigned)sh.C;
+    const unsigned p2 = v % (unsigned)sh.P[2], r = v / (unsigned)sh.P[2];
+    const unsigned u0 = r / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = r % (unsigned)sh.P[1] - (unsigned)cd.lo[1], u2 = p2 - (unsigned)cd.lo[2];
+    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2])
+        return cd.img[(((size_t)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + (cd.src[2] + u2)) * sh.C + c];
+    return fill_value(j, cd.s_fill);
+}
+
+// voxel v of a slot's [P0, P1, P2] patch: its index in the volume, or -1 outside the copied box
+__device__ __forceinline__ long long voxel_source(const PatchCand& cd, const PatchShape& sh, unsigned v)
+{
+    const unsigned p2 = v % (unsigned)sh.P[2], r = v / (unsigned)sh.P[2];
+    const unsigned u0 = r / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = r % (unsigned)sh.P[1] - (unsigned)cd.lo[1], u2 = p2 - (unsigned)cd.lo[2];
+    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2])
+        return ((long long)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + (cd.src[2] + u2);
+    return -1;
+}
+
+// four image elements from e0 on (e0 % 4 == 0), of the batch's E; ROW4: P2 * C % 4 == 0, the four share a row of one slot
+template <bool ROW4>
+__device__ __forceinline__ void image_quad(const PatchCand* s_c, const PatchShape& sh, unsigned L, size_t e0, size_t E, float (&o)[4])
+{
+    if (ROW4) {
+        const unsigned b = (unsigned)(e0 / L), j = (unsigned)(e0 - (size_t)b * L);
+        const PatchCand& cd = s_c[b];
+        const unsigned rowlen = (unsigned)sh.P[2] * (unsigned)sh.C, row = j / rowlen, col = j - row * rowlen;
+        const unsigned u0 = row / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = row % (unsigned)sh.P[1] - (unsigned)cd.lo[1];
+        const unsigned lo = (unsigned)cd.lo[2] * (unsigned)sh.C, hi = lo + (unsigned)cd.n[2] * (unsigned)sh.C;
+        const bool row_in = u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1];
+        if (row_in && col >= lo && col + 4 <= hi) {  // four consecutive floats of the source: at the alignment that address has
+            const float* p = cd.img + (((size_t)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + cd.src[2]) * sh.C + (col - lo);
+            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+            if ((a & 15) == 0) {
+                const float4 f = *reinterpret_cast<const float4*>(p);
+                o[0] = f.x, o[1] = f.y, o[2] = f.z, o[3] = f.w;
+            } else if ((a & 7) == 0) {
+                const float2 f = *reinterpret_cast<const float2*>(p), g = *reinterpret_cast<const float2*>(p + 2);
+                o[0] = f.x, o[1] = f.y, o[2] = g.x, o[3] = g.y;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = p[k];
+            }
+            return;
+        }
+        if (!row_in || col + 4 <= lo || col >= hi) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = fill_value(j + k, cd.s_fill);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t e = e0 + k;
+        o[k] = 0.f;
+        if (e < E) {
+            const unsigned b = (unsigned)(e / L);
+            o[k] = image_element(s_c[b], sh, (unsigned)(e - (size_t)b * L));
+        }
+    }
+}
+
+// Launch 2.  Workgroups [0, img_blocks) write 1024 quads of images each, the rest 1024 quads of labels and weights; workgroup 0 also
+// writes info.  vec_i / vec_v: the image / the label and weight outputs are 16-byte aligned.
+template <bool ROW4>
+__global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts, PatchShape sh,
+                                                           unsigned img_blocks, bool vec_i, bool vec_v, float* __restrict__ out_i,
+                                                           float* __restrict__ out_w, int32_t* __restrict__ out_l, int32_t* __restrict__ info)
+{
+    __shared__ PatchCand s_c[PS_PATCH_MAX_B];
+    const int t = threadIdx.x;
+    bool pos0 = false;
+    if (sh.mode == PS_PATCH_ONE_POSITIVE && t < sh.B - 1) pos0 = counts[cands[t * sh.T].count] > 0;
+    const bool any_earlier = __syncthreads_or(pos0) != 0;
+    if (t < sh.B) {
+        int ok;
+        const int tr = choose_try(cands, counts, sh, t, any_earlier, ok);
+        const PatchCand cd = cands[t * sh.T + tr];
+        s_c[t] = cd;
+        if (blockIdx.x == 0) {
+            int32_t* r = info + 8 * t;
+            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = 0;
+        }
+    }
+    __syncthreads();
+    const unsigned V = (unsigned)sh.P[0] * (unsigned)sh.P[1] * (unsigned)sh.P[2], L = V * (unsigned)sh.C;
+    if (blockIdx.x < img_blocks) {
+        const size_t E = (size_t)sh.B * L;
+#pragma unroll 2
+        for (int u = 0; u < 4; ++u) {
+            const size_t e0 = 4 * ((size_t)blockIdx.x * 1024 + u * 256 + t);
+            if (e0 >= E) break;
+            float o[4];
+            image_quad<ROW4>(s_c, sh, L, e0, E, o);
+            if (vec_i && e0 + 4 <= E) {
+                *reinterpret_cast<float4*>(out_i + e0) = make_float4(o[0], o[1], o[2], o[3]);
+            } else {
+                for (int k = 0; k < 4; ++k)
+                    if (e0 + k < E) out_i[e0 + k] = o[k];
+            }
+        }
+        return;
+    }
+    const size_t E = (size_t)sh.B * V;
+    for (int u = 0; u < 4; ++u) {
+        const size_t e0 = 4 * ((size_t)(blockIdx.x - img_blocks) * 1024 + u * 256 + t);
+        if (e0 >= E) break;
+        int l[4] = {0, 0, 0, 0};
+        float w[4] = {0.f, 0.f, 0.f, 0.f};
+        bool done = false;
+        if ((sh.P[2] & 3) == 0) {  // the four voxels share a row of one slot: one word each where the box holds them all and the bytes are aligned
+            const unsigned b = (unsigned)(e0 / V), v = (unsigned)(e0 - (size_t)b * V);
+            const PatchCand& cd = s_c[b];
+            const long long s0 = voxel_source(cd, sh, v), s3 = voxel_source(cd, sh, v + 3);
+            if (s0 >= 0 && s3 >= 0 && ((reinterpret_cast<uintptr_t>(cd.lab + s0) | reinterpret_cast<uintptr_t>(cd.wgt + s0)) & 3) == 0) {
+                const unsigned x = *reinterpret_cast<const unsigned*>(cd.lab + s0), y = *reinterpret_cast<const unsigned*>(cd.wgt + s0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    l[k] = (int)((x >> (8 * k)) & 255u);
+                    w[k] = (float)((y >> (8 * k)) & 255u);
+                }
+                done = true;
+            }
+        }
+        if (!done) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const size_t e = e0 + k;
+                if (e >= E) break;
+                const unsigned b = (unsigned)(e / V);
+                const PatchCand& cd = s_c[b];
+                const long long s = voxel_source(cd, sh, (unsigned)(e - (size_t)b * V));
+                if (s >= 0) {
+                    l[k] = cd.lab[s];
+                    w[k] = (float)cd.wgt[s];
+                }
+            }
+        }
+        if (vec_v && e0 + 4 <= E) {
+            *reinterpret_cast<int4*>(out_l + e0) = make_int4(l[0], l[1], l[2], l[3]);
+            *reinterpret_cast<float4*>(out_w + e0) = make_float4(w[0], w[1], w[2], w[3]);
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < E) {
+                    out_l[e0 + k] = l[k];
+                    out_w[e0 + k] = w[k];
+                }
+        }
+    }
+}
+
+inline int volume_shape_ok(const char* who, int32_t C, int64_t D, int64_t H, int64_t W)
+{
+    PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
+    PS_CHECK(D >= 1 && H >= 1 && W >= 1 && D < (1ll << 31) && H < (1ll << 31) && W < (1ll << 31) && D * H < (1ll << 31) && D * H * W < (1ll << 31),
+             "%s: the volume is [%lld, %lld, %lld] (every extent >= 1, D * H * W < 2^31)", who, (long long)D, (long long)H, (long long)W);
+    return PS_OK;
+}
+
+}  // namespace
+
+}  // namespace ps
+
+using namespace ps;
+
+extern "C" int ps_saliency_brats_measure(ps_context* c, const float* raw, int32_t C, int64_t D, int64_t H, int64_t W, int32_t margin, int64_t* box,
+                                         double* stats)
+{
+    const char* who = "ps_saliency_brats_measure";
+    PS_TRY(volume_shape_ok(who, C, D, H, W));
+    PS_CHECK(margin >= 0, "%s: margin = %d is negative", who, (int)margin);
+    PS_CHECK(raw && box && stats, "%s: NULL raw, box or stats", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t nvox = (size_t)D * H * W;
+    const int slabs = ceil_div((int64_t)nvox, kCropSlab);
+    Arena& A = c->sample_arena;
+    double *part = nullptr, *res = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        A.begin(pass == 0);
+        part = A.take<double>((size_t)slabs * C * 2);
+        res = A.take<double>(3 * (size_t)C + 3);  // [tot: C x (sum, count)][dev2: C][the raw min / max: 6 int]
+        if (pass == 0) PS_TRY(A.buf.reserve(A.off));
+    }
+    double *tot = res, *dev2 = res + 2 * C;
+    int* mm = reinterpret_cast<int*>(res + 3 * C);
+    const int mm0[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
+    std::vector<char> h((3 * (size_t)C + 3) * sizeof(double));
+    {
+        Stage stg(c, "saliency_prepare", 5);
+        PS_TRY(c->upload_async(mm, mm0, sizeof mm0));
+        hipLaunchKernelGGL(brats_box_kernel, dim3((unsigned)std::min<size_t>(blocks256(nvox), 2048)), dim3(256), 0, st, raw, (unsigned)nvox, (int)H, (int)W, mm);
+        const dim3 grid((unsigned)slabs, (unsigned)C);
+        hipLaunchKernelGGL(brats_stats_kernel<false>, grid, dim3(256), 0, st, raw, nvox, (int)D, (int)H, (int)W, (int)margin, mm, tot, part);
+        hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(2 * C, 16)), dim3(256), 0, st, part, slabs, 2 * C, tot);
+        hipLaunchKernelGGL(brats_stats_kernel<true>, grid, dim3(256), 0, st, raw, nvox, (int)D, (int)H, (int)W, (int)margin, mm, tot, part);
+        hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(C, 16)), dim3(256), 0, st, part, slabs, (int)C, dev2);
+        PS_HIP(hipGetLastError());
+        PS_HIP(hipMemcpyAsync(h.data(), res, h.size(), hipMemcpyDeviceToHost, st));
+        PS_HIP(hipStreamSynchronize(st));
+    }
+    const double* ht = reinterpret_cast<const double*>(h.data());
+    const int* hm = reinterpret_cast<const int*>(ht + 3 * C);
+    PS_CHECK(hm[3] >= hm[0], "%s: raw[0] is all zero, there is no region to crop", who);
+    const int64_t dims[3] = {D, H, W};
+    int64_t b[6];
+    for (int a = 0; a < 3; ++a) {
+        b[a] = std::max<int64_t>(hm[a] - margin, 0);
+        b[3 + a] = std::min<int64_t>((int64_t)hm[3 + a] + margin, dims[a] - 1);
+    }
+    std::vector<double> s(2 * (size_t)C);
+    for (int m = 0; m < C; ++m) {
+        const double n = ht[2 * m + 1];
+        PS_CHECK(n > 0.0, "%s: modality %d has no voxel above zero inside the box (mean / std undefined)", who, m);
+        s[2 * m] = ht[2 * m] / n;
+        s[2 * m + 1] = std::sqrt(ht[2 * C + m] / n);
+        PS_CHECK(s[2 * m + 1] > 0.0 && std::isfinite(s[2 * m + 1]) && std::isfinite(s[2 * m]),
+                 "%s: modality %d has mean %g and std %g over its voxels above zero: it cannot be normalised", who, m, s[2 * m], s[2 * m + 1]);
+    }
+    std::copy(b, b + 6, box);
+    std::copy(s.begin(), s.end(), stats);
+    return PS_OK;
+}
+
+extern "C" int ps_saliency_brats_apply(ps_context* c, const float* raw, const int32_t* seg, int32_t C, int64_t D, int64_t H, int64_t W, int32_t num_class,
+                                       const int64_t* box, const double* stats, float* image, uint8_t* label, uint8_t* weight)
+{
+    const char* who = "ps_saliency_brats_apply";
+    PS_TRY(volume_shape_ok(who, C, D, H, W));
+    PS_CHECK(num_class >= 2, "%s: num_class = %d, must be at least 2", who, (int)num_class);
+    PS_CHECK(raw && box && stats && image && label && weight, "%s: NULL raw, box, stats, image, label or weight", who);
+    const int64_t dims[3] = {D, H, W};
+    ApplyArgs a;
+    for (int k = 0; k < 3; ++k) {
+        PS_CHECK(box[k] >= 0 && box[3 + k] >= box[k] && box[3 + k] < dims[k], "%s: box axis %d is [%lld, %lld] in a volume of %lld", who, k,
+                 (long long)box[k], (long long)box[3 + k], (long long)dims[k]);
+        a.box.lo[k] = (int)box[k];
+        a.box.ext[k] = (int)(box[3 + k] - box[k] + 1);
+    }
+    for (int m = 0; m < C; ++m) {
+        PS_CHECK(std::isfinite(stats[2 * m]) && std::isfinite(stats[2 * m + 1]) && stats[2 * m + 1] > 0.0, "%s: stats of modality %d are mean %g, std %g", who,
+                 m, stats[2 * m], stats[2 * m + 1]);
+        a.mean[m] = stats[2 * m];
+        a.sd[m] = stats[2 * m + 1];
+    }
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_HIP(hipSetDevice(c->device));
+    const unsigned ncrop = (unsigned)((size_t)a.box.ext[0] * a.box.ext[1] * a.box.ext[2]);
+    Stage stg(c, "saliency_prepare", 1);
+    hipLaunchKernelGGL(brats_apply_kernel, dim3(blocks256(ncrop)), dim3(256), 0, c->stream, raw, seg, (size_t)D * H * W, (int)H, (int)W, (int)C, (int)num_class,
+                       a, ncrop, image, label, weight);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+extern "C" int ps_saliency_pancreas_prepare(ps_context* c, const void* ct, int32_t dtype, int64_t n, const uint8_t* label, float* image, uint8_t* out_label,
+                                            uint8_t* weight)
+{
+    const char* who = "ps_saliency_pancreas_prepare";
+    PS_CHECK(dtype == PS_VOLUME_I16 || dtype == PS_VOLUME_F32, "%s: dtype = %d, must be PS_VOLUME_I16 or PS_VOLUME_F32", who, (int)dtype);
+    PS_CHECK(n >= 1 && n < (1ll << 31), "%s: n = %lld voxels, must be in [1, 2^31)", who, (long long)n);
+    PS_CHECK(ct && image && out_label && weight, "%s: NULL ct, image, out_label or weight", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_HIP(hipSetDevice(c->device));
+    const dim3 grid((unsigned)std::min<size_t>(blocks256((size_t)n), 4096));
+    Stage stg(c, "saliency_prepare", 1);
+    if (dtype == PS_VOLUME_I16)
+        hipLaunchKernelGGL(pancreas_prepare_kernel<int16_t>, grid, dim3(256), 0, c->stream, static_cast<const int16_t*>(ct), (size_t)n, label, image, out_label,
+                           weight);
+    else
+        hipLaunchKernelGGL(pancreas_prepare_kernel<float>, grid, dim3(256), 0, c->stream, static_cast<const float*>(ct), (size_t)n, label, image, out_label, weight);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                               int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode,
+                               float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+{
+    const char* who = "ps_patch_sample";
+    // every argument error is found here, before anything is enqueued
+    PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
+    PS_CHECK(B >= 1 && B <= PS_PATCH_MAX_B, "%s: B = %d, must be in [1, %d]", who, (int)B, PS_PATCH_MAX_B);
+    PS_CHECK(T >= 1 && T <= PS_PATCH_MAX_T, "%s: T = %d, must be in [1, %d]", who, (int)T, PS_PATCH_MAX_T);
+    PS_CHECK(mode == PS_PATCH_RANDOM || mode == PS_PATCH_ALL_POSITIVE || mode == PS_PATCH_ONE_POSITIVE, "%s: mode = %d is none of the three", who, (int)mode);
+    PS_CHECK(n >= 1 && n < (1ll << 31), "%s: n = %lld volumes", who, (long long)n);
+    PS_CHECK(images && labels && weights && dims && cand && P, "%s: NULL images, labels, weights, dims, cand or P table", who);
+    PS_CHECK(out_images && out_weights && out_labels && out_info, "%s: NULL out_images, out_weights, out_labels or out_info", who);
+    PS_CHECK(P[0] >= 1 && P[1] >= 1 && P[2] >= 1 && P[0] < (1ll << 31) && P[1] < (1ll << 31) && P[2] < (1ll << 31) && P[0] * P[1] < (1ll << 31)
+                 && P[0] * P[1] * P[2] < (1ll << 31) && P[0] * P[1] * P[2] * C < (1ll << 31),
+             "%s: P = [%lld, %lld, %lld] (every extent >= 1, P0 * P1 * P2 * C < 2^31)", who, (long long)P[0], (long long)P[1], (long long)P[2]);
+    for (int64_t v = 0; v < n; ++v) {
+        PS_CHECK(images[v] && labels[v] && weights[v], "%s: volume %lld has a NULL image, label or weight pointer", who, (long long)v);
+        const int64_t* d = dims + 3 * v;
+        PS_CHECK(d[0] >= 1 && d[1] >= 1 && d[2] >= 1 && d[0] < (1ll << 31) && d[1] < (1ll << 31) && d[2] < (1ll << 31) && d[0] * d[1] < (1ll << 31)
+                     && d[0] * d[1] * d[2] < (1ll << 31) && d[0] * d[1] * d[2] * C < (1ll << 31),
+                 "%s: dims of volume %lld are [%lld, %lld, %lld] (every dim >= 1, d * h * w * C < 2^31)", who, (long long)v, (long long)d[0], (long long)d[1],
+                 (long long)d[2]);
+    }
+    for (int i = 0; i < B * T; ++i)
+        PS_CHECK(cand[i] >= 0 && cand[i] < n, "%s: cand[%d, %d] = %d is not a volume of the bank (%lld volumes)", who, i / T, i % T, (int)cand[i], (long long)n);
+    PS_CHECK(c, "%s: NULL context", who);
+
+    // the table: every candidate's window; the windows the mode can ask for get a count
+    const int nc = B * T;
+    std::vector<int> win;
+    const size_t table_bytes = pad256(sizeof(PatchCand) * nc);
+    std::vector<char> host(table_bytes + pad256(sizeof(int) * nc) + pad256(sizeof(unsigned) * nc), 0);
+    PatchCand* hc = reinterpret_cast<PatchCand*>(host.data());
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t) {
+            PatchCand& cd = hc[b * T + t];
+            const int v = cand[b * T + t];
+            const unsigned s = hash32(seed + kSeedMul * (unsigned)(b * T + t + 1));
+            cd.img = images[v], cd.lab = labels[v], cd.wgt = weights[v];
+            for (int a = 0; a < 3; ++a) {
+                const int in = (int)dims[3 * v + a], out = (int)P[a];
+                const int x0 = out / 2, x1 = in - x0;
+                int ctr;
+                if (x1 <= x0) ctr = (x0 + x1) / 2;
+                else ctr = x0 + (int)(((unsigned long long)hash32(s + kAxisMul * (unsigned)(a + 1)) * (unsigned long long)(x1 - x0 + 1)) >> 32);
+                const int r0 = std::min(out / 2, ctr), r1 = std::min(out - out / 2, in - ctr);
+                cd.dim[a] = in, cd.c[a] = ctr, cd.src[a] = ctr - r0, cd.lo[a] = out / 2 - r0, cd.n[a] = r0 + r1;
+            }
+            cd.s_fill = hash32(s + kAxisMul * 4u);
+            cd.vol = v;
+            cd.pad = 0;
+            const bool counted = t == 0 || mode == PS_PATCH_ALL_POSITIVE || (mode == PS_PATCH_ONE_POSITIVE && b == B - 1);
+            cd.count = counted ? (int)win.size() : -1;
+            if (counted) win.push_back(b * T + t);
+        }
+    std::copy(win.begin(), win.end(), reinterpret_cast<int*>(host.data() + table_bytes));  // (the counts behind them stay zero)
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    Arena& A = c->sample_arena;
+    char* d_tab = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        A.begin(pass == 0);
+        d_tab = A.take<char>(host.size());
+        if (pass == 0) PS_TRY(A.buf.reserve(A.off));
+    }
+    const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
+    const int* d_win = reinterpret_cast<const int*>(d_tab + table_bytes);
+    unsigned* d_counts = reinterpret_cast<unsigned*>(d_tab + table_bytes + pad256(sizeof(int) * nc));
+    PatchShape sh;
+    sh.P[0] = (int)P[0], sh.P[1] = (int)P[1], sh.P[2] = (int)P[2], sh.C = C, sh.B = B, sh.T = T, sh.mode = mode;
+    const size_t V = (size_t)P[0] * P[1] * P[2];
+    const unsigned kdw = (unsigned)((P[2] + 6) / 4);  // a row of P2 bytes starting at byte 3 of a word touches this many
+    const unsigned count_blocks = (unsigned)(((size_t)P[0] * P[1] * kdw + 2047) / 2048);
+    const unsigned img_blocks = (unsigned)(((size_t)B * V * C + 4095) / 4096), vox_blocks = (unsigned)(((size_t)B * V + 4095) / 4096);
+    const bool vec_i = (reinterpret_cast<uintptr_t>(out_images) & 15) == 0;
+    const bool vec_v = ((reinterpret_cast<uintptr_t>(out_weights) | reinterpret_cast<uintptr_t>(out_labels)) & 15) == 0;
+    Stage stg(c, "patch_sample", 2);
+    PS_TRY(c->upload_async(d_tab, host.data(), host.size()));
+    hipLaunchKernelGGL(patch_count_kernel, dim3(count_blocks, (unsigned)win.size()), dim3(256), 0, st, d_c, d_win, d_counts, kdw);
+    if ((P[2] * C) % 4 == 0)
+        hipLaunchKernelGGL(patch_gather_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images,
+                           out_weights, out_labels, out_info);
+    else
+        hipLaunchKernelGGL(patch_gather_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images,
+                           out_weights, out_labels, out_info);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
