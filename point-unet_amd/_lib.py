@@ -3,7 +3,8 @@
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
 (PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES), include/pointseg_saliency.h
 (SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
-(SALIENCY_ATTENTION_PROTOTYPES) and include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES) and include/pointseg_saliency_step.h
+(SALIENCY_STEP_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -328,6 +329,21 @@ SALIENCY_DATA_PROTOTYPES = {
                                        ctypes.c_int32, ctypes.c_int32, c_i64p, ctypes.c_uint32, ctypes.c_int32] + [c_vp] * 4),
 }
 
+
+
+class PsSaliencyStepOptions(ctypes.Structure):
+    _fields_ = [("allreduce", PS_ALLREDUCE_FN), ("user", c_vp), ("world_size", ctypes.c_int32), ("momentum", ctypes.c_float), ("l2", ctypes.c_float)]
+
+
+# every symbol include/pointseg_saliency_step.h declares (the saliency network's training step behind one call; csrc/saliency_step.hip)
+_PATCH_SHAPE = [ctypes.c_int64] * 6  # B D H W C_in num_classes
+SALIENCY_STEP_PROTOTYPES = {
+    "ps_saliency_backward": (ctypes.c_int, [c_vp] * 4 + _PATCH_SHAPE + [c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_i64p]),
+    "ps_saliency_sgd_update": (ctypes.c_int, [c_vp] * 4 + [ctypes.c_int64] * 3 + [ctypes.c_float] * 4),
+    "ps_saliency_train_step": (ctypes.c_int, [c_vp] * 4 + _PATCH_SHAPE + [c_vp, ctypes.c_int64, c_vp, c_vp, ctypes.c_float,
+                                                                         ctypes.POINTER(PsSaliencyStepOptions), c_vp, c_vp, c_vp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -349,7 +365,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
                                   + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())
-                                  + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())):
+                                  + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
+                                  + list(SALIENCY_STEP_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,7 +1,8 @@
 """The saliency attention map in front of prepare.pancreas_mask: the reference's SaliencyAttention network (`unet3d_attention`,
 SaliencyAttention/model.py:176-314 with attention.py:79-174) run patch by patch over a volume (`overlapping_inference`,
 SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  SaliencyNet runs it for inference behind one call; the gradients of its
-ops (include/pointseg_saliency_train.h, include/pointseg_saliency_attention.h) stand behind it, op by op, and TrainableSaliencyNet composes the graph from them.
+ops (include/pointseg_saliency_train.h, include/pointseg_saliency_attention.h) stand behind it, op by op, and TrainableSaliencyNet composes the graph from them;
+SaliencyTrainer runs the whole training step behind one call (include/pointseg_saliency_step.h, csrc/saliency_step.hip).
 
 Parameters are a dict of TensorFlow-named arrays in TensorFlow layout under the `unet3d_attention/` scope: `<layer>/kernel`
 [kd, kh, kw, in, out] (dense layers: [in, out]), `<layer>/bias`, `<layer>/ins_norm/gamma`, `<layer>/ins_norm/beta`, with <layer> the
@@ -694,3 +695,122 @@ def reference_optimizer(net, lr=0.01):
     decay = [p for n, p in named if n.endswith("/kernel")]
     rest = [p for n, p in named if not n.endswith("/kernel")]
     return torch.optim.SGD([{"params": decay, "weight_decay": 1e-5}, {"params": rest, "weight_decay": 0.0}], lr=lr, momentum=0.9)
+
+
+# ---- the training step behind one call (include/pointseg_saliency_step.h, csrc/saliency_step.hip) ----------------------------------------------------
+
+class SaliencyTrainer:
+    """unet3d_attention trained without torch.autograd: the flat parameters `flat`, this rank's gradients `grad`, the momentum `accum` and
+    the cached scratch are device tensors, and one call of ps_saliency_train_step is a step of train.py:83-110 (forward, softmax + Dice, the
+    whole backward, the optional gradient all-reduce, the momentum update with the regulariser).  params: the TF-named dict."""
+
+    def __init__(self, params, in_channels, num_classes=2, device=0, momentum=0.9, l2=1e-5):
+        self.in_channels, self.num_classes = int(in_channels), int(num_classes)
+        self.momentum, self.l2 = float(momentum), float(l2)
+        flat = flatten_params(params, self.in_channels, self.num_classes)
+        want = _lib.lib().ps_saliency_weight_count(self.in_channels, self.num_classes)
+        if want != flat.size:
+            raise _lib.PointSegError("SaliencyTrainer: the library's network has %d weights, this package's layer table %d" % (want, flat.size))
+        self.device = torch.device("cuda", device)
+        self.flat = torch.from_numpy(flat).to(self.device)
+        self.grad = torch.zeros_like(self.flat)
+        self.accum = torch.zeros_like(self.flat)
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.scratch = None
+        self.scratch_bytes = 0
+        self._coll = None
+
+    def _args(self, x, labels, weight):
+        who = "SaliencyTrainer"
+        x = _f32(x, who, "x", 5)
+        if x.shape[4] != self.in_channels or any(n % 16 or n < 16 for n in x.shape[1:4]):
+            raise ValueError("SaliencyTrainer: x must be [B, D, H, W, %d] with extents that are multiples of 16, got %s" % (self.in_channels, tuple(x.shape)))
+        logits = torch.empty(tuple(x.shape[:4]) + (self.num_classes,), dtype=torch.float32, device=x.device)
+        _, labels, weight, _, _, _ = _loss_args(who, logits, labels, weight)
+        return x, labels, weight, logits
+
+    def _call(self, fn, x, head, tail):
+        """fn(ctx, *head, B, D, H, W, C_in, num_classes, *tail, scratch, &bytes) under the two-call protocol, on this trainer's own scratch."""
+        ctx = _ctx_for(x)
+        shape = tuple(x.shape[:4]) + (self.in_channels, self.num_classes)
+        need = ctypes.c_int64(0)
+        _lib.check(fn(None, *head, *shape, *tail, None, ctypes.byref(need)))
+        if self.scratch is None or self.scratch.numel() < need.value:
+            self.scratch = torch.empty(max(need.value, 1), dtype=torch.uint8, device=x.device)
+        self.scratch_bytes = need.value
+        _lib.check(fn(ctx.handle, *head, *shape, *tail, runtime.ptr(self.scratch), ctypes.byref(need)))
+
+    def backward(self, x, labels, weight=None, want_logits=False):
+        """The loss (0-dim, on the device; overwritten by the next call) of a patch x [B, D, H, W, C_in] with labels [B, D, H, W] int32 and
+        weight [B, D, H, W] or None, its gradients left in `grad`; no parameter changes.  want_logits: (loss, logits)."""
+        x, labels, weight, logits = self._args(x, labels, weight)
+        p = runtime.ptr
+        self._call(_lib.lib().ps_saliency_backward, x, (p(x), p(labels), p(weight)),
+                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.loss), p(logits) if want_logits else None))
+        return (self.loss, logits) if want_logits else self.loss
+
+    def _collective(self, dist):
+        """torch.distributed's all-reduce as the C callback, exactly as train.Trainer._collective wraps it: the raw device pointer, on the
+        context's stream (= torch's current stream), becomes a tensor without a copy through __cuda_array_interface__."""
+        if self._coll is not None and self._coll[1] is dist:
+            return self._coll[0]
+        device = self.device
+
+        class _Raw:
+            def __init__(self, ptr, count, f64):
+                self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<f8" if f64 else "<f4", "data": (int(ptr), False), "version": 2}
+
+        def cb(user, buf, count, dtype, stream):
+            try:
+                t = torch.as_tensor(_Raw(buf, count, dtype == 1), device=device)
+                dist.all_reduce(t)
+                return 0
+            except Exception as e:  # never let an exception cross the C boundary
+                import sys
+                print("all-reduce callback failed: %r" % (e,), file=sys.stderr)
+                return 1
+
+        fn = _lib.PS_ALLREDUCE_FN(cb)
+        self._coll = (fn, dist)
+        return fn
+
+    def step(self, x, labels, weight, lr, dist=None, allreduce=None, world_size=None):
+        """One training step at learning rate lr; returns the loss before it.  dist: a torch.distributed-like module (all_reduce,
+        get_world_size) whose sum the gradients go through when the world has more than one rank.  allreduce / world_size: a ready
+        PS_ALLREDUCE_FN and its world instead (a host that brings its own collective)."""
+        x, labels, weight, _ = self._args(x, labels, weight)
+        if dist is not None:
+            allreduce, world_size = self._collective(dist), dist.get_world_size()
+        opt = _lib.PsSaliencyStepOptions(allreduce if allreduce is not None else _lib.PS_ALLREDUCE_FN(), None, int(world_size or 1), self.momentum, self.l2)
+        p = runtime.ptr
+        self._call(_lib.lib().ps_saliency_train_step, x, (p(x), p(labels), p(weight)),
+                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.accum), float(lr), ctypes.byref(opt), p(self.loss), None))
+        return self.loss
+
+    def update(self, lr, grad_scale=1.0):
+        """ps_saliency_sgd_update on flat / grad / accum."""
+        p = runtime.ptr
+        ctx = runtime.default_context(self.device.index)
+        ctx.use_torch_stream()
+        _lib.check(_lib.lib().ps_saliency_sgd_update(ctx.handle, p(self.flat), p(self.grad), p(self.accum), self.in_channels, self.num_classes, self.flat.numel(),
+                                                     float(lr), self.momentum, self.l2, float(grad_scale)))
+
+    def _named(self, flat):
+        out, off = {}, 0
+        for name, shape in param_shapes(self.in_channels, self.num_classes).items():
+            n = int(np.prod(shape))
+            out[name] = flat[off:off + n].view(shape)
+            off += n
+        return out
+
+    def named_gradients(self):
+        """name -> a view of `grad`, by TensorFlow name."""
+        return self._named(self.grad)
+
+    def named_parameters(self):
+        """name -> a view of `flat`, by TensorFlow name."""
+        return self._named(self.flat)
+
+    def export(self):
+        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes."""
+        return unflatten_params(self.flat.cpu().numpy(), self.in_channels, self.num_classes)

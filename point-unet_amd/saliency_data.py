@@ -5,7 +5,8 @@ batches of patches drawn there by a stated rule with no host read.  PatchBank is
 point network's Trainer; train_saliency is the loop of train.py:83-110 over it, evaluate_saliency the Dice of EvalCallback / eval_pancreas.
 
 Not built: mixup (config.MIXUP; its one-hot labels need dice_mixup), a DIRECTION other than axial (permute before add_*), the left-right
-flip (off in the reference), the training step behind one call, data-parallel training."""
+flip (off in the reference).  The training step behind one call is saliency.SaliencyTrainer (train_saliency's engine="native");
+data-parallel training: hook built, checked with an in-process callback; no multi-process run made."""
 import ctypes
 
 import numpy as np
@@ -231,23 +232,34 @@ class PatchBank:
             yield self.sample(cand, patch, s, mode)
 
 
-def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None):
-    """The loop of train.py:83-110 on the device: `steps` steps of TrainableSaliencyNet.loss on the bank's batches (epoch_batches from
-    `epoch` on, config.DATA_SAMPLING = 'one_positive') under saliency.reference_optimizer(net, lr) (or `optimizer`).  Returns the per-step
-    losses as one device tensor [steps]; nothing is read back on the way."""
+def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None):
+    """The loop of train.py:83-110 on the device: `steps` steps on the bank's batches (epoch_batches from `epoch` on,
+    config.DATA_SAMPLING = 'one_positive').  engine "autograd": TrainableSaliencyNet.loss under saliency.reference_optimizer(net, lr) (or
+    `optimizer`); engine "native": net is a saliency.SaliencyTrainer and every step is one ps_saliency_train_step at learning rate lr
+    (dist: the torch.distributed-like module its gradients are summed through).  Returns the per-step losses as one device tensor
+    [steps]; nothing is read back on the way."""
     from . import saliency
-    if not isinstance(net, saliency.TrainableSaliencyNet):
+    if engine not in ("autograd", "native"):
+        raise ValueError("train_saliency: engine must be 'autograd' or 'native'")
+    native = engine == "native"
+    if native and (not isinstance(net, saliency.SaliencyTrainer) or optimizer is not None):
+        raise ValueError("train_saliency: the native engine takes a SaliencyTrainer and no optimizer")
+    if not native and not isinstance(net, saliency.TrainableSaliencyNet):
         raise ValueError("train_saliency: net must be a TrainableSaliencyNet")
     if int(steps) < 1 or len(bank) < int(batch_size):
         raise ValueError("train_saliency: need steps >= 1 and at least batch_size volumes in the bank")
-    opt = optimizer if optimizer is not None else saliency.reference_optimizer(net, lr)
+    if not native:
+        opt = optimizer if optimizer is not None else saliency.reference_optimizer(net, lr)
     losses = []
     while len(losses) < steps:
         for batch in bank.epoch_batches(batch_size, patch, epoch, seed):
-            opt.zero_grad(set_to_none=True)
-            loss = net.loss(batch["images"], batch["labels"], batch["weights"])
-            loss.backward()
-            opt.step()
+            if native:
+                loss = net.step(batch["images"], batch["labels"], batch["weights"], lr, dist).clone()
+            else:
+                opt.zero_grad(set_to_none=True)
+                loss = net.loss(batch["images"], batch["labels"], batch["weights"])
+                loss.backward()
+                opt.step()
             losses.append(loss.detach())
             if len(losses) == steps:
                 break

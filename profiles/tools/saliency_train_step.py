@@ -9,10 +9,16 @@ composition, over 50 calls after 5, best of 2): the comparison, not the code und
 Stage `step`: forward + backward + reference_optimizer step, the mean of 5 steps after 1 warm-up step; peak device memory; and the share of
 the step's device time spent inside the six new entry points (device events around the wrappers' calls).
 
+Stages `opbyop` and `onecall`: the same step at the same batch two ways in one session -- TrainableSaliencyNet under torch.autograd and
+reference_optimizer as it stands, and SaliencyTrainer.step (ps_saliency_train_step, include/pointseg_saliency_step.h) -- each the mean
+step over `--steps` steps between device events, 1 warm-up step, 3 windows; peak device memory (torch's allocator; for `onecall` also the
+step's scratch); and, from one more step under the context's stage timing, the launches and device time per entry point.  The yardstick
+of `onecall` is `opbyop` of the same session, never itself.
+
 Each stage runs in a child process under a time limit of its own; after a stage that fails or runs out of time nothing more starts.
 
 usage (GPU box):
-    python profiles/tools/saliency_train_step.py --out DIR [--stages ops,step] [--timeout 300]        # -> DIR/saliency_train_step.json"""
+    python profiles/tools/saliency_train_step.py --out DIR [--stages ops,step,opbyop,onecall] [--timeout 300]        # -> DIR/saliency_train_step.json"""
 import argparse
 import json
 import os
@@ -149,6 +155,87 @@ def stage_step(args):
             "losses_first_and_last": losses}
 
 
+def _step_inputs(torch):
+    g = torch.Generator().manual_seed(2)
+    shape = (2,) + PATCH
+    x = torch.randn(shape + (1,), generator=g).cuda()
+    labels = torch.randint(0, 2, shape, generator=g, dtype=torch.int32).cuda()
+    weight = torch.rand(shape, generator=g).cuda() + 0.2
+    return shape, x, labels, weight
+
+
+def _windows(torch, step, steps, windows=3):
+    """(the mean step of each window in ms, the first and the last loss): 1 warm-up step, then `windows` windows of `steps` steps."""
+    losses = [float(step())]  # warm-up: scratch buffers and torch's allocator grow here
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(windows):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(steps):
+            last = step()
+        e.record()
+        e.synchronize()
+        out.append(round(s.elapsed_time(e) / steps, 2))
+    losses.append(float(last))
+    return out, losses
+
+
+def _stage_rows(torch, step):
+    """One more step under the context's stage timing: entry point -> (launches, device ms), and the totals."""
+    from point_unet_amd import runtime
+    ctx = runtime.default_context(0)
+    ctx.use_torch_stream()
+    ctx.timing_begin()
+    step()
+    torch.cuda.synchronize()
+    rows = {}
+    for name, ms, launches in ctx.timing_end():
+        r = rows.setdefault(name, [0, 0.0])
+        r[0], r[1] = r[0] + launches, r[1] + ms
+    return {"entries": {k: [v[0], round(v[1], 3)] for k, v in rows.items()}, "launches": sum(v[0] for v in rows.values()),
+            "device_ms": round(sum(v[1] for v in rows.values()), 2)}
+
+
+def _step_result(torch, shape, args, windows, losses, rows):
+    return {"batch": shape, "steps_per_window": args.steps, "windows_ms": windows, "step_ms": min(windows),
+            "spread": round((max(windows) - min(windows)) / min(windows), 4), "peak_device_memory_gb": round(torch.cuda.max_memory_allocated() / 1e9, 2),
+            "losses_first_and_last": losses, "stage_timing": rows}
+
+
+def stage_opbyop(args):
+    import torch
+    from point_unet_amd import saliency as sal
+    shape, x, labels, weight = _step_inputs(torch)
+    net = sal.TrainableSaliencyNet(sal.init_params(1, 2, seed=0), 1, 2)
+    opt = sal.reference_optimizer(net)
+
+    def step():
+        opt.zero_grad()
+        loss = net.loss(x, labels, weight)
+        loss.backward()
+        opt.step()
+        return loss.detach()
+
+    windows, losses = _windows(torch, step, args.steps)
+    res = _step_result(torch, shape, args, windows, losses, None)  # (the peak before the stage-timing step)
+    res["stage_timing"] = _stage_rows(torch, step)  # (torch's own kernels -- cat, add, the optimiser -- are not entries and not counted)
+    return res
+
+
+def stage_onecall(args):
+    import torch
+    from point_unet_amd import saliency as sal
+    shape, x, labels, weight = _step_inputs(torch)
+    tr = sal.SaliencyTrainer(sal.init_params(1, 2, seed=0), 1, 2)
+    step = lambda: tr.step(x, labels, weight, 0.01).clone()
+    windows, losses = _windows(torch, step, args.steps)
+    res = _step_result(torch, shape, args, windows, losses, None)
+    res["scratch_gb"] = round(tr.scratch_bytes / 1e9, 2)
+    res["stage_timing"] = _stage_rows(torch, step)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -158,7 +245,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        print("RESULT " + json.dumps({"ops": stage_ops, "step": stage_step}[args.child](args)))
+        print("RESULT " + json.dumps({"ops": stage_ops, "step": stage_step, "opbyop": stage_opbyop, "onecall": stage_onecall}[args.child](args)))
         return 0
     res = {"patch": PATCH}
     for stage in args.stages.split(","):
@@ -173,6 +260,10 @@ def main():
             print("stage %s ended with status %d: nothing more is started" % (stage, done.returncode))
             return 1
         res[stage] = json.loads(lines[-1][7:])
+    if "opbyop" in res and "onecall" in res:
+        a, b = res["opbyop"], res["onecall"]
+        res["onecall_vs_opbyop"] = {"step_ms_ratio": round(b["step_ms"] / a["step_ms"], 4), "spread_of_the_session": max(a["spread"], b["spread"]),
+                                    "memory_gb": [b["peak_device_memory_gb"], a["peak_device_memory_gb"]]}
     line = json.dumps(res)
     print(line)
     if args.out:
