@@ -19,6 +19,29 @@ int ps_debug_kdtree_host(const float* support, int64_t n, int32_t* vind, int32_t
  * unspecified: compare by walking from the root. */
 int ps_debug_kdtree_device(ps_context* ctx, const float* support, int64_t n, int32_t* vind, int32_t* nodes,
                            float* pts, int32_t* root_depth, float* bbox);
+/* T trees built as ONE set, the way the product builds them (one TreeSetPlan, one build_trees); needs a GPU.  support: the trees' rows one
+ * after the other, f32 [sum n, 3]; n: i32 [T], every n[i] >= 1.  Every output is the tree-by-tree concatenation of what
+ * ps_debug_kdtree_device returns for one tree: vind i32 [sum n], nodes i32 [2 sum n, 4], pts f32 [sum n, 4], root_depth i32 [T, 2],
+ * bbox f32 [T, 6]; and with them fat i32 [6 sum n, 4], the three-record image the searches read (TreeView::fat: records 3 id .. 3 id + 2 =
+ * node id, its first child, its second child, a leaf child as zeros; only odd ids are written), and copy f32 [sum of n[i] with
+ * want_copy[i] != 0, 3]: the rows TreeSetPlan::copy_dst received, for those trees in order (want_copy i32 [T], or NULL: none).
+ * stats i32 [PS_DEBUG_KDTREE_STATS]: the counters of the plan's head block after the build.  "Node" = a node of a finished tree, root
+ * at depth 0; its size = its points; L = stats[0]; kHuge = kMid, kChunk, kSmall, kHugeLevels = 8: csrc/kdtree_build.hip.
+ *   [0]       chunked levels launched: min(kHugeLevels, the smallest L with (max n >> L) <= kMid), ONE value for the whole set
+ *   [1 + l]   l = 0..7: HugeState::ntasks[l] = nodes of all trees at depth l with more than kHuge points, for l < L; 0 from L on (route_task
+ *             is the only writer, and every ancestor of such a node is a chunked task itself)
+ *   [9 + l]   l = 0..7: HugeState::nchunks[l] = sum of ceil(size / kChunk) over the nodes counted in [1 + l]; 0 from L on
+ *   [17]      BuildQueues::level_cnt[L], the queue build_level_kernel starts from = nodes at depth L with more than kMid points (their
+ *             parents are chunked tasks of level L - 1; the kernel itself parks what it meets below on a stack in LDS and counts nothing)
+ *   [18]      BuildQueues::small_cnt[1], pushes to the mid queue = nodes of kSmall + 1 .. kMid points that are roots or whose parent has
+ *             more than kMid points (build_mid_kernel keeps its own children above kSmall in LDS)
+ *   [19]      BuildQueues::small_cnt[0], pushes to the small queue = nodes of at most kSmall points, leaves included, that are roots or
+ *             whose parent has more than kSmall points
+ *   [20] [21] flags[0] (written by searches only: 0 after a build), flags[1] (a builder queue overflowed); this door does not refuse on it
+ * (small_cnt[2], small_cnt[3] and flags[2] are written by no kernel that runs and are left out.) */
+#define PS_DEBUG_KDTREE_STATS 22
+int ps_debug_kdtree_device_set(ps_context* ctx, const float* support, const int32_t* n, int64_t T, const int32_t* want_copy, int32_t* vind,
+                               int32_t* nodes, float* pts, int32_t* fat, int32_t* root_depth, float* bbox, float* copy, int32_t* stats);
 /* MFMA B-fragment packing of a row-major W[cin,cout] (csrc/rowgemm.h). */
 int ps_debug_pack_weights(const float* W, int cin, int cout, int ntb, float* out);
 /* Three-plane bfloat16 image of a row-major W[cin,cout] for the split-bf16 attention kernels (csrc/attpool32b.hip: pack_b3):

@@ -375,3 +375,82 @@ extern "C" int ps_debug_kdtree_device(ps_context* c, const float* support, int64
     }
     return PS_OK;
 }
+
+// The same for a SET of trees in one plan, as ps_pyramid_build makes them (B clouds x levels), plus the fat image, the copied source
+// rows and the builder's counters (debug_hooks.h).
+extern "C" int ps_debug_kdtree_device_set(ps_context* c, const float* support, const int32_t* n, int64_t T, const int32_t* want_copy, int32_t* vind,
+                                          int32_t* nodes, float* pts, int32_t* fat, int32_t* root_depth, float* bbox, float* copy, int32_t* stats)
+{
+    PS_CHECK(c && support && n && T >= 1 && vind && nodes && pts && fat && root_depth && bbox && stats, "ps_debug_kdtree_device_set: bad argument");
+    size_t tot = 0, tot_copy = 0;
+    for (int64_t i = 0; i < T; ++i) {
+        PS_CHECK(n[i] >= 1, "ps_debug_kdtree_device_set: tree %lld has %d points", (long long)i, n[i]);
+        tot += (size_t)n[i];
+        if (want_copy && want_copy[i]) tot_copy += (size_t)n[i];
+    }
+    PS_CHECK(tot_copy == 0 || copy, "ps_debug_kdtree_device_set: want_copy without a copy buffer");
+    PS_HIP(hipSetDevice(c->device));
+    PS_TRY(c->stage_in.reserve(sizeof(float) * 3 * tot));
+    PS_HIP(hipMemcpyAsync(c->stage_in.p, support, sizeof(float) * 3 * tot, hipMemcpyHostToDevice, c->stream));
+    TreeSetPlan plan;
+    for (int64_t i = 0; i < T; ++i) plan.add(n[i]);
+    float* d_copy = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        c->knn_arena.begin(pass == 0);
+        plan.carve(c->knn_arena);
+        d_copy = c->knn_arena.take<float>(3 * tot_copy + 1);
+        if (pass == 0) PS_TRY(c->knn_arena.buf.reserve(c->knn_arena.off));
+    }
+    plan.copy_dst.assign((size_t)T, nullptr);
+    {
+        size_t off = 0, off_copy = 0;
+        for (int64_t i = 0; i < T; ++i) {
+            plan.src[i] = c->stage_in.as<float>() + 3 * off;
+            off += (size_t)n[i];
+            if (want_copy && want_copy[i]) {
+                plan.copy_dst[i] = d_copy + 3 * off_copy;
+                off_copy += (size_t)n[i];
+            }
+        }
+    }
+    PS_TRY(build_trees(c, plan));
+    BuildCounters bc;
+    PS_TRY(read_build_counters(c, plan, &bc));
+    int32_t flag[3] = {0, 0, 0};
+    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, 12, hipMemcpyDeviceToHost, c->stream));
+    std::vector<TreeMeta> meta((size_t)T);
+    PS_HIP(hipMemcpyAsync(meta.data(), plan.d_meta, sizeof(TreeMeta) * (size_t)T, hipMemcpyDeviceToHost, c->stream));
+    {
+        size_t off = 0;
+        for (int64_t i = 0; i < T; ++i) {
+            const size_t ni = (size_t)n[i];
+            PS_HIP(hipMemcpyAsync(nodes + 4 * 2 * off, plan.d_nodes[i], sizeof(int4) * 2 * ni, hipMemcpyDeviceToHost, c->stream));
+            PS_HIP(hipMemcpyAsync(fat + 4 * 6 * off, plan.d_fat[i], sizeof(int4) * 6 * ni, hipMemcpyDeviceToHost, c->stream));
+            PS_HIP(hipMemcpyAsync(pts + 4 * off, plan.d_pts[i], sizeof(float4) * ni, hipMemcpyDeviceToHost, c->stream));
+            off += ni;
+        }
+    }
+    if (tot_copy) PS_HIP(hipMemcpyAsync(copy, d_copy, sizeof(float) * 3 * tot_copy, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < tot; ++i) std::memcpy(&vind[i], &pts[4 * i + 3], 4);
+    for (int64_t i = 0; i < T; ++i) {
+        root_depth[2 * i] = meta[(size_t)i].root;
+        root_depth[2 * i + 1] = meta[(size_t)i].depth;
+        for (int a = 0; a < 3; ++a) {
+            bbox[6 * i + a] = meta[(size_t)i].lo[a];
+            bbox[6 * i + 3 + a] = meta[(size_t)i].hi[a];
+        }
+    }
+    static_assert(PS_DEBUG_KDTREE_STATS == 6 + 2 * kBuildCounterLevels, "stats layout (debug_hooks.h)");
+    stats[0] = bc.chunked_levels;
+    for (int l = 0; l < kBuildCounterLevels; ++l) {
+        stats[1 + l] = bc.ntasks[l];
+        stats[1 + kBuildCounterLevels + l] = bc.nchunks[l];
+    }
+    stats[1 + 2 * kBuildCounterLevels] = bc.straggler_tasks;
+    stats[2 + 2 * kBuildCounterLevels] = bc.mid_pushed;
+    stats[3 + 2 * kBuildCounterLevels] = bc.small_pushed;
+    stats[4 + 2 * kBuildCounterLevels] = flag[0];
+    stats[5 + 2 * kBuildCounterLevels] = flag[1];
+    return PS_OK;
+}

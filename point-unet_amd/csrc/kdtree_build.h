@@ -29,6 +29,7 @@ struct TreeSetPlan {
     void* d_scratch = nullptr;       // builder scratch (everything that needs no initial contents)
     size_t scratch_bytes = 0;
     int launches = 0;                // kernels launched by build_trees (for the stage timer)
+    int chunked_levels = 0;          // chunked levels build_trees launched (from the largest tree of the set)
     std::vector<char> host_blob;     // host image of the head block; the caller writes its job table at offset 0 BEFORE build_trees
     char* host_jobs() { return host_blob.data(); }
 
@@ -64,5 +65,15 @@ struct TreeSetPlan {
 // cases that remain (builder queue overflow, tree deeper than the traversal stack) -- even then every search writes valid
 // point indices, so whatever is enqueued behind the build never reads out of bounds.
 int build_trees(ps_context* c, TreeSetPlan& plan);
+
+// The counters a finished build leaves in the plan's head block, for the test door ps_debug_kdtree_device_set (debug_hooks.h says what each
+// one counts).  Copies them back and synchronises the stream: not for the product path.
+constexpr int kBuildCounterLevels = 8;  // >= kHugeLevels (kdtree_build.hip)
+struct BuildCounters {
+    int32_t chunked_levels;
+    int32_t ntasks[kBuildCounterLevels], nchunks[kBuildCounterLevels];
+    int32_t straggler_tasks, mid_pushed, small_pushed;
+};
+int read_build_counters(ps_context* c, const TreeSetPlan& plan, BuildCounters* out);
 
 }  // namespace ps

@@ -1724,8 +1724,10 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
 
     // chunked levels until the nodes of a balanced tree are below kMid; whatever is still above kMid after them (lopsided
     // splits) is finished by ONE straggler launch (build_level_kernel, depth first per node)
+    // (ceil(log2(max_n / kMid)): `max_n >> levels > kMid` dropped the low bits and stopped one level short at kMid * 2^L + 1 .. + 2^L - 1,
+    //  8 193 or 16 385 points, where a balanced split still leaves a node of kMid + 1 to the straggler kernel)
     int huge_levels = 0;
-    while (huge_levels < kHugeLevels && ((size_t)max_n >> huge_levels) > (size_t)kMid) ++huge_levels;
+    while (huge_levels < kHugeLevels && (size_t)max_n > ((size_t)kMid << huge_levels)) ++huge_levels;
     H.levels = huge_levels;
 
     const int chunks_x = std::max(1, std::min(ceil_div(max_n, 256 * 4), 256));
@@ -1755,6 +1757,27 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
         PS_HIP(hipGetLastError());
     }
     plan.launches = 6 + 5 * huge_levels;
+    plan.chunked_levels = huge_levels;
+    return PS_OK;
+}
+
+int read_build_counters(ps_context* c, const TreeSetPlan& plan, BuildCounters* out)
+{
+    static_assert(kHugeLevels <= kBuildCounterLevels, "BuildCounters holds one entry per chunked level");
+    PS_CHECK(plan.d_head && plan.head_bytes > plan.off_hcnt, "read_build_counters: the plan was not carved");
+    int32_t cnt[kMaxLevels + 8], hcnt[2 * (kHugeLevels + 2)];
+    PS_HIP(hipMemcpyAsync(cnt, plan.d_head + plan.off_cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(hipMemcpyAsync(hcnt, plan.d_head + plan.off_hcnt, sizeof(hcnt), hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(hipStreamSynchronize(c->stream));
+    std::memset(out, 0, sizeof(*out));
+    out->chunked_levels = plan.chunked_levels;
+    for (int l = 0; l < kHugeLevels; ++l) {
+        out->ntasks[l] = hcnt[l];                      // HugeState::ntasks
+        out->nchunks[l] = hcnt[kHugeLevels + 2 + l];   // HugeState::nchunks
+    }
+    out->straggler_tasks = cnt[plan.chunked_levels];   // BuildQueues::level_cnt of the level build_level_kernel starts from
+    out->mid_pushed = cnt[kMaxLevels + 1];             // BuildQueues::small_cnt[1]
+    out->small_pushed = cnt[kMaxLevels];               // BuildQueues::small_cnt[0]
     return PS_OK;
 }
 

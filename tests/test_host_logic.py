@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import kdtree_cases
 import knn_cases
 import netcase
 from conftest import brats_cloud, uniform_cloud
@@ -81,26 +82,8 @@ def test_tree_layout_against_oracle_tree(dbg, lib, oracle):
     bbox = np.zeros(6, np.float32)
     assert dbg.ps_debug_kdtree_host(p.ctypes.data, n, vind.ctypes.data, nodes.ctypes.data, pts.ctypes.data, rd.ctypes.data,
                                     bbox.ctypes.data) == 0
-    t = oracle.kdtree_export(p)
-    assert np.array_equal(vind, t["vind"])
-    assert np.array_equal(bbox, t["bbox"])
-    assert np.array_equal(pts[:, :3], p[vind]) and np.array_equal(pts[:, 3].view(np.int32), vind)
-
-    def walk(oid, ref, lo, hi):
-        pid, cnt = ref & ((1 << 26) - 1), ref >> 26  # reference = node id | leaf point count << 26 (csrc/kdtree.h)
-        if t["axis"][oid] < 0:
-            assert cnt == hi - lo and pid % 2 == 0 and pid // 2 == t["a"][oid] == lo and nodes[pid, 0] == lo and nodes[pid, 1] == t["b"][oid] == hi
-            return 1
-        assert cnt == 0 and pid % 2 == 1
-        m = (pid + 1) // 2
-        ax = (int(nodes[pid, 0]) & 0xffffffff) >> 30
-        assert ax == t["axis"][oid]
-        assert nodes[pid, 2:].view(np.float32)[0] == t["lo"][oid] and nodes[pid, 2:].view(np.float32)[1] == t["hi"][oid]
-        c1, c2 = int(nodes[pid, 0]) & 0x3fffffff, int(nodes[pid, 1])
-        return 1 + max(walk(t["a"][oid], c1, lo, m), walk(t["b"][oid], c2, m, hi))
-
-    depth = walk(0, int(rd[0]), 0, n)
-    assert depth - 1 == rd[1]
+    # (the walk and its assertions: kdtree_cases.assert_oracle_tree, shared with tests/test_kdtree_tier_coverage.py)
+    kdtree_cases.assert_oracle_tree(kdtree_cases.Tree(n, vind=vind, nodes=nodes, pts=pts, root_depth=rd, bbox=bbox), p, oracle.kdtree_export(p))
 
 
 def test_weight_packing_is_the_mfma_b_fragment_order(dbg, lib):
