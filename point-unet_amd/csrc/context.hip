@@ -1,5 +1,6 @@
 // context.hip -- ps_context lifetime, error text, workspace buffers, hipEvent stage timing.
 #include "common.h"
+#include "kdtree_build.h"
 
 #include <cstdlib>
 
@@ -54,7 +55,6 @@ int ps_context::check_flag_slot(int s)
     int rc = PS_OK;
     if (pending_mask & (1u << s)) {
         const int32_t* f = h_flags + 4 * s;
-        // (f[2], the "unfinished build" word of the first builder, is always 0: the straggler kernel finishes every tree)
         if (flag_kind[s] == 1) {  // ps_cloud_sample: {mismatch, slot, device count, host count}
             if (f[0] != 0) {
                 ps::set_error("deferred check: cloud sample #%llu of this context: slot %d has %d positive labels on the device, positives_host "
@@ -68,11 +68,11 @@ int ps_context::check_flag_slot(int s)
                               "was written outside the outputs; their rows are unspecified)", (unsigned long long)flag_serial[s], f[1], f[2]);
                 rc = PS_ESTATE;
             }
-        } else if (f[1] != 0) {
+        } else if (f[ps::kFlagQueueOverflow] != 0) {
             ps::set_error("deferred check: pyramid build #%llu of this context: kd-tree builder queue overflow (degenerate cloud); its index "
                           "tables were filled with index 0", (unsigned long long)flag_serial[s]);
             rc = PS_ESTATE;
-        } else if (f[0] != 0) {
+        } else if (f[ps::kFlagStackOverflow] != 0) {
             ps::set_error("deferred check: pyramid build #%llu of this context: kd-tree deeper than the traversal stack (degenerate cloud); "
                           "its neighbour lists are valid indices but may not be the nearest", (unsigned long long)flag_serial[s]);
             rc = PS_ESTATE;

@@ -31,14 +31,14 @@ int ps_debug_kdtree_device(ps_context* ctx, const float* support, int64_t n, int
  *   [1 + l]   l = 0..7: HugeState::ntasks[l] = nodes of all trees at depth l with more than kHuge points, for l < L; 0 from L on (route_task
  *             is the only writer, and every ancestor of such a node is a chunked task itself)
  *   [9 + l]   l = 0..7: HugeState::nchunks[l] = sum of ceil(size / kChunk) over the nodes counted in [1 + l]; 0 from L on
- *   [17]      BuildQueues::level_cnt[L], the queue build_level_kernel starts from = nodes at depth L with more than kMid points (their
+ *   [17]      QueueCounters::level[L], the queue build_level_kernel starts from = nodes at depth L with more than kMid points (their
  *             parents are chunked tasks of level L - 1; the kernel itself parks what it meets below on a stack in LDS and counts nothing)
- *   [18]      BuildQueues::small_cnt[1], pushes to the mid queue = nodes of kSmall + 1 .. kMid points that are roots or whose parent has
+ *   [18]      QueueCounters::mid, pushes to the mid queue = nodes of kSmall + 1 .. kMid points that are roots or whose parent has
  *             more than kMid points (build_mid_kernel keeps its own children above kSmall in LDS)
- *   [19]      BuildQueues::small_cnt[0], pushes to the small queue = nodes of at most kSmall points, leaves included, that are roots or
+ *   [19]      QueueCounters::small, pushes to the small queue = nodes of at most kSmall points, leaves included, that are roots or
  *             whose parent has more than kSmall points
- *   [20] [21] flags[0] (written by searches only: 0 after a build), flags[1] (a builder queue overflowed); this door does not refuse on it
- * (small_cnt[2], small_cnt[3] and flags[2] are written by no kernel that runs and are left out.) */
+ *   [20] [21] the status words (BuildFlag, csrc/kdtree_build.h): kFlagStackOverflow (written by searches only: 0 after a build),
+ *             kFlagQueueOverflow (a builder queue overflowed); this door does not refuse on it */
 #define PS_DEBUG_KDTREE_STATS 22
 int ps_debug_kdtree_device_set(ps_context* ctx, const float* support, const int32_t* n, int64_t T, const int32_t* want_copy, int32_t* vind,
                                int32_t* nodes, float* pts, int32_t* fat, int32_t* root_depth, float* bbox, float* copy, int32_t* stats);

@@ -357,10 +357,10 @@ extern "C" int ps_debug_kdtree_device(ps_context* c, const float* support, int64
     }
     plan.src[0] = c->stage_in.as<float>();
     PS_TRY(build_trees(c, plan));
-    int32_t flag[3] = {0, 0, 0};
-    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, 12, hipMemcpyDeviceToHost, c->stream));
+    int32_t flag[kBuildFlagWords] = {};
+    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
     PS_HIP(hipStreamSynchronize(c->stream));
-    PS_CHECK(flag[1] == 0, "ps_debug_kdtree_device: builder queue overflow");
+    PS_CHECK(flag[kFlagQueueOverflow] == 0, "ps_debug_kdtree_device: builder queue overflow");
     TreeMeta m;
     PS_HIP(hipMemcpyAsync(nodes, plan.d_nodes[0], sizeof(int4) * 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(hipMemcpyAsync(pts, plan.d_pts[0], sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -416,8 +416,8 @@ extern "C" int ps_debug_kdtree_device_set(ps_context* c, const float* support, c
     PS_TRY(build_trees(c, plan));
     BuildCounters bc;
     PS_TRY(read_build_counters(c, plan, &bc));
-    int32_t flag[3] = {0, 0, 0};
-    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, 12, hipMemcpyDeviceToHost, c->stream));
+    int32_t flag[kBuildFlagWords] = {};
+    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
     std::vector<TreeMeta> meta((size_t)T);
     PS_HIP(hipMemcpyAsync(meta.data(), plan.d_meta, sizeof(TreeMeta) * (size_t)T, hipMemcpyDeviceToHost, c->stream));
     {
@@ -450,7 +450,7 @@ extern "C" int ps_debug_kdtree_device_set(ps_context* c, const float* support, c
     stats[1 + 2 * kBuildCounterLevels] = bc.straggler_tasks;
     stats[2 + 2 * kBuildCounterLevels] = bc.mid_pushed;
     stats[3 + 2 * kBuildCounterLevels] = bc.small_pushed;
-    stats[4 + 2 * kBuildCounterLevels] = flag[0];
-    stats[5 + 2 * kBuildCounterLevels] = flag[1];
+    stats[4 + 2 * kBuildCounterLevels] = flag[kFlagStackOverflow];
+    stats[5 + 2 * kBuildCounterLevels] = flag[kFlagQueueOverflow];
     return PS_OK;
 }

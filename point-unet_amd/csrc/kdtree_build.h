@@ -8,6 +8,14 @@
 
 namespace ps {
 
+// The status words of a tree set (TreeSetPlan::d_flags) that anything writes: zero after the head copy, read back by whoever waits
+// for the searches (kBuildFlagWords of them).
+enum BuildFlag : int {
+    kFlagStackOverflow = 0,  // set by a search: a tree is deeper than the traversal stack (kStackMax, kdtree.h)
+    kFlagQueueOverflow = 1,  // set by the builder: a task queue overflowed and a tree has holes
+    kBuildFlagWords = 2
+};
+
 struct TreeSetPlan {
     // inputs
     std::vector<int32_t> n;          // points per tree
@@ -25,7 +33,7 @@ struct TreeSetPlan {
     char* d_head = nullptr;
     size_t head_bytes = 0, off_flags = 0, off_trees = 0, off_bbox = 0, off_cnt = 0, off_hcnt = 0;
     void* d_jobs = nullptr;          // = d_head: KnnJob table (trees + extra_jobs entries of 128 B)
-    int32_t* d_flags = nullptr;      // [16] error flags, zero after the head copy
+    int32_t* d_flags = nullptr;      // [16] status words (BuildFlag), zero after the head copy
     void* d_scratch = nullptr;       // builder scratch (everything that needs no initial contents)
     size_t scratch_bytes = 0;
     int launches = 0;                // kernels launched by build_trees (for the stage timer)
@@ -61,8 +69,8 @@ struct TreeSetPlan {
 };
 
 // Builds every tree of the plan on the context's stream WITHOUT synchronising.  The build always completes on the device
-// (very unbalanced clouds included: kdtree_build.hip, straggler kernel); d_flags[1] / d_flags[0] report the two degenerate
-// cases that remain (builder queue overflow, tree deeper than the traversal stack) -- even then every search writes valid
+// (very unbalanced clouds included: kdtree_build.hip, straggler kernel); d_flags[kFlagQueueOverflow] / d_flags[kFlagStackOverflow]
+// report the two degenerate cases that remain (builder queue overflow, tree deeper than the traversal stack) -- even then every search writes valid
 // point indices, so whatever is enqueued behind the build never reads out of bounds.
 int build_trees(ps_context* c, TreeSetPlan& plan);
 

@@ -3,16 +3,21 @@
 // (PointSegment/utils/nearest_neighbors/nanoflann.hpp:916-1043 divideTree / middleSplit_ / planeSplit, :1321-1343
 // computeBoundingBox; leaf_max_size 10, knn_.cxx:116).
 //
-// The recursion is replaced by task queues over three tiers of node size (kernel boundaries are the only global sync):
-//   init kernels     points -> (x,y,z,index) records; root bounding boxes by block reduction + ordered-uint atomics
-//   chunked levels   nodes above kMid points: every pass of a level (classify + counts, then rank -> swap for each of the two Hoare
-//                    sweeps; five in all, see "chunked levels" below) is one small kernel over 2 048-record chunks spread over the chip
-//   mid kernel       nodes of kSmall+1 .. kMid points: ONE workgroup loads the node into LDS and advances level by level
-//                    over all of its live segments at once, with __syncthreads() only
-//   flat kernel      nodes of <= kSmall points: one workgroup, one thread per point position; every round advances all live
-//                    segments of the node at once (block-wide flag scans for the ranks of the closed-form Hoare sweeps)
-//   straggler kernel (very unbalanced clouds) one workgroup per node still above kMid after the chunked levels finishes
-//                    everything above kMid below it depth first -- ONE launch, nothing left for the host to repair
+// The recursion is replaced by task queues over four tiers of node size, in launch order (kernel boundaries are the only global sync):
+//   init             init_points_kernel: points -> (x,y,z,index) records; root bounding boxes by block reduction + ordered-uint
+//                    atomics.  huge_root_kernel: root metadata, routing of every root, plan of the first chunked level
+//   chunked levels   huge_phase_kernel<0..4>, nodes above kMid points: every pass of a level (classify + counts, then rank -> swap
+//                    for each of the two Hoare sweeps; five in all, see "chunked levels" below) is one small kernel over
+//                    2 048-record chunks spread over the chip
+//   straggler kernel build_level_kernel (very unbalanced clouds): one workgroup per node still above kMid after the chunked levels
+//                    finishes everything above kMid below it depth first -- ONE launch, nothing left for the host to repair
+//   mid kernel       build_mid_kernel, nodes of kSmall+1 .. kMid points: ONE workgroup loads the node into LDS and advances level by
+//                    level over all of its live segments at once, with __syncthreads() only
+//   flat kernel      build_flat_kernel, nodes of <= kSmall points: one workgroup, one thread per point position; every round advances
+//                    all live segments of the node at once (block-wide flag scans for the ranks of the closed-form Hoare sweeps)
+//   fatten           fatten_kernel: the searches' image of the finished trees (TreeView::fat)
+// What the four tiers must agree on to the bit -- the split of a node, its record, its link to the parent, the children's boxes,
+// the counts against the cut, the sweep predicate, how a task is pushed -- is written ONCE, in "node rules" below.
 // nanoflann's two Hoare sweeps are reproduced in CLOSED FORM everywhere -- the i-th misplaced element from the left swaps
 // with the i-th misplaced element from the right, so ranks from scans of two flag vectors give every swap pair.
 // Node ids are position-derived (kdtree.h), so the result does not depend on scheduling.  divlow / divhigh are the
@@ -58,13 +63,18 @@ struct BuildTree {
     int32_t n;
 };
 
+// The queue counters as they lie in the plan's head block (TreeSetPlan::off_cnt; zero after the head copy).
+struct QueueCounters {
+    int32_t level[kMaxLevels];  // tasks pushed FOR a level: above kMid points, not chunked (build_level_kernel)
+    int32_t small, mid;         // tasks pushed to small_q / mid_q
+};
+
 struct BuildQueues {
     BuildTask* q[2];
     BuildTask* mid_q;    // nodes of kSmall+1 .. kMid points (build_mid_kernel)
     BuildTask* small_q;  // nodes of <= kSmall points (build_flat_kernel)
-    int32_t* level_cnt;  // [kMaxLevels]
-    int32_t* small_cnt;  // small_cnt[0] = pushed, [1] = mid pushed, [2] = mid done, [3] = small done
-    int32_t* flags;      // flags[1] = queue overflow
+    QueueCounters* cnt;
+    int32_t* flags;      // TreeSetPlan::d_flags (BuildFlag, kdtree_build.h)
     int32_t q_cap, small_cap;
 };
 
@@ -77,6 +87,11 @@ __device__ __forceinline__ float ord2f(unsigned u)
 {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
+// One of three values by a run-time index.  The values are passed as values: written as a choice between three array elements inside a
+// helper that takes the array by reference, the compiler folds it into one load with a run-time index, which keeps the caller's array in
+// scratch memory (28 bytes per lane in the flat and mid kernels).
+__device__ __forceinline__ float pick3(float v0, float v1, float v2, int i) { return i == 0 ? v0 : (i == 1 ? v1 : v2); }
+// a record's coordinate on an axis (on the record's own fields: through pick3 the straggler kernel needs three registers more)
 __device__ __forceinline__ float comp(const float4& p, int ax) { return ax == 0 ? p.x : (ax == 1 ? p.y : p.z); }
 
 // Global-address-space view of a device array reached through a descriptor in memory (gmem.h): reads a[i], writes a.set(i, v).
@@ -87,12 +102,276 @@ struct GArr {
     __device__ __forceinline__ void set(size_t i, const T& v) const { gstore(p + i, v); }
 };
 
+// ---- node rules: what every tier must do in exactly the same way -------------------------------------------------------------------
+// Tight extents of a set of records on the three axes: per lane, then over the wave.
+struct Extent3 {
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    __device__ __forceinline__ void add(float x, float y, float z)
+    {
+        mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
+        mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
+        mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
+    }
+    __device__ __forceinline__ void wave_reduce()
+    {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
+    }
+};
+
+// A set of split-axis values against the cut: lim1 = #(< cut), lim2 = #(<= cut), max{v < cut}, min{v > cut}.
+struct CutCount {
+    int lt = 0, le = 0;
+    float maxlt = -INFINITY, mingt = INFINITY;
+    __device__ __forceinline__ void add(float v, float cut)
+    {
+        lt += v < cut;
+        le += v <= cut;
+        if (v < cut) maxlt = fmaxf(maxlt, v);
+        if (v > cut) mingt = fminf(mingt, v);
+    }
+    __device__ __forceinline__ void wave_reduce()
+    {
+        lt = wave_sum(lt); le = wave_sum(le);
+        maxlt = wave_max(maxlt); mingt = wave_min(mingt);
+    }
+    // add + wave_reduce for ONE value per lane, every lane taking part: the two counts are ballots
+    __device__ __forceinline__ static CutCount of_wave(float v, float cut)
+    {
+        CutCount c;
+        c.lt = (int)__popcll(__ballot(v < cut));
+        c.le = (int)__popcll(__ballot(v <= cut));
+        c.maxlt = wave_max(v < cut ? v : -INFINITY);
+        c.mingt = wave_min(v > cut ? v : INFINITY);
+        return c;
+    }
+};
+
+// Where the two above are gathered for a node that several waves or workgroups work on: ordered uints, merged with integer atomics
+// (LDS in the flat and mid kernels, global memory for the chunked levels).
+struct OrdAcc {
+    unsigned mn[3], mx[3];  // ordered-uint extents
+    int lt, le;
+    unsigned maxlt, mingt;  // ordered-uint
+    __device__ __forceinline__ void reset_extent() { for (int a = 0; a < 3; ++a) { mn[a] = 0xffffffffu; mx[a] = 0u; } }
+    __device__ __forceinline__ void reset_counts() { lt = 0; le = 0; maxlt = 0u; mingt = 0xffffffffu; }
+    __device__ __forceinline__ void reset() { reset_extent(); reset_counts(); }
+    // one lane's extents: six atomics
+    __device__ __forceinline__ void merge(const Extent3& e)
+    {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { atomicMin(&mn[a], f2ord(e.mn[a])); atomicMax(&mx[a], f2ord(e.mx[a])); }
+    }
+    // a wave's reduced extents: lanes 0..2 send one axis each
+    __device__ __forceinline__ void merge_wave(const Extent3& e, int lane)
+    {
+        if (lane < 3) {
+            atomicMin(&mn[lane], f2ord(pick3(e.mn[0], e.mn[1], e.mn[2], lane)));
+            atomicMax(&mx[lane], f2ord(pick3(e.mx[0], e.mx[1], e.mx[2], lane)));
+        }
+    }
+    __device__ __forceinline__ void merge(const CutCount& c)
+    {
+        atomicAdd(&lt, c.lt); atomicAdd(&le, c.le);
+        atomicMax(&maxlt, f2ord(c.maxlt)); atomicMin(&mingt, f2ord(c.mingt));
+    }
+    // the same without the atomics that would change nothing (nothing below the cut, nothing at or below it, nothing above it)
+    __device__ __forceinline__ void merge_skipping_neutral(const CutCount& c)
+    {
+        if (c.lt) { atomicAdd(&lt, c.lt); atomicMax(&maxlt, f2ord(c.maxlt)); }
+        if (c.le) atomicAdd(&le, c.le);
+        if (c.mingt < INFINITY) atomicMin(&mingt, f2ord(c.mingt));
+    }
+    // back to floats, for the split choice and the node record
+    __device__ __forceinline__ Extent3 extent() const
+    {
+        Extent3 e;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { e.mn[a] = ord2f(mn[a]); e.mx[a] = ord2f(mx[a]); }
+        return e;
+    }
+    __device__ __forceinline__ CutCount counts() const
+    {
+        CutCount c;
+        c.lt = lt; c.le = le; c.maxlt = ord2f(maxlt); c.mingt = ord2f(mingt);
+        return c;
+    }
+};
+
+// The split of a node of `count` records starting at position l of its tree, once the counts against the cut are known
+// (middleSplit_, nanoflann.hpp:1000-1004): the left child takes the first idx records of [ < cut | == cut | > cut ].
+__device__ __forceinline__ int split_index(int count, int lim1, int lim2)
+{
+    const int half = count / 2;
+    return lim1 > half ? lim1 : (lim2 < half ? lim2 : half);
+}
+struct NodeSplit {
+    int idx, id;            // records of the left child; the node's id (position-derived, kdtree.h)
+    float divlow, divhigh;  // the children's tight extents on the split axis
+};
+__device__ __forceinline__ NodeSplit split_node(int l, int count, const CutCount& c, float cut)
+{
+    NodeSplit s;
+    s.idx = split_index(count, c.lt, c.le);
+    s.id = 2 * (l + s.idx) - 1;
+    s.divlow = s.idx > c.lt ? cut : c.maxlt;
+    s.divhigh = s.idx < c.le ? cut : c.mingt;
+    return s;
+}
+// the inner node's record; the low 30 bits of .x and .y are for the children's links
+__device__ __forceinline__ void store_inner(const BuildTree& t, const NodeSplit& s, int ax)
+{
+    t.nodes[s.id] = make_int4((int)((unsigned)ax << 30), 0, __float_as_int(s.divlow), __float_as_int(s.divhigh));
+}
+// ref = a node id or a leaf_ref
+__device__ __forceinline__ void link_to_parent(const BuildTree& t, int parent, int side, int ref)
+{
+    if (parent < 0)
+        t.meta->root = ref;
+    else if (side == 0)
+        atomicOr(&t.nodes[parent].x, ref);  // low 30 bits were written as 0 by the parent, in an earlier kernel / earlier by this workgroup
+    else
+        t.nodes[parent].y = ref;
+}
+// records [l, r) of the tree as a leaf
+__device__ __forceinline__ void emit_leaf(const BuildTree& t, int l, int r, int parent, int side)
+{
+    t.nodes[2 * l] = make_int4(l, r, 0, 0);
+    link_to_parent(t, parent, side, leaf_ref(l, r - l));
+}
+// The box a child inherits: the parent's, cut at the plane (nanoflann passes it down instead of the child's tight box).
+// (compile-time indices only: a run-time index would push the box, and the task around it, into scratch memory)
+__device__ __forceinline__ void cut_box(float (&lo)[3], float (&hi)[3], int side, int ax, float cut)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (side == 0) hi[a] = a == ax ? cut : hi[a];
+        else lo[a] = a == ax ? cut : lo[a];
+    }
+}
+
+// The two Hoare sweeps (planeSplit, nanoflann.hpp:1016-1043) in closed form.  Sweep 0 partitions [0, count) by (v < cut) around lim1,
+// sweep 1 partitions [lim1, count) by (v <= cut) around lim2.  In a sweep the records left of the boundary that fail the predicate
+// ("misplaced left", ascending) pair with the records right of it that satisfy it ("misplaced right", descending): i-th with i-th.
+// p = the record's position in the node, is_lt / is_le = its value against the cut.
+struct Misplaced { bool L, R; };
+__device__ __forceinline__ int sweep_from(int sweep, int lim1) { return sweep == 0 ? 0 : lim1; }  // the first position a sweep looks at
+__device__ __forceinline__ Misplaced sweep_flags(int sweep, int p, int lim1, int lim2, bool is_lt, bool is_le)
+{
+    const int from = sweep_from(sweep, lim1), bound = sweep == 0 ? lim1 : lim2;
+    const bool keep_left = sweep == 0 ? is_lt : is_le;
+    Misplaced m;
+    m.L = p >= from && p < bound && !keep_left;
+    m.R = p >= bound && keep_left;  // (bound >= from)
+    return m;
+}
+// Order-preserving ranks inside a wave whose lanes hold several records each, position order (e, lane)-major, from the ballots of a
+// flag, one ballot after the other: true when this lane's record is flagged in b, and then *rank = r + the flagged records of the
+// lower lanes; r moves past the whole ballot.
+__device__ __forceinline__ bool ballot_rank(unsigned long long b, int lane, int& r, int* rank)
+{
+    *rank = r + (int)__popcll(b & ((1ull << lane) - 1ull));
+    r += (int)__popcll(b);
+    return (b >> lane) & 1ull;
+}
+
+// A slot of a task queue, or -1 with the overflow flag set when the queue is full.
+__device__ __forceinline__ int take_slot(int32_t* counter, int cap, int32_t* flags)
+{
+    const int slot = atomicAdd(counter, 1);
+    if (slot < cap) return slot;
+    flags[kFlagQueueOverflow] = 1;
+    return -1;
+}
+// next_level: the level the task is pushed FOR (only tasks above kMid points have one)
+__device__ __forceinline__ void push_task(const BuildQueues& Q, const BuildTask& t, int next_level)
+{
+    if (t.r - t.l > kMid) {
+        const int slot = take_slot(&Q.cnt->level[next_level], next_level < kMaxLevels - 1 ? Q.q_cap : 0, Q.flags);
+        if (slot >= 0) Q.q[next_level & 1][slot] = t;
+    } else if (t.r - t.l > kSmall) {
+        const int slot = take_slot(&Q.cnt->mid, Q.q_cap, Q.flags);
+        if (slot >= 0) Q.mid_q[slot] = t;
+    } else {
+        const int slot = take_slot(&Q.cnt->small, Q.small_cap, Q.flags);
+        if (slot >= 0) Q.small_q[slot] = t;
+    }
+}
+
+// ---- the split decision (middleSplit_, nanoflann.hpp:966-1005) --------------------------------------------------------------------
+struct SplitChoice { int ax; float cut; };
+// the parts the two forms below share: only axes whose box span is within 1e-5 of the largest may be cut; the cut is the middle of
+// the BOX on the chosen axis, clamped to the records' tight extent on it
+__device__ __forceinline__ float span_threshold(const float* lo, const float* hi)
+{
+    float max_span = __fsub_rn(hi[0], lo[0]);
+    for (int a = 1; a < 3; ++a) {
+        const float s = __fsub_rn(hi[a], lo[a]);
+        if (s > max_span) max_span = s;
+    }
+    return __fmul_rn(__fsub_rn(1.0f, 0.00001f), max_span);
+}
+__device__ __forceinline__ SplitChoice clamped_cut(int ax, float lo_c, float hi_c, float mn_c, float mx_c)
+{
+    const float split = __fmul_rn(__fadd_rn(lo_c, hi_c), 0.5f);
+    SplitChoice c;
+    c.ax = ax;
+    c.cut = split < mn_c ? mn_c : (split > mx_c ? mx_c : split);
+    return c;
+}
+// lo / hi: the node's incoming box, mn / mx: its records' tight extents
+__device__ __forceinline__ SplitChoice choose_split(const float* lo, const float* hi, const float* mn, const float* mx)
+{
+    const float thresh = span_threshold(lo, hi);
+    int cutfeat = 0;
+    float max_spread = -1.f;
+    for (int a = 0; a < 3; ++a) {
+        if (__fsub_rn(hi[a], lo[a]) > thresh) {
+            const float spread = __fsub_rn(mx[a], mn[a]);
+            if (spread > max_spread) { cutfeat = a; max_spread = spread; }
+        }
+    }
+    return clamped_cut(cutfeat, pick3(lo[0], lo[1], lo[2], cutfeat), pick3(hi[0], hi[1], hi[2], cutfeat), pick3(mn[0], mn[1], mn[2], cutfeat),
+                       pick3(mx[0], mx[1], mx[2], cutfeat));
+}
+// The same decision with the chosen axis' values carried along while the axis is chosen, for the straggler kernel: there this form
+// compiles to 87 VGPRs and the one above to 98, a wave of occupancy less.  It cannot replace the one above either: inside
+// build_flat_kernel this body crashes the instruction selection of hipcc 7.2 (AMD clang 22.0.0git, roc-7.2.0) with a segmentation fault.
+__device__ __forceinline__ SplitChoice choose_split_scalar(const float* lo, const float* hi, const float* mn, const float* mx)
+{
+    const float thresh = span_threshold(lo, hi);
+    int cutfeat = 0;
+    float max_spread = -1.f, lo_c = lo[0], hi_c = hi[0], mn_c = mn[0], mx_c = mx[0];
+    const bool in0 = __fsub_rn(hi[0], lo[0]) > thresh, in1 = __fsub_rn(hi[1], lo[1]) > thresh, in2 = __fsub_rn(hi[2], lo[2]) > thresh;
+    const float sp0 = __fsub_rn(mx[0], mn[0]), sp1 = __fsub_rn(mx[1], mn[1]), sp2 = __fsub_rn(mx[2], mn[2]);
+    if (in0 && sp0 > max_spread) { cutfeat = 0; max_spread = sp0; }
+    if (in1 && sp1 > max_spread) { cutfeat = 1; max_spread = sp1; lo_c = lo[1]; hi_c = hi[1]; mn_c = mn[1]; mx_c = mx[1]; }
+    if (in2 && sp2 > max_spread) { cutfeat = 2; max_spread = sp2; lo_c = lo[2]; hi_c = hi[2]; mn_c = mn[2]; mx_c = mx[2]; }
+    return clamped_cut(cutfeat, lo_c, hi_c, mn_c, mx_c);
+}
+
+// Everything the parent must record once the partition is known: its record, its link, and its two children as tasks.
+__device__ __forceinline__ void emit_inner(const BuildTree& t, const BuildTask& k, int ax, float cut, const CutCount& c, BuildTask* kids /* [2] out */)
+{
+    const NodeSplit ns = split_node(k.l, k.r - k.l, c, cut);
+    store_inner(t, ns, ax);
+    link_to_parent(t, k.parent, k.side, ns.id);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        BuildTask ch = k;
+        ch.parent = ns.id; ch.side = s; ch.level = k.level + 1;
+        if (s == 0) ch.r = k.l + ns.idx; else ch.l = k.l + ns.idx;
+        cut_box(ch.lo, ch.hi, s, ax, cut);
+        kids[s] = ch;
+    }
+}
+
 // ---- init -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void init_points_kernel(const BuildTree* __restrict__ trees, int chunks_x)
 {
     __shared__ float s_mn[4][3], s_mx[4][3];
     const BuildTree t = trees[blockIdx.y];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    Extent3 ext;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < t.n; i += chunks_x * 256) {
         const float x = gload(t.src + 3 * (size_t)i), y = gload(t.src + 3 * (size_t)i + 1), z = gload(t.src + 3 * (size_t)i + 2);
         gstore(t.pts + i, make_float4(x, y, z, __int_as_float(i)));
@@ -101,18 +380,12 @@ __global__ __launch_bounds__(256) void init_points_kernel(const BuildTree* __res
             gstore(t.copy_dst + 3 * (size_t)i + 1, y);
             gstore(t.copy_dst + 3 * (size_t)i + 2, z);
         }
-        mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
-        mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
-        mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
+        ext.add(x, y, z);
     }
+    ext.wave_reduce();
+    if ((threadIdx.x & 63) == 0)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        {
-            mn[a] = wave_min(mn[a]);
-            mx[a] = wave_max(mx[a]);
-        }
-        if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6][a] = mn[a]; s_mx[threadIdx.x >> 6][a] = mx[a]; }
-    }
+        for (int a = 0; a < 3; ++a) { s_mn[threadIdx.x >> 6][a] = ext.mn[a]; s_mx[threadIdx.x >> 6][a] = ext.mx[a]; }
     __syncthreads();
     if (threadIdx.x < 3) {  // one pair of atomics per axis per workgroup
         const int a = threadIdx.x;
@@ -125,181 +398,37 @@ __global__ __launch_bounds__(256) void init_points_kernel(const BuildTree* __res
     }
 }
 
-__device__ __forceinline__ void push_task(const BuildQueues& Q, const BuildTask& t, int next_level)
-{
-    if (t.r - t.l > kMid) {
-        const int slot = atomicAdd(&Q.level_cnt[next_level], 1);
-        if (slot < Q.q_cap && next_level < kMaxLevels - 1)
-            Q.q[next_level & 1][slot] = t;
-        else
-            Q.flags[1] = 1;
-    } else if (t.r - t.l > kSmall) {
-        const int slot = atomicAdd(Q.small_cnt + 1, 1);
-        if (slot < Q.q_cap)
-            Q.mid_q[slot] = t;
-        else
-            Q.flags[1] = 1;
-    } else {
-        const int slot = atomicAdd(Q.small_cnt, 1);
-        if (slot < Q.small_cap)
-            Q.small_q[slot] = t;
-        else
-            Q.flags[1] = 1;
-    }
-}
-
-// ---- the split decision shared by both kernels (middleSplit_, nanoflann.hpp:966-1005) -------------------------
-struct SplitChoice {
-    int ax;
-    float cut;
-};
-__device__ __forceinline__ SplitChoice choose_split(const float* lo, const float* hi, const float* mn, const float* mx)
-{
-    float max_span = __fsub_rn(hi[0], lo[0]);
-    for (int a = 1; a < 3; ++a) {
-        const float s = __fsub_rn(hi[a], lo[a]);
-        if (s > max_span) max_span = s;
-    }
-    const float thresh = __fmul_rn(__fsub_rn(1.0f, 0.00001f), max_span);
-    int cutfeat = 0;
-    float max_spread = -1.f;
-    for (int a = 0; a < 3; ++a) {
-        if (__fsub_rn(hi[a], lo[a]) > thresh) {
-            const float spread = __fsub_rn(mx[a], mn[a]);
-            if (spread > max_spread) {
-                cutfeat = a;
-                max_spread = spread;
-            }
-        }
-    }
-    const float split = __fmul_rn(__fadd_rn(lo[cutfeat], hi[cutfeat]), 0.5f);
-    SplitChoice c;
-    c.ax = cutfeat;
-    c.cut = split < mn[cutfeat] ? mn[cutfeat] : (split > mx[cutfeat] ? mx[cutfeat] : split);
-    return c;
-}
-
-// The same decision with the chosen axis' values carried along as scalars: in the straggler kernel, whose box lives in LDS, the
-// run-time index `lo[cutfeat]` above put the arrays into scratch memory (16 bytes per lane -- and a kernel that needs scratch pays
-// for the private-segment set-up on every dispatch).  (Used only there: the same body inside build_flat_kernel crashes hipcc 7.2's
-// instruction selection.)
-__device__ __forceinline__ SplitChoice choose_split_scalar(const float* lo, const float* hi, const float* mn, const float* mx)
-{
-    float max_span = __fsub_rn(hi[0], lo[0]);
-    for (int a = 1; a < 3; ++a) {
-        const float s = __fsub_rn(hi[a], lo[a]);
-        if (s > max_span) max_span = s;
-    }
-    const float thresh = __fmul_rn(__fsub_rn(1.0f, 0.00001f), max_span);
-    int cutfeat = 0;
-    float max_spread = -1.f, lo_c = lo[0], hi_c = hi[0], mn_c = mn[0], mx_c = mx[0];
-    {
-        const bool in0 = __fsub_rn(hi[0], lo[0]) > thresh, in1 = __fsub_rn(hi[1], lo[1]) > thresh, in2 = __fsub_rn(hi[2], lo[2]) > thresh;
-        const float sp0 = __fsub_rn(mx[0], mn[0]), sp1 = __fsub_rn(mx[1], mn[1]), sp2 = __fsub_rn(mx[2], mn[2]);
-        if (in0 && sp0 > max_spread) { cutfeat = 0; max_spread = sp0; }
-        if (in1 && sp1 > max_spread) { cutfeat = 1; max_spread = sp1; lo_c = lo[1]; hi_c = hi[1]; mn_c = mn[1]; mx_c = mx[1]; }
-        if (in2 && sp2 > max_spread) { cutfeat = 2; max_spread = sp2; lo_c = lo[2]; hi_c = hi[2]; mn_c = mn[2]; mx_c = mx[2]; }
-    }
-    const float split = __fmul_rn(__fadd_rn(lo_c, hi_c), 0.5f);
-    SplitChoice c;
-    c.ax = cutfeat;
-    c.cut = split < mn_c ? mn_c : (split > mx_c ? mx_c : split);
-    return c;
-}
-
-// Everything the parent must record once the partition is known.
-__device__ __forceinline__ void emit_inner(const BuildQueues& Q, const BuildTree& t, const BuildTask& k, int ax, float cut, int lim1, int lim2,
-                                           float maxlt, float mingt, BuildTask* kids /* [2] out */, int* node_id)
-{
-    const int count = k.r - k.l, half = count / 2;
-    const int idx = lim1 > half ? lim1 : (lim2 < half ? lim2 : half);
-    const int m = k.l + idx;
-    const int id = 2 * m - 1;
-    // left = first idx records of [ <cut | ==cut | >cut ]
-    const float divlow = idx > lim1 ? cut : maxlt;
-    const float divhigh = idx < lim2 ? cut : mingt;
-    t.nodes[id] = make_int4((int)((unsigned)ax << 30), 0, __float_as_int(divlow), __float_as_int(divhigh));
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        BuildTask c = k;
-        c.parent = id;
-        c.side = s;
-        c.level = k.level + 1;
-        // (compile-time indices only: a run-time index would push the task into scratch memory)
-        if (s == 0) {
-            c.r = m;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) c.hi[a] = a == ax ? cut : c.hi[a];
-        } else {
-            c.l = m;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) c.lo[a] = a == ax ? cut : c.lo[a];
-        }
-        kids[s] = c;
-    }
-    *node_id = id;
-}
-
-__device__ __forceinline__ void link_to_parent(const BuildTree& t, const BuildTask& k, int id)
-{
-    if (k.parent < 0)
-        t.meta->root = id;
-    else if (k.side == 0)
-        atomicOr(&t.nodes[k.parent].x, id);  // low 30 bits were written as 0 by the parent, in an earlier kernel / earlier by this wave
-    else
-        t.nodes[k.parent].y = id;
-}
-
-// ---- level kernel: one workgroup per big node ------------------------------------------------------------------
-// Every pass walks the node in slabs of T*E records; thread t owns E CONSECUTIVE records of a slab (a wave covers
-// 8 KiB of contiguous memory, all eight 16-byte loads of a lane are independent and in flight together), so the
-// order-preserving ranks of the Hoare sweeps need one block scan per slab.
+// ---- straggler kernel (build_level_kernel): one workgroup per node still above kMid points after the chunked levels ---------------
+// Such nodes come from lopsided bounding-box-midpoint splits: very unbalanced clouds, dense clusters.  One workgroup takes the node
+// and finishes EVERYTHING above kMid points below it depth first: after a split it keeps its SMALLER big child and parks the larger
+// one on a stack in LDS; children of <= kMid points go to the mid / small queues of the kernels that follow.  One launch therefore
+// completes the top of every tree however unbalanced the cloud is -- there is no "unfinished build" state for the host to detect
+// and repair, which is what makes ps_pyramid_build safe to run without host synchronisation (deferred checks): the searches and
+// the network that are enqueued right behind it always see complete trees and write every index.  Continuing with the smaller
+// child halves the node in hand at every push, so at most log2(n / kMid) <= 12 entries are ever parked for a 2^25-point tree; 32
+// leave room to spare (overflow still sets kFlagQueueOverflow).
+// The extent and count passes read the node with a stride of T records per lane (all E 16-byte loads of a lane independent and in
+// flight together); in the sweeps a wave owns 64 * E consecutive records of a slab of T * E, so the order-preserving ranks need one
+// block scan per slab.
 constexpr int kE = 8;
-
-template <int T>
-struct BlockRed {
-    float mn[T / 64][3], mx[T / 64][3];
-    int ia[T / 64], ib[T / 64];
-    float fa[T / 64], fb[T / 64];
-    int scan[2][T / 64];
-};
-
-// Stragglers: a node that is still above kMid points after the chunked levels (lopsided bounding-box-midpoint splits: very
-// unbalanced clouds, dense clusters).  One workgroup takes the node and finishes EVERYTHING above kMid points below it depth
-// first: after a split it keeps its SMALLER big child and parks the larger one on a stack in LDS; children of <= kMid points go to the
-// mid / small queues of the kernels that follow.  One launch therefore completes the top of every tree however unbalanced the
-// cloud is -- there is no "unfinished build" state for the host to detect and repair, which is what makes ps_pyramid_build
-// safe to run without host synchronisation (deferred checks): the searches and the network that are enqueued right behind
-// it always see complete trees and write every index.  Continuing with the smaller child halves the node in hand at
-// every push, so at most log2(n / kMid) <= 12 entries are ever parked for a 2^25-point tree; 32 leave room to spare (overflow
-// still sets flags[1]).
 constexpr int kStragglerStack = 32;
 
-__device__ __forceinline__ void push_small_task(const BuildQueues& Q, const BuildTask& t)
-{
-    if (t.r - t.l > kSmall) {
-        const int slot = atomicAdd(Q.small_cnt + 1, 1);
-        if (slot < Q.q_cap)
-            Q.mid_q[slot] = t;
-        else
-            Q.flags[1] = 1;
-    } else {
-        const int slot = atomicAdd(Q.small_cnt, 1);
-        if (slot < Q.small_cap)
-            Q.small_q[slot] = t;
-        else
-            Q.flags[1] = 1;
-    }
-}
+struct BlockRed {
+    static constexpr int W = kBigThreads / 64;
+    float mn[W][3], mx[W][3];
+    int ia[W], ib[W];
+    float fa[W], fb[W];
+    int scan[2][W];
+};
 
 __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTree* __restrict__ trees, BuildQueues Q, int level)
 {
-    constexpr int T = kBigThreads, W = T / 64, E = kE;
-    __shared__ BlockRed<T> S;
+    constexpr int T = kBigThreads, W = BlockRed::W, E = kE;
+    __shared__ BlockRed S;
     __shared__ BuildTask s_stack[kStragglerStack];
     __shared__ BuildTask s_cur;
     __shared__ int s_sp;
-    const int n_tasks = min(Q.level_cnt[level], Q.q_cap);
+    const int n_tasks = min(Q.cnt->level[level], Q.q_cap);
     if ((int)blockIdx.x >= n_tasks) return;
     if (threadIdx.x == 0) {
         s_cur = Q.q[level & 1][blockIdx.x];
@@ -317,77 +446,54 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
     // ---- pass 1: min / max of the three axes ----
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    Extent3 ext;
     for (int base = tid; base < count; base += T * E) {  // coalesced: record base + e*T
         float4 p[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) p[e] = a[min(base + e * T, count - 1)];
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-            mn[0] = fminf(mn[0], p[e].x); mx[0] = fmaxf(mx[0], p[e].x);
-            mn[1] = fminf(mn[1], p[e].y); mx[1] = fmaxf(mx[1], p[e].y);
-            mn[2] = fminf(mn[2], p[e].z); mx[2] = fmaxf(mx[2], p[e].z);
-        }
+        for (int e = 0; e < E; ++e) ext.add(p[e].x, p[e].y, p[e].z);
     }
+    ext.wave_reduce();
+    if (lane == 0)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        {
-            mn[c] = wave_min(mn[c]);
-            mx[c] = wave_max(mx[c]);
-        }
-        if (lane == 0) { S.mn[wave][c] = mn[c]; S.mx[wave][c] = mx[c]; }
-    }
+        for (int c = 0; c < 3; ++c) { S.mn[wave][c] = ext.mn[c]; S.mx[wave][c] = ext.mx[c]; }
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float lo = S.mn[0][c], hi = S.mx[0][c];
         for (int w = 1; w < W; ++w) { lo = fminf(lo, S.mn[w][c]); hi = fmaxf(hi, S.mx[w][c]); }
-        mn[c] = lo; mx[c] = hi;
+        ext.mn[c] = lo; ext.mx[c] = hi;
     }
-    const SplitChoice sc = choose_split_scalar(k.lo, k.hi, mn, mx);
+    const SplitChoice sc = choose_split_scalar(k.lo, k.hi, ext.mn, ext.mx);
     const int ax = sc.ax;
     const float cut = sc.cut;
 
-    // ---- pass 2: lim1 = #(< cut), lim2 = #(<= cut), max{v < cut}, min{v > cut} ----
-    int lt = 0, le = 0;
-    float maxlt = -INFINITY, mingt = INFINITY;
+    // ---- pass 2: the counts against the cut ----
+    CutCount cc;
     for (int base = tid; base < count; base += T * E) {
         float v[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) v[e] = comp(a[min(base + e * T, count - 1)], ax);
 #pragma unroll
         for (int e = 0; e < E; ++e)
-            if (base + e * T < count) {
-                lt += v[e] < cut;
-                le += v[e] <= cut;
-                if (v[e] < cut) maxlt = fmaxf(maxlt, v[e]);
-                if (v[e] > cut) mingt = fminf(mingt, v[e]);
-            }
+            if (base + e * T < count) cc.add(v[e], cut);
     }
-    {
-        lt = wave_sum(lt);
-        le = wave_sum(le);
-        maxlt = wave_max(maxlt);
-        mingt = wave_min(mingt);
-    }
-    if (lane == 0) { S.ia[wave] = lt; S.ib[wave] = le; S.fa[wave] = maxlt; S.fb[wave] = mingt; }
+    cc.wave_reduce();
+    if (lane == 0) { S.ia[wave] = cc.lt; S.ib[wave] = cc.le; S.fa[wave] = cc.maxlt; S.fb[wave] = cc.mingt; }
     __syncthreads();
-    lt = 0; le = 0; maxlt = -INFINITY; mingt = INFINITY;
+    cc = CutCount();
     for (int w = 0; w < W; ++w) {
-        lt += S.ia[w]; le += S.ib[w];
-        maxlt = fmaxf(maxlt, S.fa[w]); mingt = fminf(mingt, S.fb[w]);
+        cc.lt += S.ia[w]; cc.le += S.ib[w];
+        cc.maxlt = fmaxf(cc.maxlt, S.fa[w]); cc.mingt = fminf(cc.mingt, S.fb[w]);
     }
-    const int lim1 = lt, lim2 = le;
+    const int lim1 = cc.lt, lim2 = cc.le;
 
-    // ---- the two Hoare sweeps (planeSplit, nanoflann.hpp:1016-1043) in closed form ----
-    // sweep 0: [0,count) by (v < cut); sweep 1: [lim1,count) by (v <= cut).  In sweep s the elements left of the
-    // boundary that fail the predicate ("misplaced left", ascending) pair with the elements right of it that satisfy
-    // it ("misplaced right", descending): i-th with i-th.
+    // ---- the two Hoare sweeps (sweep_flags) ----
     for (int sweep = 0; sweep < 2; ++sweep) {
-        const int from = sweep == 0 ? 0 : lim1, bound = sweep == 0 ? lim1 : lim2;
         int offL = 0, offR = 0;
         int slab = 0;
-        for (int s0 = from; s0 < count; s0 += T * E, ++slab) {
+        for (int s0 = sweep_from(sweep, lim1); s0 < count; s0 += T * E, ++slab) {
             // wave w owns records [s0 + w*64*E, +64*E); lane reads record  wbase + e*64 + lane  (coalesced), so the
             // position order inside the wave is e-major and ranks come from E ballots
             const int wbase = s0 + wave * (64 * E);
@@ -399,14 +505,10 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
                     const int p = wbase + e * 64 + lane;
-                    bool isL = false, isR = false;
-                    if (p < count) {
-                        const bool keep_left = sweep == 0 ? (v[e] < cut) : (v[e] <= cut);
-                        isL = p < bound && !keep_left;
-                        isR = p >= bound && keep_left;
-                    }
-                    bL[e] = __ballot(isL);
-                    bR[e] = __ballot(isR);
+                    Misplaced f = {false, false};
+                    if (p < count) f = sweep_flags(sweep, p, lim1, lim2, v[e] < cut, v[e] <= cut);
+                    bL[e] = __ballot(f.L);
+                    bR[e] = __ballot(f.R);
                 }
             }
             int wL = 0, wR = 0;
@@ -421,14 +523,12 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
                 tot += cw;
             }
             int rL = offL + (pre & 0xffff), rR = offR + (pre >> 16);
-            const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int p = wbase + e * 64 + lane;
-                if ((bL[e] >> lane) & 1ull) gstore(t.posL + k.l + rL + __popcll(bL[e] & lt_mask), p);
-                if ((bR[e] >> lane) & 1ull) gstore(t.posR + k.l + rR + __popcll(bR[e] & lt_mask), p);
-                rL += __popcll(bL[e]);
-                rR += __popcll(bR[e]);
+                int rank;
+                if (ballot_rank(bL[e], lane, rL, &rank)) gstore(t.posL + k.l + rank, p);
+                if (ballot_rank(bR[e], lane, rR, &rank)) gstore(t.posR + k.l + rank, p);
             }
             offL += tot & 0xffff;
             offR += tot >> 16;
@@ -445,10 +545,10 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
     }
 
     if (tid == 0) {
+        // (kids[small] below indexes the pair at run time, which keeps both tasks in scratch memory: the kernel's 112 bytes per lane are
+        //  these 2 x 48 and their alignment, not the split choice; only this one lane ever touches them)
         BuildTask kids[2];
-        int id;
-        emit_inner(Q, t, k, ax, cut, lim1, lim2, maxlt, mingt, kids, &id);
-        link_to_parent(t, k, id);
+        emit_inner(t, k, ax, cut, cc, kids);
         int sp = s_sp;
         bool have = false;
         const int n0 = kids[0].r - kids[0].l, n1 = kids[1].r - kids[1].l;
@@ -461,12 +561,12 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
             if (sp < kStragglerStack)
                 s_stack[sp++] = kids[small ^ 1];
             else
-                Q.flags[1] = 1;
+                Q.flags[kFlagQueueOverflow] = 1;
         } else {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 if (kids[s].r - kids[s].l <= kMid)
-                    push_small_task(Q, kids[s]);
+                    push_task(Q, kids[s], kids[s].level);
                 else {
                     s_cur = kids[s];  // carry on with the one big child
                     have = true;
@@ -486,7 +586,7 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
   }
 }
 
-// ---- flat subtree kernel: one workgroup per node of <= kSmall points, ONE THREAD PER POINT POSITION --------------------------------
+// ---- flat kernel (build_flat_kernel): one workgroup per node of <= kSmall points, ONE THREAD PER POINT POSITION --------------------
 // A wave-per-node kernel ran a subtree's ~31 splits one after the other (80-90 us for the ~1 400 subtrees of a 180 000-point
 // pyramid: a chain of LDS round trips at one or two waves per SIMD).  Here every round advances ALL live segments of the node at
 // once: thread i owns position i, carries its segment's descriptor (range, incoming box, parent link) in registers, and the
@@ -496,9 +596,7 @@ __global__ __launch_bounds__(kBigThreads) void build_level_kernel(const BuildTre
 // through LDS) minus the scan value at the segment's first position.  A round is ~12 workgroup barriers whatever the number of
 // segments, and a subtree is finished in (height + 1) rounds: 6-7 for the balanced trees of real clouds.
 struct FlatAcc {
-    unsigned mn[3], mx[3];     // ordered-uint extents
-    int lt, le;
-    unsigned maxlt, mingt;     // ordered-uint
+    OrdAcc acc;
     int base[2], endL[2];      // per sweep: packed exclusive scan (L | R << 16) at the segment start; inclusive L rank at its last position
 };
 
@@ -516,7 +614,7 @@ __global__ __launch_bounds__(kSmall) void build_flat_kernel(const BuildTree* __r
     __shared__ int s_depth;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int n_tasks = min(Q.small_cnt[0], Q.small_cap);
+    const int n_tasks = min(Q.cnt->small, Q.small_cap);
 
     for (int ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
         const BuildTask k = Q.small_q[ti];
@@ -536,11 +634,7 @@ __global__ __launch_bounds__(kSmall) void build_flat_kernel(const BuildTree* __r
         if (tid == 0) s_depth = 0;
         if (total <= kLeafMax) {  // the node itself is a leaf
             if (tid == 0) {
-                t.nodes[2 * k.l] = make_int4(k.l, k.l + total, 0, 0);
-                const int ref = leaf_ref(k.l, total);
-                if (parent < 0) t.meta->root = ref;
-                else if (side == 0) atomicOr(&t.nodes[parent].x, ref);
-                else t.nodes[parent].y = ref;
+                emit_leaf(t, k.l, k.r, parent, side);
                 atomicMax(&t.meta->depth, level);
             }
             __syncthreads();
@@ -548,12 +642,7 @@ __global__ __launch_bounds__(kSmall) void build_flat_kernel(const BuildTree* __r
         }
         for (;;) {
             // ---- 0: leaders reset their segment's accumulators ----
-            if (live && tid == s) {
-                FlatAcc& a = s_accs[s >> 3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { a.mn[c] = 0xffffffffu; a.mx[c] = 0u; }
-                a.lt = 0; a.le = 0; a.maxlt = 0u; a.mingt = 0xffffffffu;
-            }
+            if (live && tid == s) s_accs[s >> 3].acc.reset();
             if (tid == 0) { s_live[round & 1] = 0; s_mis[0] = 0; s_mis[1] = 0; }
             __syncthreads();
             // ---- 1: tight extents ----
@@ -561,65 +650,49 @@ __global__ __launch_bounds__(kSmall) void build_flat_kernel(const BuildTree* __r
             //  the first rounds, where the segments are long -- it reduces in registers and sends one atomic per quantity)
             const bool uni = __all(live) && __all(s == __builtin_amdgcn_readfirstlane(s));
             float px = 0.f, py = 0.f, pz = 0.f;
-            if (live) { px = s_p[0][tid]; py = s_p[1][tid]; pz = s_p[2][tid]; }
-            if (uni) {
-                const float mnx = wave_min(px), mxx = wave_max(px), mny = wave_min(py), mxy = wave_max(py), mnz = wave_min(pz), mxz = wave_max(pz);
-                if (lane < 3) {
-                    atomicMin(&s_accs[s >> 3].mn[lane], f2ord(lane == 0 ? mnx : (lane == 1 ? mny : mnz)));
-                    atomicMax(&s_accs[s >> 3].mx[lane], f2ord(lane == 0 ? mxx : (lane == 1 ? mxy : mxz)));
-                }
-            } else if (live) {
-                FlatAcc& a = s_accs[s >> 3];
-                atomicMin(&a.mn[0], f2ord(px)); atomicMax(&a.mx[0], f2ord(px));
-                atomicMin(&a.mn[1], f2ord(py)); atomicMax(&a.mx[1], f2ord(py));
-                atomicMin(&a.mn[2], f2ord(pz)); atomicMax(&a.mx[2], f2ord(pz));
+            Extent3 ext;
+            if (live) {
+                px = s_p[0][tid]; py = s_p[1][tid]; pz = s_p[2][tid];
+                ext.add(px, py, pz);
             }
+            if (uni) {
+                ext.wave_reduce();
+                s_accs[s >> 3].acc.merge_wave(ext, lane);
+            } else if (live)
+                s_accs[s >> 3].acc.merge(ext);
             __syncthreads();
             // ---- 2: split choice (every thread of the segment, identical), counts against the cut ----
             int ax = 0;
             float cut = 0.f, v = 0.f;
             if (live) {
-                const FlatAcc& a = s_accs[s >> 3];
-                float mn[3], mx[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { mn[c] = ord2f(a.mn[c]); mx[c] = ord2f(a.mx[c]); }
-                const SplitChoice sc = choose_split(lo, hi, mn, mx);
+                ext = s_accs[s >> 3].acc.extent();
+                const SplitChoice sc = choose_split(lo, hi, ext.mn, ext.mx);
                 ax = sc.ax;
                 cut = sc.cut;
                 v = ax == 0 ? px : (ax == 1 ? py : pz);
             }
+            // (no atomic for a neutral value: they are what the later rounds, with their short segments, mostly hold)
             if (uni) {
-                const int lt = (int)__popcll(__ballot(v < cut)), le = (int)__popcll(__ballot(v <= cut));
-                const float ml = wave_max(v < cut ? v : -INFINITY), mg = wave_min(v > cut ? v : INFINITY);
-                if (lane == 0) {
-                    FlatAcc& w = s_accs[s >> 3];
-                    if (lt) { atomicAdd(&w.lt, lt); atomicMax(&w.maxlt, f2ord(ml)); }
-                    if (le) atomicAdd(&w.le, le);
-                    if (mg < INFINITY) atomicMin(&w.mingt, f2ord(mg));
-                }
+                const CutCount cw = CutCount::of_wave(v, cut);
+                if (lane == 0) s_accs[s >> 3].acc.merge_skipping_neutral(cw);
             } else if (live) {
-                FlatAcc& w = s_accs[s >> 3];
-                if (v < cut) { atomicAdd(&w.lt, 1); atomicMax(&w.maxlt, f2ord(v)); }
-                if (v <= cut) atomicAdd(&w.le, 1);
-                if (v > cut) atomicMin(&w.mingt, f2ord(v));
+                CutCount c1;
+                c1.add(v, cut);
+                s_accs[s >> 3].acc.merge_skipping_neutral(c1);
             }
             __syncthreads();
-            int lim1 = 0, lim2 = 0;
-            float maxlt = 0.f, mingt = 0.f;
-            if (live) {
-                const FlatAcc& a = s_accs[s >> 3];
-                lim1 = a.lt; lim2 = a.le; maxlt = ord2f(a.maxlt); mingt = ord2f(a.mingt);
-            }
+            CutCount cc;
+            if (live) cc = s_accs[s >> 3].acc.counts();
+            const int lim1 = cc.lt, lim2 = cc.le;
             const int q = tid - s;
-            // ---- the two Hoare sweeps (planeSplit, nanoflann.hpp:1016-1043) in closed form ----
+            // ---- the two Hoare sweeps (sweep_flags) ----
 #pragma unroll
             for (int sweep = 0; sweep < 2; ++sweep) {
-                const int from = sweep == 0 ? 0 : lim1, bound = sweep == 0 ? lim1 : lim2;
                 bool isL = false, isR = false;
-                if (live && q >= from) {
-                    const bool keep_left = sweep == 0 ? (v < cut) : (v <= cut);
-                    isL = q < bound && !keep_left;
-                    isR = q >= bound && keep_left;
+                if (live) {
+                    const Misplaced f = sweep_flags(sweep, q, lim1, lim2, v < cut, v <= cut);
+                    isL = f.L;
+                    isR = f.R;
                 }
                 const unsigned long long bL = __ballot(isL), bR = __ballot(isR);
                 if (lane == 0) {
@@ -657,36 +730,24 @@ __global__ __launch_bounds__(kSmall) void build_flat_kernel(const BuildTree* __r
             }
             // ---- emit the node, descend into the child this position now belongs to ----
             if (live) {
-                const int count = e - s, half = count / 2;
-                const int idx = lim1 > half ? lim1 : (lim2 < half ? lim2 : half);
-                const int id = 2 * (k.l + s + idx) - 1;
+                const NodeSplit ns = split_node(k.l + s, e - s, cc, cut);
                 if (tid == s) {
-                    const float divlow = idx > lim1 ? cut : maxlt;
-                    const float divhigh = idx < lim2 ? cut : mingt;
-                    t.nodes[id] = make_int4((int)((unsigned)ax << 30), 0, __float_as_int(divlow), __float_as_int(divhigh));
-                    if (parent < 0) t.meta->root = id;
-                    else if (side == 0) atomicOr(&t.nodes[parent].x, id);
-                    else t.nodes[parent].y = id;
+                    store_inner(t, ns, ax);
+                    link_to_parent(t, parent, side, ns.id);
                 }
-                if (q < idx) {
-                    e = s + idx; side = 0;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) hi[c] = c == ax ? cut : hi[c];
-                } else {
-                    s = s + idx; side = 1;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) lo[c] = c == ax ? cut : lo[c];
-                }
-                parent = id;
+                side = q < ns.idx ? 0 : 1;
+                if (side == 0)
+                    e = s + ns.idx;
+                else
+                    s = s + ns.idx;
+                cut_box(lo, hi, side, ax, cut);
+                parent = ns.id;
                 level += 1;
             }
             __syncthreads();  // the parents' records are in memory before any child links to them
             if (live && e - s <= kLeafMax) {
                 if (tid == s) {
-                    t.nodes[2 * (k.l + s)] = make_int4(k.l + s, k.l + e, 0, 0);
-                    const int ref = leaf_ref(k.l + s, e - s);
-                    if (side == 0) atomicOr(&t.nodes[parent].x, ref);
-                    else t.nodes[parent].y = ref;
+                    emit_leaf(t, k.l + s, k.l + e, parent, side);
                     atomicMax(&s_depth, level);
                 }
                 live = false;
@@ -716,9 +777,7 @@ constexpr int kMidSlabs = kMid / kSlab + kMidSegs;  // sum of ceil(len / kSlab)
 struct MidSeg {
     int start, end, parent, side, level, slab0;
     float lo[3], hi[3];
-    unsigned mn[3], mx[3];  // ordered-uint accumulators (LDS atomics)
-    int lt, le;
-    unsigned maxlt, mingt;
+    OrdAcc acc;  // (LDS atomics)
     int ax;
     float cut;
     int mis[2];  // misplaced records per sweep
@@ -731,8 +790,7 @@ struct MidSlab {
 __device__ __forceinline__ void mid_seg_init(MidSeg& g, int start, int end, int parent, int side, int level, int slab0)
 {
     g.start = start; g.end = end; g.parent = parent; g.side = side; g.level = level; g.slab0 = slab0;
-    for (int a = 0; a < 3; ++a) { g.mn[a] = 0xffffffffu; g.mx[a] = 0u; }
-    g.lt = 0; g.le = 0; g.maxlt = 0u; g.mingt = 0xffffffffu;
+    g.acc.reset();
     g.mis[0] = 0; g.mis[1] = 0;
 }
 
@@ -748,19 +806,16 @@ struct MidPlanes {
 __device__ __forceinline__ void mid_flags(const float* V /* split-axis plane + g0 */, int q0, int q1, int lane, float cut, int sweep, int lim1, int lim2,
                                           unsigned long long (&bL)[8], unsigned long long (&bR)[8])
 {
-    const int from = sweep == 0 ? 0 : lim1, bound = sweep == 0 ? lim1 : lim2;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int q = q0 + e * 64 + lane;
-        bool isL = false, isR = false;
-        if (q < q1 && q >= from) {
+        Misplaced f = {false, false};
+        if (q < q1 && q >= sweep_from(sweep, lim1)) {  // (no LDS read for a position the sweep does not look at)
             const float v = V[q];
-            const bool keep_left = sweep == 0 ? (v < cut) : (v <= cut);
-            isL = q < bound && !keep_left;
-            isR = q >= bound && keep_left;
+            f = sweep_flags(sweep, q, lim1, lim2, v < cut, v <= cut);
         }
-        bL[e] = __ballot(isL);
-        bR[e] = __ballot(isR);
+        bL[e] = __ballot(f.L);
+        bR[e] = __ballot(f.R);
     }
 }
 
@@ -777,8 +832,7 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
     __shared__ unsigned long long s_ball[kMidSlabs][16];  // the slab's 8 + 8 flag ballots of the current sweep (written in C, reused in D and E)
     __shared__ int nseg[2], nslab[2], s_mis[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const int n_tasks = min(Q.small_cnt[1], Q.q_cap);
+    const int n_tasks = min(Q.cnt->mid, Q.q_cap);
 
     for (int ti = blockIdx.x; ti < n_tasks; ti += gridDim.x) {
         const BuildTask& k = Q.mid_q[ti];
@@ -811,63 +865,36 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
             // ---- A: tight extents of every segment ----
             for (int si = wave; si < n_sl; si += W) {
                 const int gi = SL[si].seg, s0 = SL[si].start, s1 = SL[si].end;
-                float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+                Extent3 ext;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int i = s0 + e * 64 + lane;
-                    if (i < s1) {
-                        const float x = P.c[0][i], y = P.c[1][i], z = P.c[2][i];
-                        mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
-                        mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
-                        mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
-                    }
+                    if (i < s1) ext.add(P.c[0][i], P.c[1][i], P.c[2][i]);
                 }
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    {
-                        mn[c] = wave_min(mn[c]);
-                        mx[c] = wave_max(mx[c]);
-                    }
-                if (lane < 3) {
-                    atomicMin(&G[gi].mn[lane], f2ord(lane == 0 ? mn[0] : (lane == 1 ? mn[1] : mn[2])));
-                    atomicMax(&G[gi].mx[lane], f2ord(lane == 0 ? mx[0] : (lane == 1 ? mx[1] : mx[2])));
-                }
+                ext.wave_reduce();
+                G[gi].acc.merge_wave(ext, lane);
             }
             __syncthreads();
             // ---- B: split choice (recomputed by every wave of the segment, identical), counts against the cut ----
             for (int si = wave; si < n_sl; si += W) {
                 const int gi = SL[si].seg, s0 = SL[si].start, s1 = SL[si].end;
-                float mn[3], mx[3], blo[3], bhi[3];
+                const Extent3 ext = G[gi].acc.extent();
+                float blo[3], bhi[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { mn[c] = ord2f(G[gi].mn[c]); mx[c] = ord2f(G[gi].mx[c]); blo[c] = G[gi].lo[c]; bhi[c] = G[gi].hi[c]; }
-                const SplitChoice sc = choose_split(blo, bhi, mn, mx);
+                for (int c = 0; c < 3; ++c) { blo[c] = G[gi].lo[c]; bhi[c] = G[gi].hi[c]; }
+                const SplitChoice sc = choose_split(blo, bhi, ext.mn, ext.mx);
                 const int ax = sc.ax;
                 const float cut = sc.cut;
                 const float* V = P.axis(ax);
-                int lt = 0, le = 0;
-                float maxlt = -INFINITY, mingt = INFINITY;
+                CutCount cc;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int i = s0 + e * 64 + lane;
-                    if (i < s1) {
-                        const float v = V[i];
-                        lt += v < cut;
-                        le += v <= cut;
-                        if (v < cut) maxlt = fmaxf(maxlt, v);
-                        if (v > cut) mingt = fminf(mingt, v);
-                    }
+                    if (i < s1) cc.add(V[i], cut);
                 }
-                {
-                    lt = wave_sum(lt);
-                    le = wave_sum(le);
-                    maxlt = wave_max(maxlt);
-                    mingt = wave_min(mingt);
-                }
+                cc.wave_reduce();
                 if (lane == 0) {
-                    atomicAdd(&G[gi].lt, lt);
-                    atomicAdd(&G[gi].le, le);
-                    atomicMax(&G[gi].maxlt, f2ord(maxlt));
-                    atomicMin(&G[gi].mingt, f2ord(mingt));
+                    G[gi].acc.merge(cc);
                     G[gi].ax = ax;    // (same value from every slab of the segment)
                     G[gi].cut = cut;
                 }
@@ -880,7 +907,7 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
                     const int gi = SL[si].seg;
                     const int g0 = G[gi].start;
                     unsigned long long bL[8], bR[8];
-                    mid_flags(P.axis(G[gi].ax) + g0, SL[si].start - g0, SL[si].end - g0, lane, G[gi].cut, sweep, G[gi].lt, G[gi].le, bL, bR);
+                    mid_flags(P.axis(G[gi].ax) + g0, SL[si].start - g0, SL[si].end - g0, lane, G[gi].cut, sweep, G[gi].acc.lt, G[gi].acc.le, bL, bR);
                     int wL = 0, wR = 0;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { wL += __popcll(bL[e]); wR += __popcll(bR[e]); }
@@ -907,9 +934,8 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
                     int rR = pre;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const unsigned long long b = s_ball[si][8 + e];
-                        if ((b >> lane) & 1ull) posR[g0 + rR + __popcll(b & lt_mask)] = (short)(SL[si].start - g0 + e * 64 + lane);
-                        rR += __popcll(b);
+                        int rank;
+                        if (ballot_rank(s_ball[si][8 + e], lane, rR, &rank)) posR[g0 + rank] = (short)(SL[si].start - g0 + e * 64 + lane);
                     }
                 }
                 __syncthreads();
@@ -924,10 +950,10 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
                     for (int j = 0; j < si - sl0; ++j) rL += __builtin_amdgcn_readlane(mine, j) & 0xffff;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const unsigned long long b = s_ball[si][e];
-                        if ((b >> lane) & 1ull) {
-                            const int q = g0 + SL[si].start - g0 + e * 64 + lane;
-                            const int pr = g0 + posR[g0 + m - 1 - (rL + __popcll(b & lt_mask))];
+                        int rank;
+                        if (ballot_rank(s_ball[si][e], lane, rL, &rank)) {
+                            const int q = SL[si].start + e * 64 + lane;
+                            const int pr = g0 + posR[g0 + m - 1 - rank];
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
                                 const float x = P.c[c][q], y = P.c[c][pr];
@@ -935,7 +961,6 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
                                 P.c[c][q] = y;
                             }
                         }
-                        rL += __popcll(b);
                     }
                 }
                 __syncthreads();
@@ -944,47 +969,32 @@ __global__ __launch_bounds__(kMidThreads) void build_mid_kernel(const BuildTree*
             if (tid == 0) { s_mis[0] = 0; s_mis[1] = 0; }
             if (tid < n_sg) {
                 const MidSeg& g = G[tid];
-                const int count = g.end - g.start, lim1 = g.lt, lim2 = g.le, ax = g.ax;
+                const int ax = g.ax;
                 const float cut = g.cut;
-                const int half = count / 2;
-                const int idx = lim1 > half ? lim1 : (lim2 < half ? lim2 : half);
-                const int id = 2 * (k_l + g.start + idx) - 1;
-                const float divlow = idx > lim1 ? cut : ord2f(g.maxlt);
-                const float divhigh = idx < lim2 ? cut : ord2f(g.mingt);
-                t.nodes[id] = make_int4((int)((unsigned)ax << 30), 0, __float_as_int(divlow), __float_as_int(divhigh));
-                if (g.parent < 0) t.meta->root = id;
-                else if (g.side == 0) atomicOr(&t.nodes[g.parent].x, id);
-                else t.nodes[g.parent].y = id;
+                const NodeSplit ns = split_node(k_l + g.start, g.end - g.start, g.acc.counts(), cut);
+                store_inner(t, ns, ax);
+                link_to_parent(t, g.parent, g.side, ns.id);
 #pragma unroll
                 for (int side = 0; side < 2; ++side) {
-                    const int cl = side == 0 ? g.start : g.start + idx, cr = side == 0 ? g.start + idx : g.end;
-                    float clo[3], chi[3];
+                    const int cl = side == 0 ? g.start : g.start + ns.idx, cr = side == 0 ? g.start + ns.idx : g.end;
+                    BuildTask b;  // the child as a task; it stays in this workgroup as a segment while it is above kSmall points
+                    b.tree = k_tree; b.l = k_l + cl; b.r = k_l + cr; b.parent = ns.id; b.side = side; b.level = g.level + 1;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        clo[c] = (side == 1 && c == ax) ? cut : g.lo[c];
-                        chi[c] = (side == 0 && c == ax) ? cut : g.hi[c];
-                    }
+                    for (int c = 0; c < 3; ++c) { b.lo[c] = g.lo[c]; b.hi[c] = g.hi[c]; }
+                    cut_box(b.lo, b.hi, side, ax, cut);
                     if (cr - cl > kSmall) {
-                        const int ns = (cr - cl + kSlab - 1) / kSlab;
-                        const int slot = atomicAdd(&nseg[cur ^ 1], 1), sl0 = atomicAdd(&nslab[cur ^ 1], ns);
+                        const int n_sl_ch = (cr - cl + kSlab - 1) / kSlab;
+                        const int slot = atomicAdd(&nseg[cur ^ 1], 1), sl0 = atomicAdd(&nslab[cur ^ 1], n_sl_ch);
                         MidSeg& ch = segs[cur ^ 1][slot];
-                        mid_seg_init(ch, cl, cr, id, side, g.level + 1, sl0);
+                        mid_seg_init(ch, cl, cr, b.parent, side, b.level, sl0);
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) { ch.lo[c] = clo[c]; ch.hi[c] = chi[c]; }
-                        for (int j = 0; j < ns; ++j) {
+                        for (int c = 0; c < 3; ++c) { ch.lo[c] = b.lo[c]; ch.hi[c] = b.hi[c]; }
+                        for (int j = 0; j < n_sl_ch; ++j) {
                             MidSlab& sl = slabs[cur ^ 1][sl0 + j];
                             sl.seg = slot; sl.start = cl + j * kSlab; sl.end = min(cr, cl + (j + 1) * kSlab);
                         }
-                    } else {
-                        const int slot = atomicAdd(Q.small_cnt, 1);
-                        if (slot < Q.small_cap) {
-                            BuildTask& b = Q.small_q[slot];
-                            b.tree = k_tree; b.l = k_l + cl; b.r = k_l + cr; b.parent = id; b.side = side; b.level = g.level + 1;
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) { b.lo[c] = clo[c]; b.hi[c] = chi[c]; }
-                        } else
-                            Q.flags[1] = 1;
-                    }
+                    } else
+                        push_task(Q, b, b.level);
                 }
             }
             __syncthreads();
@@ -1020,10 +1030,8 @@ struct HugeTask {
     int32_t* posL;
     int32_t* posR;
     int chunk0, nchunks;
-    unsigned mn[3], mx[3];  // ordered-uint accumulators (filled by the parent's pass E / from the bounding box)
-    int lt, le;
-    unsigned maxlt, mingt;  // ordered-uint
-    int kid[2];             // slots of the children among the next level's chunked tasks, -1 = not chunked
+    OrdAcc acc;             // extents: filled by the parent's pass E / from the bounding box; counts: pass A
+    int kid[2];            // slots of the children among the next level's chunked tasks, -1 = not chunked
     int m0, m1;             // swap pairs of sweeps 0 / 1 (passes B / D, by the workgroup of the node's last chunk)
 };
 
@@ -1034,10 +1042,16 @@ struct alignas(32) ChunkDesc {
     int32_t task, first, count, pad;  // records [first, first+count) relative to the node's first record; task < 0 = no chunk
 };
 
+// The per-level counters as they lie in the plan's head block (TreeSetPlan::off_hcnt; zero after the head copy).
+struct HugeCounters {
+    int32_t ntasks[kHugeLevels + 2];   // chunked tasks of a level
+    int32_t nchunks[kHugeLevels + 2];  // their chunks
+};
+
 struct HugeState {
     HugeTask* tasks[2];
-    int32_t* ntasks;       // [kHugeLevels + 1]
-    int32_t* nchunks;      // [kHugeLevels + 1] total chunks of the level
+    int32_t* ntasks;       // HugeCounters::ntasks
+    int32_t* nchunks;      // HugeCounters::nchunks
     int32_t* c_lt;         // [max_chunks] records < cut of a chunk (pass A)
     int32_t* c_mL;         // [max_chunks] misplaced-left count of a chunk, sweep 1 (passes B + C)
     int32_t* c_mR;
@@ -1051,19 +1065,17 @@ struct HugeState {
 __device__ __forceinline__ int route_task(const BuildQueues& Q, const HugeState& H, const BuildTree& tr, const BuildTask& t, int next_level)
 {
     if (t.r - t.l > kHuge && next_level < H.levels) {
-        const int slot = atomicAdd(&H.ntasks[next_level], 1);
-        if (slot < H.cap_tasks) {
+        const int slot = take_slot(&H.ntasks[next_level], H.cap_tasks, Q.flags);
+        if (slot >= 0) {
             HugeTask& h = H.tasks[next_level & 1][slot];
             h.k = t;
             h.pts = tr.pts + t.l;
             h.cls = tr.cls + t.l;
             h.posL = tr.posL + t.l;
             h.posR = tr.posR + t.l;
-            for (int a = 0; a < 3; ++a) { h.mn[a] = 0xffffffffu; h.mx[a] = 0u; }
-            return slot;
+            h.acc.reset_extent();  // (the counts: huge_plan_block)
         }
-        Q.flags[1] = 1;
-        return -1;
+        return slot;
     }
     push_task(Q, t, next_level);
     return -1;
@@ -1099,7 +1111,7 @@ __device__ void huge_plan_block(const HugeState& H, int level)
             HugeTask& t = tasks[i];
             t.chunk0 = c0;
             t.nchunks = nc;
-            t.lt = 0; t.le = 0; t.maxlt = 0u; t.mingt = 0xffffffffu;
+            t.acc.reset_counts();  // (the extents are the parent's to fill: route_task)
             t.kid[0] = -1; t.kid[1] = -1;
             t.m0 = 0; t.m1 = 0;
         }
@@ -1146,7 +1158,7 @@ __device__ __forceinline__ void huge_root_block(const BuildTree* __restrict__ tr
         for (int a = 0; a < 3; ++a) { k.lo[a] = m.lo[a]; k.hi[a] = m.hi[a]; }
         const int slot = route_task(Q, H, t, k, 0);
         if (slot >= 0)  // the extents of a root's records ARE its bounding box (same reduction: init_points_kernel)
-            for (int a = 0; a < 3; ++a) { H.tasks[0][slot].mn[a] = t.bbox_ord[a]; H.tasks[0][slot].mx[a] = t.bbox_ord[3 + a]; }
+            for (int a = 0; a < 3; ++a) { H.tasks[0][slot].acc.mn[a] = t.bbox_ord[a]; H.tasks[0][slot].acc.mx[a] = t.bbox_ord[3 + a]; }
     }
     __threadfence();
     __syncthreads();
@@ -1166,9 +1178,8 @@ __device__ __forceinline__ ChunkDesc load_desc(const HugeState& H, int level, in
 
 __device__ __forceinline__ SplitChoice huge_split(const HugeTask& t)
 {
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = ord2f(t.mn[a]); mx[a] = ord2f(t.mx[a]); }
-    return choose_split(t.k.lo, t.k.hi, mn, mx);
+    const Extent3 ext = t.acc.extent();
+    return choose_split(t.k.lo, t.k.hi, ext.mn, ext.mx);
 }
 
 // sum of one int2 per thread over the workgroup (256 threads), result in every thread; s_red = 8 ints of LDS
@@ -1182,6 +1193,9 @@ __device__ __forceinline__ int2 block_sum2(int x, int y, int* s_red)
     return make_int2(s_red[0] + s_red[2] + s_red[4] + s_red[6], s_red[1] + s_red[3] + s_red[5] + s_red[7]);
 }
 
+// A record's relation to the cut, kept as one byte per record for passes B to E: 0 = below, 1 = equal, 2 = above (chunk_flags reads it back).
+__device__ __forceinline__ uint8_t class_byte(bool is_lt, bool is_le) { return (uint8_t)(is_lt ? 0 : (is_le ? 1 : 2)); }
+
 // pass A
 __device__ __forceinline__ void huge_classify_chunk(const HugeState& H, int level, int chunk)
 {
@@ -1194,41 +1208,29 @@ __device__ __forceinline__ void huge_classify_chunk(const HugeState& H, int leve
     for (int e = 0; e < kChunk / 256; ++e) p[e] = gload(d.pts + min(e * 256 + (int)threadIdx.x, d.count - 1));  // all in flight
     HugeTask& t = H.tasks[level & 1][d.task];
     const SplitChoice sc = huge_split(t);
-    int lt = 0, le = 0;
-    float maxlt = -INFINITY, mingt = INFINITY;
+    CutCount cc;
 #pragma unroll
     for (int e = 0; e < kChunk / 256; ++e) {
         const int i = e * 256 + threadIdx.x;
         if (i < d.count) {
             const float v = comp(p[e], sc.ax);
-            const bool is_lt = v < sc.cut, is_le = v <= sc.cut;
-            lt += is_lt;
-            le += is_le;
-            if (is_lt) maxlt = fmaxf(maxlt, v);
-            if (v > sc.cut) mingt = fminf(mingt, v);
-            gstore(d.cls + i, (uint8_t)(is_lt ? 0 : (is_le ? 1 : 2)));
+            cc.add(v, sc.cut);
+            gstore(d.cls + i, class_byte(v < sc.cut, v <= sc.cut));
         }
     }
-    {
-        lt = wave_sum(lt);
-        le = wave_sum(le);
-        maxlt = wave_max(maxlt);
-        mingt = wave_min(mingt);
-    }
+    cc.wave_reduce();
     if ((threadIdx.x & 63) == 0) {
-        s_i[threadIdx.x >> 6][0] = lt; s_i[threadIdx.x >> 6][1] = le;
-        s_f[threadIdx.x >> 6][0] = maxlt; s_f[threadIdx.x >> 6][1] = mingt;
+        s_i[threadIdx.x >> 6][0] = cc.lt; s_i[threadIdx.x >> 6][1] = cc.le;
+        s_f[threadIdx.x >> 6][0] = cc.maxlt; s_f[threadIdx.x >> 6][1] = cc.mingt;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int clt = s_i[0][0] + s_i[1][0] + s_i[2][0] + s_i[3][0];
-        H.c_lt[chunk] = clt;
-        atomicAdd(&t.lt, clt);
-        atomicAdd(&t.le, s_i[0][1] + s_i[1][1] + s_i[2][1] + s_i[3][1]);
-        const float ml = fmaxf(fmaxf(s_f[0][0], s_f[1][0]), fmaxf(s_f[2][0], s_f[3][0]));
-        const float mg = fminf(fminf(s_f[0][1], s_f[1][1]), fminf(s_f[2][1], s_f[3][1]));
-        if (ml > -INFINITY) atomicMax(&t.maxlt, f2ord(ml));
-        if (mg < INFINITY) atomicMin(&t.mingt, f2ord(mg));
+        cc.lt = s_i[0][0] + s_i[1][0] + s_i[2][0] + s_i[3][0];
+        cc.le = s_i[0][1] + s_i[1][1] + s_i[2][1] + s_i[3][1];
+        cc.maxlt = fmaxf(fmaxf(s_f[0][0], s_f[1][0]), fmaxf(s_f[2][0], s_f[3][0]));
+        cc.mingt = fminf(fminf(s_f[0][1], s_f[1][1]), fminf(s_f[2][1], s_f[3][1]));
+        H.c_lt[chunk] = cc.lt;
+        t.acc.merge_skipping_neutral(cc);
     }
 }
 
@@ -1278,16 +1280,10 @@ __device__ __forceinline__ void chunk_flags(const int (&cl)[8], const ChunkDesc&
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int p = d.first + wave * 512 + e * 64 + lane;  // within the node
-        bool isL, isR;
-        if (S == 0) {
-            isL = cl[e] > 0 && p < lim1;
-            isR = cl[e] == 0 && p >= lim1;
-        } else {
-            isL = cl[e] == 2 && p >= lim1 && p < lim2;
-            isR = cl[e] == 1 && p >= lim2;
-        }
-        bL[e] = __ballot(isL);
-        bR[e] = __ballot(isR);
+        // (-1, past the end of the node: neither below nor equal, and p >= lim2 there, so neither flag)
+        const Misplaced f = sweep_flags(S, p, lim1, lim2, cl[e] == 0, cl[e] == 0 || cl[e] == 1);
+        bL[e] = __ballot(f.L);
+        bR[e] = __ballot(f.R);
     }
 }
 
@@ -1303,7 +1299,7 @@ __device__ __forceinline__ void huge_scatter_chunk(const HugeState& H, int level
     int cl[8];
     chunk_classes(d, wave, lane, cl);  // (in flight under the prefix below)
     HugeTask& t = H.tasks[level & 1][d.task];
-    const int lim1 = t.lt, lim2 = t.le, chunk0 = t.chunk0, nchunks = t.nchunks;
+    const int lim1 = t.acc.lt, lim2 = t.acc.le, chunk0 = t.chunk0, nchunks = t.nchunks;
     int32_t* const posL = t.posL;
     int32_t* const posR = t.posR;
     // ranks before this chunk = misplaced counts of the node's earlier chunks
@@ -1328,14 +1324,12 @@ __device__ __forceinline__ void huge_scatter_chunk(const HugeState& H, int level
         if (S == 0) t.m0 = m; else t.m1 = m;
     }
     for (int w = 0; w < wave; ++w) { rL += s_c[w][0]; rR += s_c[w][1]; }
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int p = d.first + wave * 512 + e * 64 + lane;
-        if ((bL[e] >> lane) & 1ull) gstore(posL + rL + __popcll(bL[e] & lt_mask), p);
-        if ((bR[e] >> lane) & 1ull) gstore(posR + rR + __popcll(bR[e] & lt_mask), p);
-        rL += __popcll(bL[e]);
-        rR += __popcll(bR[e]);
+        int rank;
+        if (ballot_rank(bL[e], lane, rL, &rank)) gstore(posL + rank, p);
+        if (ballot_rank(bR[e], lane, rR, &rank)) gstore(posR + rank, p);
     }
     if (S == 0) {
         // sweep-1 flags of the records sweep 0 leaves in place (right of lim1 and not "< cut"); pass C adds the arrivals
@@ -1343,7 +1337,7 @@ __device__ __forceinline__ void huge_scatter_chunk(const HugeState& H, int level
         chunk_flags<1>(cl, d, lim1, lim2, wave, lane, b1L, b1R);
         int v1L = 0, v1R = 0;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { v1L += __popcll(b1L[e]); v1R += __popcll(b1R[e]); }
+        for (int e = 0; e < 8; ++e) { v1L += __popcll(b1L[e]); v1R += __popcll(b1R[e] & ~bR[e]); }  // (~bR: "< cut" records sweep 0 takes away)
         __syncthreads();  // s_c read by everyone
         if (lane == 0) { s_c[wave][0] = v1L; s_c[wave][1] = v1R; }
         __syncthreads();
@@ -1372,7 +1366,7 @@ __device__ __forceinline__ void huge_swap0_chunk(const HugeState& H, int level, 
     const HugeTask& t = H.tasks[level & 1][d.task];
     float4* const a = t.pts;
     uint8_t* const cls = t.cls;
-    const int lim2 = t.le, chunk0 = t.chunk0;
+    const int lim2 = t.acc.le, chunk0 = t.chunk0;
     const int m = t.m0;  // (the class bytes change under this pass: the count was taken in pass B)
     int lo, hi;
     pair_share(m, chunk - chunk0, t.nchunks, &lo, &hi);
@@ -1435,8 +1429,8 @@ __device__ __forceinline__ void huge_swap1_chunk(const HugeState& H, int level, 
     }
     const HugeTask& t = H.tasks[level & 1][d.task];
     float4* const a = t.pts;
-    const int n = t.k.r - t.k.l, lim1 = t.lt, lim2 = t.le, half = n / 2;
-    const int idx = lim1 > half ? lim1 : (lim2 < half ? lim2 : half);
+    const int lim1 = t.acc.lt, lim2 = t.acc.le;
+    const int idx = split_index(t.k.r - t.k.l, lim1, lim2);  // records of the left child
     const int kid0 = t.kid[0], kid1 = t.kid[1];
     const bool want = kid0 >= 0 || kid1 >= 0;
     const int m = t.m1;
@@ -1505,10 +1499,10 @@ __device__ __forceinline__ void huge_swap1_chunk(const HugeState& H, int level, 
             HugeTask& k = H.tasks[(level + 1) & 1][kid];
             if (is_hi) {
                 const float h = fmaxf(fmaxf(s_ext[0][j], s_ext[1][j]), fmaxf(s_ext[2][j], s_ext[3][j]));
-                if (h > -INFINITY) atomicMax(&k.mx[c], f2ord(h));
+                if (h > -INFINITY) atomicMax(&k.acc.mx[c], f2ord(h));
             } else {
                 const float l = fminf(fminf(s_ext[0][j], s_ext[1][j]), fminf(s_ext[2][j], s_ext[3][j]));
-                if (l < INFINITY) atomicMin(&k.mn[c], f2ord(l));
+                if (l < INFINITY) atomicMin(&k.acc.mn[c], f2ord(l));
             }
         }
     }
@@ -1524,9 +1518,7 @@ __device__ __forceinline__ void huge_emit_block(const BuildTree* __restrict__ tr
         const BuildTree tr = trees[t.k.tree];
         const SplitChoice sc = huge_split(t);
         BuildTask kids[2];
-        int id;
-        emit_inner(Q, tr, t.k, sc.ax, sc.cut, t.lt, t.le, ord2f(t.maxlt), ord2f(t.mingt), kids, &id);
-        link_to_parent(tr, t.k, id);
+        emit_inner(tr, t.k, sc.ax, sc.cut, t.acc.counts(), kids);
         const int k0 = route_task(Q, H, tr, kids[0], level + 1);
         const int k1 = route_task(Q, H, tr, kids[1], level + 1);
         t.kid[0] = k0;
@@ -1563,12 +1555,6 @@ __global__ __launch_bounds__(256) void huge_phase_kernel(const BuildTree* __rest
     if (PHASE == 4) huge_swap1_chunk(H, level, c);
 }
 
-// Last launch of a build: clears the "unfinished" word (kept in the flag layout; the straggler kernel leaves nothing unfinished).
-__global__ void build_finish_kernel(BuildQueues Q)
-{
-    Q.flags[2] = 0;
-}
-
 // ---- fat node image (TreeView::fat): every inner node's record next to the records of its two children -------------------------------
 // One thread per node id.  Odd ids that no inner node owns (positions inside a leaf) hold whatever the arena held before: their
 // slots are never visited by a search, so the only care they need is that a stale child reference is not followed out of bounds.
@@ -1589,22 +1575,32 @@ __global__ __launch_bounds__(256) void fatten_kernel(const BuildTree* __restrict
     }
 }
 
-static int launch_mid_and_subtrees(ps_context* c, const BuildTree* d_trees, const BuildQueues& Q, size_t tot, size_t T, size_t small_cap)
-{
-    constexpr size_t mid_lds = sizeof(float4) * kMid + sizeof(short) * kMid;
-    if (!c->mid_lds_attr) {  // (per context = per device: function attributes do not carry over to another GPU)
-        PS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(build_mid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds));
-        c->mid_lds_attr = true;
-    }
-    hipStream_t st = c->stream;
-    const unsigned grid_mid = (unsigned)std::min<size_t>(tot / kSmall + T + 1, 1024);
-    hipLaunchKernelGGL(build_mid_kernel, dim3(grid_mid), dim3(kMidThreads), mid_lds, st, d_trees, Q);
-    hipLaunchKernelGGL(build_flat_kernel, dim3((unsigned)std::min<size_t>(small_cap, 4096)), dim3(kSmall), 0, st, d_trees, Q);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------
+// The builder's scratch (TreeSetPlan::d_scratch; needs no initial contents) for a set of `tot` points in T trees: the capacities
+// of the queues and the offsets of the blocks.  carve() takes its size, build_trees() its pointers.
+struct ScratchLayout {
+    size_t q_cap, small_cap;       // BuildQueues: tasks of a level queue and of the mid queue; tasks of the small queue
+    size_t cap_tasks, cap_chunks;  // HugeState: chunked tasks / chunks of a level
+    size_t pos, queues, small_q, huge_tasks, chunk_counts, chunk_desc, cls;  // block offsets
+    size_t bytes;
+    ScratchLayout(size_t tot, size_t T)
+    {
+        q_cap = tot / kSmall + 2 * T + 64;
+        small_cap = tot / 4 + 2 * T + 1024;
+        cap_tasks = tot / kHuge + T + 8;
+        cap_chunks = tot / kChunk + cap_tasks + 8;
+        bytes = 0;
+        auto add = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
+        pos = add(sizeof(int32_t) * 2 * (tot + T));          // posL | posR of every tree, n + 1 entries each
+        queues = add(sizeof(BuildTask) * q_cap * 3);         // q[0] | q[1] | mid_q
+        small_q = add(sizeof(BuildTask) * small_cap);
+        huge_tasks = add(sizeof(HugeTask) * cap_tasks * 2);  // by level parity
+        chunk_counts = add(sizeof(int32_t) * 3 * cap_chunks);  // c_mL | c_mR | c_lt
+        chunk_desc = add(sizeof(ChunkDesc) * 2 * cap_chunks);  // by level parity
+        cls = add(tot + 16 * T + 16);                        // class bytes of every tree, rounded up to 16
+    }
+};
+
 void TreeSetPlan::carve(Arena& a)
 {
     const size_t T = n.size();
@@ -1622,30 +1618,16 @@ void TreeSetPlan::carve(Arena& a)
         off_flags = addh(sizeof(int32_t) * 16);
         off_trees = addh(sizeof(BuildTree) * T);
         off_bbox = addh(sizeof(unsigned) * 8 * T);
-        off_cnt = addh(sizeof(int32_t) * (kMaxLevels + 8));
-        off_hcnt = addh(sizeof(int32_t) * 2 * (kHugeLevels + 2));
+        off_cnt = addh(sizeof(QueueCounters));
+        off_hcnt = addh(sizeof(HugeCounters));
         head_bytes = hb;
         d_head = a.take<char>(hb);
         d_jobs = d_head;
         d_flags = reinterpret_cast<int32_t*>(d_head + off_flags);
         host_blob.assign(hb, 0);
     }
-    // builder scratch: posL/posR, queues, chunked-level state (no initial contents needed)
-    const size_t q_cap = tot / kSmall + 2 * T + 64, small_cap = tot / 4 + 2 * T + 1024;
-    size_t bytes = 0;
-    auto add = [&](size_t b) { size_t o = bytes; bytes += (b + 255) & ~size_t(255); return o; };
-    add(sizeof(int32_t) * 2 * (tot + T));
-    add(sizeof(BuildTask) * q_cap * 3);
-    add(sizeof(BuildTask) * small_cap);
-    {   // chunked-level state
-        const size_t cap_tasks = tot / kHuge + T + 8, cap_chunks = tot / kChunk + cap_tasks + 8;
-        add(sizeof(HugeTask) * cap_tasks * 2);
-        add(sizeof(int32_t) * 3 * cap_chunks);
-        add(sizeof(ChunkDesc) * 2 * cap_chunks);
-        add(tot + 16 * T + 16);
-    }
-    scratch_bytes = bytes;
-    d_scratch = a.take<char>(bytes);
+    scratch_bytes = ScratchLayout(tot, T).bytes;
+    d_scratch = a.take<char>(scratch_bytes);
 }
 
 int build_trees(ps_context* c, TreeSetPlan& plan)
@@ -1653,22 +1635,13 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
     const size_t T = plan.n.size();
     if (T == 0) return PS_OK;
     const size_t tot = plan.total_points();
-    const size_t q_cap = tot / kSmall + 2 * T + 64, small_cap = tot / 4 + 2 * T + 1024;
-    char* base = static_cast<char*>(plan.d_scratch);
-    size_t off = 0;
-    auto take = [&](size_t b) { char* p = base + off; off += (b + 255) & ~size_t(255); return p; };
+    const ScratchLayout L(tot, T);
+    char* const scratch = static_cast<char*>(plan.d_scratch);
     BuildTree* d_trees = reinterpret_cast<BuildTree*>(plan.d_head + plan.off_trees);
     unsigned* d_bbox = reinterpret_cast<unsigned*>(plan.d_head + plan.off_bbox);
-    int32_t* d_cnt = reinterpret_cast<int32_t*>(plan.d_head + plan.off_cnt);
-    int32_t* d_hcnt = reinterpret_cast<int32_t*>(plan.d_head + plan.off_hcnt);
-    int32_t* d_pos = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * 2 * (tot + T)));
-    BuildTask* d_q = reinterpret_cast<BuildTask*>(take(sizeof(BuildTask) * q_cap * 3));
-    BuildTask* d_small = reinterpret_cast<BuildTask*>(take(sizeof(BuildTask) * small_cap));
-    const size_t cap_tasks = tot / kHuge + T + 8, cap_chunks = tot / kChunk + cap_tasks + 8;
-    HugeTask* d_huge = reinterpret_cast<HugeTask*>(take(sizeof(HugeTask) * cap_tasks * 2));
-    int32_t* d_cm = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * 3 * cap_chunks));
-    ChunkDesc* d_desc = reinterpret_cast<ChunkDesc*>(take(sizeof(ChunkDesc) * 2 * cap_chunks));
-    uint8_t* d_cls = reinterpret_cast<uint8_t*>(take(tot + 16 * T + 16));
+    HugeCounters* d_hcnt = reinterpret_cast<HugeCounters*>(plan.d_head + plan.off_hcnt);
+    int32_t* d_pos = reinterpret_cast<int32_t*>(scratch + L.pos);
+    uint8_t* d_cls = reinterpret_cast<uint8_t*>(scratch + L.cls);
 
     // host image of the head block (the caller has written its job table at offset 0; flags and counters are zero from carve())
     PS_CHECK(plan.host_blob.size() == plan.head_bytes, "build_trees: the plan was not carved");
@@ -1699,28 +1672,27 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
     PS_TRY(c->upload_async(plan.d_head, plan.host_blob.data(), plan.head_bytes));  // jobs, status words, tree table, accumulators, counters
 
     HugeState H;
-    H.tasks[0] = d_huge;
-    H.tasks[1] = d_huge + cap_tasks;
-    H.ntasks = d_hcnt;
-    H.nchunks = d_hcnt + (kHugeLevels + 2);
-    H.c_mL = d_cm;
-    H.c_mR = d_cm + cap_chunks;
-    H.c_lt = d_cm + 2 * cap_chunks;
-    H.desc[0] = d_desc;
-    H.desc[1] = d_desc + cap_chunks;
-    H.cap_tasks = (int32_t)cap_tasks;
-    H.cap_chunks = (int32_t)cap_chunks;
+    H.tasks[0] = reinterpret_cast<HugeTask*>(scratch + L.huge_tasks);
+    H.tasks[1] = H.tasks[0] + L.cap_tasks;
+    H.ntasks = d_hcnt->ntasks;
+    H.nchunks = d_hcnt->nchunks;
+    H.c_mL = reinterpret_cast<int32_t*>(scratch + L.chunk_counts);
+    H.c_mR = H.c_mL + L.cap_chunks;
+    H.c_lt = H.c_mR + L.cap_chunks;
+    H.desc[0] = reinterpret_cast<ChunkDesc*>(scratch + L.chunk_desc);
+    H.desc[1] = H.desc[0] + L.cap_chunks;
+    H.cap_tasks = (int32_t)L.cap_tasks;
+    H.cap_chunks = (int32_t)L.cap_chunks;
 
     BuildQueues Q;
-    Q.q[0] = d_q;
-    Q.q[1] = d_q + q_cap;
-    Q.mid_q = d_q + 2 * q_cap;
-    Q.small_q = d_small;
-    Q.level_cnt = d_cnt;
-    Q.small_cnt = d_cnt + kMaxLevels;
+    Q.q[0] = reinterpret_cast<BuildTask*>(scratch + L.queues);
+    Q.q[1] = Q.q[0] + L.q_cap;
+    Q.mid_q = Q.q[1] + L.q_cap;
+    Q.small_q = reinterpret_cast<BuildTask*>(scratch + L.small_q);
+    Q.cnt = reinterpret_cast<QueueCounters*>(plan.d_head + plan.off_cnt);
     Q.flags = plan.d_flags;
-    Q.q_cap = (int32_t)q_cap;
-    Q.small_cap = (int32_t)small_cap;
+    Q.q_cap = (int32_t)L.q_cap;
+    Q.small_cap = (int32_t)L.small_cap;
 
     // chunked levels until the nodes of a balanced tree are below kMid; whatever is still above kMid after them (lopsided
     // splits) is finished by ONE straggler launch (build_level_kernel, depth first per node)
@@ -1732,8 +1704,8 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
 
     const int chunks_x = std::max(1, std::min(ceil_div(max_n, 256 * 4), 256));
     hipLaunchKernelGGL(init_points_kernel, dim3(chunks_x, (unsigned)T), dim3(256), 0, st, d_trees, chunks_x);
-    const int grid_big = (int)std::min<size_t>(q_cap, tot / kMid + T + 1);
-    const unsigned n_chunks_max = (unsigned)std::min<size_t>(cap_chunks, tot / kChunk + cap_tasks);
+    const int grid_big = (int)std::min<size_t>(L.q_cap, tot / kMid + T + 1);
+    const unsigned n_chunks_max = (unsigned)std::min<size_t>(L.cap_chunks, tot / kChunk + L.cap_tasks);
     {
         const dim3 gc(std::max(1u, n_chunks_max)), bc(256);
         H.grid_chunks = (int32_t)gc.x;
@@ -1749,7 +1721,15 @@ int build_trees(ps_context* c, TreeSetPlan& plan)
     }
     // (the level queues are indexed by the level a task was pushed FOR: chunked level L pushes for L + 1, the roots for 0)
     hipLaunchKernelGGL(build_level_kernel, dim3(grid_big), dim3(kBigThreads), 0, st, d_trees, Q, huge_levels);
-    PS_TRY(launch_mid_and_subtrees(c, d_trees, Q, tot, T, small_cap));
+    constexpr size_t mid_lds = sizeof(float4) * kMid + sizeof(short) * kMid;
+    if (!c->mid_lds_attr) {  // (per context = per device: function attributes do not carry over to another GPU)
+        PS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(build_mid_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mid_lds));
+        c->mid_lds_attr = true;
+    }
+    const unsigned grid_mid = (unsigned)std::min<size_t>(tot / kSmall + T + 1, 1024);
+    hipLaunchKernelGGL(build_mid_kernel, dim3(grid_mid), dim3(kMidThreads), mid_lds, st, d_trees, Q);
+    hipLaunchKernelGGL(build_flat_kernel, dim3((unsigned)std::min<size_t>(L.small_cap, 4096)), dim3(kSmall), 0, st, d_trees, Q);
+    PS_HIP(hipGetLastError());
     {
         // the searches' image of the finished trees: every inner node next to its children's records (TreeView::fat)
         const int ids_x = std::max(1, std::min(ceil_div(max_n, 256), 1024));
@@ -1765,19 +1745,20 @@ int read_build_counters(ps_context* c, const TreeSetPlan& plan, BuildCounters* o
 {
     static_assert(kHugeLevels <= kBuildCounterLevels, "BuildCounters holds one entry per chunked level");
     PS_CHECK(plan.d_head && plan.head_bytes > plan.off_hcnt, "read_build_counters: the plan was not carved");
-    int32_t cnt[kMaxLevels + 8], hcnt[2 * (kHugeLevels + 2)];
-    PS_HIP(hipMemcpyAsync(cnt, plan.d_head + plan.off_cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(hipMemcpyAsync(hcnt, plan.d_head + plan.off_hcnt, sizeof(hcnt), hipMemcpyDeviceToHost, c->stream));
+    QueueCounters cnt;
+    HugeCounters hcnt;
+    PS_HIP(hipMemcpyAsync(&cnt, plan.d_head + plan.off_cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(hipMemcpyAsync(&hcnt, plan.d_head + plan.off_hcnt, sizeof(hcnt), hipMemcpyDeviceToHost, c->stream));
     PS_HIP(hipStreamSynchronize(c->stream));
     std::memset(out, 0, sizeof(*out));
     out->chunked_levels = plan.chunked_levels;
     for (int l = 0; l < kHugeLevels; ++l) {
-        out->ntasks[l] = hcnt[l];                      // HugeState::ntasks
-        out->nchunks[l] = hcnt[kHugeLevels + 2 + l];   // HugeState::nchunks
+        out->ntasks[l] = hcnt.ntasks[l];
+        out->nchunks[l] = hcnt.nchunks[l];
     }
-    out->straggler_tasks = cnt[plan.chunked_levels];   // BuildQueues::level_cnt of the level build_level_kernel starts from
-    out->mid_pushed = cnt[kMaxLevels + 1];             // BuildQueues::small_cnt[1]
-    out->small_pushed = cnt[kMaxLevels];               // BuildQueues::small_cnt[0]
+    out->straggler_tasks = cnt.level[plan.chunked_levels];  // the level build_level_kernel starts from
+    out->mid_pushed = cnt.mid;
+    out->small_pushed = cnt.small;
     return PS_OK;
 }
 

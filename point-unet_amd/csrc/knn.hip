@@ -24,7 +24,7 @@ struct KnnJob {
     const float* q3;    // raw [nq,3] queries (row = query position) when q4 == NULL
     int32_t nq;
     int32_t* out;       // [nq, K]
-    int32_t* overflow;  // set to 1 if any query overflowed the deferred-node stack
+    int32_t* overflow;  // the tree set's status words (BuildFlag): kFlagStackOverflow is set if any query overflowed the deferred-node stack
     int32_t* order;     // optional [nq]: order[t] = row of the t-th query (self queries: the tree's leaf order, for ps_pyramid.order)
     int32_t prefix = 0; // != 0: the tree holds exactly the rows [0, tree.n) of the cloud the q4 queries come from (up-sampling queries)
     int32_t sub_m = 0;  // rows [0, sub_m) are ALSO written to sub_out [sub_m, K]: the pooling table of tf_map, pool = neigh_idx[:, :N // r]
@@ -111,7 +111,7 @@ __device__ __forceinline__ void knn_body(const KnnJob& job, float* win)
     // (degenerate cloud: a builder queue overflowed and the tree has holes.  Unreachable for real clouds -- the queues are sized
     // for the worst disjoint-range count -- but whatever runs behind this kernel without a host check must still find valid
     // indices: the rows are filled with index 0 instead of walking a broken tree; the status word reports the failure.)
-    const bool broken = gload(job.overflow + 1) != 0;
+    const bool broken = gload(job.overflow + kFlagQueueOverflow) != 0;
     float qx, qy, qz;
     int row;
     if (job.q4) {
@@ -200,7 +200,7 @@ __device__ __forceinline__ void knn_body(const KnnJob& job, float* win)
     st.sp_ = &spill;
     st.w = (WindowStack::lds_float*)(win + threadIdx.x);
     const bool ok = knn_search_one<K, WindowStack>(job.tree, qx, qy, qz, dist, idx, st);
-    if (!ok) gstore(job.overflow, 1);
+    if (!ok) gstore(job.overflow + kFlagStackOverflow, 1);
     int32_t* o = job.out + (size_t)row * K;
     int32_t* o2 = row < job.sub_m ? job.sub_out + (size_t)row * K : nullptr;
     if constexpr (K % 4 == 0) {
@@ -357,7 +357,7 @@ static int knn_batch_impl(ps_context* c, const float* support, const float* quer
         for (int64_t b = 0; b < B; ++b) plan.src[b] = d_support + (size_t)b * n1 * 3;
         PS_TRY(build_trees(c, plan));
     }
-    int32_t flag[3] = {0, 0, 0};
+    int32_t flag[kBuildFlagWords] = {};
     {
         Stage st(c, "knn_search", 1);
         PS_TRY(launch_knn(c, reinterpret_cast<const KnnJob*>(plan.d_jobs), (int)B, (int)n2, (int)K));
@@ -373,11 +373,11 @@ static int knn_batch_impl(ps_context* c, const float* support, const float* quer
         else
             PS_HIP(hipMemcpyAsync(out32, d_out32, out_count * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, 12, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(hipMemcpyAsync(flag, plan.d_flags, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
     // (the job table and the plan's staging live in host memory of this frame: wait before returning)
     PS_HIP(hipStreamSynchronize(c->stream));
-    PS_CHECK(flag[1] == 0, "ps_knn_batch: kd-tree builder queue overflow (degenerate cloud)");
-    PS_CHECK(flag[0] == 0, "ps_knn_batch: kd-tree deeper than the %d-entry traversal stack", kStackMax);
+    PS_CHECK(flag[kFlagQueueOverflow] == 0, "ps_knn_batch: kd-tree builder queue overflow (degenerate cloud)");
+    PS_CHECK(flag[kFlagStackOverflow] == 0, "ps_knn_batch: kd-tree deeper than the %d-entry traversal stack", kStackMax);
     return PS_OK;
 }
 
@@ -484,7 +484,7 @@ extern "C" int ps_pyramid_build(ps_context* c, const float* xyz0, int64_t B, int
         st.n = plan.launches;
     }
     const KnnJob* dj = reinterpret_cast<const KnnJob*>(plan.d_jobs);
-    int32_t flag[3] = {0, 0, 0};
+    int32_t flag[kBuildFlagWords] = {};
     {
         {
             Stage st(c, "knn_search", 1);  // K-NN self queries and 1-NN up-sampling queries of every level, one launch
@@ -493,17 +493,17 @@ extern "C" int ps_pyramid_build(ps_context* c, const float* xyz0, int64_t B, int
         if (c->deferred) {
             // no host synchronisation: the status words go to a pinned slot that ps_synchronize() validates; the host
             // tables behind the asynchronous uploads move into the context's ring so they outlive this frame
-            PS_TRY(c->defer_status(plan.d_flags, 12, 0, c->builds));
+            PS_TRY(c->defer_status(plan.d_flags, sizeof(int32_t) * kBuildFlagWords, 0, c->builds));
             ++c->builds;
             pyr->built = pyramid_stamp(pyr);
             return PS_OK;  // (all host tables went through the context's pinned upload ring)
         }
-        PS_HIP(hipMemcpyAsync(flag, plan.d_flags, 12, hipMemcpyDeviceToHost, c->stream));
+        PS_HIP(hipMemcpyAsync(flag, plan.d_flags, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
         PS_HIP(hipStreamSynchronize(c->stream));
     }
     ++c->builds;
-    PS_CHECK(flag[1] == 0, "ps_pyramid_build: kd-tree builder queue overflow (degenerate cloud)");
-    PS_CHECK(flag[0] == 0, "ps_pyramid_build: kd-tree deeper than the %d-entry traversal stack", kStackMax);
+    PS_CHECK(flag[kFlagQueueOverflow] == 0, "ps_pyramid_build: kd-tree builder queue overflow (degenerate cloud)");
+    PS_CHECK(flag[kFlagStackOverflow] == 0, "ps_pyramid_build: kd-tree deeper than the %d-entry traversal stack", kStackMax);
     pyr->built = pyramid_stamp(pyr);
     return PS_OK;
 }
