@@ -344,6 +344,18 @@ SALIENCY_STEP_PROTOTYPES = {
                                                                          ctypes.POINTER(PsSaliencyStepOptions), c_vp, c_vp, c_vp, c_i64p]),
 }
 
+# every symbol include/pointseg_saliency_mixup.h declares (config.MIXUP: mixed batches, the soft-label Dice loss, the step on soft labels;
+# csrc/saliency_data.hip, csrc/saliency_train.hip, csrc/saliency_step.hip)
+SALIENCY_MIXUP_PROTOTYPES = {
+    "ps_patch_sample_mixup": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i64p, ctypes.c_int64, ctypes.c_int32, c_i32p,
+                                             ctypes.c_int32, ctypes.c_int32, c_i64p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_double)] + [c_vp] * 4),
+    "ps_softmax_dice_soft_loss": SALIENCY_ATTENTION_PROTOTYPES["ps_softmax_dice_loss"],
+    "ps_softmax_dice_soft_loss_bwd": SALIENCY_ATTENTION_PROTOTYPES["ps_softmax_dice_loss_bwd"],
+    "ps_saliency_backward_soft": SALIENCY_STEP_PROTOTYPES["ps_saliency_backward"],
+    "ps_saliency_train_step_soft": SALIENCY_STEP_PROTOTYPES["ps_saliency_train_step"],
+}
+
 _lib = None
 
 
@@ -366,7 +378,7 @@ def lib():
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
                                   + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
-                                  + list(SALIENCY_STEP_PROTOTYPES.items())):
+                                  + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -12,6 +12,10 @@
 // words that cover it (the row starts at an arbitrary byte); integer atomics, so two runs agree.  Launch 2 writes the batch: every
 // workgroup derives all slots' tries from the counts, then fills 16-byte pieces of the outputs -- a piece inside the copied box is loaded
 // at the alignment its source address has (16, 8 or 4 bytes; labels and weights 4 or 1), a piece outside is the fill hash.
+//
+// Mixed batches (config.MIXUP, include/pointseg_saliency_mixup.h; tests/saliency_mixup_ref.py restates the rule): the same table and the same
+// count over B + 1 drawn samples, and a gather that reads the two source windows of every output piece through the plain gather's paths,
+// mixes them (two products and a sum, each rounded) and stores once -- images, the or of the weights, and the soft one-hot rows.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -24,6 +28,7 @@
 #include "wave_ops.h"
 
 #include "../../include/pointseg_saliency_data.h"
+#include "../../include/pointseg_saliency_mixup.h"
 
 namespace ps {
 
@@ -322,6 +327,39 @@ __device__ __forceinline__ void image_quad(const PatchCand* s_c, const PatchShap
     }
 }
 
+// labels and weights of four voxels from e0 on (e0 % 4 == 0), of the batch's E = slots * V; zeros outside the copied boxes and past E
+__device__ __forceinline__ void voxel_quad(const PatchCand* s_c, const PatchShape& sh, unsigned V, size_t e0, size_t E, int (&l)[4], float (&w)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) l[k] = 0, w[k] = 0.f;
+    if ((sh.P[2] & 3) == 0) {  // the four voxels share a row of one slot: one word each where the box holds them all and the bytes are aligned
+        const unsigned b = (unsigned)(e0 / V), v = (unsigned)(e0 - (size_t)b * V);
+        const PatchCand& cd = s_c[b];
+        const long long s0 = voxel_source(cd, sh, v), s3 = voxel_source(cd, sh, v + 3);
+        if (s0 >= 0 && s3 >= 0 && ((reinterpret_cast<uintptr_t>(cd.lab + s0) | reinterpret_cast<uintptr_t>(cd.wgt + s0)) & 3) == 0) {
+            const unsigned x = *reinterpret_cast<const unsigned*>(cd.lab + s0), y = *reinterpret_cast<const unsigned*>(cd.wgt + s0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                l[k] = (int)((x >> (8 * k)) & 255u);
+                w[k] = (float)((y >> (8 * k)) & 255u);
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t e = e0 + k;
+        if (e >= E) break;
+        const unsigned b = (unsigned)(e / V);
+        const PatchCand& cd = s_c[b];
+        const long long s = voxel_source(cd, sh, (unsigned)(e - (size_t)b * V));
+        if (s >= 0) {
+            l[k] = cd.lab[s];
+            w[k] = (float)cd.wgt[s];
+        }
+    }
+}
+
 // Launch 2.  Workgroups [0, img_blocks) write 1024 quads of images each, the rest 1024 quads of labels and weights; workgroup 0 also
 // writes info.  vec_i / vec_v: the image / the label and weight outputs are 16-byte aligned.
 template <bool ROW4>
@@ -367,37 +405,9 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __re
     for (int u = 0; u < 4; ++u) {
         const size_t e0 = 4 * ((size_t)(blockIdx.x - img_blocks) * 1024 + u * 256 + t);
         if (e0 >= E) break;
-        int l[4] = {0, 0, 0, 0};
-        float w[4] = {0.f, 0.f, 0.f, 0.f};
-        bool done = false;
-        if ((sh.P[2] & 3) == 0) {  // the four voxels share a row of one slot: one word each where the box holds them all and the bytes are aligned
-            const unsigned b = (unsigned)(e0 / V), v = (unsigned)(e0 - (size_t)b * V);
-            const PatchCand& cd = s_c[b];
-            const long long s0 = voxel_source(cd, sh, v), s3 = voxel_source(cd, sh, v + 3);
-            if (s0 >= 0 && s3 >= 0 && ((reinterpret_cast<uintptr_t>(cd.lab + s0) | reinterpret_cast<uintptr_t>(cd.wgt + s0)) & 3) == 0) {
-                const unsigned x = *reinterpret_cast<const unsigned*>(cd.lab + s0), y = *reinterpret_cast<const unsigned*>(cd.wgt + s0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    l[k] = (int)((x >> (8 * k)) & 255u);
-                    w[k] = (float)((y >> (8 * k)) & 255u);
-                }
-                done = true;
-            }
-        }
-        if (!done) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const size_t e = e0 + k;
-                if (e >= E) break;
-                const unsigned b = (unsigned)(e / V);
-                const PatchCand& cd = s_c[b];
-                const long long s = voxel_source(cd, sh, (unsigned)(e - (size_t)b * V));
-                if (s >= 0) {
-                    l[k] = cd.lab[s];
-                    w[k] = (float)cd.wgt[s];
-                }
-            }
-        }
+        int l[4];
+        float w[4];
+        voxel_quad(s_c, sh, V, e0, E, l, w);
         if (vec_v && e0 + 4 <= E) {
             *reinterpret_cast<int4*>(out_l + e0) = make_int4(l[0], l[1], l[2], l[3]);
             *reinterpret_cast<float4*>(out_w + e0) = make_float4(w[0], w[1], w[2], w[3]);
@@ -411,11 +421,238 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __re
     }
 }
 
+// ---- the mixed gather (include/pointseg_saliency_mixup.h) ----------------------------------------------------------------------------------------
+
+// The mixed batch's choice of try for DRAWN sample i of sh.B + 1 (thread-serial; the same in every workgroup): the reject loop's check
+// fires on sample sh.B - 1, the last sample is free.  any_earlier: some sample i' < sh.B - 1 has pos(i', 0) > 0.
+__device__ __forceinline__ int choose_try_mixup(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts, const PatchShape& sh, int i,
+                                                bool any_earlier, int& ok)
+{
+    ok = 1;
+    if (sh.mode == PS_PATCH_RANDOM) return 0;
+    if (sh.mode == PS_PATCH_ONE_POSITIVE && (i != sh.B - 1 || any_earlier)) return 0;
+    for (int t = 0; t < sh.T; ++t)
+        if (counts[cands[i * sh.T + t].count] > 0) return t;
+    ok = 0;
+    return sh.T - 1;
+}
+
+// fl32(fl32(g * a) + fl32(h * b)): mixup's rule (utils.py:523, 525), every product and the sum rounded on its own
+__device__ __forceinline__ float mix(float2 gh, float a, float b) { return __fadd_rn(__fmul_rn(gh.x, a), __fmul_rn(gh.y, b)); }
+
+// The slots of the four elements from e0 on, `len` elements to a slot, clamped to `last` (an element past the batch's end is never stored).
+// same: the four share a slot.  One 64-bit division, the one the quad readers make as well; the rest is 32-bit.
+__device__ __forceinline__ void quad_slots(size_t e0, unsigned len, bool same, unsigned last, unsigned (&b)[4])
+{
+    const unsigned b0 = (unsigned)(e0 / len), j = (unsigned)(e0 - (size_t)b0 * len);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = same ? b0 : min(last, b0 + (j + k) / len);
+}
+
+// class c of the mixed one-hot rows of labels l1 and l2
+__device__ __forceinline__ float mix_class(float2 gh, int l1, int l2, int c) { return mix(gh, l1 == c ? 1.f : 0.f, l2 == c ? 1.f : 0.f); }
+
+// Launch 2 of the mixed batch: patch_gather_kernel's partition over sh.B MIXED slots.  s_c holds the sh.B + 1 drawn samples, so slot b's
+// two sources are s_c[b] and (s_c + 1)[b]: every piece is read twice through the plain gather's paths, mixed, and stored once.  gh[b] =
+// (float32(gamma_b), float32(1 - gamma_b)).  The soft rows are written along K: two rows in one 16-byte store for K == 2, 16 bytes at a
+// time for K % 4 == 0 (both where out_s is 16-byte aligned: al_s >= 16), 8 bytes for another even K (al_s >= 8), floats elsewhere.
+// (__launch_bounds__(256, 8): the plain gather's 8 waves per SIMD -- 63 registers, nothing spilled; left alone the compiler takes 68.)
+template <bool ROW4>
+__global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts,
+                                                        const float2* __restrict__ gh, PatchShape sh, int K, unsigned img_blocks, bool vec_i, bool vec_w,
+                                                        int al_s, float* __restrict__ out_i, float* __restrict__ out_w, float* __restrict__ out_s,
+                                                        int32_t* __restrict__ info)
+{
+    __shared__ PatchCand s_c[PS_PATCH_MAX_B];
+    __shared__ float2 s_g[PS_PATCH_MAX_B];
+    const int t = threadIdx.x;
+    bool pos0 = false;
+    if (sh.mode == PS_PATCH_ONE_POSITIVE && t < sh.B - 1) pos0 = counts[cands[t * sh.T].count] > 0;
+    const bool any_earlier = __syncthreads_or(pos0) != 0;
+    if (t <= sh.B) {
+        int ok;
+        const int tr = choose_try_mixup(cands, counts, sh, t, any_earlier, ok);
+        const PatchCand cd = cands[t * sh.T + tr];
+        s_c[t] = cd;
+        if (t < sh.B) s_g[t] = gh[t];
+        if (blockIdx.x == 0) {
+            int32_t* r = info + 8 * t;
+            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = 0;
+        }
+    }
+    __syncthreads();
+    const unsigned V = (unsigned)sh.P[0] * (unsigned)sh.P[1] * (unsigned)sh.P[2], L = V * (unsigned)sh.C;
+    if (blockIdx.x < img_blocks) {
+        const size_t E = (size_t)sh.B * L;
+#pragma unroll 2
+        for (int u = 0; u < 4; ++u) {
+            const size_t e0 = 4 * ((size_t)blockIdx.x * 1024 + u * 256 + t);
+            if (e0 >= E) break;
+            float a[4], b[4], o[4];
+            unsigned slot[4];
+            image_quad<ROW4>(s_c, sh, L, e0, E, a);
+            image_quad<ROW4>(s_c + 1, sh, L, e0, E, b);
+            quad_slots(e0, L, ROW4, (unsigned)sh.B - 1, slot);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = mix(s_g[slot[k]], a[k], b[k]);
+            if (vec_i && e0 + 4 <= E) {
+                *reinterpret_cast<float4*>(out_i + e0) = make_float4(o[0], o[1], o[2], o[3]);
+            } else {
+                for (int k = 0; k < 4; ++k)
+                    if (e0 + k < E) out_i[e0 + k] = o[k];
+            }
+        }
+        return;
+    }
+    const size_t E = (size_t)sh.B * V;
+#pragma unroll 1
+    for (int u = 0; u < 4; ++u) {
+        const size_t e0 = 4 * ((size_t)(blockIdx.x - img_blocks) * 1024 + u * 256 + t);
+        if (e0 >= E) break;
+        // (the two samples' labels as four bytes each and their weights as the or's bits: what stays in registers across the stores)
+        unsigned lp1 = 0, lp2 = 0, wm = 0;
+        {
+            int l[4];
+            float w[4];
+            voxel_quad(s_c, sh, V, e0, E, l, w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lp1 |= (unsigned)l[k] << (8 * k), wm |= (w[k] != 0.f ? 1u : 0u) << k;
+            voxel_quad(s_c + 1, sh, V, e0, E, l, w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lp2 |= (unsigned)l[k] << (8 * k), wm |= (w[k] != 0.f ? 1u : 0u) << k;
+        }
+        const bool full = e0 + 4 <= E;
+        if (vec_w && full) {
+            *reinterpret_cast<float4*>(out_w + e0) = make_float4(wm & 1u ? 1.f : 0.f, wm & 2u ? 1.f : 0.f, wm & 4u ? 1.f : 0.f, wm & 8u ? 1.f : 0.f);
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < E) out_w[e0 + k] = (wm >> k) & 1u ? 1.f : 0.f;
+        }
+        const unsigned v0 = (unsigned)e0;  // (B * V * K < 2^31)
+        unsigned slot[4];
+        quad_slots(e0, V, (sh.P[2] & 3) == 0, (unsigned)sh.B - 1, slot);
+        if (K == 2 && al_s >= 16 && full) {
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {
+                const float2 ga = s_g[slot[k]], gb = s_g[slot[k + 1]];
+                const int a1 = (int)((lp1 >> (8 * k)) & 255u), a2 = (int)((lp2 >> (8 * k)) & 255u);
+                const int b1 = (int)((lp1 >> (8 * k + 8)) & 255u), b2 = (int)((lp2 >> (8 * k + 8)) & 255u);
+                *reinterpret_cast<float4*>(out_s + (size_t)(v0 + k) * 2) =
+                    make_float4(mix_class(ga, a1, a2, 0), mix_class(ga, a1, a2, 1), mix_class(gb, b1, b2, 0), mix_class(gb, b1, b2, 1));
+            }
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (e0 + k >= E) break;
+            const float2 g = s_g[slot[k]];
+            const int l1 = (int)((lp1 >> (8 * k)) & 255u), l2 = (int)((lp2 >> (8 * k)) & 255u);
+            float* o = out_s + (size_t)(v0 + k) * K;
+            if ((K & 3) == 0 && al_s >= 16) {
+                for (int c = 0; c < K; c += 4)
+                    *reinterpret_cast<float4*>(o + c) = make_float4(mix_class(g, l1, l2, c), mix_class(g, l1, l2, c + 1), mix_class(g, l1, l2, c + 2),
+                                                                     mix_class(g, l1, l2, c + 3));
+            } else if ((K & 1) == 0 && al_s >= 8) {
+                for (int c = 0; c < K; c += 2) *reinterpret_cast<float2*>(o + c) = make_float2(mix_class(g, l1, l2, c), mix_class(g, l1, l2, c + 1));
+            } else {
+                for (int c = 0; c < K; ++c) o[c] = mix_class(g, l1, l2, c);
+            }
+        }
+    }
+}
+
 inline int volume_shape_ok(const char* who, int32_t C, int64_t D, int64_t H, int64_t W)
 {
     PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
     PS_CHECK(D >= 1 && H >= 1 && W >= 1 && D < (1ll << 31) && H < (1ll << 31) && W < (1ll << 31) && D * H < (1ll << 31) && D * H * W < (1ll << 31),
              "%s: the volume is [%lld, %lld, %lld] (every extent >= 1, D * H * W < 2^31)", who, (long long)D, (long long)H, (long long)W);
+    return PS_OK;
+}
+
+// what the two samplers check alike, in ps_patch_sample's order: `rows` rows of cand (the batch's slots, or the mixed batch's drawn samples)
+inline int sampler_args_ok(const char* who, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                           int64_t n, int32_t C, const int32_t* cand, int rows, int32_t T, const int64_t* P, int32_t mode, bool outs, const char* out_names)
+{
+    PS_CHECK(T >= 1 && T <= PS_PATCH_MAX_T, "%s: T = %d, must be in [1, %d]", who, (int)T, PS_PATCH_MAX_T);
+    PS_CHECK(mode == PS_PATCH_RANDOM || mode == PS_PATCH_ALL_POSITIVE || mode == PS_PATCH_ONE_POSITIVE, "%s: mode = %d is none of the three", who, (int)mode);
+    PS_CHECK(n >= 1 && n < (1ll << 31), "%s: n = %lld volumes", who, (long long)n);
+    PS_CHECK(images && labels && weights && dims && cand && P, "%s: NULL images, labels, weights, dims, cand or P table", who);
+    PS_CHECK(outs, "%s: NULL %s", who, out_names);
+    PS_CHECK(P[0] >= 1 && P[1] >= 1 && P[2] >= 1 && P[0] < (1ll << 31) && P[1] < (1ll << 31) && P[2] < (1ll << 31) && P[0] * P[1] < (1ll << 31)
+                 && P[0] * P[1] * P[2] < (1ll << 31) && P[0] * P[1] * P[2] * C < (1ll << 31),
+             "%s: P = [%lld, %lld, %lld] (every extent >= 1, P0 * P1 * P2 * C < 2^31)", who, (long long)P[0], (long long)P[1], (long long)P[2]);
+    for (int64_t v = 0; v < n; ++v) {
+        PS_CHECK(images[v] && labels[v] && weights[v], "%s: volume %lld has a NULL image, label or weight pointer", who, (long long)v);
+        const int64_t* d = dims + 3 * v;
+        PS_CHECK(d[0] >= 1 && d[1] >= 1 && d[2] >= 1 && d[0] < (1ll << 31) && d[1] < (1ll << 31) && d[2] < (1ll << 31) && d[0] * d[1] < (1ll << 31)
+                     && d[0] * d[1] * d[2] < (1ll << 31) && d[0] * d[1] * d[2] * C < (1ll << 31),
+                 "%s: dims of volume %lld are [%lld, %lld, %lld] (every dim >= 1, d * h * w * C < 2^31)", who, (long long)v, (long long)d[0], (long long)d[1],
+                 (long long)d[2]);
+    }
+    for (int i = 0; i < rows * T; ++i)
+        PS_CHECK(cand[i] >= 0 && cand[i] < n, "%s: cand[%d, %d] = %d is not a volume of the bank (%lld volumes)", who, i / T, i % T, (int)cand[i], (long long)n);
+    return PS_OK;
+}
+
+// The host's blob, uploaded in one copy: [the table: every candidate's window][win: the windows the mode can ask for][their counts, zero]
+// [extra bytes of the caller's].  forced: the row all of whose tries PS_PATCH_ONE_POSITIVE may ask for.
+struct SamplerBlob {
+    std::vector<char> host;
+    size_t win_off, counts_off, extra_off;
+    int windows;
+};
+
+inline void sampler_table(SamplerBlob& bl, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                          const int32_t* cand, int rows, int T, const int64_t* P, uint32_t seed, int mode, int forced, size_t extra_bytes)
+{
+    const int nc = rows * T;
+    std::vector<int> win;
+    bl.win_off = pad256(sizeof(PatchCand) * nc);
+    bl.counts_off = bl.win_off + pad256(sizeof(int) * nc);
+    bl.extra_off = bl.counts_off + pad256(sizeof(unsigned) * nc);
+    bl.host.assign(bl.extra_off + pad256(extra_bytes), 0);
+    PatchCand* hc = reinterpret_cast<PatchCand*>(bl.host.data());
+    for (int b = 0; b < rows; ++b)
+        for (int t = 0; t < T; ++t) {
+            PatchCand& cd = hc[b * T + t];
+            const int v = cand[b * T + t];
+            const unsigned s = hash32(seed + kSeedMul * (unsigned)(b * T + t + 1));
+            cd.img = images[v], cd.lab = labels[v], cd.wgt = weights[v];
+            for (int a = 0; a < 3; ++a) {
+                const int in = (int)dims[3 * v + a], out = (int)P[a];
+                const int x0 = out / 2, x1 = in - x0;
+                int ctr;
+                if (x1 <= x0) ctr = (x0 + x1) / 2;
+                else ctr = x0 + (int)(((unsigned long long)hash32(s + kAxisMul * (unsigned)(a + 1)) * (unsigned long long)(x1 - x0 + 1)) >> 32);
+                const int r0 = std::min(out / 2, ctr), r1 = std::min(out - out / 2, in - ctr);
+                cd.dim[a] = in, cd.c[a] = ctr, cd.src[a] = ctr - r0, cd.lo[a] = out / 2 - r0, cd.n[a] = r0 + r1;
+            }
+            cd.s_fill = hash32(s + kAxisMul * 4u);
+            cd.vol = v;
+            cd.pad = 0;
+            const bool counted = t == 0 || mode == PS_PATCH_ALL_POSITIVE || (mode == PS_PATCH_ONE_POSITIVE && b == forced);
+            cd.count = counted ? (int)win.size() : -1;
+            if (counted) win.push_back(b * T + t);
+        }
+    std::copy(win.begin(), win.end(), reinterpret_cast<int*>(bl.host.data() + bl.win_off));  // (the counts behind them stay zero)
+    bl.windows = (int)win.size();
+}
+
+// the blob into the context's arena, and launch 1 over its windows; d_tab: where it lies on the device
+inline int sampler_count(ps_context* c, const SamplerBlob& bl, const int64_t* P, char*& d_tab)
+{
+    hipStream_t st = c->stream;
+    Arena& A = c->sample_arena;
+    for (int pass = 0; pass < 2; ++pass) {
+        A.begin(pass == 0);
+        d_tab = A.take<char>(bl.host.size());
+        if (pass == 0) PS_TRY(A.buf.reserve(A.off));
+    }
+    const unsigned kdw = (unsigned)((P[2] + 6) / 4);  // a row of P2 bytes starting at byte 3 of a word touches this many
+    const unsigned count_blocks = (unsigned)(((size_t)P[0] * P[1] * kdw + 2047) / 2048);
+    PS_TRY(c->upload_async(d_tab, bl.host.data(), bl.host.size()));
+    hipLaunchKernelGGL(patch_count_kernel, dim3(count_blocks, (unsigned)bl.windows), dim3(256), 0, st, reinterpret_cast<const PatchCand*>(d_tab),
+                       reinterpret_cast<const int*>(d_tab + bl.win_off), reinterpret_cast<unsigned*>(d_tab + bl.counts_off), kdw);
     return PS_OK;
 }
 
@@ -536,6 +773,7 @@ extern "C" int ps_saliency_pancreas_prepare(ps_context* c, const void* ct, int32
     return PS_OK;
 }
 
+
 extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
                                int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode,
                                float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
@@ -544,85 +782,80 @@ extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const 
     // every argument error is found here, before anything is enqueued
     PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
     PS_CHECK(B >= 1 && B <= PS_PATCH_MAX_B, "%s: B = %d, must be in [1, %d]", who, (int)B, PS_PATCH_MAX_B);
-    PS_CHECK(T >= 1 && T <= PS_PATCH_MAX_T, "%s: T = %d, must be in [1, %d]", who, (int)T, PS_PATCH_MAX_T);
-    PS_CHECK(mode == PS_PATCH_RANDOM || mode == PS_PATCH_ALL_POSITIVE || mode == PS_PATCH_ONE_POSITIVE, "%s: mode = %d is none of the three", who, (int)mode);
-    PS_CHECK(n >= 1 && n < (1ll << 31), "%s: n = %lld volumes", who, (long long)n);
-    PS_CHECK(images && labels && weights && dims && cand && P, "%s: NULL images, labels, weights, dims, cand or P table", who);
-    PS_CHECK(out_images && out_weights && out_labels && out_info, "%s: NULL out_images, out_weights, out_labels or out_info", who);
-    PS_CHECK(P[0] >= 1 && P[1] >= 1 && P[2] >= 1 && P[0] < (1ll << 31) && P[1] < (1ll << 31) && P[2] < (1ll << 31) && P[0] * P[1] < (1ll << 31)
-                 && P[0] * P[1] * P[2] < (1ll << 31) && P[0] * P[1] * P[2] * C < (1ll << 31),
-             "%s: P = [%lld, %lld, %lld] (every extent >= 1, P0 * P1 * P2 * C < 2^31)", who, (long long)P[0], (long long)P[1], (long long)P[2]);
-    for (int64_t v = 0; v < n; ++v) {
-        PS_CHECK(images[v] && labels[v] && weights[v], "%s: volume %lld has a NULL image, label or weight pointer", who, (long long)v);
-        const int64_t* d = dims + 3 * v;
-        PS_CHECK(d[0] >= 1 && d[1] >= 1 && d[2] >= 1 && d[0] < (1ll << 31) && d[1] < (1ll << 31) && d[2] < (1ll << 31) && d[0] * d[1] < (1ll << 31)
-                     && d[0] * d[1] * d[2] < (1ll << 31) && d[0] * d[1] * d[2] * C < (1ll << 31),
-                 "%s: dims of volume %lld are [%lld, %lld, %lld] (every dim >= 1, d * h * w * C < 2^31)", who, (long long)v, (long long)d[0], (long long)d[1],
-                 (long long)d[2]);
-    }
-    for (int i = 0; i < B * T; ++i)
-        PS_CHECK(cand[i] >= 0 && cand[i] < n, "%s: cand[%d, %d] = %d is not a volume of the bank (%lld volumes)", who, i / T, i % T, (int)cand[i], (long long)n);
+    PS_TRY(sampler_args_ok(who, images, labels, weights, dims, n, C, cand, B, T, P, mode, out_images && out_weights && out_labels && out_info,
+                           "out_images, out_weights, out_labels or out_info"));
     PS_CHECK(c, "%s: NULL context", who);
 
-    // the table: every candidate's window; the windows the mode can ask for get a count
-    const int nc = B * T;
-    std::vector<int> win;
-    const size_t table_bytes = pad256(sizeof(PatchCand) * nc);
-    std::vector<char> host(table_bytes + pad256(sizeof(int) * nc) + pad256(sizeof(unsigned) * nc), 0);
-    PatchCand* hc = reinterpret_cast<PatchCand*>(host.data());
-    for (int b = 0; b < B; ++b)
-        for (int t = 0; t < T; ++t) {
-            PatchCand& cd = hc[b * T + t];
-            const int v = cand[b * T + t];
-            const unsigned s = hash32(seed + kSeedMul * (unsigned)(b * T + t + 1));
-            cd.img = images[v], cd.lab = labels[v], cd.wgt = weights[v];
-            for (int a = 0; a < 3; ++a) {
-                const int in = (int)dims[3 * v + a], out = (int)P[a];
-                const int x0 = out / 2, x1 = in - x0;
-                int ctr;
-                if (x1 <= x0) ctr = (x0 + x1) / 2;
-                else ctr = x0 + (int)(((unsigned long long)hash32(s + kAxisMul * (unsigned)(a + 1)) * (unsigned long long)(x1 - x0 + 1)) >> 32);
-                const int r0 = std::min(out / 2, ctr), r1 = std::min(out - out / 2, in - ctr);
-                cd.dim[a] = in, cd.c[a] = ctr, cd.src[a] = ctr - r0, cd.lo[a] = out / 2 - r0, cd.n[a] = r0 + r1;
-            }
-            cd.s_fill = hash32(s + kAxisMul * 4u);
-            cd.vol = v;
-            cd.pad = 0;
-            const bool counted = t == 0 || mode == PS_PATCH_ALL_POSITIVE || (mode == PS_PATCH_ONE_POSITIVE && b == B - 1);
-            cd.count = counted ? (int)win.size() : -1;
-            if (counted) win.push_back(b * T + t);
-        }
-    std::copy(win.begin(), win.end(), reinterpret_cast<int*>(host.data() + table_bytes));  // (the counts behind them stay zero)
-
+    SamplerBlob bl;
+    sampler_table(bl, images, labels, weights, dims, cand, B, T, P, seed, mode, B - 1, 0);
     PS_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    Arena& A = c->sample_arena;
-    char* d_tab = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-        A.begin(pass == 0);
-        d_tab = A.take<char>(host.size());
-        if (pass == 0) PS_TRY(A.buf.reserve(A.off));
-    }
-    const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
-    const int* d_win = reinterpret_cast<const int*>(d_tab + table_bytes);
-    unsigned* d_counts = reinterpret_cast<unsigned*>(d_tab + table_bytes + pad256(sizeof(int) * nc));
     PatchShape sh;
     sh.P[0] = (int)P[0], sh.P[1] = (int)P[1], sh.P[2] = (int)P[2], sh.C = C, sh.B = B, sh.T = T, sh.mode = mode;
     const size_t V = (size_t)P[0] * P[1] * P[2];
-    const unsigned kdw = (unsigned)((P[2] + 6) / 4);  // a row of P2 bytes starting at byte 3 of a word touches this many
-    const unsigned count_blocks = (unsigned)(((size_t)P[0] * P[1] * kdw + 2047) / 2048);
     const unsigned img_blocks = (unsigned)(((size_t)B * V * C + 4095) / 4096), vox_blocks = (unsigned)(((size_t)B * V + 4095) / 4096);
     const bool vec_i = (reinterpret_cast<uintptr_t>(out_images) & 15) == 0;
     const bool vec_v = ((reinterpret_cast<uintptr_t>(out_weights) | reinterpret_cast<uintptr_t>(out_labels)) & 15) == 0;
     Stage stg(c, "patch_sample", 2);
-    PS_TRY(c->upload_async(d_tab, host.data(), host.size()));
-    hipLaunchKernelGGL(patch_count_kernel, dim3(count_blocks, (unsigned)win.size()), dim3(256), 0, st, d_c, d_win, d_counts, kdw);
+    char* d_tab = nullptr;
+    PS_TRY(sampler_count(c, bl, P, d_tab));
+    const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
+    const unsigned* d_counts = reinterpret_cast<const unsigned*>(d_tab + bl.counts_off);
     if ((P[2] * C) % 4 == 0)
-        hipLaunchKernelGGL(patch_gather_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images,
-                           out_weights, out_labels, out_info);
+        hipLaunchKernelGGL(patch_gather_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, sh, img_blocks, vec_i, vec_v,
+                           out_images, out_weights, out_labels, out_info);
     else
-        hipLaunchKernelGGL(patch_gather_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images,
-                           out_weights, out_labels, out_info);
+        hipLaunchKernelGGL(patch_gather_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, sh, img_blocks, vec_i, vec_v,
+                           out_images, out_weights, out_labels, out_info);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+extern "C" int ps_patch_sample_mixup(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights,
+                                     const int64_t* dims, int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed,
+                                     int32_t mode, int32_t num_classes, const double* gamma, float* out_images, float* out_weights, float* out_soft,
+                                     int32_t* out_info)
+{
+    const char* who = "ps_patch_sample_mixup";
+    // every argument error is found here, before anything is enqueued
+    PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
+    PS_CHECK(B >= 1 && B <= PS_PATCH_MAX_B - 1, "%s: B = %d, must be in [1, %d] (B + 1 samples are drawn)", who, (int)B, PS_PATCH_MAX_B - 1);
+    PS_CHECK(num_classes >= 2 && num_classes <= 16, "%s: num_classes = %d, must be in [2, 16]", who, (int)num_classes);
+    PS_TRY(sampler_args_ok(who, images, labels, weights, dims, n, C, cand, B + 1, T, P, mode, out_images && out_weights && out_soft && out_info,
+                           "out_images, out_weights, out_soft or out_info"));
+    PS_CHECK((int64_t)B * P[0] * P[1] * P[2] * num_classes < (1ll << 31), "%s: B * P0 * P1 * P2 * num_classes = %lld, must stay below 2^31", who,
+             (long long)((int64_t)B * P[0] * P[1] * P[2] * num_classes));
+    PS_CHECK(gamma, "%s: NULL gamma", who);
+    for (int b = 0; b < B; ++b)
+        PS_CHECK(std::isfinite(gamma[b]) && gamma[b] >= 0.0 && gamma[b] <= 1.0, "%s: gamma[%d] = %g, must be finite and in [0, 1]", who, b, gamma[b]);
+    PS_CHECK(c, "%s: NULL context", who);
+
+    SamplerBlob bl;
+    sampler_table(bl, images, labels, weights, dims, cand, B + 1, T, P, seed, mode, B - 1, sizeof(float2) * B);
+    float* hg = reinterpret_cast<float*>(bl.host.data() + bl.extra_off);
+    for (int b = 0; b < B; ++b) {
+        hg[2 * b] = (float)gamma[b];
+        hg[2 * b + 1] = (float)(1.0 - gamma[b]);  // (the subtraction in float64, as NumPy's scalar times a float32 array)
+    }
+    PS_HIP(hipSetDevice(c->device));
+    PatchShape sh;
+    sh.P[0] = (int)P[0], sh.P[1] = (int)P[1], sh.P[2] = (int)P[2], sh.C = C, sh.B = B, sh.T = T, sh.mode = mode;
+    const size_t V = (size_t)P[0] * P[1] * P[2];
+    const unsigned img_blocks = (unsigned)(((size_t)B * V * C + 4095) / 4096), vox_blocks = (unsigned)(((size_t)B * V + 4095) / 4096);
+    const bool vec_i = (reinterpret_cast<uintptr_t>(out_images) & 15) == 0, vec_w = (reinterpret_cast<uintptr_t>(out_weights) & 15) == 0;
+    const uintptr_t as = reinterpret_cast<uintptr_t>(out_soft);
+    const int al_s = (as & 15) == 0 ? 16 : (as & 7) == 0 ? 8 : 4;
+    Stage stg(c, "patch_sample_mixup", 2);
+    char* d_tab = nullptr;
+    PS_TRY(sampler_count(c, bl, P, d_tab));
+    const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
+    const unsigned* d_counts = reinterpret_cast<const unsigned*>(d_tab + bl.counts_off);
+    const float2* d_g = reinterpret_cast<const float2*>(d_tab + bl.extra_off);
+    if ((P[2] * C) % 4 == 0)
+        hipLaunchKernelGGL(patch_mix_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, d_g, sh, (int)num_classes,
+                           img_blocks, vec_i, vec_w, al_s, out_images, out_weights, out_soft, out_info);
+    else
+        hipLaunchKernelGGL(patch_mix_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, d_g, sh, (int)num_classes,
+                           img_blocks, vec_i, vec_w, al_s, out_images, out_weights, out_soft, out_info);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }

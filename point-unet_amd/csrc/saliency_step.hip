@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "../../include/pointseg_saliency_attention.h"
+#include "../../include/pointseg_saliency_mixup.h"
 #include "../../include/pointseg_saliency_step.h"
 #include "../../include/pointseg_saliency_train.h"
 #include "common.h"
@@ -213,7 +214,8 @@ struct Step {
         return PS_OK;
     }
 
-    int walk(const float* x, const int* labels, const float* weight, float* loss, float* logits_out)
+    // labels: [B, D, H, W] int32, or -- soft -- the f32 [B, D, H, W, K] rows of include/pointseg_saliency_mixup.h: the loss node's kind
+    int walk(const float* x, const void* labels, bool soft, const float* weight, float* loss, float* logits_out)
     {
         const int nB = p.B, K = p.K, V0 = p.Vl[0];
         // ---- forward: the encoder (model.py:182-210)
@@ -270,13 +272,15 @@ struct Step {
         float* lg = logits_out ? logits_out : at(p.logits);
         PS_TRY(fwd(net.fin, gated, c345u, 0, 64, 1, 1, 1, lg));
         double* sums = reinterpret_cast<double*>(at(p.sums));
-        PS_TRY(op([&](void* sc, int64_t* n) { return ps_softmax_dice_loss(c, lg, labels, weight, nB, V0, K, loss, sums, sc, n); }));
+        PS_TRY(op([&](void* sc, int64_t* n) {
+            return (soft ? ps_softmax_dice_soft_loss : ps_softmax_dice_loss)(c, lg, labels, weight, nB, V0, K, loss, sums, sc, n);
+        }));
 
         // ---- backward, the readers of a shared tensor in the reverse of the header's layer order
         float *gK = at(p.gK), *gA = at(p.gA), *gB = at(p.gB), *gC = at(p.gC), *gD = at(p.gD), *gS = at(p.gS), *g1 = at(p.g1), *g1b = at(p.g1b);
         float *gdn[5], *tA[5], *tB[5];
         for (int l = 0; l < 5; ++l) gdn[l] = at(p.gdn[l]), tA[l] = at(p.tA[l]), tB[l] = at(p.tB[l]);
-        if (run) PS_TRY(ps_softmax_dice_loss_bwd(c, lg, labels, weight, sums, nullptr, nB, V0, K, gK));
+        if (run) PS_TRY((soft ? ps_softmax_dice_soft_loss_bwd : ps_softmax_dice_loss_bwd)(c, lg, labels, weight, sums, nullptr, nB, V0, K, gK));
         PS_TRY(bwd(net.fin, gK, nullptr, gA, gB));  // gA: the gated C12's gradient; gB: C345's, the first of its four
         if (run) PS_TRY(ps_spatial_gate_bwd(c, gA, Y(net.c12), sa_map, nB, V0, 64, gA, g1));
         PS_TRY(bwd(net.c12, gA, gA, gC, gD));
@@ -331,8 +335,8 @@ int shapes_ok(const char* who, int64_t B, int64_t D, int64_t H, int64_t W, int64
     return PS_OK;
 }
 
-// ps_saliency_backward behind checked shapes; `who` names the entry in the messages
-int backward_run(const char* who, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C_in,
+// ps_saliency_backward behind checked shapes; `who` names the entry in the messages, `soft` is the kind of `labels`
+int backward_run(const char* who, bool soft, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C_in,
                  int64_t K, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
     PS_CHECK(scratch_bytes && (c || !scratch), "%s: NULL argument", who);
@@ -342,7 +346,7 @@ int backward_run(const char* who, ps_context* c, const void* x, const void* labe
     PS_CHECK(weight_count == s.net.count, "%s: weight_count = %lld, the network has %lld weights", who, (long long)weight_count, (long long)s.net.count);
     s.c = c, s.run = false, s.base = nullptr, s.wt = nullptr, s.gr = nullptr;
     step_plan(s.net, (int)B, (int)D, (int)H, (int)W, (int)K, 0, s.p);
-    PS_TRY(s.walk(nullptr, nullptr, nullptr, nullptr, nullptr));  // every op's size, and its own view of the shapes
+    PS_TRY(s.walk(nullptr, nullptr, soft, nullptr, nullptr, nullptr));  // every op's size, and its own view of the shapes
     step_plan(s.net, (int)B, (int)D, (int)H, (int)W, (int)K, s.ops_need, s.p);
     if (!scratch) {
         *scratch_bytes = (int64_t)s.p.total;
@@ -354,8 +358,7 @@ int backward_run(const char* who, ps_context* c, const void* x, const void* labe
     PS_TRY(check_scratch(who, scratch, scratch_bytes, s.p.total));
     PS_HIP(hipSetDevice(c->device));
     s.run = true, s.base = static_cast<char*>(scratch), s.wt = static_cast<const float*>(weights), s.gr = static_cast<float*>(grads);
-    return s.walk(static_cast<const float*>(x), static_cast<const int*>(labels), static_cast<const float*>(weight), static_cast<float*>(loss),
-                  static_cast<float*>(logits));
+    return s.walk(static_cast<const float*>(x), labels, soft, static_cast<const float*>(weight), static_cast<float*>(loss), static_cast<float*>(logits));
 }
 
 int update_check(const char* who, const void* params, const void* grads, const void* accum, int64_t C_in, int64_t K, int64_t weight_count, Net& net)
@@ -388,7 +391,7 @@ extern "C" int ps_saliency_backward(ps_context* c, const void* x, const void* la
                                     int64_t C_in, int64_t num_classes, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits,
                                     void* scratch, int64_t* scratch_bytes)
 {
-    return ps::backward_run("ps_saliency_backward", c, x, labels, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits, scratch,
+    return ps::backward_run("ps_saliency_backward", false, c, x, labels, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits, scratch,
                             scratch_bytes);
 }
 
@@ -407,12 +410,15 @@ extern "C" int ps_saliency_sgd_update(ps_context* c, void* params, const void* g
     return PS_OK;
 }
 
-extern "C" int ps_saliency_train_step(ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
-                                      int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
-                                      const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
+namespace ps {
+
+namespace {
+
+// ps_saliency_train_step / ps_saliency_train_step_soft
+int train_step_run(const char* who, bool soft, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                   int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
+                   const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
-    using namespace ps;
-    static const char* who = "ps_saliency_train_step";
     const ps_saliency_step_options dflt = {nullptr, nullptr, 1, 0.9f, 1e-5f};
     const ps_saliency_step_options& o = options ? *options : dflt;
     PS_CHECK(o.world_size >= 1, "%s: world_size = %d, must be >= 1", who, (int)o.world_size);
@@ -421,7 +427,7 @@ extern "C" int ps_saliency_train_step(ps_context* c, const void* x, const void* 
         Net net;
         PS_TRY(update_check(who, params, grads, accum, C_in, num_classes, weight_count, net));
     }
-    PS_TRY(backward_run(who, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, loss, logits, scratch, scratch_bytes));
+    PS_TRY(backward_run(who, soft, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, loss, logits, scratch, scratch_bytes));
     if (!scratch) return PS_OK;
     float grad_scale = 1.f;
     if (o.allreduce && o.world_size > 1) {
@@ -438,4 +444,32 @@ extern "C" int ps_saliency_train_step(ps_context* c, const void* x, const void* 
     update_run(c->stream, net, static_cast<float*>(params), static_cast<const float*>(grads), static_cast<float*>(accum), learning_rate, o.momentum, o.l2, grad_scale);
     PS_HIP(hipGetLastError());
     return PS_OK;
+}
+
+}  // namespace
+
+}  // namespace ps
+
+extern "C" int ps_saliency_train_step(ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                                      int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
+                                      const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
+{
+    return ps::train_step_run("ps_saliency_train_step", false, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
+                              learning_rate, options, loss, logits, scratch, scratch_bytes);
+}
+
+extern "C" int ps_saliency_backward_soft(ps_context* c, const void* x, const void* soft, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                                         int64_t C_in, int64_t num_classes, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits,
+                                         void* scratch, int64_t* scratch_bytes)
+{
+    return ps::backward_run("ps_saliency_backward_soft", true, c, x, soft, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits,
+                            scratch, scratch_bytes);
+}
+
+extern "C" int ps_saliency_train_step_soft(ps_context* c, const void* x, const void* soft, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                                           int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
+                                           const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
+{
+    return ps::train_step_run("ps_saliency_train_step_soft", true, c, x, soft, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
+                              learning_rate, options, loss, logits, scratch, scratch_bytes);
 }

@@ -7,6 +7,7 @@
 // and the tensors are 16-byte aligned (VEC = 4), a float at a time elsewhere (VEC = 1) -- the same values either way, a lane adds its own
 // channels only.  Every sum over voxels goes through the kit's slab-sum frame (the loss keeps its own wave-butterfly form).
 #include "../../include/pointseg_saliency_attention.h"
+#include "../../include/pointseg_saliency_mixup.h"
 #include "../../include/pointseg_saliency_train.h"
 #include "saliency_kit.h"
 
@@ -235,11 +236,61 @@ __device__ __forceinline__ double wave_sum(double a)
     return a;
 }
 
+// Where a voxel's label row g_vc comes from -- the one thing the hard-label and the soft-label (mixup, include/pointseg_saliency_mixup.h)
+// forms of the two kernels below differ in.  at<MODE>(row, C) is voxel `row`; of it, has(c): g_vc can be non-zero, times(a, c) = a g_vc,
+// asked once per class, ascending.  HardLabels: an integer g, g_vc = [g = c] -- a class that is not the voxel's adds nothing and a product
+// by 1 is not made.  SoftLabels: C floats, moved like the logits (MODE 2: one 8-byte load; MODE 4: 16 bytes when the class enters a new
+// four, so that only four are in registers beside the 16 logits; MODE 1: floats).  A product by exactly 0 or 1 and the addition of +0 to a
+// float64 sum are exact, so one-hot soft rows give the bytes of the integer form.
+struct HardLabels {
+    const int* __restrict__ p;
+    struct At {
+        int g;
+        __device__ __forceinline__ bool has(int c) const { return g == c; }
+        __device__ __forceinline__ double times(double a, int) { return a; }
+    };
+    template <int MODE>
+    __device__ __forceinline__ At at(size_t row, int) const
+    {
+        return At{p[row]};
+    }
+};
+
+struct SoftLabels {
+    const float* __restrict__ p;
+    template <int MODE>
+    struct At {
+        const float* __restrict__ r;
+        float q[MODE == 1 ? 1 : MODE];
+        __device__ __forceinline__ bool has(int) const { return true; }
+        __device__ __forceinline__ double times(double a, int c)
+        {
+            if (MODE == 1) return a * (double)r[c];
+            if (MODE == 4 && (c & 3) == 0) {
+                const float4 f = *reinterpret_cast<const float4*>(r + c);
+                q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
+            }
+            return a * (double)q[c & (MODE - 1)];
+        }
+    };
+    template <int MODE>
+    __device__ __forceinline__ At<MODE> at(size_t row, int C) const
+    {
+        At<MODE> a;
+        a.r = p + row * C;
+        if (MODE == 2) {
+            const float2 f = *reinterpret_cast<const float2*>(a.r);
+            a.q[0] = f.x, a.q[1] = f.y;
+        }
+        return a;
+    }
+};
+
 // grid (slabs, B): thread t adds the voxels v0 + t, v0 + t + 256, ... of its slab, the 64 lanes of a wave meet in a butterfly, the four
 // waves are added ascending.  part [slab][B][C][3] = (S0, S1, S2).
-template <int MODE>
-__global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ logits, const int* __restrict__ labels, const float* __restrict__ weight, int V,
-                                                        int C, double* __restrict__ part)
+template <int MODE, class LAB>
+__global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ logits, LAB labels, const float* __restrict__ weight, int V, int C,
+                                                        double* __restrict__ part)
 {
     constexpr int NC = Row<MODE>::NC;
     __shared__ double red[4][3 * NC];
@@ -252,16 +303,17 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict_
         Row<MODE> p;
         row_load<MODE>(logits + row * C, C, p);
         row_softmax<MODE>(C, p);
-        const int g = labels[row];
+        auto g = labels.template at<MODE>(row, C);
         const double w = weight ? (double)weight[row] : 1.0;
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             if (c < C) {
                 const double pc = (double)p.v[c];
                 s1[c] += (w * pc) * pc;
-                if (g == c) {
-                    s0[c] += w * pc;
-                    s2[c] += w;
+                if (g.has(c)) {
+                    const double wg = g.times(w, c);
+                    s0[c] += wg * pc;
+                    s2[c] += wg;
                 }
             }
     }
@@ -292,11 +344,11 @@ __global__ void dice_finish_kernel(const double* __restrict__ sums, int B, int C
     *loss = (float)(total / B);
 }
 
-// grid (ceil(V / 256), B), a thread per voxel.  G_vc = w ([g = c] kA_c + kB_c p_vc) with kA_c = -k 2 / D_c, kB_c = k 2 num_c / D_c^2,
-// k = dloss / (B C); past the softmax everything is float64, rounded once.  A thread reads its row before it writes it: dlogits may be logits.
-template <int MODE>
-__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* logits, const int* __restrict__ labels, const float* __restrict__ weight,
-                                                       const double* __restrict__ sums, const float* __restrict__ dloss, int B, int V, int C, float* dlogits)
+// grid (ceil(V / 256), B), a thread per voxel.  G_vc = w (g_vc kA_c + kB_c p_vc) with kA_c = -k 2 / D_c, kB_c = k 2 num_c / D_c^2,
+// k = dloss / (B C); past the softmax everything is float64, rounded once.  A thread reads its rows before it writes: dlogits may be logits.
+template <int MODE, class LAB>
+__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* logits, LAB labels, const float* __restrict__ weight, const double* __restrict__ sums,
+                                                       const float* __restrict__ dloss, int B, int V, int C, float* dlogits)
 {
     constexpr int NC = Row<MODE>::NC;
     __shared__ double kA[NC], kB[NC];
@@ -314,20 +366,85 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* logits, cons
     Row<MODE> p;
     row_load<MODE>(logits + row * C, C, p);
     row_softmax<MODE>(C, p);
-    const int g = labels[row];
+    auto g = labels.template at<MODE>(row, C);
     const double w = weight ? (double)weight[row] : 1.0;
     double G[NC], dot = 0.0;
 #pragma unroll
     for (int c = 0; c < NC; ++c)
         if (c < C) {
             const double pc = (double)p.v[c];
-            G[c] = w * ((g == c ? kA[c] : 0.0) + kB[c] * pc);
+            G[c] = w * ((g.has(c) ? g.times(kA[c], c) : 0.0) + kB[c] * pc);
             dot += pc * G[c];
         }
 #pragma unroll
     for (int c = 0; c < NC; ++c)
         if (c < C) p.v[c] = (float)((double)p.v[c] * (G[c] - dot));
     row_store<MODE>(dlogits + row * C, C, p);
+}
+
+// the vector MODE all of a call's rows can be moved in: the logits (read at a, written at b) and, soft labels, their rows
+inline int dice_mode_with(int C, const void* a, const void* b, const SoftLabels& l)
+{
+    const int m = dice_mode(C, a, b);
+    return dice_mode(C, l.p, l.p) == m ? m : 1;
+}
+inline int dice_mode_with(int C, const void* a, const void* b, const HardLabels&) { return dice_mode(C, a, b); }
+
+// ps_softmax_dice_loss / ps_softmax_dice_soft_loss behind one body; `what` names the label argument in the messages
+template <class LAB>
+int dice_loss_run(const char* who, const char* what, ps_context* c, const void* logits, LAB labels, const void* weight, int64_t B, int64_t V, int64_t C,
+                  void* loss, void* sums, void* scratch, int64_t* scratch_bytes)
+{
+    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
+    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
+    const int slabs = ceil_div(V, kSlab), nv = (int)(B * C * 3);
+    Carver cv{static_cast<char*>(scratch)};
+    double* part = cv.take<double>((size_t)slabs * nv);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)cv.off;
+        return PS_OK;
+    }
+    PS_CHECK(logits && labels.p, "%s: NULL logits or %s (they may be NULL only in the call that sizes the scratch; weight may be NULL)", who, what);
+    PS_CHECK(loss && sums, "%s: NULL loss or sums", who);
+    PS_CHECK(c, "%s: NULL context", who);
+    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
+
+    PS_HIP(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    Stage stg(c, who + 3, 3);  // (the stage is the entry's name without "ps_")
+    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight);
+    const dim3 grid((unsigned)slabs, (unsigned)B);
+    const int mode = dice_mode_with((int)C, logits, logits, labels);
+    if (mode == 2) hipLaunchKernelGGL((dice_sums_kernel<2, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
+    else if (mode == 4) hipLaunchKernelGGL((dice_sums_kernel<4, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
+    else hipLaunchKernelGGL((dice_sums_kernel<1, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
+    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, static_cast<double*>(sums));
+    hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, sm, static_cast<const double*>(sums), (int)B, (int)C, static_cast<float*>(loss));
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+template <class LAB>
+int dice_bwd_run(const char* who, const char* what, ps_context* c, const void* logits, LAB labels, const void* weight, const void* sums, const void* dloss,
+                 int64_t B, int64_t V, int64_t C, void* dlogits)
+{
+    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
+    PS_CHECK(logits && labels.p && sums, "%s: NULL logits, %s or sums (weight and dloss may be NULL)", who, what);
+    PS_CHECK(dlogits, "%s: NULL dlogits", who);
+    PS_CHECK(c, "%s: NULL context", who);
+
+    PS_HIP(hipSetDevice(c->device));
+    Stage stg(c, who + 3, 1);
+    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight), *dl = static_cast<const float*>(dloss);
+    const double* sd = static_cast<const double*>(sums);
+    float* out = static_cast<float*>(dlogits);
+    const dim3 grid((unsigned)ceil_div(V, 256), (unsigned)B);
+    const int mode = dice_mode_with((int)C, logits, dlogits, labels);
+    if (mode == 2) hipLaunchKernelGGL((dice_bwd_kernel<2, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
+    else if (mode == 4) hipLaunchKernelGGL((dice_bwd_kernel<4, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
+    else hipLaunchKernelGGL((dice_bwd_kernel<1, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
 }
 
 }  // namespace
@@ -494,59 +611,27 @@ extern "C" int ps_spatial_gate_bwd(ps_context* c, const void* dy, const void* f,
 extern "C" int ps_softmax_dice_loss(ps_context* c, const void* logits, const void* labels, const void* weight, int64_t B, int64_t V, int64_t C, void* loss,
                                     void* sums, void* scratch, int64_t* scratch_bytes)
 {
-    using namespace ps;
-    static const char* who = "ps_softmax_dice_loss";
-    PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
-    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
-    const int slabs = ceil_div(V, kSlab), nv = (int)(B * C * 3);
-    Carver cv{static_cast<char*>(scratch)};
-    double* part = cv.take<double>((size_t)slabs * nv);
-    if (!scratch) {
-        *scratch_bytes = (int64_t)cv.off;
-        return PS_OK;
-    }
-    PS_CHECK(logits && labels, "%s: NULL logits or labels (they may be NULL only in the call that sizes the scratch; weight may be NULL)", who);
-    PS_CHECK(loss && sums, "%s: NULL loss or sums", who);
-    PS_CHECK(c, "%s: NULL context", who);
-    PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
-
-    PS_HIP(hipSetDevice(c->device));
-    hipStream_t sm = c->stream;
-    Stage stg(c, "softmax_dice_loss", 3);
-    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight);
-    const int* gl = static_cast<const int*>(labels);
-    const dim3 grid((unsigned)slabs, (unsigned)B);
-    const int mode = dice_mode((int)C, logits, logits);
-    if (mode == 2) hipLaunchKernelGGL(dice_sums_kernel<2>, grid, dim3(256), 0, sm, lf, gl, wf, (int)V, (int)C, part);
-    else if (mode == 4) hipLaunchKernelGGL(dice_sums_kernel<4>, grid, dim3(256), 0, sm, lf, gl, wf, (int)V, (int)C, part);
-    else hipLaunchKernelGGL(dice_sums_kernel<1>, grid, dim3(256), 0, sm, lf, gl, wf, (int)V, (int)C, part);
-    hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, static_cast<double*>(sums));
-    hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, sm, static_cast<const double*>(sums), (int)B, (int)C, static_cast<float*>(loss));
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+    return ps::dice_loss_run("ps_softmax_dice_loss", "labels", c, logits, ps::HardLabels{static_cast<const int*>(labels)}, weight, B, V, C, loss, sums, scratch,
+                             scratch_bytes);
 }
 
 extern "C" int ps_softmax_dice_loss_bwd(ps_context* c, const void* logits, const void* labels, const void* weight, const void* sums, const void* dloss, int64_t B,
                                         int64_t V, int64_t C, void* dlogits)
 {
-    using namespace ps;
-    static const char* who = "ps_softmax_dice_loss_bwd";
-    PS_TRY(rows_shape_ok(who, B, V, C, 2, kMaxClasses, kLimitV));
-    PS_CHECK(logits && labels && sums, "%s: NULL logits, labels or sums (weight and dloss may be NULL)", who);
-    PS_CHECK(dlogits, "%s: NULL dlogits", who);
-    PS_CHECK(c, "%s: NULL context", who);
+    return ps::dice_bwd_run("ps_softmax_dice_loss_bwd", "labels", c, logits, ps::HardLabels{static_cast<const int*>(labels)}, weight, sums, dloss, B, V, C,
+                            dlogits);
+}
 
-    PS_HIP(hipSetDevice(c->device));
-    Stage stg(c, "softmax_dice_loss_bwd", 1);
-    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight), *dl = static_cast<const float*>(dloss);
-    const int* gl = static_cast<const int*>(labels);
-    const double* sd = static_cast<const double*>(sums);
-    float* out = static_cast<float*>(dlogits);
-    const dim3 grid((unsigned)ceil_div(V, 256), (unsigned)B);
-    const int mode = dice_mode((int)C, logits, dlogits);
-    if (mode == 2) hipLaunchKernelGGL(dice_bwd_kernel<2>, grid, dim3(256), 0, c->stream, lf, gl, wf, sd, dl, (int)B, (int)V, (int)C, out);
-    else if (mode == 4) hipLaunchKernelGGL(dice_bwd_kernel<4>, grid, dim3(256), 0, c->stream, lf, gl, wf, sd, dl, (int)B, (int)V, (int)C, out);
-    else hipLaunchKernelGGL(dice_bwd_kernel<1>, grid, dim3(256), 0, c->stream, lf, gl, wf, sd, dl, (int)B, (int)V, (int)C, out);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+extern "C" int ps_softmax_dice_soft_loss(ps_context* c, const void* logits, const void* soft, const void* weight, int64_t B, int64_t V, int64_t C, void* loss,
+                                         void* sums, void* scratch, int64_t* scratch_bytes)
+{
+    return ps::dice_loss_run("ps_softmax_dice_soft_loss", "soft", c, logits, ps::SoftLabels{static_cast<const float*>(soft)}, weight, B, V, C, loss, sums,
+                             scratch, scratch_bytes);
+}
+
+extern "C" int ps_softmax_dice_soft_loss_bwd(ps_context* c, const void* logits, const void* soft, const void* weight, const void* sums, const void* dloss,
+                                             int64_t B, int64_t V, int64_t C, void* dlogits)
+{
+    return ps::dice_bwd_run("ps_softmax_dice_soft_loss_bwd", "soft", c, logits, ps::SoftLabels{static_cast<const float*>(soft)}, weight, sums, dloss, B, V, C,
+                            dlogits);
 }

@@ -501,12 +501,17 @@ def spatial_gate_backward(dy, f, sa, need=("f", "a")):
     return {k: v for k, v in (("f", df), ("a", da)) if v is not None}
 
 
+def _is_soft(labels):
+    """Soft labels (include/pointseg_saliency_mixup.h): a float32 row of C values per voxel, where hard labels are one int32."""
+    return labels.dtype == torch.float32
+
+
 def _loss_args(who, logits, labels, weight):
     logits, B, V, C = _rows(logits, who, "logits")
-    if not isinstance(labels, torch.Tensor) or labels.device != logits.device or labels.dtype != torch.int32:
-        raise ValueError("%s: labels must be an int32 tensor on the logits' device" % who)
-    if labels.numel() != B * V:
-        raise ValueError("%s: labels must have one value per voxel of logits %s" % (who, tuple(logits.shape)))
+    if not isinstance(labels, torch.Tensor) or labels.device != logits.device or labels.dtype not in (torch.int32, torch.float32):
+        raise ValueError("%s: labels must be an int32 tensor, or a float32 tensor of soft labels, on the logits' device" % who)
+    if labels.numel() != (B * V * C if _is_soft(labels) else B * V):
+        raise ValueError("%s: labels must have one value per voxel of logits %s (soft labels: one per logit)" % (who, tuple(logits.shape)))
     if weight is not None:
         weight = _f32(weight, who, "weight")
         if weight.numel() != B * V:
@@ -515,21 +520,24 @@ def _loss_args(who, logits, labels, weight):
 
 
 def softmax_dice_loss(logits, labels, weight=None):
-    """Loss / dice of model.py:491-548, 592-618 (weight_map branch, no mixup): logits [B, ..., C], labels [B, ...] int32, weight [B, ...] or
-    None (ones) -> (loss, a 0-dim device tensor; sums [B, C, 3] float64, what softmax_dice_loss_backward takes)."""
+    """Loss / dice of model.py:491-548, 592-618 (weight_map branch): logits [B, ..., C], labels [B, ...] int32, weight [B, ...] or None
+    (ones) -> (loss, a 0-dim device tensor; sums [B, C, 3] float64, what softmax_dice_loss_backward takes).  float32 labels [B, ..., C] are
+    soft labels (mixup's): dice_mixup, model.py:550-590, 602-612."""
     who = "softmax_dice_loss"
     logits, labels, weight, B, V, C = _loss_args(who, logits, labels, weight)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
     sums = torch.empty((B, C, 3), dtype=torch.float64, device=logits.device)
     ctx = _ctx_for(logits)
-    fn = _lib.lib().ps_softmax_dice_loss
-    _two_call("ps_softmax_dice_loss", logits.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight), B, V, C,
+    name = "ps_softmax_dice_soft_loss" if _is_soft(labels) else "ps_softmax_dice_loss"
+    fn = getattr(_lib.lib(), name)
+    _two_call(name, logits.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight), B, V, C,
                                                                            runtime.ptr(loss), runtime.ptr(sums), scratch, n))
     return loss, sums
 
 
 def softmax_dice_loss_backward(logits, labels, weight, sums, dloss=None):
-    """d loss / d logits times dloss (a device tensor of one float32, handed over as a pointer; None: 1)."""
+    """d loss / d logits times dloss (a device tensor of one float32, handed over as a pointer; None: 1).  labels as softmax_dice_loss
+    takes them, hard or soft."""
     who = "softmax_dice_loss_backward"
     logits, labels, weight, B, V, C = _loss_args(who, logits, labels, weight)
     if not isinstance(sums, torch.Tensor) or sums.device != logits.device or sums.dtype != torch.float64 or tuple(sums.shape) != (B, C, 3):
@@ -539,8 +547,9 @@ def softmax_dice_loss_backward(logits, labels, weight, sums, dloss=None):
         if dloss.numel() != 1:
             raise ValueError("softmax_dice_loss_backward: dloss must hold one value")
     dlogits = torch.empty_like(logits)
-    _lib.check(_lib.lib().ps_softmax_dice_loss_bwd(_ctx_for(logits).handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight),
-                                                   runtime.ptr(sums.contiguous()), runtime.ptr(dloss), B, V, C, runtime.ptr(dlogits)))
+    fn = _lib.lib().ps_softmax_dice_soft_loss_bwd if _is_soft(labels) else _lib.lib().ps_softmax_dice_loss_bwd
+    _lib.check(fn(_ctx_for(logits).handle, runtime.ptr(logits), runtime.ptr(labels), runtime.ptr(weight), runtime.ptr(sums.contiguous()), runtime.ptr(dloss),
+                  B, V, C, runtime.ptr(dlogits)))
     return dlogits
 
 
@@ -615,7 +624,7 @@ def differentiable_spatial_gate(a1, a2, a3, f):
 
 
 def differentiable_softmax_dice_loss(logits, labels, weight=None):
-    """softmax_dice_loss's loss (0-dim, on the device), recorded by torch.autograd."""
+    """softmax_dice_loss's loss (0-dim, on the device), recorded by torch.autograd.  The labels, hard or soft, receive no gradient."""
     return SoftmaxDiceLossFunction.apply(logits, labels, weight)
 
 
@@ -679,7 +688,8 @@ class TrainableSaliencyNet(torch.nn.Module):
         return conv("final", C12, norm=False, x2=C345)
 
     def loss(self, x, labels, weight=None, masks=None):
-        """The reference's training loss (train.py:83-110 without the regulariser, which reference_optimizer carries as weight decay)."""
+        """The reference's training loss (train.py:83-110 without the regulariser, which reference_optimizer carries as weight decay).
+        labels: [B, D, H, W] int32, or soft labels float32 [B, D, H, W, num_classes] (PatchBank.sample(mixup=...))."""
         return differentiable_softmax_dice_loss(self.logits(x, masks), labels, weight)
 
     def export(self):
@@ -741,11 +751,12 @@ class SaliencyTrainer:
         _lib.check(fn(ctx.handle, *head, *shape, *tail, runtime.ptr(self.scratch), ctypes.byref(need)))
 
     def backward(self, x, labels, weight=None, want_logits=False):
-        """The loss (0-dim, on the device; overwritten by the next call) of a patch x [B, D, H, W, C_in] with labels [B, D, H, W] int32 and
-        weight [B, D, H, W] or None, its gradients left in `grad`; no parameter changes.  want_logits: (loss, logits)."""
+        """The loss (0-dim, on the device; overwritten by the next call) of a patch x [B, D, H, W, C_in] with labels [B, D, H, W] int32 (or
+        soft labels float32 [B, D, H, W, num_classes]: ps_saliency_backward_soft) and weight [B, D, H, W] or None, its gradients left in
+        `grad`; no parameter changes.  want_logits: (loss, logits)."""
         x, labels, weight, logits = self._args(x, labels, weight)
         p = runtime.ptr
-        self._call(_lib.lib().ps_saliency_backward, x, (p(x), p(labels), p(weight)),
+        self._call(_lib.lib().ps_saliency_backward_soft if _is_soft(labels) else _lib.lib().ps_saliency_backward, x, (p(x), p(labels), p(weight)),
                    (p(self.flat), self.flat.numel(), p(self.grad), p(self.loss), p(logits) if want_logits else None))
         return (self.loss, logits) if want_logits else self.loss
 
@@ -775,7 +786,7 @@ class SaliencyTrainer:
         return fn
 
     def step(self, x, labels, weight, lr, dist=None, allreduce=None, world_size=None):
-        """One training step at learning rate lr; returns the loss before it.  dist: a torch.distributed-like module (all_reduce,
+        """One training step at learning rate lr (labels hard or soft, as backward takes them); returns the loss before it.  dist: a torch.distributed-like module (all_reduce,
         get_world_size) whose sum the gradients go through when the world has more than one rank.  allreduce / world_size: a ready
         PS_ALLREDUCE_FN and its world instead (a host that brings its own collective)."""
         x, labels, weight, _ = self._args(x, labels, weight)
@@ -783,7 +794,7 @@ class SaliencyTrainer:
             allreduce, world_size = self._collective(dist), dist.get_world_size()
         opt = _lib.PsSaliencyStepOptions(allreduce if allreduce is not None else _lib.PS_ALLREDUCE_FN(), None, int(world_size or 1), self.momentum, self.l2)
         p = runtime.ptr
-        self._call(_lib.lib().ps_saliency_train_step, x, (p(x), p(labels), p(weight)),
+        self._call(_lib.lib().ps_saliency_train_step_soft if _is_soft(labels) else _lib.lib().ps_saliency_train_step, x, (p(x), p(labels), p(weight)),
                    (p(self.flat), self.flat.numel(), p(self.grad), p(self.accum), float(lr), ctypes.byref(opt), p(self.loss), None))
         return self.loss
 

@@ -4,8 +4,9 @@ sample on the host -- crop_brain_region / load_pancreas_img (SaliencyAttention/u
 batches of patches drawn there by a stated rule with no host read.  PatchBank is to TrainableSaliencyNet what dataset.CloudBank is to the
 point network's Trainer; train_saliency is the loop of train.py:83-110 over it, evaluate_saliency the Dice of EvalCallback / eval_pancreas.
 
-Not built: mixup (config.MIXUP; its one-hot labels need dice_mixup), a DIRECTION other than axial (permute before add_*), the left-right
-flip (off in the reference).  The training step behind one call is saliency.SaliencyTrainer (train_saliency's engine="native");
+config.MIXUP (include/pointseg_saliency_mixup.h): PatchBank.sample(mixup=num_classes) draws B + 1 samples and mixes neighbour pairs on the
+device into images, or-ed weights and soft labels, which the loss and both training engines take.  Not built: a DIRECTION other than axial
+(permute before add_*), the left-right flip (off in the reference).  The training step behind one call is saliency.SaliencyTrainer (train_saliency's engine="native");
 data-parallel training: hook built, checked with an in-process callback; no multi-process run made."""
 import ctypes
 
@@ -191,14 +192,23 @@ class PatchBank:
             self._tables = (ptrs[0], ptrs[1], ptrs[2], dims, n)
         return self._tables
 
-    def sample(self, cand, patch, seed=0, mode="one_positive"):
+    def sample(self, cand, patch, seed=0, mode="one_positive", mixup=None, gamma=None):
         """One batch, drawn on the device on torch's current stream: cand [B, T] volume ids (cand[b, t] is try t of slot b; a flat [B]
         list is T = 1), patch (P0, P1, P2).  Returns {"images" f32 [B, P0, P1, P2, C], "weights" f32 [B, P0, P1, P2], "labels" i32
         [B, P0, P1, P2], "info" i32 [B, 8] = (try, volume, c0, c1, c2, pos, ok, 0)}, CUDA tensors: the first three are what
-        TrainableSaliencyNet.loss takes.  info's ok is 0 for a slot none of whose tries met the mode's demand (it holds the last try)."""
+        TrainableSaliencyNet.loss takes.  info's ok is 0 for a slot none of whose tries met the mode's demand (it holds the last try).
+
+        mixup=K, the class count (config.MIXUP, ps_patch_sample_mixup): cand is [B + 1, T], one row per DRAWN sample, and slot b of the B
+        mixed slots is gamma[b] * sample b + (1 - gamma[b]) * sample b + 1.  gamma: B float64 values in [0, 1]; None draws
+        np.random.default_rng(seed).beta(0.4, 0.4, B) on the host.  "labels" is then f32 [B, P0, P1, P2, K] (soft labels), "info" is
+        [B + 1, 8], one row per drawn sample, and "gamma" (float64 numpy [B]) is returned with them."""
         who = "PatchBank.sample"
         if mode not in MODES:
             raise ValueError("%s: mode must be one of %s" % (who, sorted(MODES)))
+        if mixup is None and gamma is not None:
+            raise ValueError("%s: gamma is mixup's argument" % who)
+        if mixup is not None and (isinstance(mixup, bool) or int(mixup) != mixup or not 2 <= int(mixup) <= 16):
+            raise ValueError("%s: mixup must be the class count, an integer in [2, 16], got %r" % (who, mixup))
         cand = np.asarray(cand)
         if cand.ndim == 1:
             cand = cand[:, None]
@@ -211,6 +221,8 @@ class PatchBank:
         P = tuple(int(p) for p in patch)
         if len(P) != 3 or min(P) < 1:
             raise ValueError("%s: patch must be three extents >= 1, got %s" % (who, (patch,)))
+        if mixup is not None:
+            return self._sample_mixup(cand, P, seed, mode, int(mixup), gamma)
         C, dev = self.channels, self.device
         stream = torch.cuda.current_stream(dev)
         if self._done is not None:
@@ -226,18 +238,48 @@ class PatchBank:
         self._done.record(stream)
         return out
 
-    def epoch_batches(self, batch_size, patch, epoch, seed=0, tries=8, rank=0, world=1, mode="one_positive"):
-        """The batches of one epoch on one rank (epoch_plan), each drawn when the iterator reaches it."""
-        for _, cand, s in epoch_plan(len(self), batch_size, epoch, seed, tries, rank, world):
-            yield self.sample(cand, patch, s, mode)
+    def _sample_mixup(self, cand, P, seed, mode, K, gamma):
+        who = "PatchBank.sample"
+        B, T = cand.shape[0] - 1, cand.shape[1]
+        if not 1 <= B <= _lib.PS_PATCH_MAX_B - 1:
+            raise ValueError("%s: with mixup cand must be [B + 1, T] with B in [1, %d], got %s" % (who, _lib.PS_PATCH_MAX_B - 1, cand.shape))
+        if gamma is None:
+            gamma = np.random.default_rng(int(seed) & _M32).beta(0.4, 0.4, B)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+        if gamma.shape != (B,) or not np.all(np.isfinite(gamma)) or gamma.min() < 0.0 or gamma.max() > 1.0:
+            raise ValueError("%s: gamma must be %d finite values in [0, 1]" % (who, B))
+        C, dev = self.channels, self.device
+        stream = torch.cuda.current_stream(dev)
+        if self._done is not None:
+            stream.wait_event(self._done)
+        out = {"images": torch.empty((B,) + P + (C,), dtype=torch.float32, device=dev), "weights": torch.empty((B,) + P, dtype=torch.float32, device=dev),
+               "labels": torch.empty((B,) + P + (K,), dtype=torch.float32, device=dev), "info": torch.empty((B + 1, 8), dtype=torch.int32, device=dev),
+               "gamma": gamma}
+        images, labels, weights, dims, n = self.c_tables()
+        self.ctx.use_torch_stream()
+        _lib.check(_lib.lib().ps_patch_sample_mixup(self.ctx.handle, images, labels, weights, dims, n, C, cand.ctypes.data_as(_lib.c_i32p), B, T,
+                                                    (ctypes.c_int64 * 3)(*P), int(seed) & _M32, MODES[mode], K,
+                                                    gamma.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), runtime.ptr(out["images"]),
+                                                    runtime.ptr(out["weights"]), runtime.ptr(out["labels"]), runtime.ptr(out["info"])))
+        self._done = torch.cuda.Event()
+        self._done.record(stream)
+        return out
+
+    def epoch_batches(self, batch_size, patch, epoch, seed=0, tries=8, rank=0, world=1, mode="one_positive", mixup=None):
+        """The batches of one epoch on one rank (epoch_plan), each drawn when the iterator reaches it.  mixup=K: mixed batches of batch_size
+        slots, planned as epoch_plan(len(self), batch_size + 1, ...) -- the reference consumes B + 1 datapoints per mixed batch and then
+        clears its holder."""
+        for _, cand, s in epoch_plan(len(self), batch_size + (0 if mixup is None else 1), epoch, seed, tries, rank, world):
+            yield self.sample(cand, patch, s, mode, mixup)
 
 
-def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None):
+def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None, mixup=None):
     """The loop of train.py:83-110 on the device: `steps` steps on the bank's batches (epoch_batches from `epoch` on,
     config.DATA_SAMPLING = 'one_positive').  engine "autograd": TrainableSaliencyNet.loss under saliency.reference_optimizer(net, lr) (or
     `optimizer`); engine "native": net is a saliency.SaliencyTrainer and every step is one ps_saliency_train_step at learning rate lr
     (dist: the torch.distributed-like module its gradients are summed through).  Returns the per-step losses as one device tensor
-    [steps]; nothing is read back on the way."""
+    [steps]; nothing is read back on the way.  mixup=num_classes: config.MIXUP, every batch is a mixed one (epoch_batches(mixup=...)) and
+    the loss is dice_mixup's, on soft labels."""
     from . import saliency
     if engine not in ("autograd", "native"):
         raise ValueError("train_saliency: engine must be 'autograd' or 'native'")
@@ -246,13 +288,15 @@ def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch
         raise ValueError("train_saliency: the native engine takes a SaliencyTrainer and no optimizer")
     if not native and not isinstance(net, saliency.TrainableSaliencyNet):
         raise ValueError("train_saliency: net must be a TrainableSaliencyNet")
-    if int(steps) < 1 or len(bank) < int(batch_size):
-        raise ValueError("train_saliency: need steps >= 1 and at least batch_size volumes in the bank")
+    if int(steps) < 1 or len(bank) < int(batch_size) + (0 if mixup is None else 1):
+        raise ValueError("train_saliency: need steps >= 1 and at least batch_size volumes (one more with mixup) in the bank")
+    if mixup is not None and int(mixup) != net.num_classes:
+        raise ValueError("train_saliency: mixup must be the network's class count %d" % net.num_classes)
     if not native:
         opt = optimizer if optimizer is not None else saliency.reference_optimizer(net, lr)
     losses = []
     while len(losses) < steps:
-        for batch in bank.epoch_batches(batch_size, patch, epoch, seed):
+        for batch in bank.epoch_batches(batch_size, patch, epoch, seed, mixup=mixup):
             if native:
                 loss = net.step(batch["images"], batch["labels"], batch["weights"], lr, dist).clone()
             else:
