@@ -3,8 +3,8 @@
 The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (PROTOTYPES) and include/pointseg_prepare.h
 (PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES), include/pointseg_saliency.h
 (SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
-(SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES) and include/pointseg_saliency_step.h
-(SALIENCY_STEP_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
+(SALIENCY_STEP_PROTOTYPES) and include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -297,6 +297,15 @@ SALIENCY_PROTOTYPES = {
     "ps_saliency_finish": (ctypes.c_int, [c_vp, c_vp, c_vp] + [ctypes.c_int64] * 4 + [c_vp]),
 }
 
+# every symbol include/pointseg_saliency_precision.h declares (ps_conv3d and ps_saliency_forward with a choice of arithmetic for the
+# convolutions; csrc/conv3d_bf16.hip): the arguments of the entries they extend, then the precision
+PS_PREC_FP32, PS_PREC_BF16X3, PS_PREC_BF16 = 0, 1, 2
+SALIENCY_PRECISIONS = {"fp32": PS_PREC_FP32, "bf16x3": PS_PREC_BF16X3, "bf16": PS_PREC_BF16}
+SALIENCY_PRECISION_PROTOTYPES = {
+    "ps_conv3d_prec": (ctypes.c_int, SALIENCY_PROTOTYPES["ps_conv3d"][1] + [ctypes.c_int32]),
+    "ps_saliency_forward_prec": (ctypes.c_int, SALIENCY_PROTOTYPES["ps_saliency_forward"][1] + [ctypes.c_int32]),
+}
+
 # every symbol include/pointseg_saliency_train.h declares (the gradients of ps_conv3d and ps_instance_norm_relu; csrc/conv3d_train.hip, csrc/saliency_train.hip)
 _CONV_GEOMETRY = [ctypes.c_int64] * 6 + [ctypes.c_int32] * 4 + [ctypes.c_int64] + [ctypes.c_int32] * 2  # B Ds Hs Ws C1 C2 up kd kh kw C_out stride dilation
 SALIENCY_TRAIN_PROTOTYPES = {
@@ -376,7 +385,8 @@ def lib():
             pass
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
-                                  + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PROTOTYPES.items())
+                                  + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_PRECISION_PROTOTYPES.items())
+                                  + list(SALIENCY_TRAIN_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())):
             fn = getattr(handle, name)

@@ -171,6 +171,7 @@ void conv3d_plan(Conv3dArgs& a)
 // of the full patch); 128 rows per workgroup where there are enough output voxels to fill the device with them, else 64.
 void conv3d_launch(hipStream_t sm, const Conv3dArgs& a)
 {
+    if (a.precision != PS_PREC_FP32) return conv3d_b_launch(sm, a);
     const bool wide = (int64_t)a.Do * a.Ho * a.Wo >= 2048;
     if (a.cout <= 16) wide ? launch<2, 1>(sm, a) : launch<1, 1>(sm, a);
     else if (a.cout <= 32) wide ? launch<2, 2>(sm, a) : launch<1, 2>(sm, a);
@@ -182,9 +183,17 @@ void conv3d_launch(hipStream_t sm, const Conv3dArgs& a)
 extern "C" int ps_conv3d(ps_context* c, const void* x, const void* x2, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2, int32_t up,
                          const void* w, const void* bias, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* y)
 {
+    return ps_conv3d_prec(c, x, x2, B, Ds, Hs, Ws, C1, C2, up, w, bias, kd, kh, kw, C_out, stride, dilation, y, PS_PREC_FP32);
+}
+
+extern "C" int ps_conv3d_prec(ps_context* c, const void* x, const void* x2, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2,
+                              int32_t up, const void* w, const void* bias, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride,
+                              int32_t dilation, void* y, int32_t precision)
+{
     using namespace ps;
-    static const char* who = "ps_conv3d";
+    const char* who = precision == PS_PREC_FP32 ? "ps_conv3d" : "ps_conv3d_prec";
     const int64_t lim = 1ll << 31;
+    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
     auto kext = [](int k) { return k == 1 || k == 3 || k == 9; };
     PS_CHECK(kext(kd) && kext(kh) && kext(kw), "%s: kernel %d x %d x %d, every extent must be 1, 3 or 9", who, (int)kd, (int)kh, (int)kw);
     PS_CHECK(stride == 1 || stride == 2, "%s: stride = %d, must be 1 or 2", who, (int)stride);
@@ -210,6 +219,7 @@ extern "C" int ps_conv3d(ps_context* c, const void* x, const void* x2, int64_t B
     a.B = (int)B, a.Ds = (int)Ds, a.Hs = (int)Hs, a.Ws = (int)Ws, a.C1 = (int)C1, a.C2 = (int)C2, a.ldx = (int)C1, a.ldx2 = (int)C2, a.up = up;
     a.kd = kd, a.kh = kh, a.kw = kw, a.cout = (int)C_out, a.stride = stride, a.dil = dilation, a.ldy = (int)C_out;
     a.w_bstride = 0;
+    a.precision = precision;
     conv3d_plan(a);
     PS_HIP(hipSetDevice(c->device));
     Stage stg(c, "conv3d", 1);

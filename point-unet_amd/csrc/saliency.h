@@ -2,7 +2,7 @@
 // every concat part straight into the concat's buffer, so a tensor has a channel pitch), include/pointseg_saliency.h.
 #pragma once
 
-#include "../../include/pointseg_saliency.h"
+#include "../../include/pointseg_saliency_precision.h"
 #include "common.h"
 
 namespace ps {
@@ -19,6 +19,7 @@ struct Conv3dArgs {
     int B, Ds, Hs, Ws, C1, C2, ldx, ldx2, up;
     int kd, kh, kw, cout, stride, dil, ldy;
     int64_t w_bstride;
+    int precision;  // PS_PREC_*: 0 (what `= {}` leaves) is the fp32 kernel of conv3d.hip, the others run conv3d_bf16.hip
     // derived by conv3d_plan
     int D, H, W, Do, Ho, Wo, pd, ph, pw;
 };
@@ -32,5 +33,8 @@ inline int same_pad_before(int in, int k, int stride, int dil)
 
 void conv3d_plan(Conv3dArgs& a);                   // fills the derived fields
 void conv3d_launch(hipStream_t sm, const Conv3dArgs& a);  // (a planned; every limit checked by the caller)
+void conv3d_b_launch(hipStream_t sm, const Conv3dArgs& a);  // conv3d_bf16.hip: what conv3d_launch calls for PS_PREC_BF16X3 and PS_PREC_BF16
+
+inline bool precision_ok(int32_t p) { return p == PS_PREC_FP32 || p == PS_PREC_BF16X3 || p == PS_PREC_BF16; }
 
 }  // namespace ps

@@ -1,5 +1,6 @@
 // saliency.hip -- the saliency attention network around conv3d.hip (include/pointseg_saliency.h): instance norm + ReLU,
-// the channel and the spatial attention, softmax, the graph of unet3d_attention behind one call, and the window average.
+// the channel and the spatial attention, softmax, the graph of unet3d_attention behind one call, and the window average.  The graph's
+// convolutions run at the precision of include/pointseg_saliency_precision.h (conv3d_launch switches); nothing else here depends on it.
 //
 // Instance norm: per (sample, channel) sum and sum of squares in float64 by saliency_kit.h's slab-sum frame -- a workgroup adds a slab of
 // 4096 voxels, its threads in a fixed order, reduce_partials.h adds the slabs in a fixed order -- so two runs give the same bytes and
@@ -166,9 +167,17 @@ extern "C" int ps_saliency_forward(ps_context* c, const void* x, int64_t B, int6
                                    const void* weights, int64_t weight_count, void* logits, void* probs, const ps_saliency_taps* taps, void* scratch,
                                    int64_t* scratch_bytes)
 {
+    return ps_saliency_forward_prec(c, x, B, D, H, W, C_in, num_classes, weights, weight_count, logits, probs, taps, scratch, scratch_bytes, PS_PREC_FP32);
+}
+
+extern "C" int ps_saliency_forward_prec(ps_context* c, const void* x, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C_in, int64_t num_classes,
+                                        const void* weights, int64_t weight_count, void* logits, void* probs, const ps_saliency_taps* taps,
+                                        void* scratch, int64_t* scratch_bytes, int32_t precision)
+{
     using namespace ps;
-    static const char* who = "ps_saliency_forward";
+    const char* who = precision == PS_PREC_FP32 ? "ps_saliency_forward" : "ps_saliency_forward_prec";
     PS_CHECK(scratch_bytes && (c || !scratch), "%s: NULL argument", who);
+    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
     PS_CHECK(net_args_ok(C_in, num_classes), "%s: C_in = %lld, num_classes = %lld (1 <= C_in <= 16, 2 <= num_classes <= 16)", who, (long long)C_in,
              (long long)num_classes);
     PS_CHECK(B >= 1 && B <= 1024, "%s: B = %lld, must be in [1, 1024]", who, (long long)B);
@@ -231,6 +240,7 @@ extern "C" int ps_saliency_forward(ps_context* c, const void* x, int64_t B, int6
         a.x = in, a.x2 = nullptr, a.w = w_over ? w_over : wt + L.w, a.bias = L.b >= 0 ? wt + L.b : nullptr, a.y = out;
         a.B = nB, a.Ds = Dl[l], a.Hs = Hl[l], a.Ws = Wl[l], a.C1 = L.cin, a.C2 = 0, a.ldx = ldx, a.ldx2 = 0, a.up = up;
         a.kd = L.kd, a.kh = L.kh, a.kw = L.kw, a.cout = L.cout, a.stride = stride, a.dil = dil, a.ldy = ldy, a.w_bstride = w_bstride;
+        a.precision = precision;
         conv3d_plan(a);
         conv3d_launch(sm, a);
         if (L.g >= 0) norm_run(sm, out, ldy, out, ldy, res, ldres, nB, a.Do * a.Ho * a.Wo, L.cout, wt + L.g, wt + L.be, eps, ws);

@@ -1,6 +1,7 @@
 """The saliency attention map in front of prepare.pancreas_mask: the reference's SaliencyAttention network (`unet3d_attention`,
 SaliencyAttention/model.py:176-314 with attention.py:79-174) run patch by patch over a volume (`overlapping_inference`,
-SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  SaliencyNet runs it for inference behind one call; the gradients of its
+SaliencyAttention/eval.py:103-193), on the device -- include/pointseg_saliency.h, csrc/conv3d.hip, csrc/saliency.hip.  SaliencyNet runs it for inference behind one call, its convolutions in fp32 or on the
+bf16 matrix pipe (precision="fp32" | "bf16x3" | "bf16": include/pointseg_saliency_precision.h, csrc/conv3d_bf16.hip); the gradients of its
 ops (include/pointseg_saliency_train.h, include/pointseg_saliency_attention.h) stand behind it, op by op, and TrainableSaliencyNet composes the graph from them;
 SaliencyTrainer runs the whole training step behind one call (include/pointseg_saliency_step.h, csrc/saliency_step.hip).
 
@@ -162,18 +163,29 @@ def _conv_args(who, x, w, x2, up, stride):
     return x, w, x2, (B, Ds, Hs, Ws, C1, C2), (B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4])
 
 
-def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
+def _precision(who, precision):
+    """"fp32" | "bf16x3" | "bf16" -> the PS_PREC_* value of include/pointseg_saliency_precision.h."""
+    try:
+        return _lib.SALIENCY_PRECISIONS[precision]
+    except (KeyError, TypeError):
+        raise ValueError("%s: precision must be one of %s, got %r" % (who, ", ".join(map(repr, _lib.SALIENCY_PRECISIONS)), precision)) from None
+
+
+def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1, precision="fp32"):
     """tf.layers.conv3d(x, padding="SAME") without activation: x [B, D, H, W, C1] (and x2 [B, D, H, W, C2], concatenated behind it on the
-    channel axis; both up-sampled `up` times by repetition first), w [kd, kh, kw, C1 + C2, C_out], bias [C_out] or None.  CUDA float32."""
+    channel axis; both up-sampled `up` times by repetition first), w [kd, kh, kw, C1 + C2, C_out], bias [C_out] or None.  CUDA float32.
+    precision: "fp32" (ps_conv3d), or "bf16x3" / "bf16" on the bf16 matrix pipe (ps_conv3d_prec, include/pointseg_saliency_precision.h)."""
     who = "conv3d"
+    prec = _precision(who, precision)
     x, w, x2, dims, out_shape = _conv_args(who, x, w, x2, up, stride)
     if bias is not None:
         bias = _f32(bias, who, "bias", 1)
         if bias.shape[0] != w.shape[4]:
             raise ValueError("conv3d: bias must have C_out values")
     y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ps_conv3d(_ctx_for(x).handle, runtime.ptr(x), runtime.ptr(x2), *dims, up, runtime.ptr(w), runtime.ptr(bias), w.shape[0], w.shape[1],
-                                    w.shape[2], w.shape[4], stride, dilation, runtime.ptr(y)))
+    args = (_ctx_for(x).handle, runtime.ptr(x), runtime.ptr(x2), *dims, up, runtime.ptr(w), runtime.ptr(bias), w.shape[0], w.shape[1], w.shape[2], w.shape[4],
+            stride, dilation, runtime.ptr(y))
+    _lib.check(_lib.lib().ps_conv3d_prec(*args, prec) if prec else _lib.lib().ps_conv3d(*args))
     return y
 
 
@@ -200,9 +212,13 @@ def instance_norm_relu(x, gamma, beta, eps=EPS):
 
 class SaliencyNet:
     """unet3d_attention for inference.  params: the TF-named dict (see the module's docstring); the weights live on `device` as one flat
-    buffer.  A patch is [B, D, H, W, C_in] (or [D, H, W, C_in]) CUDA float32 with D, H, W multiples of 16."""
+    buffer.  A patch is [B, D, H, W, C_in] (or [D, H, W, C_in]) CUDA float32 with D, H, W multiples of 16.  precision: the arithmetic of
+    every convolution -- "fp32", "bf16x3" (fp32-level results from split bfloat16 operands) or "bf16" (operands rounded to bfloat16):
+    include/pointseg_saliency_precision.h; forward, probs and forward_taps use it, and so does saliency_map through the net it is given."""
 
-    def __init__(self, params, in_channels, num_classes=2, device=0):
+    def __init__(self, params, in_channels, num_classes=2, device=0, precision="fp32"):
+        self.precision = precision
+        self._prec = _precision("SaliencyNet", precision)
         self.in_channels, self.num_classes = int(in_channels), int(num_classes)
         flat = flatten_params(params, self.in_channels, self.num_classes)
         want = _lib.lib().ps_saliency_weight_count(self.in_channels, self.num_classes)
@@ -233,10 +249,11 @@ class SaliencyNet:
             out["c12"] = torch.empty((B, D, H, W, 64), dtype=torch.float32, device=x.device)
             tp = _lib.PsSaliencyTaps(*(runtime.ptr(out[k]) for k in ("down4", "c345", "sa", "c12")))
         ctx = _ctx_for(x)
-        fn = _lib.lib().ps_saliency_forward
+        fn = _lib.lib().ps_saliency_forward_prec if self._prec else _lib.lib().ps_saliency_forward
+        tail = (self._prec,) if self._prec else ()
         self.scratch_bytes = _two_call("ps_saliency_forward", x.device, lambda scratch, n: fn(
             ctx.handle, runtime.ptr(x), B, D, H, W, self.in_channels, K, runtime.ptr(self.weights), self.weights.numel(), runtime.ptr(logits), runtime.ptr(probs),
-            ctypes.byref(tp) if tp is not None else None, scratch, n))
+            ctypes.byref(tp) if tp is not None else None, scratch, n, *tail))
         return out
 
     def forward(self, patch):
@@ -692,9 +709,13 @@ class TrainableSaliencyNet(torch.nn.Module):
         labels: [B, D, H, W] int32, or soft labels float32 [B, D, H, W, num_classes] (PatchBank.sample(mixup=...))."""
         return differentiable_softmax_dice_loss(self.logits(x, masks), labels, weight)
 
-    def export(self):
-        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes."""
-        return {name: p.detach().cpu().numpy() for name, p in self.named_parameters()}
+    def export(self, precision=None):
+        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes; with precision ("fp32" | "bf16x3" | "bf16"),
+        the SaliencyNet of them at that precision, on this net's device."""
+        params = {name: p.detach().cpu().numpy() for name, p in self.named_parameters()}
+        if precision is None:
+            return params
+        return SaliencyNet(params, self.in_channels, self.num_classes, self.device.index, precision)
 
 
 def reference_optimizer(net, lr=0.01):

@@ -7,8 +7,13 @@ region).  MACs per layer are counted from the layer table and the shapes.
 
 The work runs in a child process under a time limit of its own, so a hang ends there.
 
+--precision compares the arithmetic modes of include/pointseg_saliency_precision.h instead: the whole patch and the same five convolutions
+in "fp32", "bf16x3" and "bf16", in ONE process, the modes interleaved round by round (a drift of the clock or the device hits all three
+alike), device events after a warm-up, best-of and the spread of the rounds recorded; the baseline is the fp32 mode of the same session.
+
 usage (GPU box):
-    python profiles/tools/saliency_patch.py --out DIR [--timeout 420] [--no-torch]        # -> DIR/saliency_patch.json"""
+    python profiles/tools/saliency_patch.py --out DIR [--timeout 420] [--no-torch]        # -> DIR/saliency_patch.json
+    python profiles/tools/saliency_patch.py --precision [--out DIR]                       # -> DIR/saliency_patch_precision.json (DIR: profiles/)"""
 import argparse
 import ctypes
 import json
@@ -62,7 +67,68 @@ def event_ms(torch, fn, reps):
     return s.elapsed_time(e) / reps
 
 
+def interleaved_ms(torch, fns, rounds, reps):
+    """fns: mode -> callable.  `rounds` rounds, each timing every mode once (reps calls between two events), in the dict's order.
+    Returns mode -> {best, median, worst} in ms."""
+    for fn in fns.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    runs = {m: [] for m in fns}
+    for _ in range(rounds):
+        for m, fn in fns.items():
+            runs[m].append(event_ms(torch, fn, reps))
+    return {m: {"best": round(min(r), 3), "median": round(sorted(r)[len(r) // 2], 3), "worst": round(max(r), 3)} for m, r in runs.items()}
+
+
+def child_precision(args):
+    import numpy as np
+    import torch
+    from point_unet_amd import saliency as sal
+    modes = ("fp32", "bf16x3", "bf16")
+    res = {"patch": PATCH, "in_channels": 1, "num_classes": 2, "modes": modes,
+           "method": "one process, modes interleaved per round, device events around 3 calls, 2 warm-up calls per mode; ms: best / median / worst of the rounds"}
+    params = sal.init_params(1, 2, seed=0)
+    nets = {m: sal.SaliencyNet(params, 1, 2, precision=m) for m in modes}
+    x = torch.from_numpy(np.random.default_rng(1).standard_normal((1,) + PATCH + (1,)).astype(np.float32)).cuda()
+    ok = True
+    probs = {}
+    for m in modes:
+        p = nets[m].probs(x)
+        good = bool(torch.isfinite(p).all().item()) and float((p.sum(-1) - 1.0).abs().max().item()) <= 1e-6 and torch.equal(nets[m].probs(x), p)
+        ok = ok and good
+        probs[m] = p
+    res["checks_pass"] = ok
+    res["max_abs_prob_diff_to_fp32"] = {m: float((probs[m] - probs["fp32"]).abs().max().item()) for m in modes[1:]}
+    del probs
+    rows = mac_table(sal, 1, 2, PATCH)
+    total = sum(r[2] for r in rows)
+    res["gmac_total"] = round(total / 1e9, 1)
+    res["ms_per_patch"] = interleaved_ms(torch, {m: (lambda n=nets[m]: n.probs(x)) for m in modes}, 7, 3)
+    res["convs"] = {}
+    for name, shape, macs in sorted(rows, key=lambda r: -r[2])[:5]:
+        up = 4 if "up4" in name else (2 if "up2" in name else 1)
+        src = tuple(p // up for p in PATCH)
+        g = torch.Generator().manual_seed(len(name))
+        xi = torch.randn((1,) + src + (shape[3],), generator=g).cuda()
+        w = (torch.randn(shape, generator=g) * (2.0 / (shape[0] * shape[1] * shape[2] * shape[3])) ** 0.5).cuda()
+        ms = interleaved_ms(torch, {m: (lambda m=m: sal.conv3d(xi, w, up=up, precision=m)) for m in modes}, 5, 3)
+        res["convs"][name] = {"kernel": shape, "up": up, "gmac": round(macs / 1e9, 2), "ms": ms,
+                              "tflops_best": {m: round(2 * macs / (ms[m]["best"] * 1e-3) / 1e12, 1) for m in modes}}
+        del xi, w
+    res["ok"] = bool(ok)
+    line = json.dumps(res)
+    print(line)
+    out = args.out or os.path.join(ROOT, "profiles")
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "saliency_patch_precision.json"), "w") as f:
+        f.write(line + "\n")
+    return 0 if ok else 1
+
+
 def child(args):
+    if args.precision:
+        return child_precision(args)
     import numpy as np
     import torch
     import torch.nn.functional as F
@@ -157,11 +223,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--timeout", type=int, default=420, help="seconds the child process may take")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch.nn.functional.conv3d comparison")
+    ap.add_argument("--precision", action="store_true", help="compare the fp32, bf16x3 and bf16 modes -> saliency_patch_precision.json")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         sys.exit(child(args))
-    cmd = [sys.executable, os.path.abspath(__file__), "--child"] + (["--out", args.out] if args.out else []) + (["--no-torch"] if args.no_torch else [])
+    cmd = [sys.executable, os.path.abspath(__file__), "--child"] + (["--out", args.out] if args.out else []) + (["--no-torch"] if args.no_torch else []) \
+        + (["--precision"] if args.precision else [])
     sys.exit(subprocess.run(cmd, timeout=args.timeout).returncode)
 
 
