@@ -84,6 +84,24 @@ __device__ __forceinline__ f32x16 b3_mfma6(const BPlanes<P>& a, const BPlanes<P>
     return acc;
 }
 
+// The same on v_mfma_f32_16x16x32_bf16 (regchain.hip): A[m][k]: lane (m = lane & 15, g = lane >> 4) holds k = 8 g + j, j = 0..7;
+// B[k][n]: lane (n = lane & 15, g) holds k = 8 g + j; C[m][n]: lane (n, g), register q holds m = 4 g + q -- the C layout of 16x16x4.
+// The eight k values of a lane are the two float4 a lane of that C layout holds of two adjacent 16-channel tiles: b3_split8(lo, hi).
+__device__ __forceinline__ f32x4 b3_mfma16(const uint4& a, const uint4& b, f32x4 acc)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 b3_mfma16_6(const B3Planes& a, const B3Planes& b, f32x4 acc)  // the six kept piece products, smallest first
+{
+    acc = b3_mfma16(a.p[2], b.p[0], acc);
+    acc = b3_mfma16(a.p[0], b.p[2], acc);
+    acc = b3_mfma16(a.p[1], b.p[1], acc);
+    acc = b3_mfma16(a.p[1], b.p[0], acc);
+    acc = b3_mfma16(a.p[0], b.p[1], acc);
+    acc = b3_mfma16(a.p[0], b.p[0], acc);
+    return acc;
+}
+
 // Host: bfloat16 piece `plane` (0..2) of w, the same split as b3_split_pair, for the weight images packed on the host (pack_p32b,
 // pack_b3, pack_b3_locse).  The volatiles are load-bearing: do not remove them.
 inline uint16_t b3_piece_of(float w, int plane)

@@ -89,6 +89,9 @@ int ps_debug_chain(ps_context* ctx, const ps_debug_chain_desc* d, int form);
  * waves that each take one 16-row tile per round: past workgroups * 64 rows a wave walks to a second tile.  Host only: reads the channel counts
  * and the alignment of the pointers, never what they point to; W / bias may be NULL. */
 int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4);
+/* The operand policy of regchain's routed chain shapes on this context (on by default): 1 = bf16 MFMA over exact three-way splits, 0 = the fp32
+ * MFMA for every shape.  ps_debug_chain forms 0 and 1 follow it; ps_debug_chain_plan has no context and reports the fp32 launch. */
+int ps_debug_set_regchain_b3(ps_context* ctx, int on);
 /* One attentive-pooling stage (1 or 2) of encoder level `level` of a live network with its weights set, on the network's own packed images
  * (log2(e) scaling and weight halves included); AttStage is filled as ps_randla_forward fills it.  xyz f32[n_total, 3], idx i32[n_total, K]
  * (cloud-local), order i32[n_total] or NULL, fg f32[n_total, d/2 + d] = [f | G] for d >= 64 and f32[n_total, d/2] = f below, agg f32[n_total, d]:

@@ -233,6 +233,13 @@ extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int f
     return rc;
 }
 
+extern "C" int ps_debug_set_regchain_b3(ps_context* c, int on)
+{
+    PS_CHECK(c && (on == 0 || on == 1), "ps_debug_set_regchain_b3: bad argument");
+    c->regchain_b3 = on != 0;
+    return PS_OK;
+}
+
 // --------------------------------------------------------------------------------------------------------
 // one attentive-pooling stage of a live network (randla_net.h), through each of its stage functions (attpool.h)
 // --------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ namespace ps {
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;  // accumulator of the 32x32 MFMAs
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;  // operand of v_mfma_f32_32x32x16_bf16
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;  // operand of v_mfma_f32_32x32x16_bf16 / _16x16x32_bf16
 
 // LDS hand-off between the lanes of ONE wave: DS operations of a wave execute in order, so only the compiler
 // has to be kept from moving LDS accesses across this point.

@@ -101,9 +101,10 @@ bool rowchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const 
 // register-resident evaluation of the network's own chain shapes (regchain.hip); rowchain() prefers it when the shape matches
 bool regchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2);
 // per-network cache of the chains' re-ordered weight images (built on first use on the caller's stream; clear() when the
-// weights change).  Entries are keyed by the first / last layer's packed weights and the split of the first K axis.
+// weights change).  Entries are keyed by the first / last layer's packed weights, the split of the first K axis and the operand policy
+// (split: the three-plane bfloat16 image of regchain.hip's RcB3).
 struct ChainCache {
-    struct Entry { const float* wp0 = nullptr; const float* wp_last = nullptr; int n = 0, ca = 0, cb = 0; DevBuf img; };
+    struct Entry { const float* wp0 = nullptr; const float* wp_last = nullptr; int n = 0, ca = 0, cb = 0; bool split = false; DevBuf img; };
     std::vector<Entry> entries;
     void clear()
     {
