@@ -3,8 +3,8 @@
  * bfloat16 (csrc/conv3d_bf16.hip; the fp32 kernel stays csrc/conv3d.hip).  Same conventions as pointseg_saliency.h, whose ps_conv3d and
  * ps_saliency_forward these two entries extend: every argument before `precision` is theirs, with their limits, their checks, their
  * two-call scratch protocol and their scratch SIZE (the same number of bytes in every mode).  ps_conv3d is ps_conv3d_prec(..., PS_PREC_FP32)
- * and ps_saliency_forward is ps_saliency_forward_prec(..., PS_PREC_FP32): one body each.  Training (pointseg_saliency_train.h,
- * pointseg_saliency_step.h) stays fp32.
+ * and ps_saliency_forward is ps_saliency_forward_prec(..., PS_PREC_FP32): one body each.  In training, the convolution's two
+ * gradients take the same choice op by op (pointseg_saliency_train_precision.h); the one-call step (pointseg_saliency_step.h) stays fp32.
  *
  * The rule, for every convolution of the call
  * -------------------------------------------

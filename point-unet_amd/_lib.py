@@ -314,6 +314,13 @@ SALIENCY_TRAIN_PROTOTYPES = {
     "ps_instance_norm_relu_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp] + [ctypes.c_int64] * 3 + [c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64p]),
 }
 
+# every symbol include/pointseg_saliency_train_precision.h declares (the convolution's two gradients with a choice of arithmetic;
+# csrc/conv3d_train.hip, csrc/conv3d_bf16.hip, csrc/conv3d_train_bf16.hip): the arguments of the entries they extend, then the precision
+SALIENCY_TRAIN_PRECISION_PROTOTYPES = {
+    "ps_conv3d_bwd_data_prec": (ctypes.c_int, SALIENCY_TRAIN_PROTOTYPES["ps_conv3d_bwd_data"][1] + [ctypes.c_int32]),
+    "ps_conv3d_bwd_weight_prec": (ctypes.c_int, SALIENCY_TRAIN_PROTOTYPES["ps_conv3d_bwd_weight"][1] + [ctypes.c_int32]),
+}
+
 # every symbol include/pointseg_saliency_attention.h declares (the channel attention, the spatial gate and softmax + Dice, each with its
 # gradient; csrc/saliency_train.hip)
 SALIENCY_ATTENTION_PROTOTYPES = {
@@ -386,7 +393,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(PROTOTYPES.items()) + list(PREPARE_PROTOTYPES.items()) + list(POSTPROCESS_PROTOTYPES.items())
                                   + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_PRECISION_PROTOTYPES.items())
-                                  + list(SALIENCY_TRAIN_PROTOTYPES.items())
+                                  + list(SALIENCY_TRAIN_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PRECISION_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())):
             fn = getattr(handle, name)

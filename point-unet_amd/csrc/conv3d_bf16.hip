@@ -1,6 +1,7 @@
 // conv3d_bf16.hip -- conv3d.hip's implicit-GEMM 3-D convolution on v_mfma_f32_32x32x16_bf16 (b3_ops.h's fragment maps and split helpers):
 // the PS_PREC_BF16X3 and PS_PREC_BF16 modes of ps_conv3d_prec and ps_saliency_forward_prec (include/pointseg_saliency_precision.h,
-// DESIGN.md 4.15).
+// DESIGN.md 4.15), and -- the same kernel with its gather policy GRAD -- the data gradient of ps_conv3d_bwd_data_prec in those modes
+// (include/pointseg_saliency_train_precision.h).
 //
 // The frame is conv3d.hip's: Y[v, co] = sum over k of A[v, k] . Wm[k, co], k = tap * C_in + ci, TensorFlow's kernel buffer as the row-major
 // [K, C_out] matrix, A never materialised; a workgroup of four waves owns 64 * RT output voxels and 32 * NT output channels, the rows' input
@@ -21,34 +22,24 @@
 //     output has fewer than 2048 voxels).
 #include <cstdint>
 
-#include "b3_ops.h"
-#include "saliency.h"
+#include "conv3d_b.h"
 
 namespace ps {
 
 namespace {
 
-constexpr int kKC = 32;  // K chunk: two k-steps of the instruction
-constexpr int kPW = 20;  // tile pitch in 32-bit words: 32 bfloat16 and 16 bytes (see above)
-
-// x / up for 0 <= x < 2^31 and up >= 2 without a division: the high word of x * (floor(2^32 / up) + 1) is the quotient or one above it (the
-// excess is below x / 2^32 < 1/2), which one multiplication tells apart
-__device__ __forceinline__ int div_by(int x, unsigned up, unsigned magic)
-{
-    const unsigned q = __umulhi((unsigned)x, magic);
-    return (int)(q - (q * up > (unsigned)x ? 1u : 0u));
-}
-
-template <int P, int RT, int NT, bool VEC>
+// GRAD: the data gradient (saliency.h's grad fields) -- the fetch's coordinate step and the epilogue's column split are the
+// whole difference: the forward walks corner + tap * dil, the gradient gathers from (row + pad - tap * dil) / stride where that is whole.
+template <int P, int RT, int NT, bool VEC, bool GRAD>
 __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
 {
     constexpr int M = 64 * RT, N = 32 * NT;
     constexpr int KW = VEC ? 4 : 2;    // consecutive k a thread fetches for one row
-    constexpr int CG = kKC / KW;       // such groups in a chunk
+    constexpr int CG = kBKC / KW;      // such groups in a chunk
     constexpr int RS = 256 / CG;       // rows between a thread's fetches
     constexpr int AI = M / RS;         // rows per thread and chunk
     constexpr int RPC = 8 / KW;        // rows that share one b3_split8
-    constexpr int BK = kKC * N / 256;  // consecutive k of one column per thread: 4 or 8
+    constexpr int BK = kBKC * N / 256;  // consecutive k of one column per thread: 4 or 8
     static_assert(AI % RPC == 0, "a split takes 8 values");
     __shared__ __attribute__((aligned(16))) unsigned As[P][M * kPW];
     __shared__ __attribute__((aligned(16))) unsigned Bs[P][N * kPW];
@@ -62,7 +53,8 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
         int4 ri = {0, 0, 0, 0};
         if (v < Vo) {
             const int ow = v % a.Wo, oh = v / a.Wo % a.Ho, od = v / (a.Wo * a.Ho);
-            ri = {od * a.stride - a.pd, oh * a.stride - a.ph, ow * a.stride - a.pw, 1};
+            if constexpr (GRAD) ri = {od + a.pd, oh + a.ph, ow + a.pw, 1};
+            else ri = {od * a.stride - a.pd, oh * a.stride - a.ph, ow * a.stride - a.pw, 1};
         }
         rows[r] = ri;
     }
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
 
     const int cin = a.C1 + a.C2;
     const int Ktot = a.kd * a.kh * a.kw * cin;
-    const int nchunks = (Ktot + kKC - 1) / kKC;
+    const int nchunks = (Ktot + kBKC - 1) / kBKC;
     const int acg = t % CG, arow = t / CG;
     const int bcol = t % N, bk0 = (t / N) * BK;
     const size_t xs = (size_t)a.Ds * a.Hs * a.Ws;  // voxels of one source sample
@@ -90,7 +82,9 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
         kci[e] = k - tap * cin, ktx[e] = tap % a.kw, kty[e] = tap / a.kw % a.kh, ktz[e] = tap / (a.kw * a.kh);
     }
     const unsigned upm = (unsigned)((1ull << 32) / (unsigned)a.up) + 1u;  // (used where up > 1)
-    const float* wp = wb + (size_t)bk0 * a.cout + n0 + bcol;  // the thread's weights of the chunk to fetch
+    const int ldw = GRAD ? a.ldw : a.cout;
+    const int sm1 = a.stride - 1;  // (GRAD) the stride is 1 or 2: zz % stride is zz & sm1, zz / stride is zz >> sm1
+    const float* wp = wb + (size_t)bk0 * ldw + n0 + bcol;  // the thread's weights of the chunk to fetch
     const bool bin = n0 + bcol < a.cout;
     int kb = bk0;
     auto fetch = [&]() {
@@ -104,10 +98,19 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
 #pragma unroll
             for (int i = 0; i < AI; ++i) {
                 const int4 ri = rows[arow + RS * i];
-                int z = ri.x + dz, y = ri.y + dy, x = ri.z + dx;
-                const bool ok = kin && ri.w && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+                int z, y, x;
+                bool ok = kin && ri.w;
+                if constexpr (GRAD) {
+                    z = ri.x - dz, y = ri.y - dy, x = ri.z - dx;  // o * stride
+                    ok = ok && (z | y | x) >= 0 && ((z | y | x) & sm1) == 0;
+                    z >>= sm1, y >>= sm1, x >>= sm1;
+                    ok = ok && z < a.D && y < a.H && x < a.W;
+                } else {
+                    z = ri.x + dz, y = ri.y + dy, x = ri.z + dx;
+                    ok = ok && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+                }
                 if (!ok) z = y = x = 0;
-                if (a.up > 1) z = div_by(z, a.up, upm), y = div_by(y, a.up, upm), x = div_by(x, a.up, upm);
+                if (!GRAD && a.up > 1) z = div_by(z, a.up, upm), y = div_by(y, a.up, upm), x = div_by(x, a.up, upm);
                 const float* p = src + (unsigned)((z * a.Hs + y) * a.Ws + x) * ld;  // (a source sample has fewer than 2^31 elements)
                 // (the load is unconditional: without `ok` it reads the sample's voxel 0, which exists, and is dropped)
                 if constexpr (VEC) {
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
                     areg[i][e] = ok ? v : 0.f;
                 }
             }
-            kci[e] += kKC;
+            kci[e] += kBKC;
             while (kci[e] >= cin) {
                 kci[e] -= cin;
                 if (++ktx[e] == a.kw) {
@@ -128,9 +131,9 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
             }
         }
 #pragma unroll
-        for (int i = 0; i < BK; ++i) breg[i] = (bin && kb + i < Ktot) ? wp[(size_t)i * a.cout] : 0.f;
-        wp += (size_t)kKC * a.cout;
-        kb += kKC;
+        for (int i = 0; i < BK; ++i) breg[i] = (bin && kb + i < Ktot) ? wp[(size_t)i * ldw] : 0.f;
+        wp += (size_t)kBKC * ldw;
+        kb += kBKC;
     };
     // split or round the fetched chunk into the planes
     auto stage = [&]() {
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) part[j][r] = 0.f;
 #pragma unroll
-            for (int s = 0; s < kKC / 16; ++s) {
+            for (int s = 0; s < kBKC / 16; ++s) {
                 BPlanes<P> af;
 #pragma unroll
                 for (int pl = 0; pl < P; ++pl) af.p[pl] = *reinterpret_cast<const uint4*>(&As[pl][fa + s * 8]);
@@ -212,11 +215,22 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
     for (int j = 0; j < NT; ++j) {
         const int col = n0 + j * 32 + c32;
         if (col >= a.cout) continue;
-        const float bias = a.bias ? a.bias[col] : 0.f;
+        if constexpr (GRAD) {
+            const bool first = col < a.nsplit;
+            float* o = first ? yb + col : a.y2 + (size_t)b * Vo * a.ldy2 + (col - a.nsplit);
+            const int ld = first ? a.ldy : a.ldy2;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-            if (v < Vo) yb[(size_t)v * a.ldy + col] = acc[j][r] + bias;
+            for (int r = 0; r < 16; ++r) {
+                const int v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+                if (v < Vo) o[(size_t)v * ld] = acc[j][r];
+            }
+        } else {
+            const float bias = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+                if (v < Vo) yb[(size_t)v * a.ldy + col] = acc[j][r] + bias;
+            }
         }
     }
 }
@@ -226,8 +240,12 @@ void launch(hipStream_t sm, const Conv3dArgs& a, bool vec)
 {
     const int Vo = a.Do * a.Ho * a.Wo;
     const dim3 grid((unsigned)ceil_div(Vo, 64 * RT), (unsigned)ceil_div(a.cout, 32 * NT), (unsigned)a.B);
-    if (vec) hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, true>), grid, dim3(256), 0, sm, a);
-    else hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, false>), grid, dim3(256), 0, sm, a);
+    if (a.grad) {
+        // (the split data gradient exists with the 16-byte fetch alone: conv3d_train.hip routes the other to the fp32 kernel)
+        if (vec) hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, true, true>), grid, dim3(256), 0, sm, a);
+        else if constexpr (P == 1) hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, false, true>), grid, dim3(256), 0, sm, a);
+    } else if (vec) hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, true, false>), grid, dim3(256), 0, sm, a);
+    else hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, false, false>), grid, dim3(256), 0, sm, a);
 }
 
 // Which form: conv3d_launch's rule with this instruction's 32-wide column tiles -- one tile up to 32 output channels (C_out <= 16 leaves
@@ -236,13 +254,18 @@ template <int P>
 void launch_p(hipStream_t sm, const Conv3dArgs& a)
 {
     const bool wide = (int64_t)a.Do * a.Ho * a.Wo >= 2048;
-    const bool vec = a.C1 % 4 == 0 && a.C2 % 4 == 0 && a.ldx % 4 == 0 && (a.C2 == 0 || a.ldx2 % 4 == 0)
-                     && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.x2)) & 15) == 0;
+    const bool vec = conv3d_b_vec(a);
     if (a.cout <= 32) wide ? launch<P, 2, 1>(sm, a, vec) : launch<P, 1, 1>(sm, a, vec);
     else wide ? launch<P, 2, 2>(sm, a, vec) : launch<P, 1, 2>(sm, a, vec);
 }
 
 }  // namespace
+
+bool conv3d_b_vec(const Conv3dArgs& a)
+{
+    return a.C1 % 4 == 0 && a.C2 % 4 == 0 && a.ldx % 4 == 0 && (a.C2 == 0 || a.ldx2 % 4 == 0)
+           && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.x2)) & 15) == 0;
+}
 
 void conv3d_b_launch(hipStream_t sm, const Conv3dArgs& a)
 {

@@ -14,10 +14,13 @@
 // Rounding (both): a chunk of 32 k is summed in a fresh accumulator and then added to the running one, as in conv3d.hip.
 // The data gradient is a kernel of its own and not conv3d_kernel behind a flipped kernel: its fetch would have to branch on its caller
 // (a negative tap step, the stride's parity test, the split result), and the forward has to stay byte for byte what it is.
-#include "../../include/pointseg_saliency_train.h"
+// At PS_PREC_BF16X3 / PS_PREC_BF16 (include/pointseg_saliency_train_precision.h) the same entries run the bf16 matrix pipe:
+// the data gradient conv3d_bf16.hip's kernel with its gather policy, the weight gradient conv3d_train_bf16.hip's; the transposed kernel
+// copy, the up-sampling's sum, the slab partials and their float64 reduction are the ones below.
+#include "../../include/pointseg_saliency_train_precision.h"
+#include "conv3d_b.h"
 #include "mfma_tile.h"
 #include "reduce_partials.h"
-#include "saliency.h"
 #include "scratch.h"
 
 namespace ps {
@@ -27,7 +30,6 @@ namespace {
 constexpr int kKC = 32;        // K chunk
 constexpr int kAP = kKC + 2;   // row-major A tile pitch, as conv3d.hip
 constexpr int kBP = 80;        // k-major tile pitch for up to 64 columns: the four k rows of a fragment read start 16 banks apart
-constexpr int kWSlab = 4096;   // output voxels per workgroup of the weight gradient
 
 // One K chunk of a wave's RT x NT tiles: the chunk's 8 k-steps in a fresh accumulator, then added to the running one (conv3d.hip's
 // rounding).  a0: this lane's A element of row tile 0, k-step 0 (row tiles a_rt floats apart, k-steps a_s); b0: the same in the k-major B tile.
@@ -207,17 +209,6 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 
 // ---- weight and bias gradient ------------------------------------------------------------------------------------------------------------------
 
-struct BwdWeightArgs {
-    const float* x;
-    const float* x2;
-    const float* dy;
-    float* part;       // [B * slabs][nrows][cout]
-    int r0, nrows;     // the rows this call computes: [r0, r0 + nrows) of the Ktot kernel rows (tap, ci) and the row of ones (the bias) behind them
-    int Ktot, slabs, mtiles;
-    int B, Ds, Hs, Ws, C1, C2, up, D, H, W, Do, Ho, Wo, cout;
-    int kd, kh, kw, stride, dil, pd, ph, pw;
-};
-
 // grid (mtiles * B * slabs, column tiles).  Both tiles are k-major in LDS (k = a voxel of the slab): thread t fetches rows t % 64 (+ 64)
 // -- adjacent lanes adjacent input channels -- of the voxels t / 64 + 4 i, whose input corners come from LDS.
 template <int RT, int NT>
@@ -371,8 +362,16 @@ extern "C" int ps_conv3d_bwd_data(ps_context* c, const void* dy, const void* w, 
                                   int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* dx, void* dx2, void* scratch,
                                   int64_t* scratch_bytes)
 {
+    return ps_conv3d_bwd_data_prec(c, dy, w, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation, dx, dx2, scratch, scratch_bytes, PS_PREC_FP32);
+}
+
+extern "C" int ps_conv3d_bwd_data_prec(ps_context* c, const void* dy, const void* w, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2,
+                                       int32_t up, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* dx, void* dx2,
+                                       void* scratch, int64_t* scratch_bytes, int32_t precision)
+{
     using namespace ps;
-    static const char* who = "ps_conv3d_bwd_data";
+    const char* who = precision == PS_PREC_FP32 ? "ps_conv3d_bwd_data" : "ps_conv3d_bwd_data_prec";
+    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
     PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
     const int cin = (int)(C1 + C2), taps = kd * kh * kw;
@@ -408,11 +407,26 @@ extern "C" int ps_conv3d_bwd_data(ps_context* c, const void* dy, const void* w, 
     Stage stg(c, "conv3d_bwd_data", 3);
     const unsigned wn = (unsigned)((size_t)taps * cin * C_out);
     hipLaunchKernelGGL(transpose_kernel_kernel, dim3(blocks256(wn)), dim3(256), 0, sm, static_cast<const float*>(w), wn, cin, (int)C_out, wt);
-    // the forward's forms: 16 * NT columns per workgroup, 128 rows where there are enough voxels to fill the device with them
-    const bool wide = (int64_t)D * H * W >= 2048;
-    if (a.ncols <= 16) wide ? launch_data<2, 1>(sm, a) : launch_data<1, 1>(sm, a);
-    else if (a.ncols <= 32) wide ? launch_data<2, 2>(sm, a) : launch_data<1, 2>(sm, a);
-    else wide ? launch_data<2, 4>(sm, a) : launch_data<1, 4>(sm, a);
+    // conv3d_bf16.hip's kernel on the turned roles (saliency.h): its "input" is dy, its rows the virtual input's voxels
+    Conv3dArgs f = {};
+    if (precision != PS_PREC_FP32) {
+        f.x = a.dy, f.w = wt + a.c0, f.ldw = cin, f.grad = 1, f.precision = precision;
+        f.B = a.B, f.Ds = f.D = a.Do, f.Hs = f.H = a.Ho, f.Ws = f.W = a.Wo, f.C1 = f.ldx = a.cout, f.up = 1;
+        f.Do = D, f.Ho = H, f.Wo = W, f.cout = a.ncols;
+        f.kd = kd, f.kh = kh, f.kw = kw, f.stride = stride, f.dil = dilation, f.pd = a.pd, f.ph = a.ph, f.pw = a.pw;
+        f.nsplit = a.split - a.c0;
+        f.y = a.out0 ? a.out0 + (a.c0 - a.obase) : nullptr, f.ldy = a.ld0, f.y2 = a.out1, f.ldy2 = a.ld1;
+    }
+    // (PS_PREC_BF16X3 keeps the fp32 kernel where dy does not take the 16-byte fetch: conv3d_b.h)
+    if (precision == PS_PREC_BF16 || (precision == PS_PREC_BF16X3 && conv3d_b_vec(f))) {
+        conv3d_b_launch(sm, f);
+    } else {
+        // the forward's forms: 16 * NT columns per workgroup, 128 rows where there are enough voxels to fill the device with them
+        const bool wide = (int64_t)D * H * W >= 2048;
+        if (a.ncols <= 16) wide ? launch_data<2, 1>(sm, a) : launch_data<1, 1>(sm, a);
+        else if (a.ncols <= 32) wide ? launch_data<2, 2>(sm, a) : launch_data<1, 2>(sm, a);
+        else wide ? launch_data<2, 4>(sm, a) : launch_data<1, 4>(sm, a);
+    }
     if (up > 1)
         hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks256((size_t)Ds * Hs * Ws * a.ncols), (unsigned)B), dim3(256), 0, sm, g, a.ncols, a.c0, (int)Ds, (int)Hs,
                            (int)Ws, (int)up, (int)C1, (int)C2, static_cast<float*>(dx), static_cast<float*>(dx2));
@@ -424,8 +438,17 @@ extern "C" int ps_conv3d_bwd_weight(ps_context* c, const void* x, const void* x2
                                     int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride, int32_t dilation, void* dw,
                                     void* dbias, void* scratch, int64_t* scratch_bytes)
 {
+    return ps_conv3d_bwd_weight_prec(c, x, x2, dy, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation, dw, dbias, scratch, scratch_bytes,
+                                     PS_PREC_FP32);
+}
+
+extern "C" int ps_conv3d_bwd_weight_prec(ps_context* c, const void* x, const void* x2, const void* dy, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws,
+                                         int64_t C1, int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw, int64_t C_out, int32_t stride,
+                                         int32_t dilation, void* dw, void* dbias, void* scratch, int64_t* scratch_bytes, int32_t precision)
+{
     using namespace ps;
-    static const char* who = "ps_conv3d_bwd_weight";
+    const char* who = precision == PS_PREC_FP32 ? "ps_conv3d_bwd_weight" : "ps_conv3d_bwd_weight_prec";
+    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
     PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
     Conv3dArgs f = {};
@@ -461,7 +484,9 @@ extern "C" int ps_conv3d_bwd_weight(ps_context* c, const void* x, const void* x2
     hipStream_t sm = c->stream;
     Stage stg(c, "conv3d_bwd_weight", 2);
     const bool tall = a.nrows > 64;
-    if (a.cout <= 16) tall ? launch_weight<2, 1>(sm, a) : launch_weight<1, 1>(sm, a);
+    if (precision == PS_PREC_BF16 || (precision == PS_PREC_BF16X3 && conv3d_bwd_weight_split_pays(a.C1 + a.C2, a.cout)))
+        conv3d_bwd_weight_b_launch(sm, a, precision);
+    else if (a.cout <= 16) tall ? launch_weight<2, 1>(sm, a) : launch_weight<1, 1>(sm, a);
     else if (a.cout <= 32) tall ? launch_weight<2, 2>(sm, a) : launch_weight<1, 2>(sm, a);
     else tall ? launch_weight<2, 4>(sm, a) : launch_weight<1, 4>(sm, a);
     const int nv = a.nrows * a.cout, n0 = dw ? Ktot * a.cout : 0;

@@ -22,6 +22,13 @@ struct Conv3dArgs {
     int precision;  // PS_PREC_*: 0 (what `= {}` leaves) is the fp32 kernel of conv3d.hip, the others run conv3d_bf16.hip
     // derived by conv3d_plan
     int D, H, W, Do, Ho, Wo, pd, ph, pw;
+    // conv3d_bf16.hip's data-gradient form alone (grad != 0; conv3d_train.hip fills it, include/pointseg_saliency_train_precision.h): the
+    // same implicit GEMM with the roles turned.  x is dy ([B, D, H, W, C1], C2 = 0, up = 1: D, H, W the convolution's OUTPUT extents), the
+    // rows are the Do * Ho * Wo voxels i of the convolution's virtual INPUT, the fetch gathers dy[(i + pad - tap * dil) / stride] where that
+    // is whole and inside, w is the transposed kernel [taps * C1][ldw] (its first column the first computed channel), cout the computed
+    // channels; those below nsplit go to y (pitch ldy), the others to y2 (pitch ldy2).  No bias.
+    int grad, ldw, nsplit, ldy2;
+    float* y2;
 };
 
 inline int same_out(int in, int stride) { return (in + stride - 1) / stride; }
@@ -34,6 +41,7 @@ inline int same_pad_before(int in, int k, int stride, int dil)
 void conv3d_plan(Conv3dArgs& a);                   // fills the derived fields
 void conv3d_launch(hipStream_t sm, const Conv3dArgs& a);  // (a planned; every limit checked by the caller)
 void conv3d_b_launch(hipStream_t sm, const Conv3dArgs& a);  // conv3d_bf16.hip: what conv3d_launch calls for PS_PREC_BF16X3 and PS_PREC_BF16
+bool conv3d_b_vec(const Conv3dArgs& a);                     // whether conv3d_b_launch takes the 16-byte activation fetch
 
 inline bool precision_ok(int32_t p) { return p == PS_PREC_FP32 || p == PS_PREC_BF16X3 || p == PS_PREC_BF16; }
 

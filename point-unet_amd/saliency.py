@@ -311,10 +311,14 @@ def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118)):
 
 # ---- the gradients of the two op wrappers (include/pointseg_saliency_train.h, csrc/conv3d_train.hip, csrc/saliency_train.hip) ---------------------------------------------
 
-def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x2", "w", "bias")):
+def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x2", "w", "bias"), precision="fp32"):
     """The gradients of conv3d(x, w, bias, stride, dilation, x2, up) for the output gradient dy: a dict with the entries of `need` --
-    "x" [like x], "x2" [like x2; only with x2], "w" [like w], "bias" [C_out].  Arguments are checked as conv3d checks them."""
+    "x" [like x], "x2" [like x2; only with x2], "w" [like w], "bias" [C_out].  Arguments are checked as conv3d checks them.
+    precision: "fp32" (ps_conv3d_bwd_data, ps_conv3d_bwd_weight), or "bf16x3" / "bf16" on the bf16 matrix pipe (their _prec entries,
+    include/pointseg_saliency_train_precision.h)."""
     who = "conv3d_backward"
+    prec = _precision(who, precision)
+    tail = (prec,) if prec else ()
     x, w, x2, dims, want = _conv_args(who, x, w, x2, up, stride)
     dy = _f32(dy, who, "dy", 5)
     if tuple(dy.shape) != want:
@@ -332,9 +336,9 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
     if need & {"x", "x2"}:
         dx = torch.empty_like(x) if "x" in need else None
         dx2 = torch.empty_like(x2) if "x2" in need else None
-        fn = _lib.lib().ps_conv3d_bwd_data
+        fn = _lib.lib().ps_conv3d_bwd_data_prec if prec else _lib.lib().ps_conv3d_bwd_data
         _two_call("ps_conv3d_bwd_data", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(dy), runtime.ptr(w), *geometry, runtime.ptr(dx),
-                                                                        runtime.ptr(dx2), scratch, n))
+                                                                        runtime.ptr(dx2), scratch, n, *tail))
         if dx is not None:
             out["x"] = dx
         if dx2 is not None:
@@ -342,9 +346,9 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
     if need & {"w", "bias"}:
         dw = torch.empty_like(w) if "w" in need else None
         db = torch.empty((w.shape[4],), dtype=torch.float32, device=x.device) if "bias" in need else None
-        fn = _lib.lib().ps_conv3d_bwd_weight
+        fn = _lib.lib().ps_conv3d_bwd_weight_prec if prec else _lib.lib().ps_conv3d_bwd_weight
         _two_call("ps_conv3d_bwd_weight", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(x2), runtime.ptr(dy), *geometry,
-                                                                          runtime.ptr(dw), runtime.ptr(db), scratch, n))
+                                                                          runtime.ptr(dw), runtime.ptr(db), scratch, n, *tail))
         if dw is not None:
             out["w"] = dw
         if db is not None:
@@ -382,13 +386,15 @@ def instance_norm_relu_backward(dy, x, y, gamma, eps=EPS):
 
 
 class Conv3dFunction(torch.autograd.Function):
-    """conv3d with its gradients: forward ps_conv3d, backward ps_conv3d_bwd_data and ps_conv3d_bwd_weight.  Saves x, x2 and w."""
+    """conv3d with its gradients: forward ps_conv3d, backward ps_conv3d_bwd_data and ps_conv3d_bwd_weight, all three at `precision`.
+    Saves x, x2 and w."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, dilation, x2, up):
+    def forward(ctx, x, w, bias, stride, dilation, x2, up, precision="fp32"):
         ctx.save_for_backward(x, x2, w)
         ctx.geometry = (stride, dilation, up)
-        return conv3d(x, w, bias, stride, dilation, x2, up)
+        ctx.precision = precision
+        return conv3d(x, w, bias, stride, dilation, x2, up, precision)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -397,8 +403,8 @@ class Conv3dFunction(torch.autograd.Function):
         stride, dilation, up = ctx.geometry
         wanted = ctx.needs_input_grad
         need = [name for name, i in (("x", 0), ("w", 1), ("bias", 2), ("x2", 5)) if wanted[i] and (name != "x2" or x2 is not None)]
-        g = conv3d_backward(dy, x, w, stride, dilation, x2, up, need) if need else {}
-        return g.get("x"), g.get("w"), g.get("bias"), None, None, g.get("x2"), None
+        g = conv3d_backward(dy, x, w, stride, dilation, x2, up, need, ctx.precision) if need else {}
+        return g.get("x"), g.get("w"), g.get("bias"), None, None, g.get("x2"), None, None
 
 
 class InstanceNormReluFunction(torch.autograd.Function):
@@ -422,9 +428,10 @@ class InstanceNormReluFunction(torch.autograd.Function):
         return dx, dgamma, dbeta, None
 
 
-def differentiable_conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1):
-    """conv3d, recorded by torch.autograd."""
-    return Conv3dFunction.apply(x, w, bias, stride, dilation, x2, up)
+def differentiable_conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1, precision="fp32"):
+    """conv3d, recorded by torch.autograd: the forward and both gradients run at `precision`."""
+    _precision("differentiable_conv3d", precision)
+    return Conv3dFunction.apply(x, w, bias, stride, dilation, x2, up, precision)
 
 
 def differentiable_instance_norm_relu(x, gamma, beta, eps=EPS):
@@ -647,10 +654,17 @@ def differentiable_softmax_dice_loss(logits, labels, weight=None):
 
 class TrainableSaliencyNet(torch.nn.Module):
     """unet3d_attention (model.py:176-314) composed from the differentiable ops above: one torch.nn.Parameter per entry of param_shapes,
-    under the same name, so torch.autograd and a torch optimiser train it on this package's kernels.  params: the TF-named dict."""
+    under the same name, so torch.autograd and a torch optimiser train it on this package's kernels.  params: the TF-named dict.
+    precision: the arithmetic of every convolution and of its two gradients -- "fp32", "bf16x3" or "bf16"
+    (include/pointseg_saliency_train_precision.h); everything between the convolutions stays fp32, as in SaliencyNet.  One difference from
+    SaliencyNet: here the channel attention scales the ACTIVATION in front of C345_conv, where inference folds the scale into that layer's
+    kernel; under "bf16" this graph therefore rounds the scaled activation (and the plain kernel), inference the activation and the scaled
+    kernel."""
 
-    def __init__(self, params, in_channels, num_classes=2, device=0):
+    def __init__(self, params, in_channels, num_classes=2, device=0, precision="fp32"):
         super().__init__()
+        _precision("TrainableSaliencyNet", precision)
+        self.precision = precision
         self.in_channels, self.num_classes = int(in_channels), int(num_classes)
         self.device = torch.device("cuda", device)
         flat = flatten_params(params, self.in_channels, self.num_classes)  # (checks the names and the shapes)
@@ -667,7 +681,7 @@ class TrainableSaliencyNet(torch.nn.Module):
 
         def conv(name, t, stride=1, dilation=1, norm=True, x2=None, up=1):
             n = SCOPE + name
-            y = differentiable_conv3d(t, P[n + "/kernel"], P.get(n + "/bias"), stride, dilation, x2, up)
+            y = differentiable_conv3d(t, P[n + "/kernel"], P.get(n + "/bias"), stride, dilation, x2, up, self.precision)
             if not norm:
                 return y
             y = differentiable_instance_norm_relu(y, P[n + "/ins_norm/gamma"], P[n + "/ins_norm/beta"])
