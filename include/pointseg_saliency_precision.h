@@ -4,7 +4,7 @@
  * ps_saliency_forward these two entries extend: every argument before `precision` is theirs, with their limits, their checks, their
  * two-call scratch protocol and their scratch SIZE (the same number of bytes in every mode).  ps_conv3d is ps_conv3d_prec(..., PS_PREC_FP32)
  * and ps_saliency_forward is ps_saliency_forward_prec(..., PS_PREC_FP32): one body each.  In training, the convolution's two
- * gradients take the same choice op by op (pointseg_saliency_train_precision.h); the one-call step (pointseg_saliency_step.h) stays fp32.
+ * gradients take the same choice op by op (pointseg_saliency_train_precision.h), the one-call step per role (pointseg_saliency_step_precision.h).
  *
  * The rule, for every convolution of the call
  * -------------------------------------------

@@ -8,7 +8,7 @@
  * bytes in every mode).  ps_conv3d_bwd_data is ps_conv3d_bwd_data_prec(..., PS_PREC_FP32) and ps_conv3d_bwd_weight is
  * ps_conv3d_bwd_weight_prec(..., PS_PREC_FP32): one body each, the same bytes as before this header.  Any other value than the three
  * returns PS_EINVAL before anything is enqueued, also in the call that only sizes the scratch (*scratch_bytes is then left alone).
- * The one-call training step (pointseg_saliency_step.h) and the instance norm's gradient stay fp32.
+ * The instance norm's gradient stays fp32.  The one-call training step takes one precision per role: pointseg_saliency_step_precision.h.
  *
  * The rule
  * --------

@@ -4,7 +4,8 @@ The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (P
 (PREPARE_PROTOTYPES), include/pointseg_postprocess.h (POSTPROCESS_PROTOTYPES), include/pointseg_saliency.h
 (SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
 (SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
-(SALIENCY_STEP_PROTOTYPES) and include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES).  The library is built in-tree by compile_op.sh
+(SALIENCY_STEP_PROTOTYPES), include/pointseg_saliency_step_precision.h (SALIENCY_STEP_PRECISION_PROTOTYPES) and
+include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES).  The library is built in-tree by compile_op.sh
 (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -372,6 +373,14 @@ SALIENCY_MIXUP_PROTOTYPES = {
     "ps_saliency_train_step_soft": SALIENCY_STEP_PROTOTYPES["ps_saliency_train_step"],
 }
 
+# every symbol include/pointseg_saliency_step_precision.h declares (the one-call step with a precision per role of its convolutions;
+# csrc/saliency_step.hip): the arguments of the entries they extend, then soft_labels and the forward's, the data gradient's and the
+# weight gradient's precision
+SALIENCY_STEP_PRECISION_PROTOTYPES = {
+    "ps_saliency_backward_prec": (ctypes.c_int, SALIENCY_STEP_PROTOTYPES["ps_saliency_backward"][1] + [ctypes.c_int32] * 4),
+    "ps_saliency_train_step_prec": (ctypes.c_int, SALIENCY_STEP_PROTOTYPES["ps_saliency_train_step"][1] + [ctypes.c_int32] * 4),
+}
+
 _lib = None
 
 
@@ -395,7 +404,8 @@ def lib():
                                   + list(SALIENCY_PROTOTYPES.items()) + list(SALIENCY_PRECISION_PROTOTYPES.items())
                                   + list(SALIENCY_TRAIN_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PRECISION_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
-                                  + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())):
+                                  + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())
+                                  + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

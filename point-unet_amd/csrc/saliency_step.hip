@@ -5,13 +5,18 @@
 //
 // The walker runs twice over the same code: once with `run` off, where every op only reports its scratch (and refuses a shape it cannot
 // take, before anything is enqueued), once enqueueing.  Where everything lies is saliency_step_plan.h's, a function of the shapes.
+//
+// The convolutions run at one precision per role -- forward, data gradient, weight gradient -- through the _prec entries of their ops
+// (include/pointseg_saliency_step_precision.h); PS_PREC_FP32 three times is the step as it was, byte for byte.
 #include <algorithm>
 
 #include "../../include/pointseg_saliency_attention.h"
 #include "../../include/pointseg_saliency_mixup.h"
 #include "../../include/pointseg_saliency_step.h"
+#include "../../include/pointseg_saliency_step_precision.h"
 #include "../../include/pointseg_saliency_train.h"
 #include "common.h"
+#include "saliency.h"
 #include "saliency_kit.h"
 #include "saliency_step_plan.h"
 
@@ -129,6 +134,7 @@ struct Step {
     char* base;
     const float* wt;
     float* gr;
+    int prec_fwd, prec_data, prec_weight;  // PS_PREC_*: the convolutions of each role
     size_t ops_need = 0;
     Rec rec[48];
 
@@ -166,8 +172,8 @@ struct Step {
         rec[li] = {in, in2, l, L.cin - C2, C2, up, stride, dil};
         float* x = x_over ? x_over : X(li);
         if (run)
-            PS_TRY(ps_conv3d(c, in, in2, p.B, p.Dl[l], p.Hl[l], p.Wl[l], L.cin - C2, C2, up, wt + L.w, L.b >= 0 ? wt + L.b : nullptr, L.kd, L.kh, L.kw, L.cout,
-                             stride, dil, x));
+            PS_TRY(ps_conv3d_prec(c, in, in2, p.B, p.Dl[l], p.Hl[l], p.Wl[l], L.cin - C2, C2, up, wt + L.w, L.b >= 0 ? wt + L.b : nullptr, L.kd, L.kh, L.kw,
+                                  L.cout, stride, dil, x, prec_fwd));
         if (L.g < 0) return PS_OK;
         const int lo = p.level[li];
         return op([&](void* sc, int64_t* n) {
@@ -190,13 +196,13 @@ struct Step {
             g = dxn;
         }
         PS_TRY(op([&](void* sc, int64_t* n) {
-            return ps_conv3d_bwd_weight(c, r.in, r.in2, g, p.B, p.Dl[r.l], p.Hl[r.l], p.Wl[r.l], r.C1, r.C2, r.up, L.kd, L.kh, L.kw, L.cout, r.stride, r.dil,
-                                        gr + L.w, L.b >= 0 ? gr + L.b : nullptr, sc, n);
+            return ps_conv3d_bwd_weight_prec(c, r.in, r.in2, g, p.B, p.Dl[r.l], p.Hl[r.l], p.Wl[r.l], r.C1, r.C2, r.up, L.kd, L.kh, L.kw, L.cout, r.stride,
+                                             r.dil, gr + L.w, L.b >= 0 ? gr + L.b : nullptr, sc, n, prec_weight);
         }));
         if (!data) return PS_OK;
         return op([&](void* sc, int64_t* n) {
-            return ps_conv3d_bwd_data(c, g, wt + L.w, p.B, p.Dl[r.l], p.Hl[r.l], p.Wl[r.l], r.C1, r.C2, r.up, L.kd, L.kh, L.kw, L.cout, r.stride, r.dil, dx, dx2,
-                                      sc, n);
+            return ps_conv3d_bwd_data_prec(c, g, wt + L.w, p.B, p.Dl[r.l], p.Hl[r.l], p.Wl[r.l], r.C1, r.C2, r.up, L.kd, L.kh, L.kw, L.cout, r.stride, r.dil, dx,
+                                           dx2, sc, n, prec_data);
         });
     }
 
@@ -335,13 +341,33 @@ int shapes_ok(const char* who, int64_t B, int64_t D, int64_t H, int64_t W, int64
     return PS_OK;
 }
 
-// ps_saliency_backward behind checked shapes; `who` names the entry in the messages, `soft` is the kind of `labels`
-int backward_run(const char* who, bool soft, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C_in,
+// soft_labels and the three precisions of include/pointseg_saliency_step_precision.h, as the caller gave them
+struct Modes {
+    int32_t soft, fwd, data, weight;
+};
+
+const Modes kFp32Hard = {0, PS_PREC_FP32, PS_PREC_FP32, PS_PREC_FP32}, kFp32Soft = {1, PS_PREC_FP32, PS_PREC_FP32, PS_PREC_FP32};
+
+int modes_ok(const char* who, const Modes& m)
+{
+    PS_CHECK(m.soft == 0 || m.soft == 1, "%s: soft_labels = %d, must be 0 (int32 labels) or 1 (float32 rows)", who, (int)m.soft);
+    PS_CHECK(precision_ok(m.fwd) && precision_ok(m.data) && precision_ok(m.weight),
+             "%s: precision_forward = %d, precision_data_grad = %d, precision_weight_grad = %d, each must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or "
+             "PS_PREC_BF16 (2)",
+             who, (int)m.fwd, (int)m.data, (int)m.weight);
+    return PS_OK;
+}
+
+// ps_saliency_backward_prec behind checked shapes; `who` names the entry in the messages
+int backward_run(const char* who, const Modes& m, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C_in,
                  int64_t K, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
+    PS_TRY(modes_ok(who, m));
     PS_CHECK(scratch_bytes && (c || !scratch), "%s: NULL argument", who);
     PS_TRY(shapes_ok(who, B, D, H, W, C_in, K));
+    const bool soft = m.soft != 0;
     Step s;
+    s.prec_fwd = m.fwd, s.prec_data = m.data, s.prec_weight = m.weight;
     build_net(s.net, (int)C_in, (int)K);
     PS_CHECK(weight_count == s.net.count, "%s: weight_count = %lld, the network has %lld weights", who, (long long)weight_count, (long long)s.net.count);
     s.c = c, s.run = false, s.base = nullptr, s.wt = nullptr, s.gr = nullptr;
@@ -391,7 +417,7 @@ extern "C" int ps_saliency_backward(ps_context* c, const void* x, const void* la
                                     int64_t C_in, int64_t num_classes, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits,
                                     void* scratch, int64_t* scratch_bytes)
 {
-    return ps::backward_run("ps_saliency_backward", false, c, x, labels, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits, scratch,
+    return ps::backward_run("ps_saliency_backward", ps::kFp32Hard, c, x, labels, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits, scratch,
                             scratch_bytes);
 }
 
@@ -414,11 +440,12 @@ namespace ps {
 
 namespace {
 
-// ps_saliency_train_step / ps_saliency_train_step_soft
-int train_step_run(const char* who, bool soft, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+// ps_saliency_train_step_prec
+int train_step_run(const char* who, const Modes& m, ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
                    int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
                    const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
+    PS_TRY(modes_ok(who, m));
     const ps_saliency_step_options dflt = {nullptr, nullptr, 1, 0.9f, 1e-5f};
     const ps_saliency_step_options& o = options ? *options : dflt;
     PS_CHECK(o.world_size >= 1, "%s: world_size = %d, must be >= 1", who, (int)o.world_size);
@@ -427,7 +454,7 @@ int train_step_run(const char* who, bool soft, ps_context* c, const void* x, con
         Net net;
         PS_TRY(update_check(who, params, grads, accum, C_in, num_classes, weight_count, net));
     }
-    PS_TRY(backward_run(who, soft, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, loss, logits, scratch, scratch_bytes));
+    PS_TRY(backward_run(who, m, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, loss, logits, scratch, scratch_bytes));
     if (!scratch) return PS_OK;
     float grad_scale = 1.f;
     if (o.allreduce && o.world_size > 1) {
@@ -454,7 +481,7 @@ extern "C" int ps_saliency_train_step(ps_context* c, const void* x, const void* 
                                       int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
                                       const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
-    return ps::train_step_run("ps_saliency_train_step", false, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
+    return ps::train_step_run("ps_saliency_train_step", ps::kFp32Hard, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
                               learning_rate, options, loss, logits, scratch, scratch_bytes);
 }
 
@@ -462,7 +489,7 @@ extern "C" int ps_saliency_backward_soft(ps_context* c, const void* x, const voi
                                          int64_t C_in, int64_t num_classes, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits,
                                          void* scratch, int64_t* scratch_bytes)
 {
-    return ps::backward_run("ps_saliency_backward_soft", true, c, x, soft, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits,
+    return ps::backward_run("ps_saliency_backward_soft", ps::kFp32Soft, c, x, soft, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits,
                             scratch, scratch_bytes);
 }
 
@@ -470,6 +497,26 @@ extern "C" int ps_saliency_train_step_soft(ps_context* c, const void* x, const v
                                            int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
                                            const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes)
 {
-    return ps::train_step_run("ps_saliency_train_step_soft", true, c, x, soft, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
+    return ps::train_step_run("ps_saliency_train_step_soft", ps::kFp32Soft, c, x, soft, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
+                              learning_rate, options, loss, logits, scratch, scratch_bytes);
+}
+
+extern "C" int ps_saliency_backward_prec(ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                                         int64_t C_in, int64_t num_classes, const void* weights, int64_t weight_count, void* grads, void* loss, void* logits,
+                                         void* scratch, int64_t* scratch_bytes, int32_t soft_labels, int32_t precision_forward, int32_t precision_data_grad,
+                                         int32_t precision_weight_grad)
+{
+    const ps::Modes m = {soft_labels, precision_forward, precision_data_grad, precision_weight_grad};
+    return ps::backward_run("ps_saliency_backward_prec", m, c, x, labels, weight, B, D, H, W, C_in, num_classes, weights, weight_count, grads, loss, logits, scratch,
+                            scratch_bytes);
+}
+
+extern "C" int ps_saliency_train_step_prec(ps_context* c, const void* x, const void* labels, const void* weight, int64_t B, int64_t D, int64_t H, int64_t W,
+                                           int64_t C_in, int64_t num_classes, void* params, int64_t weight_count, void* grads, void* accum, float learning_rate,
+                                           const ps_saliency_step_options* options, void* loss, void* logits, void* scratch, int64_t* scratch_bytes,
+                                           int32_t soft_labels, int32_t precision_forward, int32_t precision_data_grad, int32_t precision_weight_grad)
+{
+    const ps::Modes m = {soft_labels, precision_forward, precision_data_grad, precision_weight_grad};
+    return ps::train_step_run("ps_saliency_train_step_prec", m, c, x, labels, weight, B, D, H, W, C_in, num_classes, params, weight_count, grads, accum,
                               learning_rate, options, loss, logits, scratch, scratch_bytes);
 }

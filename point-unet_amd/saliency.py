@@ -163,12 +163,22 @@ def _conv_args(who, x, w, x2, up, stride):
     return x, w, x2, (B, Ds, Hs, Ws, C1, C2), (B, _same_out(Ds * up, stride), _same_out(Hs * up, stride), _same_out(Ws * up, stride), w.shape[4])
 
 
-def _precision(who, precision):
-    """"fp32" | "bf16x3" | "bf16" -> the PS_PREC_* value of include/pointseg_saliency_precision.h."""
+def _precision(who, precision, roles=3):
+    """"fp32" | "bf16x3" | "bf16", or a triple (forward, data_grad, weight_grad) of those names, -> the three PS_PREC_* values of
+    include/pointseg_saliency_precision.h, one per role of a convolution in training; a single name means that name three times.
+    roles=1 (inference: one role): a single name alone -> its one value."""
+    names = _lib.SALIENCY_PRECISIONS
     try:
-        return _lib.SALIENCY_PRECISIONS[precision]
+        if roles == 3 and isinstance(precision, (tuple, list)):
+            if len(precision) != 3:
+                raise KeyError(precision)
+            return tuple(names[p] for p in precision)
+        return names[precision] if roles == 1 else (names[precision],) * 3
     except (KeyError, TypeError):
-        raise ValueError("%s: precision must be one of %s, got %r" % (who, ", ".join(map(repr, _lib.SALIENCY_PRECISIONS)), precision)) from None
+        what = "one of %s" % ", ".join(map(repr, names))
+        if roles == 3:
+            what += ", or a triple (forward, data_grad, weight_grad) of them"
+        raise ValueError("%s: precision must be %s, got %r" % (who, what, precision)) from None
 
 
 def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1, precision="fp32"):
@@ -176,7 +186,7 @@ def conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1, precision="fp32
     channel axis; both up-sampled `up` times by repetition first), w [kd, kh, kw, C1 + C2, C_out], bias [C_out] or None.  CUDA float32.
     precision: "fp32" (ps_conv3d), or "bf16x3" / "bf16" on the bf16 matrix pipe (ps_conv3d_prec, include/pointseg_saliency_precision.h)."""
     who = "conv3d"
-    prec = _precision(who, precision)
+    prec = _precision(who, precision, roles=1)
     x, w, x2, dims, out_shape = _conv_args(who, x, w, x2, up, stride)
     if bias is not None:
         bias = _f32(bias, who, "bias", 1)
@@ -218,7 +228,7 @@ class SaliencyNet:
 
     def __init__(self, params, in_channels, num_classes=2, device=0, precision="fp32"):
         self.precision = precision
-        self._prec = _precision("SaliencyNet", precision)
+        self._prec = _precision("SaliencyNet", precision, roles=1)
         self.in_channels, self.num_classes = int(in_channels), int(num_classes)
         flat = flatten_params(params, self.in_channels, self.num_classes)
         want = _lib.lib().ps_saliency_weight_count(self.in_channels, self.num_classes)
@@ -315,10 +325,10 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
     """The gradients of conv3d(x, w, bias, stride, dilation, x2, up) for the output gradient dy: a dict with the entries of `need` --
     "x" [like x], "x2" [like x2; only with x2], "w" [like w], "bias" [C_out].  Arguments are checked as conv3d checks them.
     precision: "fp32" (ps_conv3d_bwd_data, ps_conv3d_bwd_weight), or "bf16x3" / "bf16" on the bf16 matrix pipe (their _prec entries,
-    include/pointseg_saliency_train_precision.h)."""
+    include/pointseg_saliency_train_precision.h); a triple (forward, data_grad, weight_grad) gives the data gradient (x, x2) its second
+    name and the weight gradient (w, bias) its third."""
     who = "conv3d_backward"
-    prec = _precision(who, precision)
-    tail = (prec,) if prec else ()
+    _, prec_data, prec_weight = _precision(who, precision)
     x, w, x2, dims, want = _conv_args(who, x, w, x2, up, stride)
     dy = _f32(dy, who, "dy", 5)
     if tuple(dy.shape) != want:
@@ -336,7 +346,8 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
     if need & {"x", "x2"}:
         dx = torch.empty_like(x) if "x" in need else None
         dx2 = torch.empty_like(x2) if "x2" in need else None
-        fn = _lib.lib().ps_conv3d_bwd_data_prec if prec else _lib.lib().ps_conv3d_bwd_data
+        fn = _lib.lib().ps_conv3d_bwd_data_prec if prec_data else _lib.lib().ps_conv3d_bwd_data
+        tail = (prec_data,) if prec_data else ()
         _two_call("ps_conv3d_bwd_data", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(dy), runtime.ptr(w), *geometry, runtime.ptr(dx),
                                                                         runtime.ptr(dx2), scratch, n, *tail))
         if dx is not None:
@@ -346,7 +357,8 @@ def conv3d_backward(dy, x, w, stride=1, dilation=1, x2=None, up=1, need=("x", "x
     if need & {"w", "bias"}:
         dw = torch.empty_like(w) if "w" in need else None
         db = torch.empty((w.shape[4],), dtype=torch.float32, device=x.device) if "bias" in need else None
-        fn = _lib.lib().ps_conv3d_bwd_weight_prec if prec else _lib.lib().ps_conv3d_bwd_weight
+        fn = _lib.lib().ps_conv3d_bwd_weight_prec if prec_weight else _lib.lib().ps_conv3d_bwd_weight
+        tail = (prec_weight,) if prec_weight else ()
         _two_call("ps_conv3d_bwd_weight", x.device, lambda scratch, n: fn(ctx.handle, runtime.ptr(x), runtime.ptr(x2), runtime.ptr(dy), *geometry,
                                                                           runtime.ptr(dw), runtime.ptr(db), scratch, n, *tail))
         if dw is not None:
@@ -386,15 +398,15 @@ def instance_norm_relu_backward(dy, x, y, gamma, eps=EPS):
 
 
 class Conv3dFunction(torch.autograd.Function):
-    """conv3d with its gradients: forward ps_conv3d, backward ps_conv3d_bwd_data and ps_conv3d_bwd_weight, all three at `precision`.
-    Saves x, x2 and w."""
+    """conv3d with its gradients: forward ps_conv3d, backward ps_conv3d_bwd_data and ps_conv3d_bwd_weight, all three at `precision`, or
+    each at its own name of a triple (forward, data_grad, weight_grad).  Saves x, x2 and w."""
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, dilation, x2, up, precision="fp32"):
         ctx.save_for_backward(x, x2, w)
         ctx.geometry = (stride, dilation, up)
         ctx.precision = precision
-        return conv3d(x, w, bias, stride, dilation, x2, up, precision)
+        return conv3d(x, w, bias, stride, dilation, x2, up, precision[0] if isinstance(precision, (tuple, list)) else precision)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -429,7 +441,8 @@ class InstanceNormReluFunction(torch.autograd.Function):
 
 
 def differentiable_conv3d(x, w, bias=None, stride=1, dilation=1, x2=None, up=1, precision="fp32"):
-    """conv3d, recorded by torch.autograd: the forward and both gradients run at `precision`."""
+    """conv3d, recorded by torch.autograd: the forward and both gradients run at `precision`, or -- a triple (forward, data_grad,
+    weight_grad) -- each at its own."""
     _precision("differentiable_conv3d", precision)
     return Conv3dFunction.apply(x, w, bias, stride, dilation, x2, up, precision)
 
@@ -656,7 +669,8 @@ class TrainableSaliencyNet(torch.nn.Module):
     """unet3d_attention (model.py:176-314) composed from the differentiable ops above: one torch.nn.Parameter per entry of param_shapes,
     under the same name, so torch.autograd and a torch optimiser train it on this package's kernels.  params: the TF-named dict.
     precision: the arithmetic of every convolution and of its two gradients -- "fp32", "bf16x3" or "bf16"
-    (include/pointseg_saliency_train_precision.h); everything between the convolutions stays fp32, as in SaliencyNet.  One difference from
+    (include/pointseg_saliency_train_precision.h), or a triple (forward, data_grad, weight_grad) of those names, one per role;
+    everything between the convolutions stays fp32, as in SaliencyNet.  One difference from
     SaliencyNet: here the channel attention scales the ACTIVATION in front of C345_conv, where inference folds the scale into that layer's
     kernel; under "bf16" this graph therefore rounds the scaled activation (and the plain kernel), inference the activation and the scaled
     kernel."""
@@ -724,11 +738,14 @@ class TrainableSaliencyNet(torch.nn.Module):
         return differentiable_softmax_dice_loss(self.logits(x, masks), labels, weight)
 
     def export(self, precision=None):
-        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes; with precision ("fp32" | "bf16x3" | "bf16"),
-        the SaliencyNet of them at that precision, on this net's device."""
+        """The parameters as the TF-named dict of float32 numpy arrays that SaliencyNet takes; with precision ("fp32" | "bf16x3" | "bf16":
+        one name, inference has one role), the SaliencyNet of them at that precision, on this net's device; with precision="forward", at
+        the precision this net's forward runs at (the first name of a triple)."""
         params = {name: p.detach().cpu().numpy() for name, p in self.named_parameters()}
         if precision is None:
             return params
+        if precision == "forward":
+            precision = self.precision[0] if isinstance(self.precision, (tuple, list)) else self.precision
         return SaliencyNet(params, self.in_channels, self.num_classes, self.device.index, precision)
 
 
@@ -747,9 +764,14 @@ def reference_optimizer(net, lr=0.01):
 class SaliencyTrainer:
     """unet3d_attention trained without torch.autograd: the flat parameters `flat`, this rank's gradients `grad`, the momentum `accum` and
     the cached scratch are device tensors, and one call of ps_saliency_train_step is a step of train.py:83-110 (forward, softmax + Dice, the
-    whole backward, the optional gradient all-reduce, the momentum update with the regulariser).  params: the TF-named dict."""
+    whole backward, the optional gradient all-reduce, the momentum update with the regulariser).  params: the TF-named dict.
+    precision: the arithmetic of the step's convolutions -- "fp32", "bf16x3" or "bf16", or a triple (forward, data_grad, weight_grad) of
+    those names, one per role (include/pointseg_saliency_step_precision.h); backward and step run ps_saliency_backward_prec and
+    ps_saliency_train_step_prec with it, and "fp32" gives the bytes of the entries without a precision."""
 
-    def __init__(self, params, in_channels, num_classes=2, device=0, momentum=0.9, l2=1e-5):
+    def __init__(self, params, in_channels, num_classes=2, device=0, momentum=0.9, l2=1e-5, precision="fp32"):
+        self._prec = _precision("SaliencyTrainer", precision)
+        self.precision = precision
         self.in_channels, self.num_classes = int(in_channels), int(num_classes)
         self.momentum, self.l2 = float(momentum), float(l2)
         flat = flatten_params(params, self.in_channels, self.num_classes)
@@ -774,25 +796,27 @@ class SaliencyTrainer:
         _, labels, weight, _, _, _ = _loss_args(who, logits, labels, weight)
         return x, labels, weight, logits
 
-    def _call(self, fn, x, head, tail):
-        """fn(ctx, *head, B, D, H, W, C_in, num_classes, *tail, scratch, &bytes) under the two-call protocol, on this trainer's own scratch."""
+    def _call(self, fn, x, head, tail, soft):
+        """fn(ctx, *head, B, D, H, W, C_in, num_classes, *tail, scratch, &bytes, soft, *the three precisions) under the two-call protocol, on
+        this trainer's own scratch."""
         ctx = _ctx_for(x)
         shape = tuple(x.shape[:4]) + (self.in_channels, self.num_classes)
+        modes = (soft,) + self._prec
         need = ctypes.c_int64(0)
-        _lib.check(fn(None, *head, *shape, *tail, None, ctypes.byref(need)))
+        _lib.check(fn(None, *head, *shape, *tail, None, ctypes.byref(need), *modes))
         if self.scratch is None or self.scratch.numel() < need.value:
             self.scratch = torch.empty(max(need.value, 1), dtype=torch.uint8, device=x.device)
         self.scratch_bytes = need.value
-        _lib.check(fn(ctx.handle, *head, *shape, *tail, runtime.ptr(self.scratch), ctypes.byref(need)))
+        _lib.check(fn(ctx.handle, *head, *shape, *tail, runtime.ptr(self.scratch), ctypes.byref(need), *modes))
 
     def backward(self, x, labels, weight=None, want_logits=False):
         """The loss (0-dim, on the device; overwritten by the next call) of a patch x [B, D, H, W, C_in] with labels [B, D, H, W] int32 (or
-        soft labels float32 [B, D, H, W, num_classes]: ps_saliency_backward_soft) and weight [B, D, H, W] or None, its gradients left in
-        `grad`; no parameter changes.  want_logits: (loss, logits)."""
+        soft labels float32 [B, D, H, W, num_classes]: soft_labels = 1) and weight [B, D, H, W] or None, its gradients left in `grad`; no
+        parameter changes.  want_logits: (loss, logits)."""
         x, labels, weight, logits = self._args(x, labels, weight)
         p = runtime.ptr
-        self._call(_lib.lib().ps_saliency_backward_soft if _is_soft(labels) else _lib.lib().ps_saliency_backward, x, (p(x), p(labels), p(weight)),
-                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.loss), p(logits) if want_logits else None))
+        self._call(_lib.lib().ps_saliency_backward_prec, x, (p(x), p(labels), p(weight)),
+                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.loss), p(logits) if want_logits else None), int(_is_soft(labels)))
         return (self.loss, logits) if want_logits else self.loss
 
     def _collective(self, dist):
@@ -829,8 +853,8 @@ class SaliencyTrainer:
             allreduce, world_size = self._collective(dist), dist.get_world_size()
         opt = _lib.PsSaliencyStepOptions(allreduce if allreduce is not None else _lib.PS_ALLREDUCE_FN(), None, int(world_size or 1), self.momentum, self.l2)
         p = runtime.ptr
-        self._call(_lib.lib().ps_saliency_train_step_soft if _is_soft(labels) else _lib.lib().ps_saliency_train_step, x, (p(x), p(labels), p(weight)),
-                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.accum), float(lr), ctypes.byref(opt), p(self.loss), None))
+        self._call(_lib.lib().ps_saliency_train_step_prec, x, (p(x), p(labels), p(weight)),
+                   (p(self.flat), self.flat.numel(), p(self.grad), p(self.accum), float(lr), ctypes.byref(opt), p(self.loss), None), int(_is_soft(labels)))
         return self.loss
 
     def update(self, lr, grad_scale=1.0):

@@ -276,8 +276,9 @@ class PatchBank:
 def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None, mixup=None):
     """The loop of train.py:83-110 on the device: `steps` steps on the bank's batches (epoch_batches from `epoch` on,
     config.DATA_SAMPLING = 'one_positive').  engine "autograd": TrainableSaliencyNet.loss under saliency.reference_optimizer(net, lr) (or
-    `optimizer`); engine "native": net is a saliency.SaliencyTrainer and every step is one ps_saliency_train_step at learning rate lr
-    (dist: the torch.distributed-like module its gradients are summed through).  Returns the per-step losses as one device tensor
+    `optimizer`); engine "native": net is a saliency.SaliencyTrainer and every step is one ps_saliency_train_step_prec at learning rate lr
+    (dist: the torch.distributed-like module its gradients are summed through), at the precision the trainer was made with
+    (SaliencyTrainer(precision=...): the trainer carries it, this loop takes no argument for it).  Returns the per-step losses as one device tensor
     [steps]; nothing is read back on the way.  mixup=num_classes: config.MIXUP, every batch is a mixed one (epoch_batches(mixup=...)) and
     the loss is dice_mixup's, on soft labels."""
     from . import saliency

@@ -15,10 +15,18 @@ step over `--steps` steps between device events, 1 warm-up step, 3 windows; peak
 step's scratch); and, from one more step under the context's stage timing, the launches and device time per entry point.  The yardstick
 of `onecall` is `opbyop` of the same session, never itself.
 
+Stage `onecall_precision`: SaliencyTrainer.step at the same batch in four combinations of (forward, data gradient, weight gradient)
+precision -- "fp32", "bf16x3", "bf16" and ("bf16x3", "bf16", "bf16") (include/pointseg_saliency_step_precision.h) -- in ONE process, their
+windows interleaved (window 1 of each, then window 2 of each, ...) so that a drift of the device meets all four alike; the same window
+discipline (device events, 1 warm-up step each, `--steps` steps per window, 3 windows).  The four trainers share one scratch (its size is
+the same in every combination).  Per combination: the windows, the best one, the peak device memory and the first three losses.  Its
+yardstick is `onecall` of the same session (name both in --stages): "fp32" runs the same code.  -> DIR/saliency_train_step_precision.json
+
 Each stage runs in a child process under a time limit of its own; after a stage that fails or runs out of time nothing more starts.
 
 usage (GPU box):
-    python profiles/tools/saliency_train_step.py --out DIR [--stages ops,step,opbyop,onecall] [--timeout 300]        # -> DIR/saliency_train_step.json"""
+    python profiles/tools/saliency_train_step.py --out DIR [--stages ops,step,opbyop,onecall,onecall_precision] [--timeout 300]
+                                                                                                         # -> DIR/saliency_train_step.json"""
 import argparse
 import json
 import os
@@ -164,20 +172,25 @@ def _step_inputs(torch):
     return shape, x, labels, weight
 
 
+def _window(torch, step, steps):
+    """(the mean step of one window of `steps` steps in ms, between device events; the steps' results)."""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    got = [step() for _ in range(steps)]
+    e.record()
+    e.synchronize()
+    return round(s.elapsed_time(e) / steps, 2), got
+
+
 def _windows(torch, step, steps, windows=3):
     """(the mean step of each window in ms, the first and the last loss): 1 warm-up step, then `windows` windows of `steps` steps."""
     losses = [float(step())]  # warm-up: scratch buffers and torch's allocator grow here
     torch.cuda.synchronize()
     out = []
     for _ in range(windows):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(steps):
-            last = step()
-        e.record()
-        e.synchronize()
-        out.append(round(s.elapsed_time(e) / steps, 2))
-    losses.append(float(last))
+        ms, got = _window(torch, step, steps)
+        out.append(ms)
+    losses.append(float(got[-1]))
     return out, losses
 
 
@@ -236,6 +249,40 @@ def stage_onecall(args):
     return res
 
 
+PRECISIONS = ("fp32", "bf16x3", "bf16", ("bf16x3", "bf16", "bf16"))
+
+
+def stage_onecall_precision(args, windows=3):
+    import torch
+    from point_unet_amd import saliency as sal
+    shape, x, labels, weight = _step_inputs(torch)
+    params = sal.init_params(1, 2, seed=0)
+    rows = []
+    for precision in PRECISIONS:
+        tr = sal.SaliencyTrainer(params, 1, 2, precision=precision)
+        if rows:
+            tr.scratch = rows[0]["trainer"].scratch  # (the same size in every combination; the first warm-up step made it)
+        step = lambda tr=tr: tr.step(x, labels, weight, 0.01).clone()
+        torch.cuda.reset_peak_memory_stats()
+        losses = [step()]  # warm-up
+        torch.cuda.synchronize()
+        rows.append({"trainer": tr, "step": step, "losses": losses, "windows_ms": [], "peak": torch.cuda.max_memory_allocated()})
+    for _ in range(max(windows, 3)):
+        for row in rows:
+            ms, got = _window(torch, row["step"], args.steps)
+            row["windows_ms"].append(ms)
+            row["losses"] += got
+    res = {"batch": shape, "steps_per_window": args.steps, "scratch_gb": round(rows[0]["trainer"].scratch_bytes / 1e9, 2), "combinations": []}
+    for precision, row in zip(PRECISIONS, rows):
+        w = row["windows_ms"]
+        res["combinations"].append({"precision": precision, "windows_ms": w, "step_ms": min(w), "spread": round((max(w) - min(w)) / min(w), 4),
+                                    "peak_device_memory_gb": round(row["peak"] / 1e9, 2), "first_three_losses": [float(l) for l in row["losses"][:3]]})
+    base = res["combinations"][0]["step_ms"]
+    for row in res["combinations"]:
+        row["fp32_over_this"] = round(base / row["step_ms"], 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -245,7 +292,8 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        print("RESULT " + json.dumps({"ops": stage_ops, "step": stage_step, "opbyop": stage_opbyop, "onecall": stage_onecall}[args.child](args)))
+        print("RESULT " + json.dumps({"ops": stage_ops, "step": stage_step, "opbyop": stage_opbyop, "onecall": stage_onecall,
+                                      "onecall_precision": stage_onecall_precision}[args.child](args)))
         return 0
     res = {"patch": PATCH}
     for stage in args.stages.split(","):
@@ -264,12 +312,20 @@ def main():
         a, b = res["opbyop"], res["onecall"]
         res["onecall_vs_opbyop"] = {"step_ms_ratio": round(b["step_ms"] / a["step_ms"], 4), "spread_of_the_session": max(a["spread"], b["spread"]),
                                     "memory_gb": [b["peak_device_memory_gb"], a["peak_device_memory_gb"]]}
+    if "onecall" in res and "onecall_precision" in res:
+        a, b = res["onecall"], res["onecall_precision"]["combinations"][0]
+        res["fp32_vs_onecall"] = {"step_ms": [b["step_ms"], a["step_ms"]], "step_ms_ratio": round(b["step_ms"] / a["step_ms"], 4),
+                                  "spread_of_the_session": max(a["spread"], b["spread"])}
     line = json.dumps(res)
     print(line)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, "saliency_train_step.json"), "w") as f:
             f.write(line + "\n")
+        if "onecall_precision" in res:
+            keep = {k: res[k] for k in ("patch", "onecall", "onecall_precision", "fp32_vs_onecall") if k in res}
+            with open(os.path.join(args.out, "saliency_train_step_precision.json"), "w") as f:
+                f.write(json.dumps(keep) + "\n")
     return 0
 
 
