@@ -108,7 +108,8 @@ int ps_saliency_forward(ps_context* ctx, const void* x, int64_t B, int64_t D, in
  * ps_saliency_accumulate: sum[o0 + i, o1 + j, o2 + k, :] += probs[i, j, k, :] and count[o0 + i, o1 + j, o2 + k] += 1 for the part of the
  * window inside the volume (eval.py:168-174).  probs: [p0, p1, p2, C] float32; sum: [D, H, W, C] float32; count: [D, H, W] int32; the
  * caller zeroes sum and count before the first window.  0 <= o < extent per axis, 1 <= C <= 16.  No scratch.
- * ps_saliency_finish: out[v, :] = sum[v, :] / count[v] (eval.py:176-177); out may be sum.  A voxel no window covered (count 0) gives 0. */
+ * ps_saliency_finish: out[v, :] = sum[v, :] / count[v] (eval.py:176-177); out may be sum.  A voxel no window covered (count 0) gives 0.
+ * The window loop around these two has an entry of its own: ps_saliency_map (pointseg_saliency_map.h), with the views, the flip and the fusion. */
 int ps_saliency_accumulate(ps_context* ctx, const void* probs, int64_t p0, int64_t p1, int64_t p2, int64_t C, int64_t o0, int64_t o1, int64_t o2,
                            int64_t D, int64_t H, int64_t W, void* sum, void* count);
 int ps_saliency_finish(ps_context* ctx, const void* sum, const void* count, int64_t D, int64_t H, int64_t W, int64_t C, void* out);

@@ -5,8 +5,8 @@ The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (P
 (SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
 (SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
 (SALIENCY_STEP_PROTOTYPES), include/pointseg_saliency_step_precision.h (SALIENCY_STEP_PRECISION_PROTOTYPES) and
-include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES).  The library is built in-tree by compile_op.sh
-(csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
+include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES) and include/pointseg_saliency_map.h (SALIENCY_MAP_PROTOTYPES).
+The library is built in-tree by compile_op.sh (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
 import os
@@ -381,6 +381,16 @@ SALIENCY_STEP_PRECISION_PROTOTYPES = {
     "ps_saliency_train_step_prec": (ctypes.c_int, SALIENCY_STEP_PROTOTYPES["ps_saliency_train_step"][1] + [ctypes.c_int32] * 4),
 }
 
+# every symbol include/pointseg_saliency_map.h declares (the saliency map of a whole volume behind one call: views, flip, fusion;
+# csrc/saliency_map.hip)
+PS_VIEW_AXIAL, PS_VIEW_SAGITTAL, PS_VIEW_CORONAL = 0, 1, 2
+SALIENCY_VIEWS = {"axial": PS_VIEW_AXIAL, "sagittal": PS_VIEW_SAGITTAL, "coronal": PS_VIEW_CORONAL}
+PS_VOLUME_CDHW, PS_VOLUME_DHWC = 0, 1
+SALIENCY_MAP_PROTOTYPES = {
+    "ps_saliency_map": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32] + [ctypes.c_int64] * 5 + [ctypes.c_int32, c_i32p, ctypes.POINTER(c_vp), ctypes.c_int64, c_i64p,
+                                       c_i64p] + [ctypes.c_int32] * 3 + [c_vp, c_vp, c_i64p]),
+}
+
 _lib = None
 
 
@@ -405,7 +415,7 @@ def lib():
                                   + list(SALIENCY_TRAIN_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PRECISION_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())
-                                  + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items())):
+                                  + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items()) + list(SALIENCY_MAP_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

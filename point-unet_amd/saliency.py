@@ -284,39 +284,55 @@ def window_origins(n, crop, step):
     return list(range(0, max(1, n - crop + step), step))
 
 
-def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118)):
-    """overlapping_inference (eval.py:103-193) on the device: volume [C_in, D, H, W] or [D, H, W] (CUDA float32) -> the window-averaged
-    softmax probabilities [D, H, W, num_classes].  A window that overhangs the volume is zero-filled and its prediction cut back to the
-    part inside.  The reference feeds BATCH_SIZE copies of the window and keeps pred[0]; with instance norm the samples of a batch do not
-    see each other, so one copy gives the same result.  The window loop runs on the host; nothing is read back."""
+def saliency_map(volume, net, patch=(64, 160, 160), steps=(48, 118, 118), direction="axial", flip=False, batch=1, layout=None):
+    """segment_one_image / overlapping_inference (eval.py:103-193, 355-411) on the device, one ps_saliency_map call
+    (include/pointseg_saliency_map.h states the rule): volume [C_in, D, H, W] or [D, H, W], or with layout="DHWC" a PatchBank image
+    [D, H, W, C_in] (CUDA float32) -> the window-averaged softmax probabilities [D, H, W, num_classes], in the volume's orientation.
+    net: a SaliencyNet, whose view is `direction` ("axial", "sagittal", "coronal": config.DIRECTION, utils.py:80-104), or a dict that maps
+    view names to the SaliencyNet trained for each (config.MULTI_VIEW, eval.py:254): the maps are fused in the dict's order, and
+    `direction` must be left at its default.  patch and steps are in the view's axes.  flip: config.TEST_FLIP, the average with the map of
+    the left-right mirrored volume (utils.py:15-28, eval.py:461-463).  batch: windows per forward call, 1 .. 8; the result does not depend
+    on it.  A window that overhangs the volume is zero-filled and its prediction cut back to the part inside.  The reference feeds
+    BATCH_SIZE copies of the window and keeps pred[0]; with instance norm the samples of a batch do not see each other, so one copy gives
+    the same result.  The window loop, the views and the flip run inside the library; no permuted copy is made, nothing is read back."""
     who = "saliency_map"
+    if isinstance(net, dict):
+        if direction != "axial":
+            raise ValueError("saliency_map: with a dict of nets the views are the dict's keys; leave direction at its default")
+        names, nets = list(net.keys()), list(net.values())
+    else:
+        names, nets = [direction], [net]
+    if not 1 <= len(nets) <= 3 or any(n not in _lib.SALIENCY_VIEWS for n in names):
+        raise ValueError("saliency_map: the views must be one to three of %s, got %r" % (", ".join(map(repr, _lib.SALIENCY_VIEWS)), names))
+    first = nets[0]
+    if any((n.in_channels, n.num_classes, n._prec) != (first.in_channels, first.num_classes, first._prec) for n in nets):
+        raise ValueError("saliency_map: the nets of a multi-view call must share in_channels, num_classes and precision")
+    if layout not in (None, "CDHW", "DHWC"):
+        raise ValueError("saliency_map: layout must be None, 'CDHW' or 'DHWC', got %r" % (layout,))
     v = _f32(volume, who, "volume")
     if v.dim() == 3:
-        v = v[None]
-    if v.dim() != 4 or v.shape[0] != net.in_channels:
-        raise ValueError("saliency_map: volume must be [%d, D, H, W] or [D, H, W], got %s" % (net.in_channels, tuple(volume.shape)))
+        v = v[None] if layout != "DHWC" else v[..., None]
+    C, K = first.in_channels, first.num_classes
+    if layout == "DHWC":
+        ok, (D, H, W) = v.dim() == 4 and v.shape[3] == C, tuple(v.shape[:3])
+    else:
+        ok, (D, H, W) = v.dim() == 4 and v.shape[0] == C, tuple(v.shape[1:])
+    if not ok:
+        raise ValueError("saliency_map: volume must be [%d, D, H, W] or [D, H, W] (layout='DHWC': [D, H, W, %d]), got %s" % (C, C, tuple(volume.shape)))
     if len(patch) != 3 or len(steps) != 3 or min(steps) < 1 or any(p % 16 or p < 16 for p in patch):
         raise ValueError("saliency_map: patch %s (multiples of 16) / steps %s (>= 1)" % (tuple(patch), tuple(steps)))
-    C, D, H, W = v.shape
-    K = net.num_classes
-    vol = v.permute(1, 2, 3, 0).contiguous()  # [D, H, W, C]: np.rollaxis(image, 0, 4)
-    total = torch.zeros((D, H, W, K), dtype=torch.float32, device=v.device)
-    count = torch.zeros((D, H, W), dtype=torch.int32, device=v.device)
-    crop = torch.empty((1,) + tuple(patch) + (C,), dtype=torch.float32, device=v.device)
+    if any(n.weights.device != v.device for n in nets):
+        raise ValueError("saliency_map: the volume and the nets must be on one device")
+    out = torch.empty((D, H, W, K), dtype=torch.float32, device=v.device)
+    views = (ctypes.c_int32 * len(nets))(*(_lib.SALIENCY_VIEWS[n] for n in names))
+    weights = (ctypes.c_void_p * len(nets))(*(runtime.ptr(n.weights) for n in nets))
+    patch_c, step_c = (ctypes.c_int64 * 3)(*map(int, patch)), (ctypes.c_int64 * 3)(*map(int, steps))
     ctx = _ctx_for(v)
-    lib = _lib.lib()
-    for o0 in window_origins(D, patch[0], steps[0]):
-        for o1 in window_origins(H, patch[1], steps[1]):
-            for o2 in window_origins(W, patch[2], steps[2]):
-                part = vol[o0:o0 + patch[0], o1:o1 + patch[1], o2:o2 + patch[2]]
-                if tuple(part.shape[:3]) != tuple(patch):
-                    crop.zero_()
-                crop[0, :part.shape[0], :part.shape[1], :part.shape[2]] = part
-                p = net.probs(crop)
-                _lib.check(lib.ps_saliency_accumulate(ctx.handle, runtime.ptr(p), patch[0], patch[1], patch[2], K, o0, o1, o2, D, H, W,
-                                                      runtime.ptr(total), runtime.ptr(count)))
-    _lib.check(lib.ps_saliency_finish(ctx.handle, runtime.ptr(total), runtime.ptr(count), D, H, W, K, runtime.ptr(total)))
-    return total
+    fn = _lib.lib().ps_saliency_map
+    _two_call("ps_saliency_map", v.device, lambda scratch, n: fn(
+        ctx.handle, runtime.ptr(v), _lib.PS_VOLUME_DHWC if layout == "DHWC" else _lib.PS_VOLUME_CDHW, C, D, H, W, K, len(nets), views, weights,
+        first.weights.numel(), patch_c, step_c, int(bool(flip)), int(batch), first._prec, runtime.ptr(out), scratch, n))
+    return out
 
 
 # ---- the gradients of the two op wrappers (include/pointseg_saliency_train.h, csrc/conv3d_train.hip, csrc/saliency_train.hip) ---------------------------------------------

@@ -312,21 +312,27 @@ def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch
     return torch.stack(losses)
 
 
-def evaluate_saliency(bank, net, volumes, patch, steps):
-    """EvalCallback / eval_pancreas: per volume c of `volumes`, saliency.saliency_map on bank.whole(c), its argmax, and binary_dice3d
+def evaluate_saliency(bank, net, volumes, patch, steps, direction="axial", flip=False, batch=1):
+    """EvalCallback / eval_pancreas: per volume c of `volumes`, saliency.saliency_map on the bank's image, its argmax, and binary_dice3d
     (utils.py:275-293: (2 s0 + 1e-10) / (s1 + s2 + 1e-10) with s0 = sum(pred * label), s1 = sum(pred), s2 = sum(label)) of the prediction
     against the label.  The three sums come from the device's confusion matrix (metrics.confusion: argmax with ties to the lowest index, as
-    np.argmax): one read of num_classes^2 integers per volume.  net: a SaliencyNet, or a TrainableSaliencyNet (its weights are exported).
-    Returns the list of Dice values (float)."""
+    np.argmax): one read of num_classes^2 integers per volume.  net: a SaliencyNet, or a TrainableSaliencyNet (its weights are exported), or
+    a dict of view name -> either, fused as saliency_map fuses it; direction, flip and batch are saliency_map's.  The image goes in as the
+    bank keeps it, channels last.  Returns the list of Dice values (float)."""
     from . import metrics, saliency
-    if isinstance(net, saliency.TrainableSaliencyNet):
-        net = saliency.SaliencyNet(net.export(), net.in_channels, net.num_classes, device=bank.device.index)
-    K = net.num_classes
+
+    def exported(n):
+        if isinstance(n, saliency.TrainableSaliencyNet):
+            return saliency.SaliencyNet(n.export(), n.in_channels, n.num_classes, device=bank.device.index)
+        return n
+
+    net = {name: exported(n) for name, n in net.items()} if isinstance(net, dict) else exported(net)
+    K = next(iter(net.values())).num_classes if isinstance(net, dict) else net.num_classes
     idx = np.arange(K, dtype=np.int64)
     out = []
     for c in volumes:
-        image, label, _ = bank.whole(c)
-        probs = saliency.saliency_map(image, net, patch, steps)
+        image, label, _, _ = bank._vols[c]
+        probs = saliency.saliency_map(image, net, patch, steps, direction=direction, flip=flip, batch=batch, layout="DHWC")
         cm = metrics.confusion(probs, label, K).cpu().numpy()  # rows truth, columns prediction
         s0 = int((cm * np.outer(idx, idx)).sum())
         s1, s2 = int((cm.sum(0) * idx).sum()), int((cm.sum(1) * idx).sum())
