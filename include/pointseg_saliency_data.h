@@ -14,8 +14,8 @@
  *                                      -- and BatchData.get_data's reject loop (data_sampler.py:77-88, config.DATA_SAMPLING)
  *
  * A prepared volume is channels-last, so that a patch row is one contiguous run: image f32 [d, h, w, C], label u8 [d, h, w], weight u8
- * [d, h, w] (0 / 1).  Mixed batches (config.MIXUP) are pointseg_saliency_mixup.h's.  Not built: a DIRECTION other than axial (permute
- * before preparing), the left-right flip.
+ * [d, h, w] (0 / 1).  Mixed batches (config.MIXUP) are pointseg_saliency_mixup.h's; a DIRECTION other than axial and the left-right
+ * flip are pointseg_saliency_view.h's, whose PS_VIEW_AXIAL, flip = NULL call ps_patch_sample is.
  */
 #ifndef POINTSEG_SALIENCY_DATA_H
 #define POINTSEG_SALIENCY_DATA_H

@@ -5,7 +5,8 @@ The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (P
 (SALIENCY_PROTOTYPES), include/pointseg_saliency_train.h (SALIENCY_TRAIN_PROTOTYPES), include/pointseg_saliency_attention.h
 (SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
 (SALIENCY_STEP_PROTOTYPES), include/pointseg_saliency_step_precision.h (SALIENCY_STEP_PRECISION_PROTOTYPES) and
-include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES) and include/pointseg_saliency_map.h (SALIENCY_MAP_PROTOTYPES).
+include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES), include/pointseg_saliency_map.h (SALIENCY_MAP_PROTOTYPES) and
+include/pointseg_saliency_view.h (SALIENCY_VIEW_PROTOTYPES).
 The library is built in-tree by compile_op.sh (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -391,6 +392,13 @@ SALIENCY_MAP_PROTOTYPES = {
                                        c_i64p] + [ctypes.c_int32] * 3 + [c_vp, c_vp, c_i64p]),
 }
 
+# every symbol include/pointseg_saliency_view.h declares (the two patch samplers through an anatomical view, with the per-sample flip;
+# csrc/saliency_data.hip): the arguments of the entries they extend, with view and flip in front of the outputs
+SALIENCY_VIEW_PROTOTYPES = {
+    "ps_patch_sample_view": (ctypes.c_int, SALIENCY_DATA_PROTOTYPES["ps_patch_sample"][1][:-4] + [ctypes.c_int32, c_i32p] + [c_vp] * 4),
+    "ps_patch_sample_mixup_view": (ctypes.c_int, SALIENCY_MIXUP_PROTOTYPES["ps_patch_sample_mixup"][1][:-4] + [ctypes.c_int32, c_i32p] + [c_vp] * 4),
+}
+
 _lib = None
 
 
@@ -415,7 +423,8 @@ def lib():
                                   + list(SALIENCY_TRAIN_PROTOTYPES.items()) + list(SALIENCY_TRAIN_PRECISION_PROTOTYPES.items())
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())
-                                  + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items()) + list(SALIENCY_MAP_PROTOTYPES.items())):
+                                  + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items()) + list(SALIENCY_MAP_PROTOTYPES.items())
+                                  + list(SALIENCY_VIEW_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -16,6 +16,13 @@
 // Mixed batches (config.MIXUP, include/pointseg_saliency_mixup.h; tests/saliency_mixup_ref.py restates the rule): the same table and the same
 // count over B + 1 drawn samples, and a gather that reads the two source windows of every output piece through the plain gather's paths,
 // mixes them (two products and a sum, each rounded) and stores once -- images, the or of the weights, and the soft one-hot rows.
+//
+// Views and the flip (config.DIRECTION and sampler3d's np.flip, include/pointseg_saliency_view.h; tests/saliency_view_ref.py restates the
+// rule): the table (saliency_sampler_plan.h) derives every candidate on the VIEW's extents and keeps its box in view and in volume axes;
+// the count walks the volume-axes box as before.  The axial and coronal views' rows run along the volume's W: the two gathers above with a
+// compile-time policy on the source index.  The sagittal view's rows run along H: one gather of its own through saliency_view.h's LDS
+// tile, plain or mixed.  A drawn sample's flip is a bit of its table entries: the gathers read the mirrored element.  No permuted or
+// mirrored copy of a volume is made.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -24,11 +31,14 @@
 #include "common.h"
 #include "reduce_partials.h"
 #include "sample_hash.h"
+#include "saliency_sampler_plan.h"
+#include "saliency_view.h"
 #include "scratch.h"
 #include "wave_ops.h"
 
 #include "../../include/pointseg_saliency_data.h"
 #include "../../include/pointseg_saliency_mixup.h"
+#include "../../include/pointseg_saliency_view.h"
 
 namespace ps {
 
@@ -186,20 +196,22 @@ __global__ __launch_bounds__(256) void pancreas_prepare_kernel(const T* __restri
 
 // ---- the sampler ---------------------------------------------------------------------------------------------------------------------------
 
-// candidate (slot b, try t), host-filled: the window of the rule, as the kernels need it
+// candidate (slot b, try t), host-filled (saliency_sampler_plan.h): the window of the rule, as the kernels need it.  The patch side is in
+// VIEW axes, the volume side in VOLUME axes [d, h, w]; with the axial view the two are the same.
 struct PatchCand {
     const float* img;
     const uint8_t* lab;
     const uint8_t* wgt;
-    int dim[3];   // the volume's extents
-    int c[3];     // the centre
-    int src[3];   // c - r0: the box's first voxel in the volume
-    int lo[3];    // out / 2 - r0: the box's first voxel in the patch
-    int n[3];     // r0 + r1: the box's extents (0 is possible: a patch of extent 1 centred on `in`)
+    int dim[3];   // the volume's extents (volume axes)
+    int c[3];     // the centre (view axes)
+    int src[3];   // the box's first voxel in the volume (volume axes)
+    int vn[3];    // the box's extents (volume axes): what the count walks
+    int lo[3];    // out / 2 - r0: the box's first voxel in the patch (view axes)
+    int n[3];     // r0 + r1: the box's extents (view axes; 0 is possible: a patch of extent 1 centred on `in`)
     unsigned s_fill;
     int vol;
     int count;    // its index in the counts, -1: never asked for
-    int pad;
+    int flip;     // the drawn sample's flip bit: its patch is written mirrored along the view's last axis
 };
 
 struct PatchShape {
@@ -223,14 +235,15 @@ __device__ __forceinline__ unsigned count_word(uintptr_t q, uintptr_t a, uintptr
     return n;
 }
 
-// Launch 1.  grid (blocks of 2048 words, windows); a window's rows are kdw words each (the most a row of P2 bytes can touch).
+// Launch 1.  grid (blocks of 2048 words, windows); a window's rows -- along the volume's W, over the box in volume axes: a box is the same
+// set of voxels in any view -- are kdw words each (the most a row of the patch's extent along W can touch).
 __global__ __launch_bounds__(256) void patch_count_kernel(const PatchCand* __restrict__ cands, const int* __restrict__ win, unsigned* __restrict__ counts,
                                                           unsigned kdw)
 {
     const PatchCand& cd = cands[win[blockIdx.y]];
-    const unsigned rows = (unsigned)cd.n[0] * (unsigned)cd.n[1], total = rows * kdw;
+    const unsigned rows = (unsigned)cd.vn[0] * (unsigned)cd.vn[1], total = rows * kdw;
     const unsigned i0 = blockIdx.x * 2048u;
-    if (i0 >= total || cd.n[2] == 0) return;
+    if (i0 >= total || cd.vn[2] == 0) return;
     const uintptr_t base = reinterpret_cast<uintptr_t>(cd.lab);
     const uintptr_t end = base + (size_t)cd.dim[0] * cd.dim[1] * cd.dim[2];
     unsigned n = 0;
@@ -239,9 +252,9 @@ __global__ __launch_bounds__(256) void patch_count_kernel(const PatchCand* __res
         const unsigned i = i0 + u * 256u + threadIdx.x;
         if (i < total) {
             const unsigned row = i / kdw, k = i - row * kdw;
-            const unsigned y = row % (unsigned)cd.n[1], z = row / (unsigned)cd.n[1];
+            const unsigned y = row % (unsigned)cd.vn[1], z = row / (unsigned)cd.vn[1];
             const uintptr_t a = base + ((size_t)(cd.src[0] + z) * cd.dim[1] + (cd.src[1] + y)) * cd.dim[2] + cd.src[2];
-            n += count_word((a & ~(uintptr_t)3) + 4 * (uintptr_t)k, a, a + cd.n[2], base, end);
+            n += count_word((a & ~(uintptr_t)3) + 4 * (uintptr_t)k, a, a + cd.vn[2], base, end);
         }
     }
     n = (unsigned)wave_sum((int)n);
@@ -263,40 +276,66 @@ __device__ __forceinline__ int choose_try(const PatchCand* __restrict__ cands, c
 
 __device__ __forceinline__ float fill_value(unsigned j, unsigned s_fill) { return (float)(point_hash(j, s_fill) >> 8) * 0x1p-24f; }
 
-// element j of a slot's [P0, P1, P2, C] patch
+// voxel (u0, u1, u2) of the copied box, counted in VIEW axes from the box's first voxel: its index in the volume
+template <int VIEW>
+__device__ __forceinline__ size_t box_voxel(const PatchCand& cd, unsigned u0, unsigned u1, unsigned u2)
+{
+    int d, h, w;
+    to_volume<VIEW>((int)u0, (int)u1, (int)u2, d, h, w);
+    return ((size_t)(cd.src[0] + d) * cd.dim[1] + (cd.src[1] + h)) * cd.dim[2] + (cd.src[2] + w);
+}
+
+// element j of a slot's [P0, P1, P2, C] patch.  A flipped sample's element (.., k, c) is the unflipped one's (.., P2 - 1 - k, c), its fill
+// included: the fill is keyed by the index before the flip.
+template <int VIEW>
 __device__ __forceinline__ float image_element(const PatchCand& cd, const PatchShape& sh, unsigned j)
 {
     const unsigned c = j % (unsigned)sh.C, v = j / (unsigned)sh.C;
-    const unsigned p2 = v % (unsigned)sh.P[2], r = v / (unsigned)sh.P[2];
+    unsigned p2 = v % (unsigned)sh.P[2];
+    const unsigned r = v / (unsigned)sh.P[2];
+    if (cd.flip) {
+        p2 = (unsigned)sh.P[2] - 1u - p2;
+        j = (r * (unsigned)sh.P[2] + p2) * (unsigned)sh.C + c;
+    }
     const unsigned u0 = r / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = r % (unsigned)sh.P[1] - (unsigned)cd.lo[1], u2 = p2 - (unsigned)cd.lo[2];
-    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2])
-        return cd.img[(((size_t)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + (cd.src[2] + u2)) * sh.C + c];
+    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2]) return cd.img[box_voxel<VIEW>(cd, u0, u1, u2) * sh.C + c];
     return fill_value(j, cd.s_fill);
 }
 
 // voxel v of a slot's [P0, P1, P2] patch: its index in the volume, or -1 outside the copied box
+template <int VIEW>
 __device__ __forceinline__ long long voxel_source(const PatchCand& cd, const PatchShape& sh, unsigned v)
 {
-    const unsigned p2 = v % (unsigned)sh.P[2], r = v / (unsigned)sh.P[2];
+    unsigned p2 = v % (unsigned)sh.P[2];
+    const unsigned r = v / (unsigned)sh.P[2];
+    if (cd.flip) p2 = (unsigned)sh.P[2] - 1u - p2;
     const unsigned u0 = r / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = r % (unsigned)sh.P[1] - (unsigned)cd.lo[1], u2 = p2 - (unsigned)cd.lo[2];
-    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2])
-        return ((long long)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + (cd.src[2] + u2);
+    if (u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1] && u2 < (unsigned)cd.n[2]) return (long long)box_voxel<VIEW>(cd, u0, u1, u2);
     return -1;
 }
 
-// four image elements from e0 on (e0 % 4 == 0), of the batch's E; ROW4: P2 * C % 4 == 0, the four share a row of one slot
-template <bool ROW4>
+// four image elements from e0 on (e0 % 4 == 0), of the batch's E; ROW4: P2 * C % 4 == 0, the four share a row of one slot.  VIEW is axial
+// or coronal: the view's last axis is the volume's W, a patch row is one run of the source.  (A flipped sample keeps the row path where
+// C % 4 == 0 -- the four are one voxel's channels -- and goes element by element elsewhere.)
+template <bool ROW4, int VIEW>
 __device__ __forceinline__ void image_quad(const PatchCand* s_c, const PatchShape& sh, unsigned L, size_t e0, size_t E, float (&o)[4])
 {
-    if (ROW4) {
-        const unsigned b = (unsigned)(e0 / L), j = (unsigned)(e0 - (size_t)b * L);
+    const unsigned b = (unsigned)(e0 / L);
+    if (ROW4 && (!s_c[b].flip || (sh.C & 3) == 0)) {
+        unsigned j = (unsigned)(e0 - (size_t)b * L);
         const PatchCand& cd = s_c[b];
-        const unsigned rowlen = (unsigned)sh.P[2] * (unsigned)sh.C, row = j / rowlen, col = j - row * rowlen;
+        const unsigned rowlen = (unsigned)sh.P[2] * (unsigned)sh.C, row = j / rowlen;
+        unsigned col = j - row * rowlen;
+        if (cd.flip) {
+            const unsigned k = col / (unsigned)sh.C;
+            col = ((unsigned)sh.P[2] - 1u - k) * (unsigned)sh.C + (col - k * (unsigned)sh.C);
+            j = row * rowlen + col;
+        }
         const unsigned u0 = row / (unsigned)sh.P[1] - (unsigned)cd.lo[0], u1 = row % (unsigned)sh.P[1] - (unsigned)cd.lo[1];
         const unsigned lo = (unsigned)cd.lo[2] * (unsigned)sh.C, hi = lo + (unsigned)cd.n[2] * (unsigned)sh.C;
         const bool row_in = u0 < (unsigned)cd.n[0] && u1 < (unsigned)cd.n[1];
         if (row_in && col >= lo && col + 4 <= hi) {  // four consecutive floats of the source: at the alignment that address has
-            const float* p = cd.img + (((size_t)(cd.src[0] + u0) * cd.dim[1] + (cd.src[1] + u1)) * cd.dim[2] + cd.src[2]) * sh.C + (col - lo);
+            const float* p = cd.img + box_voxel<VIEW>(cd, u0, u1, 0) * sh.C + (col - lo);
             const uintptr_t a = reinterpret_cast<uintptr_t>(p);
             if ((a & 15) == 0) {
                 const float4 f = *reinterpret_cast<const float4*>(p);
@@ -321,13 +360,14 @@ __device__ __forceinline__ void image_quad(const PatchCand* s_c, const PatchShap
         const size_t e = e0 + k;
         o[k] = 0.f;
         if (e < E) {
-            const unsigned b = (unsigned)(e / L);
-            o[k] = image_element(s_c[b], sh, (unsigned)(e - (size_t)b * L));
+            const unsigned be = (unsigned)(e / L);
+            o[k] = image_element<VIEW>(s_c[be], sh, (unsigned)(e - (size_t)be * L));
         }
     }
 }
 
 // labels and weights of four voxels from e0 on (e0 % 4 == 0), of the batch's E = slots * V; zeros outside the copied boxes and past E
+template <int VIEW>
 __device__ __forceinline__ void voxel_quad(const PatchCand* s_c, const PatchShape& sh, unsigned V, size_t e0, size_t E, int (&l)[4], float (&w)[4])
 {
 #pragma unroll
@@ -335,9 +375,11 @@ __device__ __forceinline__ void voxel_quad(const PatchCand* s_c, const PatchShap
     if ((sh.P[2] & 3) == 0) {  // the four voxels share a row of one slot: one word each where the box holds them all and the bytes are aligned
         const unsigned b = (unsigned)(e0 / V), v = (unsigned)(e0 - (size_t)b * V);
         const PatchCand& cd = s_c[b];
-        const long long s0 = voxel_source(cd, sh, v), s3 = voxel_source(cd, sh, v + 3);
-        if (s0 >= 0 && s3 >= 0 && ((reinterpret_cast<uintptr_t>(cd.lab + s0) | reinterpret_cast<uintptr_t>(cd.wgt + s0)) & 3) == 0) {
-            const unsigned x = *reinterpret_cast<const unsigned*>(cd.lab + s0), y = *reinterpret_cast<const unsigned*>(cd.wgt + s0);
+        const long long s0 = voxel_source<VIEW>(cd, sh, v), s3 = voxel_source<VIEW>(cd, sh, v + 3);
+        const long long sl = cd.flip ? s3 : s0;  // (a flipped sample's four lie the other way round)
+        if (s0 >= 0 && s3 >= 0 && ((reinterpret_cast<uintptr_t>(cd.lab + sl) | reinterpret_cast<uintptr_t>(cd.wgt + sl)) & 3) == 0) {
+            unsigned x = *reinterpret_cast<const unsigned*>(cd.lab + sl), y = *reinterpret_cast<const unsigned*>(cd.wgt + sl);
+            if (cd.flip) x = __builtin_bswap32(x), y = __builtin_bswap32(y);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 l[k] = (int)((x >> (8 * k)) & 255u);
@@ -352,7 +394,7 @@ __device__ __forceinline__ void voxel_quad(const PatchCand* s_c, const PatchShap
         if (e >= E) break;
         const unsigned b = (unsigned)(e / V);
         const PatchCand& cd = s_c[b];
-        const long long s = voxel_source(cd, sh, (unsigned)(e - (size_t)b * V));
+        const long long s = voxel_source<VIEW>(cd, sh, (unsigned)(e - (size_t)b * V));
         if (s >= 0) {
             l[k] = cd.lab[s];
             w[k] = (float)cd.wgt[s];
@@ -362,7 +404,7 @@ __device__ __forceinline__ void voxel_quad(const PatchCand* s_c, const PatchShap
 
 // Launch 2.  Workgroups [0, img_blocks) write 1024 quads of images each, the rest 1024 quads of labels and weights; workgroup 0 also
 // writes info.  vec_i / vec_v: the image / the label and weight outputs are 16-byte aligned.
-template <bool ROW4>
+template <bool ROW4, int VIEW>
 __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts, PatchShape sh,
                                                            unsigned img_blocks, bool vec_i, bool vec_v, float* __restrict__ out_i,
                                                            float* __restrict__ out_w, int32_t* __restrict__ out_l, int32_t* __restrict__ info)
@@ -379,7 +421,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __re
         s_c[t] = cd;
         if (blockIdx.x == 0) {
             int32_t* r = info + 8 * t;
-            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = 0;
+            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = cd.flip;
         }
     }
     __syncthreads();
@@ -391,7 +433,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __re
             const size_t e0 = 4 * ((size_t)blockIdx.x * 1024 + u * 256 + t);
             if (e0 >= E) break;
             float o[4];
-            image_quad<ROW4>(s_c, sh, L, e0, E, o);
+            image_quad<ROW4, VIEW>(s_c, sh, L, e0, E, o);
             if (vec_i && e0 + 4 <= E) {
                 *reinterpret_cast<float4*>(out_i + e0) = make_float4(o[0], o[1], o[2], o[3]);
             } else {
@@ -407,7 +449,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const PatchCand* __re
         if (e0 >= E) break;
         int l[4];
         float w[4];
-        voxel_quad(s_c, sh, V, e0, E, l, w);
+        voxel_quad<VIEW>(s_c, sh, V, e0, E, l, w);
         if (vec_v && e0 + 4 <= E) {
             *reinterpret_cast<int4*>(out_l + e0) = make_int4(l[0], l[1], l[2], l[3]);
             *reinterpret_cast<float4*>(out_w + e0) = make_float4(w[0], w[1], w[2], w[3]);
@@ -457,7 +499,7 @@ __device__ __forceinline__ float mix_class(float2 gh, int l1, int l2, int c) { r
 // (float32(gamma_b), float32(1 - gamma_b)).  The soft rows are written along K: two rows in one 16-byte store for K == 2, 16 bytes at a
 // time for K % 4 == 0 (both where out_s is 16-byte aligned: al_s >= 16), 8 bytes for another even K (al_s >= 8), floats elsewhere.
 // (__launch_bounds__(256, 8): the plain gather's 8 waves per SIMD -- 63 registers, nothing spilled; left alone the compiler takes 68.)
-template <bool ROW4>
+template <bool ROW4, int VIEW>
 __global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts,
                                                         const float2* __restrict__ gh, PatchShape sh, int K, unsigned img_blocks, bool vec_i, bool vec_w,
                                                         int al_s, float* __restrict__ out_i, float* __restrict__ out_w, float* __restrict__ out_s,
@@ -477,7 +519,7 @@ __global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __re
         if (t < sh.B) s_g[t] = gh[t];
         if (blockIdx.x == 0) {
             int32_t* r = info + 8 * t;
-            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = 0;
+            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = cd.flip;
         }
     }
     __syncthreads();
@@ -490,8 +532,8 @@ __global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __re
             if (e0 >= E) break;
             float a[4], b[4], o[4];
             unsigned slot[4];
-            image_quad<ROW4>(s_c, sh, L, e0, E, a);
-            image_quad<ROW4>(s_c + 1, sh, L, e0, E, b);
+            image_quad<ROW4, VIEW>(s_c, sh, L, e0, E, a);
+            image_quad<ROW4, VIEW>(s_c + 1, sh, L, e0, E, b);
             quad_slots(e0, L, ROW4, (unsigned)sh.B - 1, slot);
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = mix(s_g[slot[k]], a[k], b[k]);
@@ -514,10 +556,10 @@ __global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __re
         {
             int l[4];
             float w[4];
-            voxel_quad(s_c, sh, V, e0, E, l, w);
+            voxel_quad<VIEW>(s_c, sh, V, e0, E, l, w);
 #pragma unroll
             for (int k = 0; k < 4; ++k) lp1 |= (unsigned)l[k] << (8 * k), wm |= (w[k] != 0.f ? 1u : 0u) << k;
-            voxel_quad(s_c + 1, sh, V, e0, E, l, w);
+            voxel_quad<VIEW>(s_c + 1, sh, V, e0, E, l, w);
 #pragma unroll
             for (int k = 0; k < 4; ++k) lp2 |= (unsigned)l[k] << (8 * k), wm |= (w[k] != 0.f ? 1u : 0u) << k;
         }
@@ -557,6 +599,172 @@ __global__ __launch_bounds__(256, 8) void patch_mix_kernel(const PatchCand* __re
             } else {
                 for (int c = 0; c < K; ++c) o[c] = mix_class(g, l1, l2, c);
             }
+        }
+    }
+}
+
+// ---- the sagittal gather (include/pointseg_saliency_view.h) --------------------------------------------------------------------
+// patch[i, j, k, c] = vol[d = j, h = k, w = i, c]: the patch's rows run along the volume's H, whose stride is W * C floats.  A workgroup
+// owns one (slot b, view row j) and a tile of TW view-i by 32 view-k OUTPUT voxels; grid (b * P1 + j, tiles along i, tiles along k).  The
+// volume side is read in rows along W into an LDS tile of odd pitch (saliency_view.h), the patch side is written in rows along k.  What
+// lies outside the copied box is never staged: the write side takes the fill hash of the element's patch index (before the flip) there.
+// A flipped sample's tile holds source k in [P2 - k1, P2 - k0) for the output's [k0, k1).  MIX: both drawn samples of slot b are staged,
+// each with its own box and flip, mixed by mix() / mix_class() and stored once.  Labels and weights then go through the same tile, a voxel
+// packed as label | weight << 8.  vec_i / vec_v: 16-byte stores of images / of labels and weights (the rows' lengths and the outputs'
+// addresses allow them); the soft rows are written as floats, consecutive lanes on consecutive addresses.
+
+// the tile's source range along k of one sample, and whether row j of the patch meets its box
+struct SagittalRow {
+    int ks0;
+    bool in;
+};
+
+template <bool MIX>
+__global__ __launch_bounds__(256) void patch_gather_sagittal_kernel(const PatchCand* __restrict__ cands, const unsigned* __restrict__ counts,
+                                                                    const float2* __restrict__ gh, PatchShape sh, int K, int TW, bool vec_i, bool vec_v,
+                                                                    float* __restrict__ out_i, float* __restrict__ out_w, int32_t* __restrict__ out_l,
+                                                                    float* __restrict__ out_s, int32_t* __restrict__ info)
+{
+    constexpr int NS = MIX ? 2 : 1;
+    __shared__ float tile[NS][kTileH * (kTileFloats + 1)];
+    __shared__ PatchCand s_c[NS];
+    __shared__ float2 s_g;
+    const int t = threadIdx.x;
+    const int P0 = sh.P[0], P1 = sh.P[1], P2 = sh.P[2], C = sh.C;
+    const int b = (int)(blockIdx.x / (unsigned)P1), j = (int)(blockIdx.x - (unsigned)b * (unsigned)P1);
+    const int i0 = blockIdx.y * TW, k0 = blockIdx.z * kTileH, k1 = min(k0 + kTileH, P2);
+    bool pos0 = false;
+    if (sh.mode == PS_PATCH_ONE_POSITIVE && t < sh.B - 1) pos0 = counts[cands[t * sh.T].count] > 0;
+    const bool any_earlier = __syncthreads_or(pos0) != 0;
+    if (t < sh.B + (MIX ? 1 : 0)) {
+        int ok;
+        const int tr = MIX ? choose_try_mixup(cands, counts, sh, t, any_earlier, ok) : choose_try(cands, counts, sh, t, any_earlier, ok);
+        const PatchCand cd = cands[t * sh.T + tr];
+        if (t == b) s_c[0] = cd;
+        if (MIX && t == b + 1) s_c[NS - 1] = cd;
+        if (MIX && t == b) s_g = gh[b];
+        if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+            int32_t* r = info + 8 * t;
+            r[0] = tr, r[1] = cd.vol, r[2] = cd.c[0], r[3] = cd.c[1], r[4] = cd.c[2], r[5] = (int32_t)counts[cd.count], r[6] = ok, r[7] = cd.flip;
+        }
+    }
+    __syncthreads();
+    SagittalRow row[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        row[s].ks0 = s_c[s].flip ? P2 - k1 : k0;
+        row[s].in = (unsigned)j - (unsigned)s_c[s].lo[1] < (unsigned)s_c[s].n[1];
+    }
+    const float2 g = MIX ? s_g : make_float2(1.f, 0.f);
+
+    // ---- images: stage (rows along W) ...
+    const int rowf = TW * C, S = rowf | 1;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const PatchCand& cd = s_c[s];
+        if (!row[s].in) continue;
+        const unsigned u1 = (unsigned)j - (unsigned)cd.lo[1];
+        for (int r = t; r < kTileH * rowf; r += 256) {
+            const int kk = r / rowf, rem = r - kk * rowf, ii = rem / C, c = rem - ii * C;
+            const unsigned u0 = (unsigned)(i0 + ii) - (unsigned)cd.lo[0], u2 = (unsigned)(row[s].ks0 + kk) - (unsigned)cd.lo[2];
+            if (u0 < (unsigned)cd.n[0] && u2 < (unsigned)cd.n[2]) tile[s][kk * S + ii * C + c] = cd.img[box_voxel<kViewSagittal>(cd, u0, u1, u2) * C + c];
+        }
+    }
+    __syncthreads();
+    // ... and write (rows along k).  element (i0 + ii, j, ko, c) of sample s: staged inside its box, the fill outside
+    auto image_at = [&](int s, int ii, int ko, int c) -> float {
+        const PatchCand& cd = s_c[s];
+        const int ks = cd.flip ? P2 - 1 - ko : ko;
+        const unsigned u0 = (unsigned)(i0 + ii) - (unsigned)cd.lo[0], u2 = (unsigned)ks - (unsigned)cd.lo[2];
+        if (row[s].in && u0 < (unsigned)cd.n[0] && u2 < (unsigned)cd.n[2]) return tile[s][(ks - row[s].ks0) * S + ii * C + c];
+        return fill_value((((unsigned)(i0 + ii) * (unsigned)P1 + (unsigned)j) * (unsigned)P2 + (unsigned)ks) * (unsigned)C + (unsigned)c, cd.s_fill);
+    };
+    auto image_out = [&](int ii, int ko, int c) -> float {
+        const float a = image_at(0, ii, ko, c);
+        return MIX ? mix(g, a, image_at(NS - 1, ii, ko, c)) : a;
+    };
+    const int runf = kTileH * C, nkf = (k1 - k0) * C;  // floats of one i's run over (k, c): of a whole tile, of this one
+    if (vec_i) {
+        for (int r = t; r < TW * (runf / 4); r += 256) {
+            const int ii = r / (runf / 4), q0 = (r - ii * (runf / 4)) * 4;
+            if (i0 + ii >= P0 || q0 >= nkf) continue;  // nkf is a multiple of 4: a unit is inside or outside as a whole
+            float v[4];
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int kk = (q0 + n) / C, c = (q0 + n) - kk * C;
+                v[n] = image_out(ii, k0 + kk, c);
+            }
+            float* dst = out_i + ((((size_t)b * P0 + i0 + ii) * P1 + j) * P2 + k0) * C + q0;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    } else {
+        for (int r = t; r < TW * runf; r += 256) {
+            const int ii = r / runf, q = r - ii * runf;
+            if (i0 + ii >= P0 || q >= nkf) continue;
+            const int kk = q / C, c = q - kk * C;
+            out_i[((((size_t)b * P0 + i0 + ii) * P1 + j) * P2 + k0) * C + q] = image_out(ii, k0 + kk, c);
+        }
+    }
+    __syncthreads();
+
+    // ---- labels and weights through the same tile: label | weight << 8 per voxel, pitch TW | 1
+    const int SV = TW | 1;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const PatchCand& cd = s_c[s];
+        if (!row[s].in) continue;
+        const unsigned u1 = (unsigned)j - (unsigned)cd.lo[1];
+        unsigned* tv = reinterpret_cast<unsigned*>(tile[s]);
+        for (int r = t; r < kTileH * TW; r += 256) {
+            const int kk = r / TW, ii = r - kk * TW;
+            const unsigned u0 = (unsigned)(i0 + ii) - (unsigned)cd.lo[0], u2 = (unsigned)(row[s].ks0 + kk) - (unsigned)cd.lo[2];
+            if (u0 < (unsigned)cd.n[0] && u2 < (unsigned)cd.n[2]) {
+                const size_t v = box_voxel<kViewSagittal>(cd, u0, u1, u2);
+                tv[kk * SV + ii] = (unsigned)cd.lab[v] | (unsigned)cd.wgt[v] << 8;
+            }
+        }
+    }
+    __syncthreads();
+    auto voxel_at = [&](int s, int ii, int ko) -> unsigned {  // 0 outside the copied box: label 0, weight 0
+        const PatchCand& cd = s_c[s];
+        const int ks = cd.flip ? P2 - 1 - ko : ko;
+        const unsigned u0 = (unsigned)(i0 + ii) - (unsigned)cd.lo[0], u2 = (unsigned)ks - (unsigned)cd.lo[2];
+        if (row[s].in && u0 < (unsigned)cd.n[0] && u2 < (unsigned)cd.n[2]) return reinterpret_cast<const unsigned*>(tile[s])[(ks - row[s].ks0) * SV + ii];
+        return 0u;
+    };
+    auto weight_out = [&](int ii, int ko) -> float {  // the drawn sample's weight, or the or of the two
+        unsigned w = voxel_at(0, ii, ko) >> 8;
+        if (MIX) return (w | voxel_at(NS - 1, ii, ko) >> 8) != 0u ? 1.f : 0.f;
+        return (float)w;
+    };
+    const int nk = k1 - k0;
+    if (vec_v) {
+        for (int r = t; r < TW * (kTileH / 4); r += 256) {
+            const int ii = r / (kTileH / 4), q0 = (r - ii * (kTileH / 4)) * 4;
+            if (i0 + ii >= P0 || q0 >= nk) continue;  // P2 % 4 == 0: a unit is inside or outside as a whole
+            const size_t at = (((size_t)b * P0 + i0 + ii) * P1 + j) * P2 + k0 + q0;
+            *reinterpret_cast<float4*>(out_w + at) =
+                make_float4(weight_out(ii, k0 + q0), weight_out(ii, k0 + q0 + 1), weight_out(ii, k0 + q0 + 2), weight_out(ii, k0 + q0 + 3));
+            if (!MIX)
+                *reinterpret_cast<int4*>(out_l + at) = make_int4((int)(voxel_at(0, ii, k0 + q0) & 255u), (int)(voxel_at(0, ii, k0 + q0 + 1) & 255u),
+                                                                 (int)(voxel_at(0, ii, k0 + q0 + 2) & 255u), (int)(voxel_at(0, ii, k0 + q0 + 3) & 255u));
+        }
+    } else {
+        for (int r = t; r < TW * kTileH; r += 256) {
+            const int ii = r / kTileH, kk = r - ii * kTileH;
+            if (i0 + ii >= P0 || kk >= nk) continue;
+            const size_t at = (((size_t)b * P0 + i0 + ii) * P1 + j) * P2 + k0 + kk;
+            out_w[at] = weight_out(ii, k0 + kk);
+            if (!MIX) out_l[at] = (int)(voxel_at(0, ii, k0 + kk) & 255u);
+        }
+    }
+    if (MIX) {  // the soft rows, [.., k, K]: one run of nk * K floats per i
+        const int runs = kTileH * K;
+        for (int r = t; r < TW * runs; r += 256) {
+            const int ii = r / runs, q = r - ii * runs, kk = q / K, cls = q - kk * K;
+            if (i0 + ii >= P0 || kk >= nk) continue;
+            const int l1 = (int)(voxel_at(0, ii, k0 + kk) & 255u), l2 = (int)(voxel_at(NS - 1, ii, k0 + kk) & 255u);
+            out_s[((((size_t)b * P0 + i0 + ii) * P1 + j) * P2 + k0) * K + q] = mix_class(g, l1, l2, cls);
         }
     }
 }
@@ -602,8 +810,10 @@ struct SamplerBlob {
     int windows;
 };
 
+// view: the PS_VIEW_* value P is given in; flip: one 0 / 1 per row, or NULL
 inline void sampler_table(SamplerBlob& bl, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
-                          const int32_t* cand, int rows, int T, const int64_t* P, uint32_t seed, int mode, int forced, size_t extra_bytes)
+                          const int32_t* cand, int rows, int T, const int64_t* P, uint32_t seed, int mode, int forced, size_t extra_bytes, int view,
+                          const int32_t* flip)
 {
     const int nc = rows * T;
     std::vector<int> win;
@@ -618,18 +828,16 @@ inline void sampler_table(SamplerBlob& bl, const float* const* images, const uin
             const int v = cand[b * T + t];
             const unsigned s = hash32(seed + kSeedMul * (unsigned)(b * T + t + 1));
             cd.img = images[v], cd.lab = labels[v], cd.wgt = weights[v];
+            const unsigned h[3] = {hash32(s + kAxisMul * 1u), hash32(s + kAxisMul * 2u), hash32(s + kAxisMul * 3u)};
+            SamplerBox bx;
+            sampler_box(view, dims + 3 * v, P, h, bx);
             for (int a = 0; a < 3; ++a) {
-                const int in = (int)dims[3 * v + a], out = (int)P[a];
-                const int x0 = out / 2, x1 = in - x0;
-                int ctr;
-                if (x1 <= x0) ctr = (x0 + x1) / 2;
-                else ctr = x0 + (int)(((unsigned long long)hash32(s + kAxisMul * (unsigned)(a + 1)) * (unsigned long long)(x1 - x0 + 1)) >> 32);
-                const int r0 = std::min(out / 2, ctr), r1 = std::min(out - out / 2, in - ctr);
-                cd.dim[a] = in, cd.c[a] = ctr, cd.src[a] = ctr - r0, cd.lo[a] = out / 2 - r0, cd.n[a] = r0 + r1;
+                cd.dim[a] = (int)dims[3 * v + a], cd.src[a] = bx.vsrc[a], cd.vn[a] = bx.vn[a];
+                cd.c[a] = bx.c[a], cd.lo[a] = bx.lo[a], cd.n[a] = bx.n[a];
             }
             cd.s_fill = hash32(s + kAxisMul * 4u);
             cd.vol = v;
-            cd.pad = 0;
+            cd.flip = flip ? flip[b] : 0;
             const bool counted = t == 0 || mode == PS_PATCH_ALL_POSITIVE || (mode == PS_PATCH_ONE_POSITIVE && b == forced);
             cd.count = counted ? (int)win.size() : -1;
             if (counted) win.push_back(b * T + t);
@@ -638,7 +846,8 @@ inline void sampler_table(SamplerBlob& bl, const float* const* images, const uin
     bl.windows = (int)win.size();
 }
 
-// the blob into the context's arena, and launch 1 over its windows; d_tab: where it lies on the device
+// the blob into the context's arena, and launch 1 over its windows; d_tab: where it lies on the device.  P: the patch as the VOLUME's
+// axes see it (sampler_patch_in_volume)
 inline int sampler_count(ps_context* c, const SamplerBlob& bl, const int64_t* P, char*& d_tab)
 {
     hipStream_t st = c->stream;
@@ -774,20 +983,69 @@ extern "C" int ps_saliency_pancreas_prepare(ps_context* c, const void* ct, int32
 }
 
 
-extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
-                               int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode,
-                               float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+namespace ps {
+
+namespace {
+
+// what the view entries check on top of the old ones: the view, the flip bits (one per drawn sample), the sagittal gather's grid
+inline int sampler_view_ok(const char* who, int32_t view, const int32_t* flip, int rows, int32_t B, int32_t C, const int64_t* P)
 {
-    const char* who = "ps_patch_sample";
+    PS_CHECK(view >= PS_VIEW_AXIAL && view <= PS_VIEW_CORONAL, "%s: view = %d, must be a PS_VIEW_* value (0, 1, 2)", who, (int)view);
+    for (int i = 0; flip && i < rows; ++i) PS_CHECK(flip[i] == 0 || flip[i] == 1, "%s: flip[%d] = %d, must be 0 or 1", who, i, (int)flip[i]);
+    if (view == PS_VIEW_SAGITTAL)
+        PS_CHECK((int64_t)B * P[1] < (1ll << 24) && ceil_div(P[0], (int64_t)tile_w(C)) <= 65535 && ceil_div(P[2], (int64_t)kTileH) <= 65535,
+                 "%s: the sagittal view takes B * P1 < 2^24, P0 <= 65535 * %d and P2 <= 65535 * %d, got B = %d, P = [%lld, %lld, %lld]", who, tile_w(C), kTileH,
+                 (int)B, (long long)P[0], (long long)P[1], (long long)P[2]);
+    return PS_OK;
+}
+
+template <int VIEW>
+void gather_rows_launch(hipStream_t st, bool row4, unsigned blocks, const PatchCand* d_c, const unsigned* d_counts, const PatchShape& sh, unsigned img_blocks,
+                        bool vec_i, bool vec_v, float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+{
+    if (row4)
+        hipLaunchKernelGGL((patch_gather_kernel<true, VIEW>), dim3(blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images, out_weights,
+                           out_labels, out_info);
+    else
+        hipLaunchKernelGGL((patch_gather_kernel<false, VIEW>), dim3(blocks), dim3(256), 0, st, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images, out_weights,
+                           out_labels, out_info);
+}
+
+template <int VIEW>
+void mix_rows_launch(hipStream_t st, bool row4, unsigned blocks, const PatchCand* d_c, const unsigned* d_counts, const float2* d_g, const PatchShape& sh, int K,
+                     unsigned img_blocks, bool vec_i, bool vec_w, int al_s, float* out_images, float* out_weights, float* out_soft, int32_t* out_info)
+{
+    if (row4)
+        hipLaunchKernelGGL((patch_mix_kernel<true, VIEW>), dim3(blocks), dim3(256), 0, st, d_c, d_counts, d_g, sh, K, img_blocks, vec_i, vec_w, al_s, out_images,
+                           out_weights, out_soft, out_info);
+    else
+        hipLaunchKernelGGL((patch_mix_kernel<false, VIEW>), dim3(blocks), dim3(256), 0, st, d_c, d_counts, d_g, sh, K, img_blocks, vec_i, vec_w, al_s, out_images,
+                           out_weights, out_soft, out_info);
+}
+
+// the sagittal gather's grid: (slot, view row j) x tiles along i x tiles along k
+inline dim3 sagittal_grid(int slots, const PatchShape& sh, int TW)
+{
+    return dim3((unsigned)(slots * sh.P[1]), (unsigned)ceil_div(sh.P[0], TW), (unsigned)ceil_div(sh.P[2], kTileH));
+}
+
+// the one body of ps_patch_sample (the axial view, no flip) and ps_patch_sample_view
+int patch_sample(const char* who, ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                 int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode, int32_t view,
+                 const int32_t* flip, float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+{
     // every argument error is found here, before anything is enqueued
     PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
     PS_CHECK(B >= 1 && B <= PS_PATCH_MAX_B, "%s: B = %d, must be in [1, %d]", who, (int)B, PS_PATCH_MAX_B);
     PS_TRY(sampler_args_ok(who, images, labels, weights, dims, n, C, cand, B, T, P, mode, out_images && out_weights && out_labels && out_info,
                            "out_images, out_weights, out_labels or out_info"));
+    PS_TRY(sampler_view_ok(who, view, flip, B, B, C, P));
     PS_CHECK(c, "%s: NULL context", who);
 
     SamplerBlob bl;
-    sampler_table(bl, images, labels, weights, dims, cand, B, T, P, seed, mode, B - 1, 0);
+    sampler_table(bl, images, labels, weights, dims, cand, B, T, P, seed, mode, B - 1, 0, view, flip);
+    int64_t PV[3];
+    sampler_patch_in_volume(view, P, PV);
     PS_HIP(hipSetDevice(c->device));
     PatchShape sh;
     sh.P[0] = (int)P[0], sh.P[1] = (int)P[1], sh.P[2] = (int)P[2], sh.C = C, sh.B = B, sh.T = T, sh.mode = mode;
@@ -797,25 +1055,31 @@ extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const 
     const bool vec_v = ((reinterpret_cast<uintptr_t>(out_weights) | reinterpret_cast<uintptr_t>(out_labels)) & 15) == 0;
     Stage stg(c, "patch_sample", 2);
     char* d_tab = nullptr;
-    PS_TRY(sampler_count(c, bl, P, d_tab));
+    PS_TRY(sampler_count(c, bl, PV, d_tab));
     const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
     const unsigned* d_counts = reinterpret_cast<const unsigned*>(d_tab + bl.counts_off);
-    if ((P[2] * C) % 4 == 0)
-        hipLaunchKernelGGL(patch_gather_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, sh, img_blocks, vec_i, vec_v,
-                           out_images, out_weights, out_labels, out_info);
-    else
-        hipLaunchKernelGGL(patch_gather_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, sh, img_blocks, vec_i, vec_v,
-                           out_images, out_weights, out_labels, out_info);
+    const bool row4 = (P[2] * C) % 4 == 0;
+    if (view == PS_VIEW_AXIAL)
+        gather_rows_launch<kViewAxial>(c->stream, row4, img_blocks + vox_blocks, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images, out_weights, out_labels,
+                                       out_info);
+    else if (view == PS_VIEW_CORONAL)
+        gather_rows_launch<kViewCoronal>(c->stream, row4, img_blocks + vox_blocks, d_c, d_counts, sh, img_blocks, vec_i, vec_v, out_images, out_weights, out_labels,
+                                         out_info);
+    else {
+        const int TW = tile_w(C);
+        hipLaunchKernelGGL(patch_gather_sagittal_kernel<false>, sagittal_grid(B, sh, TW), dim3(256), 0, c->stream, d_c, d_counts, (const float2*)nullptr, sh, 0, TW,
+                           vec_i && row4, vec_v && P[2] % 4 == 0, out_images, out_weights, out_labels, (float*)nullptr, out_info);
+    }
     PS_HIP(hipGetLastError());
     return PS_OK;
 }
 
-extern "C" int ps_patch_sample_mixup(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights,
-                                     const int64_t* dims, int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed,
-                                     int32_t mode, int32_t num_classes, const double* gamma, float* out_images, float* out_weights, float* out_soft,
-                                     int32_t* out_info)
+// the one body of ps_patch_sample_mixup (the axial view, no flip) and ps_patch_sample_mixup_view
+int patch_sample_mixup(const char* who, ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights,
+                       const int64_t* dims, int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode,
+                       int32_t num_classes, const double* gamma, int32_t view, const int32_t* flip, float* out_images, float* out_weights, float* out_soft,
+                       int32_t* out_info)
 {
-    const char* who = "ps_patch_sample_mixup";
     // every argument error is found here, before anything is enqueued
     PS_CHECK(C >= 1 && C <= PS_PATCH_MAX_C, "%s: C = %d, must be in [1, %d]", who, (int)C, PS_PATCH_MAX_C);
     PS_CHECK(B >= 1 && B <= PS_PATCH_MAX_B - 1, "%s: B = %d, must be in [1, %d] (B + 1 samples are drawn)", who, (int)B, PS_PATCH_MAX_B - 1);
@@ -827,10 +1091,13 @@ extern "C" int ps_patch_sample_mixup(ps_context* c, const float* const* images, 
     PS_CHECK(gamma, "%s: NULL gamma", who);
     for (int b = 0; b < B; ++b)
         PS_CHECK(std::isfinite(gamma[b]) && gamma[b] >= 0.0 && gamma[b] <= 1.0, "%s: gamma[%d] = %g, must be finite and in [0, 1]", who, b, gamma[b]);
+    PS_TRY(sampler_view_ok(who, view, flip, B + 1, B, C, P));
     PS_CHECK(c, "%s: NULL context", who);
 
     SamplerBlob bl;
-    sampler_table(bl, images, labels, weights, dims, cand, B + 1, T, P, seed, mode, B - 1, sizeof(float2) * B);
+    sampler_table(bl, images, labels, weights, dims, cand, B + 1, T, P, seed, mode, B - 1, sizeof(float2) * B, view, flip);
+    int64_t PV[3];
+    sampler_patch_in_volume(view, P, PV);
     float* hg = reinterpret_cast<float*>(bl.host.data() + bl.extra_off);
     for (int b = 0; b < B; ++b) {
         hg[2 * b] = (float)gamma[b];
@@ -846,16 +1113,60 @@ extern "C" int ps_patch_sample_mixup(ps_context* c, const float* const* images, 
     const int al_s = (as & 15) == 0 ? 16 : (as & 7) == 0 ? 8 : 4;
     Stage stg(c, "patch_sample_mixup", 2);
     char* d_tab = nullptr;
-    PS_TRY(sampler_count(c, bl, P, d_tab));
+    PS_TRY(sampler_count(c, bl, PV, d_tab));
     const PatchCand* d_c = reinterpret_cast<const PatchCand*>(d_tab);
     const unsigned* d_counts = reinterpret_cast<const unsigned*>(d_tab + bl.counts_off);
     const float2* d_g = reinterpret_cast<const float2*>(d_tab + bl.extra_off);
-    if ((P[2] * C) % 4 == 0)
-        hipLaunchKernelGGL(patch_mix_kernel<true>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, d_g, sh, (int)num_classes,
-                           img_blocks, vec_i, vec_w, al_s, out_images, out_weights, out_soft, out_info);
-    else
-        hipLaunchKernelGGL(patch_mix_kernel<false>, dim3(img_blocks + vox_blocks), dim3(256), 0, c->stream, d_c, d_counts, d_g, sh, (int)num_classes,
-                           img_blocks, vec_i, vec_w, al_s, out_images, out_weights, out_soft, out_info);
+    const bool row4 = (P[2] * C) % 4 == 0;
+    if (view == PS_VIEW_AXIAL)
+        mix_rows_launch<kViewAxial>(c->stream, row4, img_blocks + vox_blocks, d_c, d_counts, d_g, sh, (int)num_classes, img_blocks, vec_i, vec_w, al_s, out_images,
+                                    out_weights, out_soft, out_info);
+    else if (view == PS_VIEW_CORONAL)
+        mix_rows_launch<kViewCoronal>(c->stream, row4, img_blocks + vox_blocks, d_c, d_counts, d_g, sh, (int)num_classes, img_blocks, vec_i, vec_w, al_s, out_images,
+                                      out_weights, out_soft, out_info);
+    else {
+        const int TW = tile_w(C);
+        hipLaunchKernelGGL(patch_gather_sagittal_kernel<true>, sagittal_grid(B, sh, TW), dim3(256), 0, c->stream, d_c, d_counts, d_g, sh, (int)num_classes, TW,
+                           vec_i && row4, vec_w && P[2] % 4 == 0, out_images, out_weights, (int32_t*)nullptr, out_soft, out_info);
+    }
     PS_HIP(hipGetLastError());
     return PS_OK;
+}
+
+}  // namespace
+
+}  // namespace ps
+
+extern "C" int ps_patch_sample(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                               int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode,
+                               float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+{
+    return patch_sample("ps_patch_sample", c, images, labels, weights, dims, n, C, cand, B, T, P, seed, mode, PS_VIEW_AXIAL, nullptr, out_images, out_weights,
+                        out_labels, out_info);
+}
+
+extern "C" int ps_patch_sample_view(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights, const int64_t* dims,
+                                    int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed, int32_t mode, int32_t view,
+                                    const int32_t* flip, float* out_images, float* out_weights, int32_t* out_labels, int32_t* out_info)
+{
+    return patch_sample("ps_patch_sample_view", c, images, labels, weights, dims, n, C, cand, B, T, P, seed, mode, view, flip, out_images, out_weights, out_labels,
+                        out_info);
+}
+
+extern "C" int ps_patch_sample_mixup(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights,
+                                     const int64_t* dims, int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed,
+                                     int32_t mode, int32_t num_classes, const double* gamma, float* out_images, float* out_weights, float* out_soft,
+                                     int32_t* out_info)
+{
+    return patch_sample_mixup("ps_patch_sample_mixup", c, images, labels, weights, dims, n, C, cand, B, T, P, seed, mode, num_classes, gamma, PS_VIEW_AXIAL,
+                              nullptr, out_images, out_weights, out_soft, out_info);
+}
+
+extern "C" int ps_patch_sample_mixup_view(ps_context* c, const float* const* images, const uint8_t* const* labels, const uint8_t* const* weights,
+                                          const int64_t* dims, int64_t n, int32_t C, const int32_t* cand, int32_t B, int32_t T, const int64_t* P, uint32_t seed,
+                                          int32_t mode, int32_t num_classes, const double* gamma, int32_t view, const int32_t* flip, float* out_images,
+                                          float* out_weights, float* out_soft, int32_t* out_info)
+{
+    return patch_sample_mixup("ps_patch_sample_mixup_view", c, images, labels, weights, dims, n, C, cand, B, T, P, seed, mode, num_classes, gamma, view, flip,
+                              out_images, out_weights, out_soft, out_info);
 }

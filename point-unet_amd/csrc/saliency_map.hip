@@ -5,21 +5,17 @@
 //
 // The sagittal view's fastest axis runs along the volume's H, whose stride is W * C floats.  Both of its kernels go through an LDS tile
 // over (32 h, TW w) voxels instead: the volume side is walked in rows along W, the window side in rows along the view's axis 2, and the
-// tile's row pitch is odd, so that the column walk of either side meets every bank once.
+// tile's row pitch is odd, so that the column walk of either side meets every bank once (saliency_view.h: the tile and the view permutation).
 #include "saliency.h"
 #include "saliency_map_plan.h"
 #include "saliency_net.h"
+#include "saliency_view.h"
 #include "scratch.h"
 #include "../../include/pointseg_saliency_map.h"
 
 namespace ps {
 
 namespace {
-
-constexpr int kTileH = 32;        // voxels along the volume's H (the view's axis 2) in a sagittal tile
-constexpr int kTileFloats = 128;  // floats of one tile row: TW voxels along W, each of C (or K) floats
-
-inline int tile_w(int E) { return std::min(32, kTileFloats / E); }
 
 // what the kernels of one pass share
 struct MapGeom {
@@ -37,15 +33,7 @@ __device__ __forceinline__ void window_origin(const MapGeom& g, int t, int& o0, 
     o0 = t / (g.c2 * g.c1) * g.s0;
 }
 
-// view voxel (v0, v1, v2) -> the volume's (d, h, w) of the PASS (before the flip's mirror)
-template <int VIEW>
-__device__ __forceinline__ void to_volume(int v0, int v1, int v2, int& d, int& h, int& w)
-{
-    if (VIEW == kViewAxial) d = v0, h = v1, w = v2;
-    else if (VIEW == kViewSagittal) w = v0, d = v1, h = v2;
-    else h = v0, d = v1, w = v2;
-}
-
+// (to_volume<VIEW> of saliency_view.h gives the volume's (d, h, w) of the PASS: before the flip's mirror)
 template <int LAYOUT>
 __device__ __forceinline__ float volume_at(const float* __restrict__ vol, const MapGeom& g, int C, int d, int h, int w, int c)
 {

@@ -5,8 +5,17 @@ batches of patches drawn there by a stated rule with no host read.  PatchBank is
 point network's Trainer; train_saliency is the loop of train.py:83-110 over it, evaluate_saliency the Dice of EvalCallback / eval_pancreas.
 
 config.MIXUP (include/pointseg_saliency_mixup.h): PatchBank.sample(mixup=num_classes) draws B + 1 samples and mixes neighbour pairs on the
-device into images, or-ed weights and soft labels, which the loss and both training engines take.  Not built: a DIRECTION other than axial
-(permute before add_*), the left-right flip (off in the reference).  The training step behind one call is saliency.SaliencyTrainer (train_saliency's engine="native");
+device into images, or-ed weights and soft labels, which the loss and both training engines take.  config.DIRECTION and sampler3d's
+np.flip(..., -1) (include/pointseg_saliency_view.h): sample(direction=, flip=) draws the batch through an anatomical view of the SAME
+resident volumes, with no permuted or mirrored copy, so one bank trains the three networks saliency_map fuses:
+
+    nets = {}
+    for view in ("axial", "sagittal", "coronal"):           # P is in the view's axes
+        nets[view] = TrainableSaliencyNet(init_params(1, 2, seed=0), 1)
+        train_saliency(nets[view], bank, steps=250, patch=P, direction=view, flip="random")
+    dice = evaluate_saliency(bank, nets, range(len(bank)), P, steps)    # {view: net}: fused as MULTI_VIEW fuses them
+
+The training step behind one call is saliency.SaliencyTrainer (train_saliency's engine="native");
 data-parallel training: hook built, checked with an in-process callback; no multi-process run made."""
 import ctypes
 
@@ -192,16 +201,39 @@ class PatchBank:
             self._tables = (ptrs[0], ptrs[1], ptrs[2], dims, n)
         return self._tables
 
-    def sample(self, cand, patch, seed=0, mode="one_positive", mixup=None, gamma=None):
+    def _view_args(self, who, direction, flip, drawn, seed):
+        """(the PS_VIEW_* value, the flip bits as a ctypes int32 array or None) of sample's direction and flip, for `drawn` samples."""
+        if direction not in _lib.SALIENCY_VIEWS:
+            raise ValueError("%s: direction must be one of %s, got %r" % (who, sorted(_lib.SALIENCY_VIEWS), direction))
+        if flip is None:
+            return _lib.SALIENCY_VIEWS[direction], None
+        if isinstance(flip, str):
+            if flip != "random":
+                raise ValueError("%s: flip must be None, 'random' or %d values of 0 / 1, got %r" % (who, drawn, flip))
+            bits = np.random.default_rng(int(seed) & _M32).integers(0, 2, drawn)  # (a generator of its own: gamma's draw does not move it)
+        else:
+            bits = np.asarray(flip)
+            if bits.shape != (drawn,) or not np.isin(bits, (0, 1)).all():
+                raise ValueError("%s: flip must be None, 'random' or %d values of 0 / 1 (one per drawn sample)" % (who, drawn))
+        return _lib.SALIENCY_VIEWS[direction], (ctypes.c_int32 * drawn)(*[int(v) for v in bits])
+
+    def sample(self, cand, patch, seed=0, mode="one_positive", mixup=None, gamma=None, direction="axial", flip=None):
         """One batch, drawn on the device on torch's current stream: cand [B, T] volume ids (cand[b, t] is try t of slot b; a flat [B]
         list is T = 1), patch (P0, P1, P2).  Returns {"images" f32 [B, P0, P1, P2, C], "weights" f32 [B, P0, P1, P2], "labels" i32
         [B, P0, P1, P2], "info" i32 [B, 8] = (try, volume, c0, c1, c2, pos, ok, 0)}, CUDA tensors: the first three are what
-        TrainableSaliencyNet.loss takes.  info's ok is 0 for a slot none of whose tries met the mode's demand (it holds the last try).
+        TrainableSaliencyNet.loss takes (info's last column is the sample's flip bit).  info's ok is 0 for a slot none of whose tries met the mode's demand (it holds the last try).
 
         mixup=K, the class count (config.MIXUP, ps_patch_sample_mixup): cand is [B + 1, T], one row per DRAWN sample, and slot b of the B
         mixed slots is gamma[b] * sample b + (1 - gamma[b]) * sample b + 1.  gamma: B float64 values in [0, 1]; None draws
         np.random.default_rng(seed).beta(0.4, 0.4, B) on the host.  "labels" is then f32 [B, P0, P1, P2, K] (soft labels), "info" is
-        [B + 1, 8], one row per drawn sample, and "gamma" (float64 numpy [B]) is returned with them."""
+        [B + 1, 8], one row per drawn sample, and "gamma" (float64 numpy [B]) is returned with them.
+
+        direction (config.DIRECTION; "axial", "sagittal" or "coronal", the names saliency_map takes; ps_patch_sample_view): every candidate
+        volume is seen as transpose_volumes shows it -- sagittal view[i, j, k] = vol[j, k, i], coronal view[i, j, k] = vol[j, i, k] -- and
+        patch, the centres in info and the outputs are in the VIEW's axes; no permuted copy of a volume is made.  flip: None, a sequence of
+        0 / 1 per DRAWN sample (B, or B + 1 with mixup), or "random" (np.random.default_rng(seed).integers(0, 2, drawn) on the host, a
+        generator of its own): a flagged sample is mirrored along the view's last axis -- image, fill, weight and label, before mixing --
+        and info[:, 7] carries the bits.  The defaults give the bytes of ps_patch_sample / ps_patch_sample_mixup."""
         who = "PatchBank.sample"
         if mode not in MODES:
             raise ValueError("%s: mode must be one of %s" % (who, sorted(MODES)))
@@ -222,7 +254,8 @@ class PatchBank:
         if len(P) != 3 or min(P) < 1:
             raise ValueError("%s: patch must be three extents >= 1, got %s" % (who, (patch,)))
         if mixup is not None:
-            return self._sample_mixup(cand, P, seed, mode, int(mixup), gamma)
+            return self._sample_mixup(cand, P, seed, mode, int(mixup), gamma, direction, flip)
+        view, bits = self._view_args(who, direction, flip, B, seed)
         C, dev = self.channels, self.device
         stream = torch.cuda.current_stream(dev)
         if self._done is not None:
@@ -231,18 +264,19 @@ class PatchBank:
                "labels": torch.empty((B,) + P, dtype=torch.int32, device=dev), "info": torch.empty((B, 8), dtype=torch.int32, device=dev)}
         images, labels, weights, dims, n = self.c_tables()
         self.ctx.use_torch_stream()
-        _lib.check(_lib.lib().ps_patch_sample(self.ctx.handle, images, labels, weights, dims, n, C, cand.ctypes.data_as(_lib.c_i32p), B, T,
-                                              (ctypes.c_int64 * 3)(*P), int(seed) & _M32, MODES[mode], runtime.ptr(out["images"]), runtime.ptr(out["weights"]),
-                                              runtime.ptr(out["labels"]), runtime.ptr(out["info"])))
+        _lib.check(_lib.lib().ps_patch_sample_view(self.ctx.handle, images, labels, weights, dims, n, C, cand.ctypes.data_as(_lib.c_i32p), B, T,
+                                                   (ctypes.c_int64 * 3)(*P), int(seed) & _M32, MODES[mode], view, bits, runtime.ptr(out["images"]),
+                                                   runtime.ptr(out["weights"]), runtime.ptr(out["labels"]), runtime.ptr(out["info"])))
         self._done = torch.cuda.Event()
         self._done.record(stream)
         return out
 
-    def _sample_mixup(self, cand, P, seed, mode, K, gamma):
+    def _sample_mixup(self, cand, P, seed, mode, K, gamma, direction="axial", flip=None):
         who = "PatchBank.sample"
         B, T = cand.shape[0] - 1, cand.shape[1]
         if not 1 <= B <= _lib.PS_PATCH_MAX_B - 1:
             raise ValueError("%s: with mixup cand must be [B + 1, T] with B in [1, %d], got %s" % (who, _lib.PS_PATCH_MAX_B - 1, cand.shape))
+        view, bits = self._view_args(who, direction, flip, B + 1, seed)
         if gamma is None:
             gamma = np.random.default_rng(int(seed) & _M32).beta(0.4, 0.4, B)
         gamma = np.ascontiguousarray(gamma, dtype=np.float64)
@@ -257,30 +291,34 @@ class PatchBank:
                "gamma": gamma}
         images, labels, weights, dims, n = self.c_tables()
         self.ctx.use_torch_stream()
-        _lib.check(_lib.lib().ps_patch_sample_mixup(self.ctx.handle, images, labels, weights, dims, n, C, cand.ctypes.data_as(_lib.c_i32p), B, T,
-                                                    (ctypes.c_int64 * 3)(*P), int(seed) & _M32, MODES[mode], K,
-                                                    gamma.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), runtime.ptr(out["images"]),
-                                                    runtime.ptr(out["weights"]), runtime.ptr(out["labels"]), runtime.ptr(out["info"])))
+        _lib.check(_lib.lib().ps_patch_sample_mixup_view(self.ctx.handle, images, labels, weights, dims, n, C, cand.ctypes.data_as(_lib.c_i32p), B, T,
+                                                         (ctypes.c_int64 * 3)(*P), int(seed) & _M32, MODES[mode], K,
+                                                         gamma.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), view, bits, runtime.ptr(out["images"]),
+                                                         runtime.ptr(out["weights"]), runtime.ptr(out["labels"]), runtime.ptr(out["info"])))
         self._done = torch.cuda.Event()
         self._done.record(stream)
         return out
 
-    def epoch_batches(self, batch_size, patch, epoch, seed=0, tries=8, rank=0, world=1, mode="one_positive", mixup=None):
+    def epoch_batches(self, batch_size, patch, epoch, seed=0, tries=8, rank=0, world=1, mode="one_positive", mixup=None, direction="axial", flip=None):
         """The batches of one epoch on one rank (epoch_plan), each drawn when the iterator reaches it.  mixup=K: mixed batches of batch_size
         slots, planned as epoch_plan(len(self), batch_size + 1, ...) -- the reference consumes B + 1 datapoints per mixed batch and then
-        clears its holder."""
+        clears its holder.  direction and flip are sample's, the same for every batch (flip="random" draws from each batch's own seed)."""
+        view = {} if direction == "axial" and flip is None else {"direction": direction, "flip": flip}  # (the defaults: today's call of sample)
         for _, cand, s in epoch_plan(len(self), batch_size + (0 if mixup is None else 1), epoch, seed, tries, rank, world):
-            yield self.sample(cand, patch, s, mode, mixup)
+            yield self.sample(cand, patch, s, mode, mixup, **view)
 
 
-def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None, mixup=None):
+def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch=0, optimizer=None, engine="autograd", dist=None, mixup=None,
+                   direction="axial", flip=None):
     """The loop of train.py:83-110 on the device: `steps` steps on the bank's batches (epoch_batches from `epoch` on,
     config.DATA_SAMPLING = 'one_positive').  engine "autograd": TrainableSaliencyNet.loss under saliency.reference_optimizer(net, lr) (or
     `optimizer`); engine "native": net is a saliency.SaliencyTrainer and every step is one ps_saliency_train_step_prec at learning rate lr
     (dist: the torch.distributed-like module its gradients are summed through), at the precision the trainer was made with
     (SaliencyTrainer(precision=...): the trainer carries it, this loop takes no argument for it).  Returns the per-step losses as one device tensor
     [steps]; nothing is read back on the way.  mixup=num_classes: config.MIXUP, every batch is a mixed one (epoch_batches(mixup=...)) and
-    the loss is dice_mixup's, on soft labels."""
+    the loss is dice_mixup's, on soft labels.  direction, flip: config.DIRECTION and sampler3d's flip, as PatchBank.sample takes them (patch
+    in the view's axes; flip None, "random", or one 0 / 1 per drawn sample): the network trained with direction=view is the one
+    saliency_map / evaluate_saliency take under that view's name."""
     from . import saliency
     if engine not in ("autograd", "native"):
         raise ValueError("train_saliency: engine must be 'autograd' or 'native'")
@@ -297,7 +335,7 @@ def train_saliency(net, bank, steps, patch, batch_size=2, lr=0.01, seed=0, epoch
         opt = optimizer if optimizer is not None else saliency.reference_optimizer(net, lr)
     losses = []
     while len(losses) < steps:
-        for batch in bank.epoch_batches(batch_size, patch, epoch, seed, mixup=mixup):
+        for batch in bank.epoch_batches(batch_size, patch, epoch, seed, mixup=mixup, direction=direction, flip=flip):
             if native:
                 loss = net.step(batch["images"], batch["labels"], batch["weights"], lr, dist).clone()
             else:
