@@ -10,18 +10,16 @@
 // sources and the nearest up-sampling are part of that fetch (channel >= C1 reads x2; coordinate / up).
 // Rounding: a chunk is summed in a fresh accumulator and then added to the running one, so the dependent chain of a K = 10 368 layer is
 // 32 + 324 roundings long (an MFMA is an ordered chain of its four products) and not 10 368.
-#include "mfma_tile.h"
-#include "saliency.h"
+#include "conv3d_kit.h"
 
 namespace ps {
 
 namespace {
 
-constexpr int kKC = 32;        // K chunk
-constexpr int kAP = kKC + 2;   // A tile pitch: 2 (mod 32) floats, the A-fragment read is conflict free (mfma_tile.h)
-constexpr int kBP = 80;        // B tile pitch: the four k rows of a fragment read start 16 banks apart
-
-template <int RT, int NT>
+// GRAD: the data gradient (saliency.h's grad fields) -- the same implicit GEMM with the roles turned.  The row's corner
+// (conv3d_kit.h's conv_row), the fetch's coordinate step and the epilogue's column split are the whole difference, each behind
+// `if constexpr`, so the forward compiles to what it was.
+template <int RT, int NT, bool GRAD>
 __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
 {
     constexpr int M = 64 * RT, N = 16 * NT;
@@ -30,20 +28,12 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
     constexpr int BKS = 256 / N;         // k rows between a thread's B elements
     __shared__ float As[M * kAP];
     __shared__ float Bs[kKC * kBP];
-    __shared__ int4 rows[M];  // the input corner of the row's receptive field (z, y, x) and whether the row exists
+    __shared__ int4 rows[M];  // conv_row: the input corner of the row's receptive field (GRAD: the row's voxel + pad) and whether the row exists
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int b = blockIdx.z, n0 = blockIdx.y * N, m0 = blockIdx.x * M;
     const int Vo = a.Do * a.Ho * a.Wo;
-    for (int r = t; r < M; r += 256) {
-        const int v = m0 + r;
-        int4 ri = {0, 0, 0, 0};
-        if (v < Vo) {
-            const int ow = v % a.Wo, oh = v / a.Wo % a.Ho, od = v / (a.Wo * a.Ho);
-            ri = {od * a.stride - a.pd, oh * a.stride - a.ph, ow * a.stride - a.pw, 1};
-        }
-        rows[r] = ri;
-    }
+    for (int r = t; r < M; r += 256) rows[r] = conv_row<GRAD>(a, m0 + r, Vo);
     __syncthreads();
 
     const int cin = a.C1 + a.C2;
@@ -55,6 +45,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
     const float* xb = a.x + (size_t)b * xs * a.ldx;
     const float* x2b = a.x2 ? a.x2 + (size_t)b * xs * a.ldx2 : nullptr;
     const float* wb = a.w + (size_t)b * a.w_bstride;
+    const bool s2 = a.stride == 2;  // (GRAD)
 
     float areg[AI], breg[BI];
     auto fetch = [&](int chunk) {
@@ -62,26 +53,38 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
         const bool kin = k < Ktot;
         const int tap = kin ? k / cin : 0, ci = kin ? k - tap * cin : 0;
         const int dx = (tap % a.kw) * a.dil, dy = (tap / a.kw % a.kh) * a.dil, dz = (tap / (a.kw * a.kh)) * a.dil;
-        const bool second = ci >= a.C1;
+        const bool second = !GRAD && ci >= a.C1;  // (the gradient's operand is dy alone, not up-sampled)
         const float* src = second ? x2b + (ci - a.C1) : xb + ci;
         const int ld = second ? a.ldx2 : a.ldx;
 #pragma unroll
         for (int i = 0; i < AI; ++i) {
             const int4 ri = rows[arow + 8 * i];
-            int z = ri.x + dz, y = ri.y + dy, x = ri.z + dx;
-            const bool ok = kin && ri.w && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+            int z, y, x;
+            bool ok;
+            if constexpr (GRAD) {
+                z = ri.x - dz, y = ri.y - dy, x = ri.z - dx;  // o * stride
+                ok = kin && ri.w && (z | y | x) >= 0;
+                if (s2) {
+                    ok = ok && ((z | y | x) & 1) == 0;
+                    z >>= 1, y >>= 1, x >>= 1;
+                }
+                ok = ok && z < a.D && y < a.H && x < a.W;
+            } else {
+                z = ri.x + dz, y = ri.y + dy, x = ri.z + dx;
+                ok = kin && ri.w && (unsigned)z < (unsigned)a.D && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+            }
             if (!ok) z = y = x = 0;
-            if (a.up > 1) {
+            if (!GRAD && a.up > 1) {
                 z = (int)((unsigned)z / (unsigned)a.up);
                 y = (int)((unsigned)y / (unsigned)a.up);
                 x = (int)((unsigned)x / (unsigned)a.up);
             }
-            areg[i] = ok ? src[(size_t)((z * a.Hs + y) * a.Ws + x) * ld] : 0.f;
+            areg[i] = ok ? src[(size_t)((z * (GRAD ? a.H : a.Hs) + y) * (GRAD ? a.W : a.Ws) + x) * ld] : 0.f;  // (GRAD: the operand is not up-sampled)
         }
 #pragma unroll
         for (int i = 0; i < BI; ++i) {
             const int kb = chunk * kKC + bk + BKS * i;
-            breg[i] = (kb < Ktot && n0 + bcol < a.cout) ? wb[(size_t)kb * a.cout + n0 + bcol] : 0.f;
+            breg[i] = (kb < Ktot && n0 + bcol < a.cout) ? wb[(size_t)kb * (GRAD ? a.ldw : a.cout) + n0 + bcol] : 0.f;
         }
     };
 
@@ -102,27 +105,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
         for (int i = 0; i < BI; ++i) Bs[(bk + BKS * i) * kBP + bcol] = breg[i];
         __syncthreads();
         if (chunk + 1 < nchunks) fetch(chunk + 1);
-        f32x4 part[RT][NT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) part[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < kKC / 4; ++s) {
-            float av[RT], bv[NT];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) av[rt] = a0[rt * 16 * kAP + s * 4];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bv[j] = b0[s * 4 * kBP + j * 16];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) part[rt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt], bv[j], part[rt][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[rt][j] += part[rt][j];
+        chunk_mma<RT, NT>(a0, 16 * kAP, 4, b0, acc);
         __syncthreads();
     }
 
@@ -132,14 +115,27 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dArgs a)
     for (int j = 0; j < NT; ++j) {
         const int col = n0 + j * 16 + (lane & 15);
         if (col >= a.cout) continue;
-        const float bias = a.bias ? a.bias[col] : 0.f;
+        if constexpr (GRAD) {
+            const bool first = col < a.nsplit;
+            float* o = first ? yb + col : a.y2 + (size_t)b * Vo * a.ldy2 + (col - a.nsplit);
+            const int ld = first ? a.ldy : a.ldy2;
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+            for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
-                if (v < Vo) yb[(size_t)v * a.ldy + col] = acc[rt][j][r] + bias;
-            }
+                for (int r = 0; r < 4; ++r) {
+                    const int v = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
+                    if (v < Vo) o[(size_t)v * ld] = acc[rt][j][r];
+                }
+        } else {
+            const float bias = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int v = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
+                    if (v < Vo) yb[(size_t)v * a.ldy + col] = acc[rt][j][r] + bias;
+                }
+        }
     }
 }
 
@@ -148,7 +144,8 @@ void launch(hipStream_t sm, const Conv3dArgs& a)
 {
     const int Vo = a.Do * a.Ho * a.Wo;
     const dim3 grid((unsigned)ceil_div(Vo, 64 * RT), (unsigned)ceil_div(a.cout, 16 * NT), (unsigned)a.B);
-    hipLaunchKernelGGL((conv3d_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
+    if (a.grad) hipLaunchKernelGGL((conv3d_kernel<RT, NT, true>), grid, dim3(256), 0, sm, a);
+    else hipLaunchKernelGGL((conv3d_kernel<RT, NT, false>), grid, dim3(256), 0, sm, a);
 }
 
 }  // namespace
@@ -166,16 +163,11 @@ void conv3d_plan(Conv3dArgs& a)
     a.pw = same_pad_before(a.W, a.kw, a.stride, a.dil);
 }
 
-// Which form: 16 * NT output channels per workgroup, the smallest that holds C_out up to 64 (C_out = 1 and 2 -- the attention's second
-// convolutions and `final` -- run the one-tile form: their K is 288 and 3 456, the matrix pipe's empty columns cost less than a millisecond
-// of the full patch); 128 rows per workgroup where there are enough output voxels to fill the device with them, else 64.
+// (conv3d_kit.h's form rule; the data gradient's rows are the virtual input's voxels and its columns the computed channels)
 void conv3d_launch(hipStream_t sm, const Conv3dArgs& a)
 {
     if (a.precision != PS_PREC_FP32) return conv3d_b_launch(sm, a);
-    const bool wide = (int64_t)a.Do * a.Ho * a.Wo >= 2048;
-    if (a.cout <= 16) wide ? launch<2, 1>(sm, a) : launch<1, 1>(sm, a);
-    else if (a.cout <= 32) wide ? launch<2, 2>(sm, a) : launch<1, 2>(sm, a);
-    else wide ? launch<2, 4>(sm, a) : launch<1, 4>(sm, a);
+    conv_form((int64_t)a.Do * a.Ho * a.Wo >= 2048, a.cout, [&](auto rt, auto nt) { launch<decltype(rt)::value, decltype(nt)::value>(sm, a); });
 }
 
 }  // namespace ps
@@ -192,20 +184,8 @@ extern "C" int ps_conv3d_prec(ps_context* c, const void* x, const void* x2, int6
 {
     using namespace ps;
     const char* who = precision == PS_PREC_FP32 ? "ps_conv3d" : "ps_conv3d_prec";
-    const int64_t lim = 1ll << 31;
-    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
-    auto kext = [](int k) { return k == 1 || k == 3 || k == 9; };
-    PS_CHECK(kext(kd) && kext(kh) && kext(kw), "%s: kernel %d x %d x %d, every extent must be 1, 3 or 9", who, (int)kd, (int)kh, (int)kw);
-    PS_CHECK(stride == 1 || stride == 2, "%s: stride = %d, must be 1 or 2", who, (int)stride);
-    PS_CHECK(dilation == 1 || dilation == 3 || dilation == 5 || dilation == 7, "%s: dilation = %d, must be 1, 3, 5 or 7", who, (int)dilation);
-    PS_CHECK(up >= 1 && up <= 8, "%s: up = %d, must be in [1, 8]", who, (int)up);
-    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
-    PS_CHECK(C1 >= 1 && C2 >= 0 && C1 + C2 <= 384, "%s: C1 = %lld, C2 = %lld (C1 >= 1, C2 >= 0, C1 + C2 <= 384)", who, (long long)C1, (long long)C2);
-    PS_CHECK(C_out >= 1 && C_out <= 256, "%s: C_out = %lld, must be in [1, 256]", who, (long long)C_out);
-    PS_CHECK(Ds >= 1 && Hs >= 1 && Ws >= 1 && Ds < lim && Hs < lim && Ws < lim && Ds * up * Hs * up < lim && Ds * up * Hs * up * Ws * up < lim
-                 && Ds * Hs * Ws * (C1 > C2 ? C1 : C2) < lim && Ds * up * Hs * up * Ws * up * C_out < lim,
-             "%s: input %lld x %lld x %lld (every extent >= 1, every tensor below 2^31 elements per sample)", who, (long long)Ds, (long long)Hs,
-             (long long)Ws);
+    PS_TRY(precision_check(who, precision));
+    PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
     PS_CHECK(c && x && w && y, "%s: NULL argument", who);
     PS_CHECK((C2 == 0) == (x2 == nullptr), "%s: x2 must be given exactly when C2 > 0", who);
     PS_CHECK(y != x && y != x2, "%s: y must not overlap x or x2", who);

@@ -22,14 +22,15 @@
 //     output has fewer than 2048 voxels).
 #include <cstdint>
 
-#include "conv3d_b.h"
+#include "conv3d_kit.h"
 
 namespace ps {
 
 namespace {
 
-// GRAD: the data gradient (saliency.h's grad fields) -- the fetch's coordinate step and the epilogue's column split are the
-// whole difference: the forward walks corner + tap * dil, the gradient gathers from (row + pad - tap * dil) / stride where that is whole.
+// GRAD: the data gradient (saliency.h's grad fields) -- the row's corner (conv3d_kit.h's conv_row), the fetch's coordinate
+// step and the epilogue's column split are the whole difference: the forward walks corner + tap * dil, the gradient gathers from
+// (row + pad - tap * dil) / stride where that is whole.
 template <int P, int RT, int NT, bool VEC, bool GRAD>
 __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
 {
@@ -43,21 +44,12 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
     static_assert(AI % RPC == 0, "a split takes 8 values");
     __shared__ __attribute__((aligned(16))) unsigned As[P][M * kPW];
     __shared__ __attribute__((aligned(16))) unsigned Bs[P][N * kPW];
-    __shared__ int4 rows[M];  // the input corner of the row's receptive field (z, y, x) and whether the row exists
+    __shared__ int4 rows[M];  // conv_row: the input corner of the row's receptive field (GRAD: the row's voxel + pad) and whether the row exists
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int b = blockIdx.z, n0 = blockIdx.y * N, m0 = blockIdx.x * M;
     const int Vo = a.Do * a.Ho * a.Wo;
-    for (int r = t; r < M; r += 256) {
-        const int v = m0 + r;
-        int4 ri = {0, 0, 0, 0};
-        if (v < Vo) {
-            const int ow = v % a.Wo, oh = v / a.Wo % a.Ho, od = v / (a.Wo * a.Ho);
-            if constexpr (GRAD) ri = {od + a.pd, oh + a.ph, ow + a.pw, 1};
-            else ri = {od * a.stride - a.pd, oh * a.stride - a.ph, ow * a.stride - a.pw, 1};
-        }
-        rows[r] = ri;
-    }
+    for (int r = t; r < M; r += 256) rows[r] = conv_row<GRAD>(a, m0 + r, Vo);
     __syncthreads();
 
     const int cin = a.C1 + a.C2;
@@ -81,9 +73,9 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
         const int k = acg * KW + e, tap = k / cin;
         kci[e] = k - tap * cin, ktx[e] = tap % a.kw, kty[e] = tap / a.kw % a.kh, ktz[e] = tap / (a.kw * a.kh);
     }
-    const unsigned upm = (unsigned)((1ull << 32) / (unsigned)a.up) + 1u;  // (used where up > 1)
+    const unsigned upm = div_magic(a.up);  // (used where up > 1)
     const int ldw = GRAD ? a.ldw : a.cout;
-    const int sm1 = a.stride - 1;  // (GRAD) the stride is 1 or 2: zz % stride is zz & sm1, zz / stride is zz >> sm1
+    const int sm1 = a.stride - 1;
     const float* wp = wb + (size_t)bk0 * ldw + n0 + bcol;  // the thread's weights of the chunk to fetch
     const bool bin = n0 + bcol < a.cout;
     int kb = bk0;
@@ -97,6 +89,7 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
             const unsigned ld = second ? a.ldx2 : a.ldx;
 #pragma unroll
             for (int i = 0; i < AI; ++i) {
+                // (sm1 = stride - 1 and the stride is 1 or 2: % stride is & sm1, / stride is >> sm1)
                 const int4 ri = rows[arow + RS * i];
                 int z, y, x;
                 bool ok = kin && ri.w;
@@ -156,16 +149,7 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
                 }
             }
         }
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = i < BK ? breg[i < BK ? i : 0] : 0.f;
-        const BPlanes<P> p = b3_split8<P>(v);
-#pragma unroll
-        for (int pl = 0; pl < P; ++pl) {
-            unsigned* dst = &Bs[pl][bcol * kPW + bk0 / 2];
-            if constexpr (BK == 8) *reinterpret_cast<uint4*>(dst) = p.p[pl];
-            else *reinterpret_cast<uint2*>(dst) = make_uint2(p.p[pl].x, p.p[pl].y);
-        }
+        stage_b<P, BK>(breg, &Bs[0][bcol * kPW + bk0 / 2], N * kPW);
     };
 
     f32x16 acc[NT];
@@ -209,7 +193,6 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
     }
     if (!mma) return;
 
-    // C[m][n]: lane (n = c32, hl), register r holds m = (r & 3) + 8 (r >> 2) + 4 hl
     float* yb = a.y + (size_t)b * Vo * a.ldy;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -221,14 +204,14 @@ __global__ __launch_bounds__(256) void conv3d_b_kernel(Conv3dArgs a)
             const int ld = first ? a.ldy : a.ldy2;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+                const int v = c_row_b(m0 + wave * 32, r, hl);
                 if (v < Vo) o[(size_t)v * ld] = acc[j][r];
             }
         } else {
             const float bias = a.bias ? a.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+                const int v = c_row_b(m0 + wave * 32, r, hl);
                 if (v < Vo) yb[(size_t)v * a.ldy + col] = acc[j][r] + bias;
             }
         }
@@ -248,15 +231,12 @@ void launch(hipStream_t sm, const Conv3dArgs& a, bool vec)
     else hipLaunchKernelGGL((conv3d_b_kernel<P, RT, NT, false, false>), grid, dim3(256), 0, sm, a);
 }
 
-// Which form: conv3d_launch's rule with this instruction's 32-wide column tiles -- one tile up to 32 output channels (C_out <= 16 leaves
-// columns empty, as the fp32 kernel's 16-wide tile does at C_out = 1 and 2), two above; 128 rows where the output has 2048 voxels, else 64.
+// (conv3d_kit.h's form rule)
 template <int P>
 void launch_p(hipStream_t sm, const Conv3dArgs& a)
 {
-    const bool wide = (int64_t)a.Do * a.Ho * a.Wo >= 2048;
     const bool vec = conv3d_b_vec(a);
-    if (a.cout <= 32) wide ? launch<P, 2, 1>(sm, a, vec) : launch<P, 1, 1>(sm, a, vec);
-    else wide ? launch<P, 2, 2>(sm, a, vec) : launch<P, 1, 2>(sm, a, vec);
+    conv_form_b((int64_t)a.Do * a.Ho * a.Wo >= 2048, a.cout, [&](auto rt, auto nt) { launch<P, decltype(rt)::value, decltype(nt)::value>(sm, a, vec); });
 }
 
 }  // namespace

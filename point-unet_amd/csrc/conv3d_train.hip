@@ -12,14 +12,15 @@
 // [rows, columns] tile to scratch, and reduce_partials.h adds the slabs in one fixed order in float64.  `in` is fetched as the forward
 // fetches it (concat, / up, 0 in the padding).
 // Rounding (both): a chunk of 32 k is summed in a fresh accumulator and then added to the running one, as in conv3d.hip.
-// The data gradient is a kernel of its own and not conv3d_kernel behind a flipped kernel: its fetch would have to branch on its caller
-// (a negative tap step, the stride's parity test, the split result), and the forward has to stay byte for byte what it is.
-// At PS_PREC_BF16X3 / PS_PREC_BF16 (include/pointseg_saliency_train_precision.h) the same entries run the bf16 matrix pipe:
-// the data gradient conv3d_bf16.hip's kernel with its gather policy, the weight gradient conv3d_train_bf16.hip's; the transposed kernel
-// copy, the up-sampling's sum, the slab partials and their float64 reduction are the ones below.
+// The data gradient is the forward's kernel with its compile-time gather policy: conv3d_kernel<RT, NT, GRAD = true> (conv3d_bf16.hip's
+// conv3d_b_kernel at the other precisions) differs from the forward in the row's corner, the fetch's coordinate step and the epilogue's
+// column split, each behind `if constexpr`, so the forward's instantiations stay what they are.  The entry below describes the op once,
+// as a Conv3dArgs with the grad fields (saliency.h), and conv3d_launch picks the pipe.
+// At PS_PREC_BF16X3 / PS_PREC_BF16 (include/pointseg_saliency_train_precision.h) the same entries run the bf16 matrix pipe,
+// the weight gradient through conv3d_train_bf16.hip; the transposed kernel copy, the up-sampling's sum, the slab partials and their float64
+// reduction are the ones below.  conv3d_kit.h holds what the four sources share.
 #include "../../include/pointseg_saliency_train_precision.h"
-#include "conv3d_b.h"
-#include "mfma_tile.h"
+#include "conv3d_kit.h"
 #include "reduce_partials.h"
 #include "scratch.h"
 
@@ -27,154 +28,7 @@ namespace ps {
 
 namespace {
 
-constexpr int kKC = 32;        // K chunk
-constexpr int kAP = kKC + 2;   // row-major A tile pitch, as conv3d.hip
-constexpr int kBP = 80;        // k-major tile pitch for up to 64 columns: the four k rows of a fragment read start 16 banks apart
-
-// One K chunk of a wave's RT x NT tiles: the chunk's 8 k-steps in a fresh accumulator, then added to the running one (conv3d.hip's
-// rounding).  a0: this lane's A element of row tile 0, k-step 0 (row tiles a_rt floats apart, k-steps a_s); b0: the same in the k-major B tile.
-template <int RT, int NT>
-__device__ __forceinline__ void chunk_mma(const float* a0, int a_rt, int a_s, const float* b0, f32x4 (&acc)[RT][NT])
-{
-    f32x4 part[RT][NT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) part[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < kKC / 4; ++s) {
-        float av[RT], bv[NT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) av[rt] = a0[rt * a_rt + s * a_s];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) bv[j] = b0[s * 4 * kBP + j * 16];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) part[rt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt], bv[j], part[rt][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[rt][j] += part[rt][j];
-}
-
 // ---- data gradient -----------------------------------------------------------------------------------------------------------------------------
-
-struct BwdDataArgs {
-    const float* dy;  // [B, Do, Ho, Wo, cout]
-    const float* wt;  // [taps][cout][cin], the transposed kernel
-    float* out0;      // columns below `split`, pitch ld0
-    float* out1;      // the others, pitch ld1
-    int ld0, ld1, split;
-    int obase;        // out0's first column
-    int c0, ncols;    // the columns (channels of the virtual input) this call computes: [c0, c0 + ncols)
-    int B, D, H, W, Do, Ho, Wo, cin, cout;
-    int kd, kh, kw, stride, dil, pd, ph, pw;
-};
-
-template <int RT, int NT>
-__global__ __launch_bounds__(256) void conv3d_bwd_data_kernel(BwdDataArgs a)
-{
-    constexpr int M = 64 * RT, N = 16 * NT;
-    constexpr int AI = M / 8;
-    constexpr int BI = kKC * N / 256;
-    constexpr int BKS = 256 / N;
-    __shared__ float As[M * kAP];
-    __shared__ float Bs[kKC * kBP];
-    __shared__ int4 rows[M];  // the row's voxel plus the padding (z, y, x) and whether the row exists
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = blockIdx.z, n0 = blockIdx.y * N, m0 = blockIdx.x * M;
-    const int V = a.D * a.H * a.W, Vo = a.Do * a.Ho * a.Wo;
-    for (int r = t; r < M; r += 256) {
-        const int v = m0 + r;
-        int4 ri = {0, 0, 0, 0};
-        if (v < V) ri = {v / (a.W * a.H) + a.pd, v / a.W % a.H + a.ph, v % a.W + a.pw, 1};
-        rows[r] = ri;
-    }
-    __syncthreads();
-
-    const int Ktot = a.kd * a.kh * a.kw * a.cout;
-    const int nchunks = (Ktot + kKC - 1) / kKC;
-    const int akk = t & 31, arow = t >> 5;
-    const int bcol = t % N, bk = t / N;
-    const float* dyb = a.dy + (size_t)b * Vo * a.cout;
-    const float* wb = a.wt + a.c0;
-    const bool s2 = a.stride == 2;
-
-    float areg[AI], breg[BI];
-    auto fetch = [&](int chunk) {
-        const int k = chunk * kKC + akk;
-        const bool kin = k < Ktot;
-        const int tap = kin ? k / a.cout : 0, co = kin ? k - tap * a.cout : 0;
-        const int dx = (tap % a.kw) * a.dil, dy = (tap / a.kw % a.kh) * a.dil, dz = (tap / (a.kw * a.kh)) * a.dil;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int4 ri = rows[arow + 8 * i];
-            int z = ri.x - dz, y = ri.y - dy, x = ri.z - dx;  // o * stride
-            bool ok = kin && ri.w && (z | y | x) >= 0;
-            if (s2) {
-                ok = ok && ((z | y | x) & 1) == 0;
-                z >>= 1, y >>= 1, x >>= 1;
-            }
-            ok = ok && z < a.Do && y < a.Ho && x < a.Wo;
-            if (!ok) z = y = x = 0;
-            areg[i] = ok ? dyb[(size_t)((z * a.Ho + y) * a.Wo + x) * a.cout + co] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < BI; ++i) {
-            const int kb = chunk * kKC + bk + BKS * i;
-            breg[i] = (kb < Ktot && n0 + bcol < a.ncols) ? wb[(size_t)kb * a.cin + n0 + bcol] : 0.f;
-        }
-    };
-
-    f32x4 acc[RT][NT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[rt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    fetch(0);
-    const float* a0 = As + (wave * RT * 16 + (lane & 15)) * kAP + (lane >> 4);
-    const float* b0 = Bs + (lane >> 4) * kBP + (lane & 15);
-#pragma unroll 1
-    for (int chunk = 0; chunk < nchunks; ++chunk) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) As[(arow + 8 * i) * kAP + akk] = areg[i];
-#pragma unroll
-        for (int i = 0; i < BI; ++i) Bs[(bk + BKS * i) * kBP + bcol] = breg[i];
-        __syncthreads();
-        if (chunk + 1 < nchunks) fetch(chunk + 1);
-        chunk_mma<RT, NT>(a0, 16 * kAP, 4, b0, acc);
-        __syncthreads();
-    }
-
-    // C[i][j]: lane = j + 16 * (i / 4), reg = i % 4
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int lc = n0 + j * 16 + (lane & 15);
-        if (lc >= a.ncols) continue;
-        const int col = a.c0 + lc;
-        const bool first = col < a.split;
-        float* o = first ? a.out0 + (col - a.obase) : a.out1 + (col - a.split);
-        const int ld = first ? a.ld0 : a.ld1;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = m0 + wave * RT * 16 + rt * 16 + (lane >> 4) * 4 + r;
-                if (v < V) o[((size_t)b * V + v) * ld] = acc[rt][j][r];
-            }
-    }
-}
-
-template <int RT, int NT>
-void launch_data(hipStream_t sm, const BwdDataArgs& a)
-{
-    const dim3 grid((unsigned)ceil_div((int64_t)a.D * a.H * a.W, 64 * RT), (unsigned)ceil_div(a.ncols, 16 * NT), (unsigned)a.B);
-    hipLaunchKernelGGL((conv3d_bwd_data_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
-}
 
 // wt[(tap * cout + co) * cin + ci] = w[(tap * cin + ci) * cout + co]
 __global__ __launch_bounds__(256) void transpose_kernel_kernel(const float* __restrict__ w, unsigned total, int cin, int cout, float* __restrict__ wt)
@@ -333,27 +187,6 @@ void launch_weight(hipStream_t sm, BwdWeightArgs& a)
     hipLaunchKernelGGL((conv3d_bwd_weight_kernel<RT, NT>), grid, dim3(256), 0, sm, a);
 }
 
-// ---- the argument checks the two convolution entries share -------------------------------------------------------------------------------------
-
-int conv_geometry_ok(const char* who, int64_t B, int64_t Ds, int64_t Hs, int64_t Ws, int64_t C1, int64_t C2, int32_t up, int32_t kd, int32_t kh, int32_t kw,
-                     int64_t C_out, int32_t stride, int32_t dilation)
-{
-    const int64_t lim = 1ll << 31;
-    auto kext = [](int k) { return k == 1 || k == 3 || k == 9; };
-    PS_CHECK(kext(kd) && kext(kh) && kext(kw), "%s: kernel %d x %d x %d, every extent must be 1, 3 or 9", who, (int)kd, (int)kh, (int)kw);
-    PS_CHECK(stride == 1 || stride == 2, "%s: stride = %d, must be 1 or 2", who, (int)stride);
-    PS_CHECK(dilation == 1 || dilation == 3 || dilation == 5 || dilation == 7, "%s: dilation = %d, must be 1, 3, 5 or 7", who, (int)dilation);
-    PS_CHECK(up >= 1 && up <= 8, "%s: up = %d, must be in [1, 8]", who, (int)up);
-    PS_CHECK(B >= 1 && B <= 65535, "%s: B = %lld, must be in [1, 65535]", who, (long long)B);
-    PS_CHECK(C1 >= 1 && C2 >= 0 && C1 + C2 <= 384, "%s: C1 = %lld, C2 = %lld (C1 >= 1, C2 >= 0, C1 + C2 <= 384)", who, (long long)C1, (long long)C2);
-    PS_CHECK(C_out >= 1 && C_out <= 256, "%s: C_out = %lld, must be in [1, 256]", who, (long long)C_out);
-    PS_CHECK(Ds >= 1 && Hs >= 1 && Ws >= 1 && Ds < lim && Hs < lim && Ws < lim && Ds * up * Hs * up < lim && Ds * up * Hs * up * Ws * up < lim
-                 && Ds * Hs * Ws * (C1 > C2 ? C1 : C2) < lim && Ds * up * Hs * up * Ws * up * C_out < lim,
-             "%s: input %lld x %lld x %lld (every extent >= 1, every tensor below 2^31 elements per sample)", who, (long long)Ds, (long long)Hs,
-             (long long)Ws);
-    return PS_OK;
-}
-
 }  // namespace
 
 }  // namespace ps
@@ -371,7 +204,7 @@ extern "C" int ps_conv3d_bwd_data_prec(ps_context* c, const void* dy, const void
 {
     using namespace ps;
     const char* who = precision == PS_PREC_FP32 ? "ps_conv3d_bwd_data" : "ps_conv3d_bwd_data_prec";
-    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
+    PS_TRY(precision_check(who, precision));
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
     PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
     const int cin = (int)(C1 + C2), taps = kd * kh * kw;
@@ -390,45 +223,30 @@ extern "C" int ps_conv3d_bwd_data_prec(ps_context* c, const void* dy, const void
     PS_CHECK(c, "%s: NULL context", who);
     PS_TRY(check_scratch(who, scratch, scratch_bytes, cv.off));
 
-    BwdDataArgs a = {};
-    a.dy = static_cast<const float*>(dy);
-    a.wt = wt;
-    a.c0 = dx ? 0 : (int)C1;
-    a.ncols = (dx2 ? cin : (int)C1) - a.c0;
-    if (up > 1) a.out0 = g, a.out1 = nullptr, a.ld0 = a.ncols, a.ld1 = 0, a.split = cin, a.obase = a.c0;
-    else a.out0 = static_cast<float*>(dx), a.out1 = static_cast<float*>(dx2), a.ld0 = (int)C1, a.ld1 = (int)C2, a.split = (int)C1, a.obase = 0;
-    a.B = (int)B, a.D = D, a.H = H, a.W = W, a.cin = cin, a.cout = (int)C_out;
-    a.Do = same_out(D, stride), a.Ho = same_out(H, stride), a.Wo = same_out(W, stride);
+    // the forward's kernels on the turned roles (saliency.h's grad fields): their "input" is dy, their rows the virtual input's voxels, their
+    // columns the channels [c0, c0 + ncols) of the virtual input that this call computes
+    const int c0 = dx ? 0 : (int)C1, ncols = (dx2 ? cin : (int)C1) - c0;
+    Conv3dArgs a = {};
+    a.x = static_cast<const float*>(dy), a.w = wt + c0, a.ldw = cin, a.grad = 1, a.precision = precision;
+    a.B = (int)B, a.C1 = a.ldx = (int)C_out, a.up = 1, a.cout = ncols;
+    a.Do = D, a.Ho = H, a.Wo = W;
+    a.Ds = a.D = same_out(D, stride), a.Hs = a.H = same_out(H, stride), a.Ws = a.W = same_out(W, stride);
     a.kd = kd, a.kh = kh, a.kw = kw, a.stride = stride, a.dil = dilation;
     a.pd = same_pad_before(D, kd, stride, dilation), a.ph = same_pad_before(H, kh, stride, dilation), a.pw = same_pad_before(W, kw, stride, dilation);
+    // up == 1: straight into dx / dx2, the columns split at C1; else the whole tile to scratch, for upsample_bwd_kernel
+    if (up > 1) a.y = g, a.ldy = ncols, a.nsplit = cin - c0;
+    else a.y = static_cast<float*>(dx), a.ldy = (int)C1, a.y2 = static_cast<float*>(dx2), a.ldy2 = (int)C2, a.nsplit = (int)C1 - c0;
+    // PS_PREC_BF16X3 keeps the fp32 kernel where dy does not take the 16-byte fetch (conv3d_bwd_weight_split_pays' comment)
+    if (precision == PS_PREC_BF16X3 && !conv3d_b_vec(a)) a.precision = PS_PREC_FP32;
 
     PS_HIP(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     Stage stg(c, "conv3d_bwd_data", 3);
     const unsigned wn = (unsigned)((size_t)taps * cin * C_out);
     hipLaunchKernelGGL(transpose_kernel_kernel, dim3(blocks256(wn)), dim3(256), 0, sm, static_cast<const float*>(w), wn, cin, (int)C_out, wt);
-    // conv3d_bf16.hip's kernel on the turned roles (saliency.h): its "input" is dy, its rows the virtual input's voxels
-    Conv3dArgs f = {};
-    if (precision != PS_PREC_FP32) {
-        f.x = a.dy, f.w = wt + a.c0, f.ldw = cin, f.grad = 1, f.precision = precision;
-        f.B = a.B, f.Ds = f.D = a.Do, f.Hs = f.H = a.Ho, f.Ws = f.W = a.Wo, f.C1 = f.ldx = a.cout, f.up = 1;
-        f.Do = D, f.Ho = H, f.Wo = W, f.cout = a.ncols;
-        f.kd = kd, f.kh = kh, f.kw = kw, f.stride = stride, f.dil = dilation, f.pd = a.pd, f.ph = a.ph, f.pw = a.pw;
-        f.nsplit = a.split - a.c0;
-        f.y = a.out0 ? a.out0 + (a.c0 - a.obase) : nullptr, f.ldy = a.ld0, f.y2 = a.out1, f.ldy2 = a.ld1;
-    }
-    // (PS_PREC_BF16X3 keeps the fp32 kernel where dy does not take the 16-byte fetch: conv3d_b.h)
-    if (precision == PS_PREC_BF16 || (precision == PS_PREC_BF16X3 && conv3d_b_vec(f))) {
-        conv3d_b_launch(sm, f);
-    } else {
-        // the forward's forms: 16 * NT columns per workgroup, 128 rows where there are enough voxels to fill the device with them
-        const bool wide = (int64_t)D * H * W >= 2048;
-        if (a.ncols <= 16) wide ? launch_data<2, 1>(sm, a) : launch_data<1, 1>(sm, a);
-        else if (a.ncols <= 32) wide ? launch_data<2, 2>(sm, a) : launch_data<1, 2>(sm, a);
-        else wide ? launch_data<2, 4>(sm, a) : launch_data<1, 4>(sm, a);
-    }
+    conv3d_launch(sm, a);
     if (up > 1)
-        hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks256((size_t)Ds * Hs * Ws * a.ncols), (unsigned)B), dim3(256), 0, sm, g, a.ncols, a.c0, (int)Ds, (int)Hs,
+        hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks256((size_t)Ds * Hs * Ws * ncols), (unsigned)B), dim3(256), 0, sm, g, ncols, c0, (int)Ds, (int)Hs,
                            (int)Ws, (int)up, (int)C1, (int)C2, static_cast<float*>(dx), static_cast<float*>(dx2));
     PS_HIP(hipGetLastError());
     return PS_OK;
@@ -448,7 +266,7 @@ extern "C" int ps_conv3d_bwd_weight_prec(ps_context* c, const void* x, const voi
 {
     using namespace ps;
     const char* who = precision == PS_PREC_FP32 ? "ps_conv3d_bwd_weight" : "ps_conv3d_bwd_weight_prec";
-    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
+    PS_TRY(precision_check(who, precision));
     PS_CHECK(scratch_bytes, "%s: NULL scratch_bytes", who);
     PS_TRY(conv_geometry_ok(who, B, Ds, Hs, Ws, C1, C2, up, kd, kh, kw, C_out, stride, dilation));
     Conv3dArgs f = {};
@@ -483,12 +301,9 @@ extern "C" int ps_conv3d_bwd_weight_prec(ps_context* c, const void* x, const voi
     PS_HIP(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     Stage stg(c, "conv3d_bwd_weight", 2);
-    const bool tall = a.nrows > 64;
     if (precision == PS_PREC_BF16 || (precision == PS_PREC_BF16X3 && conv3d_bwd_weight_split_pays(a.C1 + a.C2, a.cout)))
         conv3d_bwd_weight_b_launch(sm, a, precision);
-    else if (a.cout <= 16) tall ? launch_weight<2, 1>(sm, a) : launch_weight<1, 1>(sm, a);
-    else if (a.cout <= 32) tall ? launch_weight<2, 2>(sm, a) : launch_weight<1, 2>(sm, a);
-    else tall ? launch_weight<2, 4>(sm, a) : launch_weight<1, 4>(sm, a);
+    else conv_form(a.nrows > 64, a.cout, [&](auto rt, auto nt) { launch_weight<decltype(rt)::value, decltype(nt)::value>(sm, a); });
     const int nv = a.nrows * a.cout, n0 = dw ? Ktot * a.cout : 0;
     hipLaunchKernelGGL((reduce_partials2_kernel<float, double>), dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, (int)n_part, nv, n0,
                        static_cast<float*>(dw), static_cast<float*>(dbias));

@@ -11,7 +11,7 @@
 // k is a voxel here and memory is channel-contiguous per voxel, so the transposition happens in the fetch: thread (lane = row, wave) fetches
 // its row's value of the 8 CONSECUTIVE voxels 8 * wave .. 8 * wave + 7 of the chunk -- adjacent lanes adjacent channels of one voxel, as in the
 // fp32 kernel -- which is exactly one b3_split8 and one 16-byte LDS store per plane.  A wave owns 32 rows and all NT column tiles.
-#include "conv3d_b.h"
+#include "conv3d_kit.h"
 
 namespace ps {
 
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_b_kernel(BwdWeightArgs 
     }
     const int bcol = t % N, bk0 = (t / N) * BK;
     const bool bin = n0 + bcol < a.cout;
-    const unsigned upm = (unsigned)((1ull << 32) / (unsigned)a.up) + 1u;  // (used where up > 1)
+    const unsigned upm = div_magic(a.up);  // (used where up > 1)
 
     auto put_vox = [&](int chunk) {
         if (t < kBKC) {
@@ -92,16 +92,7 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_b_kernel(BwdWeightArgs 
 #pragma unroll
             for (int pl = 0; pl < P; ++pl) *reinterpret_cast<uint4*>(&As[pl][(rt * 64 + lane) * kPW + wave * 4]) = p.p[pl];
         }
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = i < BK ? breg[i < BK ? i : 0] : 0.f;
-        const BPlanes<P> p = b3_split8<P>(v);
-#pragma unroll
-        for (int pl = 0; pl < P; ++pl) {
-            unsigned* dst = &Bs[pl][bcol * kPW + bk0 / 2];
-            if constexpr (BK == 8) *reinterpret_cast<uint4*>(dst) = p.p[pl];
-            else *reinterpret_cast<uint2*>(dst) = make_uint2(p.p[pl].x, p.p[pl].y);
-        }
+        stage_b<P, BK>(breg, &Bs[0][bcol * kPW + bk0 / 2], N * kPW);
     };
 
     f32x16 acc[NT];
@@ -148,7 +139,6 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_b_kernel(BwdWeightArgs 
     }
     if (!mma) return;
 
-    // C[m][n]: lane (n = c32, hl), register r holds m = (r & 3) + 8 (r >> 2) + 4 hl
     float* pb = a.part + (size_t)pidx * a.nrows * a.cout;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_b_kernel(BwdWeightArgs 
         if (col >= a.cout) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int lr = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+            const int lr = c_row_b(m0 + wave * 32, r, hl);
             if (lr < a.nrows) pb[(size_t)lr * a.cout + col] = acc[j][r];
         }
     }
@@ -170,15 +160,12 @@ void launch(hipStream_t sm, BwdWeightArgs& a)
     hipLaunchKernelGGL((conv3d_bwd_weight_b_kernel<P, RT, NT>), grid, dim3(256), 0, sm, a);
 }
 
-// Which form: the fp32 launcher's rule with this instruction's 32-wide column tiles -- 128 rows where there are more than 64, one column
-// tile up to 32 output channels, two above.  (P = 3 comes with more than 64 rows only: conv3d_bwd_weight_split_pays.)
+// (conv3d_kit.h's form rule; P = 3 comes with more than 64 rows, or with the bias row alone, and has the 128-row forms only:
+// conv3d_bwd_weight_split_pays)
 template <int P>
 void launch_p(hipStream_t sm, BwdWeightArgs& a)
 {
-    if constexpr (P == 1) {
-        if (a.nrows <= 64) return a.cout <= 32 ? launch<P, 1, 1>(sm, a) : launch<P, 1, 2>(sm, a);
-    }
-    a.cout <= 32 ? launch<P, 2, 1>(sm, a) : launch<P, 2, 2>(sm, a);
+    conv_form_b<P == 1>(a.nrows > 64, a.cout, [&](auto rt, auto nt) { launch<P, decltype(rt)::value, decltype(nt)::value>(sm, a); });
 }
 
 }  // namespace

@@ -19,11 +19,11 @@ struct Conv3dArgs {
     int B, Ds, Hs, Ws, C1, C2, ldx, ldx2, up;
     int kd, kh, kw, cout, stride, dil, ldy;
     int64_t w_bstride;
-    int precision;  // PS_PREC_*: 0 (what `= {}` leaves) is the fp32 kernel of conv3d.hip, the others run conv3d_bf16.hip
+    int precision;  // PS_PREC_*: 0 (what `= {}` leaves) is the fp32 kernel of conv3d.hip, the others run conv3d_bf16.hip's
     // derived by conv3d_plan
     int D, H, W, Do, Ho, Wo, pd, ph, pw;
-    // conv3d_bf16.hip's data-gradient form alone (grad != 0; conv3d_train.hip fills it, include/pointseg_saliency_train_precision.h): the
-    // same implicit GEMM with the roles turned.  x is dy ([B, D, H, W, C1], C2 = 0, up = 1: D, H, W the convolution's OUTPUT extents), the
+    // The data-gradient form of both kernels (grad != 0; conv3d_train.hip fills it, include/pointseg_saliency_train.h): the same implicit
+    // GEMM with the roles turned.  x is dy ([B, D, H, W, C1], C2 = 0, up = 1: D, H, W the convolution's OUTPUT extents), the
     // rows are the Do * Ho * Wo voxels i of the convolution's virtual INPUT, the fetch gathers dy[(i + pad - tap * dil) / stride] where that
     // is whole and inside, w is the transposed kernel [taps * C1][ldw] (its first column the first computed channel), cout the computed
     // channels; those below nsplit go to y (pitch ldy), the others to y2 (pitch ldy2).  No bias.
@@ -44,5 +44,11 @@ void conv3d_b_launch(hipStream_t sm, const Conv3dArgs& a);  // conv3d_bf16.hip: 
 bool conv3d_b_vec(const Conv3dArgs& a);                     // whether conv3d_b_launch takes the 16-byte activation fetch
 
 inline bool precision_ok(int32_t p) { return p == PS_PREC_FP32 || p == PS_PREC_BF16X3 || p == PS_PREC_BF16; }
+// the check of every entry that takes one precision
+inline int precision_check(const char* who, int32_t precision)
+{
+    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
+    return PS_OK;
+}
 
 }  // namespace ps

@@ -177,7 +177,7 @@ extern "C" int ps_saliency_forward_prec(ps_context* c, const void* x, int64_t B,
     using namespace ps;
     const char* who = precision == PS_PREC_FP32 ? "ps_saliency_forward" : "ps_saliency_forward_prec";
     PS_CHECK(scratch_bytes && (c || !scratch), "%s: NULL argument", who);
-    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
+    PS_TRY(precision_check(who, precision));
     PS_CHECK(net_args_ok(C_in, num_classes), "%s: C_in = %lld, num_classes = %lld (1 <= C_in <= 16, 2 <= num_classes <= 16)", who, (long long)C_in,
              (long long)num_classes);
     PS_CHECK(B >= 1 && B <= 1024, "%s: B = %lld, must be in [1, 1024]", who, (long long)B);

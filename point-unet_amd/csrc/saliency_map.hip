@@ -190,7 +190,7 @@ extern "C" int ps_saliency_map(ps_context* c, const void* volume, int32_t layout
     }
     PS_CHECK(flip == 0 || flip == 1, "%s: flip = %d, must be 0 or 1", who, (int)flip);
     PS_CHECK(batch >= 1 && batch <= 8, "%s: batch = %d, must be in [1, 8]", who, (int)batch);
-    PS_CHECK(precision_ok(precision), "%s: precision = %d, must be PS_PREC_FP32 (0), PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2)", who, (int)precision);
+    PS_TRY(precision_check(who, precision));
     PS_CHECK(net_args_ok(C_in, num_classes), "%s: C_in = %lld, num_classes = %lld (1 <= C_in <= 16, 2 <= num_classes <= 16)", who, (long long)C_in,
              (long long)num_classes);
     Net net;

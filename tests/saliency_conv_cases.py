@@ -20,6 +20,15 @@ The groups
   FUSED       the concat and the up-sampling together with stride 2, dilation 3 and non-cubic kernels.  (16 + 48 -> 36 is the one form of
               this list that "bf16x3" routes to the split weight-gradient kernel: conv3d_bwd_weight_split_pays.)
   BATCH       three joint geometries at B = 3, each with the precision at which the batch is compared with its single-sample runs.
+  FORMS       one case per kernel instantiation, sitting on the launchers' thresholds (csrc/conv3d_kit.h's form rule;
+              test_saliency_conv_geometry_rule.py restates it and shows that all 52 instantiations are reached), B = 1.  Rows of the forward
+              and the data gradient: 2048 voxels (16 x 16 x 8) against 2047 (23 x 89 x 1), each with 16, 17, 32, 33 and 36 channels in and
+              out -- the fp32 column classes 16 | 17 and 32 | 33, the bf16 pipe's 32 | 33, and the 16-byte fetch (16, 32, 36) against the
+              4-byte one (17, 33) of the activation and of dy alike.  Rows of the weight gradient: Ktot + 1 = 64 | 65 under a 1 x 1 x 1
+              kernel with 63 and 64 input channels on a few hundred voxels, with 16, 17, 32 and 33 output channels; 64 -> 32 and 64 -> 33
+              are what "bf16x3" routes to the split weight gradient.  FORMS_PARTIAL: the calls with one result NULL that land in another
+              form than the full call -- 16 + 17 channels, whose data gradient narrows from 33 columns to 16 (x alone) and 17 (x2 alone),
+              and 64 -> 32, whose weight gradient has 64 rows without the bias and one row with the bias alone.
 Every tensor of every case stays below about 10^5 elements."""
 import functools
 import itertools
@@ -97,6 +106,20 @@ def _fused():
     return cases
 
 
+FORMS_WIDE, FORMS_NARROW = (16, 16, 8), (23, 89, 1)  # 2048 voxels: the 128-row forms of the forward and the data gradient; 2047: the 64-row ones
+FORMS_CHANNELS = (16, 17, 32, 33, 36)
+FORMS_SMALL = (5, 8, 7)
+FORMS_NARROWING = (FORMS_SMALL, (3, 3, 3), 16, 17, 12, 1, 1, 1, 1)
+FORMS_SPLIT = (FORMS_SMALL, (1, 1, 1), 64, 0, 32, 1, 1, 1, 1)
+
+
+def _forms():
+    cases = [(shape, (3, 3, 3), ch, 0, ch, 1, 1, 1, 1) for shape in (FORMS_WIDE, FORMS_NARROW) for ch in FORMS_CHANNELS]
+    cases += [(FORMS_SMALL, (1, 1, 1), 63, 0, cout, 1, 1, 1, 1) for cout in (16, 17, 32, 33)]
+    cases += [FORMS_SPLIT, (FORMS_SMALL, (1, 1, 1), 64, 0, 33, 1, 1, 1, 1), FORMS_NARROWING]
+    return cases
+
+
 def at(cases, shape, k, stride, dilation):
     return next(c for c in cases if (c[0], c[1], c[5], c[6]) == (shape, k, stride, dilation))
 
@@ -108,7 +131,9 @@ FUSED = _fused()
 # (case, the precision of the batch comparison): B = 3 on three joint geometries
 BATCH = [(at(JOINT, SHAPE_A, (3, 9, 1), 2, 3)[:8] + (3,), "fp32"), (at(JOINT, SHAPE_B, (9, 3, 3), 2, 3)[:8] + (3,), "bf16x3"),
          (at(JOINT, SHAPE_A, (1, 3, 9), 1, 5)[:8] + (3,), "bf16")]
-GROUPS = {"joint": JOINT, "degenerate": DEGENERATE, "kwalk": KWALK, "fused": FUSED, "batch": [c for c, _ in BATCH]}
+FORMS = _forms()
+FORMS_PARTIAL = {FORMS_NARROWING: (("x",), ("x2",)), FORMS_SPLIT: (("w",), ("bias",))}  # case: the `need`s that reach another form
+GROUPS = {"joint": JOINT, "degenerate": DEGENERATE, "kwalk": KWALK, "fused": FUSED, "batch": [c for c, _ in BATCH], "forms": FORMS}
 ALL = [c for group in GROUPS.values() for c in group]
 
 

@@ -1,8 +1,8 @@
 """The 3-D convolution and its two gradients across JOINT geometry on the GPU: saliency.conv3d and saliency.conv3d_backward (ps_conv3d[_prec],
 ps_conv3d_bwd_data[_prec], ps_conv3d_bwd_weight[_prec]; csrc/conv3d.hip, conv3d_bf16.hip, conv3d_train.hip, conv3d_train_bf16.hip) on every
 case of saliency_conv_cases.py -- all 216 (kernel, stride, dilation) geometries on both parities and both fetch forms, the degenerate
-extents, the k walk's carries, the fused concat and up-sampling under stride 2, dilation 3 and non-cubic kernels -- in all three roles and
-all three precisions.  test_saliency_conv_geometry_rule.py holds the list and the references to account on the CPU.
+extents, the k walk's carries, the fused concat and up-sampling under stride 2, dilation 3 and non-cubic kernels, one case per kernel instantiation on the launchers'
+thresholds -- in all three roles and all three precisions.  test_saliency_conv_geometry_rule.py holds the list and the references to account on the CPU.
 
 The contract is include/pointseg_saliency.h's formula for every combination the entries accept.  TensorFlow itself refuses stride > 1
 together with dilation > 1: those cases are held to the header, not to TensorFlow.
@@ -109,6 +109,25 @@ def test_degenerate_extents():
 
 def test_k_walk():
     _run_group(cc.KWALK)
+
+
+def test_every_kernel_form():
+    """saliency_conv_cases.FORMS: one case per kernel instantiation on the launchers' thresholds (test_saliency_conv_geometry_rule.py shows
+    that they reach all 52), every role in every precision under the bars; and the calls with one result NULL that land in another form
+    than the full call (FORMS_PARTIAL) -- the bar again, and the bytes of the full call: a narrower column range or fewer rows regroup no sum."""
+    failures = []
+    for c in cc.FORMS:
+        got = _check(c, failures)
+        for need in cc.FORMS_PARTIAL.get(c, ()):
+            ops = _cuda(c)
+            for precision in cc.PRECISIONS:
+                part = _backward(c, ops, precision, need=need)
+                assert set(part) == set(need)
+                n, what = need[0], "%s %s need=%s" % (precision, cc.case_id(c), need[0])
+                _hold(failures, part[n], cc.references(c)[precision == "bf16"][n], what + " gradient d" + n)
+                if not torch.equal(part[n], got[precision][1][n]):
+                    failures.append(what + ": not the bytes of the full call")
+    assert not failures, "%d results missed:\n%s" % (len(failures), "\n".join(failures))
 
 
 def test_fused_input_jointly():

@@ -3,7 +3,8 @@ the kernels on them.
 
 Coverage: computed from the list with saliency_ref.same_padding -- all 216 geometries; on every axis an odd pad_total, a negative one that
 is clamped, a footprint larger than the extent, and extent 1; stride 2 with every dilation at both parities of every axis; every kernel,
-stride and dilation with both fetch forms; the k walk's regime.  A failed condition names what to add.
+stride and dilation with both fetch forms; the k walk's regime; every kernel instantiation -- the launchers' selection rules are restated
+here and the FORMS group is shown to reach all 52.  A failed condition names what to add.
 The yardstick agrees with itself: the float64 gradients of saliency_grad_precision_ref equal float64 autograd through
 conv3d_same(upsample(cat(x, x2))) on real operands, and on the degenerate extents a plain loop written straight from
 include/pointseg_saliency.h's formula equals conv3d_same -- the header is the contract, also where TensorFlow refuses stride > 1 with
@@ -34,7 +35,7 @@ def _raw_pad_total(n, k, stride, dilation):
 # ---- coverage -----------------------------------------------------------------------------------------------------------------------------------
 
 def test_the_groups_are_what_the_docstring_says():
-    assert (len(cc.JOINT), len(cc.DEGENERATE), len(cc.KWALK), len(cc.FUSED), len(cc.BATCH)) == (108 + 216, 64, 48, 48, 3)
+    assert (len(cc.JOINT), len(cc.DEGENERATE), len(cc.KWALK), len(cc.FUSED), len(cc.BATCH), len(cc.FORMS)) == (108 + 216, 64, 48, 48, 3, 17)
     assert len(set(cc.ALL)) == len(cc.ALL) and len(set(map(cc.case_id, cc.ALL))) == len(cc.ALL)
     for c in cc.ALL:
         shape, k, c1, c2, cout, stride, dilation, up, B = c
@@ -42,7 +43,7 @@ def test_the_groups_are_what_the_docstring_says():
         sizes = [B * int(np.prod(shape)) * max(c1, c2), B * int(np.prod(cc.virtual_shape(c))) * (c1 + c2), int(np.prod(k)) * (c1 + c2) * cout,
                  B * int(np.prod(cc.out_shape(c))) * cout]
         assert max(sizes) < 100000, "%s: a tensor of %d elements" % (cc.case_id(c), max(sizes))
-    assert all(c[8] == 2 for c in cc.JOINT + cc.DEGENERATE + cc.KWALK + cc.FUSED)
+    assert all(c[8] == 2 for c in cc.JOINT + cc.DEGENERATE + cc.KWALK + cc.FUSED) and all(c[8] == 1 for c in cc.FORMS)
     assert sorted(p for _, p in cc.BATCH) == sorted(cc.PRECISIONS) and all(c[8] == 3 and c[:8] + (2,) in cc.JOINT for c, _ in cc.BATCH)
     assert any(c[5] == 2 and c[6] == 3 for c, _ in cc.BATCH), "add a B = 3 case with stride 2 and dilation 3"
 
@@ -117,6 +118,106 @@ def test_the_k_walk_cases_carry_across_taps():
     assert {cc.is_vec(c[2]) for c in small} == {True, False}
     assert {c[1] for c in cc.KWALK if c[2] == 36} == set(cc.KWALK_KERNELS), "add C1 = 36 (just above one chunk) with every k-walk kernel"
     assert any(32 // c[2] > c[1][2] for c in small) and any(32 // c[2] > c[1][1] * c[1][2] for c in small)  # a tap row, a tap plane per step
+
+
+# ---- the launchers' selection rules, restated (csrc/conv3d_kit.h: conv_form, conv_form_b; conv3d_train.hip's routing) -------------------------------
+
+def _tiles(precision, tall, cols):
+    """(RT, NT): 128 rows per workgroup where `tall`; fp32 column tiles are 16 wide (1, 2 or 4 of them), the bf16 pipe's 32 wide (1 or 2)."""
+    if precision == "fp32":
+        return (2 if tall else 1, 1 if cols <= 16 else 2 if cols <= 32 else 4)
+    return (2 if tall else 1, 1 if cols <= 32 else 2)
+
+
+def _planes(precision):
+    return {"bf16x3": 3, "bf16": 1}[precision]
+
+
+def forward_form(c, precision):
+    """ps_conv3d[_prec]: the rows are the output voxels, the columns C_out."""
+    rt, nt = _tiles(precision, int(np.prod(cc.out_shape(c))) >= 2048, c[4])
+    if precision == "fp32":
+        return ("conv3d_kernel", rt, nt, False)
+    return ("conv3d_b_kernel", _planes(precision), rt, nt, cc.is_vec(c[2], c[3]), False)
+
+
+def data_grad_form(c, precision, need):
+    """ps_conv3d_bwd_data[_prec]: the rows are the voxels of the virtual (up-sampled) input, the columns its channels that are asked for;
+    the fetch is dy's, whose channel count is C_out; "bf16x3" keeps the fp32 kernel where dy does not take the 16-byte fetch."""
+    c1, c2, cout = c[2], c[3], c[4]
+    c0 = 0 if "x" in need else c1
+    cols = (c1 + c2 if "x2" in need and c2 else c1) - c0
+    vec = cc.is_vec(cout)
+    if precision == "bf16x3" and not vec:
+        precision = "fp32"
+    rt, nt = _tiles(precision, int(np.prod(cc.virtual_shape(c))) >= 2048, cols)
+    if precision == "fp32":
+        return ("conv3d_kernel", rt, nt, True)
+    return ("conv3d_b_kernel", _planes(precision), rt, nt, vec, True)
+
+
+def weight_grad_form(c, precision, need):
+    """ps_conv3d_bwd_weight[_prec]: the rows are the Ktot kernel rows (with dw) and the row of ones (with dbias), the columns C_out;
+    "bf16x3" runs the split kernel from 64 input and 32 output channels on (conv3d_bwd_weight_split_pays), which has the 128-row forms only."""
+    ktot, cout = int(np.prod(c[1])) * (c[2] + c[3]), c[4]
+    rows = (ktot if "w" in need else 0) + (1 if "bias" in need else 0)
+    if precision == "bf16x3" and not (cout >= 32 and c[2] + c[3] >= 64):
+        precision = "fp32"
+    rt, nt = _tiles(precision, rows > 64 or precision == "bf16x3", cout)
+    if precision == "fp32":
+        return ("conv3d_bwd_weight_kernel", rt, nt)
+    return ("conv3d_bwd_weight_b_kernel", _planes(precision), rt, nt)
+
+
+def forms_reached(c, precision, need=("x", "x2", "w", "bias")):
+    """The kernel instantiations that conv3d and conv3d_backward(need=need) launch for the case."""
+    out = {forward_form(c, precision)}
+    if set(need) & ({"x", "x2"} if c[3] else {"x"}):
+        out.add(data_grad_form(c, precision, need))
+    if set(need) & {"w", "bias"}:
+        out.add(weight_grad_form(c, precision, need))
+    return out
+
+
+INSTANTIATIONS = (
+    [("conv3d_kernel", rt, nt, grad) for rt in (1, 2) for nt in (1, 2, 4) for grad in (False, True)]
+    + [("conv3d_bwd_weight_kernel", rt, nt) for rt in (1, 2) for nt in (1, 2, 4)]
+    # (the split data gradient exists with the 16-byte fetch alone)
+    + [("conv3d_b_kernel", p, rt, nt, vec, grad) for p in (1, 3) for rt in (1, 2) for nt in (1, 2) for vec in (False, True) for grad in (False, True)
+       if not (p == 3 and grad and not vec)]
+    + [("conv3d_bwd_weight_b_kernel", 1, rt, nt) for rt in (1, 2) for nt in (1, 2)] + [("conv3d_bwd_weight_b_kernel", 3, 2, nt) for nt in (1, 2)])
+
+
+def test_the_form_cases_reach_every_kernel_instantiation():
+    assert len(INSTANTIATIONS) == len(set(INSTANTIATIONS)) == 52
+    assert [sum(1 for i in INSTANTIATIONS if i[0] in names) for names in (("conv3d_kernel", "conv3d_bwd_weight_kernel"), ("conv3d_b_kernel",),
+                                                                          ("conv3d_bwd_weight_b_kernel",))] == [18, 28, 6]
+    reached = {}
+    for c in cc.FORMS:
+        for precision in cc.PRECISIONS:
+            for form in forms_reached(c, precision):
+                reached.setdefault(form, []).append(cc.case_id(c))
+    assert not set(reached) - set(INSTANTIATIONS), "the restated rules name kernels that do not exist: %s" % sorted(set(reached) - set(INSTANTIATIONS), key=str)
+    missing = [i for i in INSTANTIATIONS if i not in reached]
+    assert not missing, "add form cases that reach %s" % missing
+    # the thresholds, from both sides: 2048 | 2047 rows, 16 | 17 and 32 | 33 columns, Ktot + 1 = 64 | 65 weight-gradient rows, the two fetches
+    voxels = {int(np.prod(cc.out_shape(c))) for c in cc.FORMS}
+    assert {2047, 2048} <= voxels and all(cc.out_shape(c) == cc.virtual_shape(c) for c in cc.FORMS)
+    for v in (2047, 2048):
+        assert {c[4] for c in cc.FORMS if int(np.prod(cc.out_shape(c))) == v} >= {16, 17, 32, 33}
+        assert {cc.is_vec(c[2]) for c in cc.FORMS if int(np.prod(cc.out_shape(c))) == v and c[2] > 32} == {True, False}
+    for rows in (64, 65):
+        assert {c[4] for c in cc.FORMS if int(np.prod(c[1])) * (c[2] + c[3]) + 1 == rows} >= ({16, 17, 32, 33} if rows == 64 else {32, 33})
+    # one result NULL lands in another form than the full call
+    for c, needs in cc.FORMS_PARTIAL.items():
+        assert c in cc.FORMS
+        for need in needs:
+            for precision in cc.PRECISIONS:
+                part, full = forms_reached(c, precision, need), forms_reached(c, precision)
+                # (the split weight gradient has one row form)
+                assert part <= set(INSTANTIATIONS) and (part - full or (precision == "bf16x3" and c == cc.FORMS_SPLIT)), (cc.case_id(c), need, precision)
+    assert {data_grad_form(cc.FORMS_NARROWING, "fp32", need)[2] for need in (("x",), ("x2",), ("x", "x2"))} == {1, 2, 4}
+    assert weight_grad_form(cc.FORMS_SPLIT, "bf16x3", ("bias",)) == ("conv3d_bwd_weight_b_kernel", 3, 2, 1)  # one row, and still the 128-row form
 
 
 # ---- the yardstick agrees with itself -------------------------------------------------------------------------------------------------------------
