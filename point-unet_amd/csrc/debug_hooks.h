@@ -111,6 +111,31 @@ int ps_debug_tuning_fields(char* buf, int cap);
 /* sizeof(ps_volume_sample_args) as the library was compiled: the ctypes mirror (point-unet_amd/_lib.py) is checked against it. */
 int ps_debug_volume_sample_args_size(void);
 
+/* The shared scan and radix sort (csrc/sortscan.h) and the partial-sum reducer (csrc/reduce_partials.h) on their own.
+ * Host only, no context: the values of scan_workspace_words(n), sort_workspace_words(n) (unsigned words), scan_launches(n) and
+ * radix_sort_pairs_launches(n, bits).  These return a value, not a status: a negative n (or bits outside 1..64) gives -1. */
+int64_t ps_debug_scan_words(int64_t n);
+int64_t ps_debug_sort_words(int64_t n);
+int ps_debug_scan_launches(int64_t n);
+int ps_debug_sort_launches(int64_t n, int bits);
+/* exclusive_scan_u32 on the context's stream, then a synchronise; needs a GPU.  in / out: DEVICE u32 [n] (in == out is allowed; any 4-byte
+ * alignment), work: the CALLER's device buffer of at least ps_debug_scan_words(n) words -- the door allocates nothing, so a test can put guard
+ * bands around it. */
+int ps_debug_scan_u32(ps_context* ctx, const uint32_t* in, uint32_t* out, int64_t n, uint32_t* work);
+/* radix_sort_pairs_u32 (key_bytes 4) / radix_sort_pairs_u64 (key_bytes 8; anything else is PS_EINVAL, as are bits outside 1..8 key_bytes) on the
+ * context's stream; needs a GPU.  k0 / k1: DEVICE keys [n] of key_bytes each, every key below 2^bits; v0 / v1: DEVICE u32 [n]; (k0, v0) is the
+ * input and is overwritten; work: the caller's DEVICE buffer of at least ps_debug_sort_words(n) words.  *which_out (HOST) = 0 / 1: the pair of
+ * arrays that holds the sorted result; written before the synchronise. */
+int ps_debug_sort_pairs(ps_context* ctx, int key_bytes, void* k0, void* k1, uint32_t* v0, uint32_t* v1, int64_t n, int bits, uint32_t* work,
+                        int* which_out);
+/* out[i] = sum over b of part[b * nv + i] through the kernels of csrc/reduce_partials.h on the grid every caller uses, ceil(nv / 16) workgroups
+ * of 256, then a synchronise; needs a GPU.  form 0: reduce_partials_kernel<float>, 1: reduce_partials_kernel<double>, 2: reduce_partials2_kernel<float>,
+ * 3: reduce_partials2_kernel<float, double> (float partials added in double).  part: DEVICE [n_part, nv] of the form's type; forms 0 / 1 write
+ * out0 [nv] (n0 and out1 are ignored); forms 2 / 3 write values [0, n0) to out0 and [n0, nv) to out1, 0 <= n0 <= nv.  The reducer is a header of
+ * templates, so the product library has no symbol to call: this door instantiates the templates from the shared header -- the same text as the
+ * product's kernels, compiled a second time. */
+int ps_debug_reduce_partials(ps_context* ctx, int form, const void* part, int n_part, int nv, int n0, void* out0, void* out1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@
 #include "attpool.h"
 #include "debug_hooks.h"
 #include "randla_net.h"
+#include "reduce_partials.h"
+#include "sortscan.h"
 
 using namespace ps;
 
@@ -459,5 +461,70 @@ extern "C" int ps_debug_kdtree_device_set(ps_context* c, const float* support, c
     stats[3 + 2 * kBuildCounterLevels] = bc.small_pushed;
     stats[4 + 2 * kBuildCounterLevels] = flag[kFlagStackOverflow];
     stats[5 + 2 * kBuildCounterLevels] = flag[kFlagQueueOverflow];
+    return PS_OK;
+}
+
+// --------------------------------------------------------------------------------------------------------
+// the shared primitives on their own: the scan and the radix sort of sortscan.hip (the product library's own code, called through
+// sortscan.h) and the partial-sum reducer of reduce_partials.h.  The reducer is a header of templates: the kernels below are the SAME
+// text as the product's, instantiated a second time in this library.
+// --------------------------------------------------------------------------------------------------------
+extern "C" int64_t ps_debug_scan_words(int64_t n) { return n < 0 ? -1 : (int64_t)scan_workspace_words((size_t)n); }
+extern "C" int64_t ps_debug_sort_words(int64_t n) { return n < 0 ? -1 : (int64_t)sort_workspace_words((size_t)n); }
+extern "C" int ps_debug_scan_launches(int64_t n) { return n < 0 ? -1 : scan_launches((size_t)n); }
+extern "C" int ps_debug_sort_launches(int64_t n, int bits) { return n < 0 || bits < 1 || bits > 64 ? -1 : radix_sort_pairs_launches((size_t)n, bits); }
+
+extern "C" int ps_debug_scan_u32(ps_context* c, const uint32_t* in, uint32_t* out, int64_t n, uint32_t* work)
+{
+    PS_CHECK(c && in && out && work && n >= 0, "ps_debug_scan_u32: bad argument");
+    PS_HIP(hipSetDevice(c->device));
+    exclusive_scan_u32(c->stream, in, out, (size_t)n, work);
+    PS_HIP(hipGetLastError());
+    PS_HIP(hipStreamSynchronize(c->stream));
+    return PS_OK;
+}
+
+extern "C" int ps_debug_sort_pairs(ps_context* c, int key_bytes, void* k0, void* k1, uint32_t* v0, uint32_t* v1, int64_t n, int bits, uint32_t* work,
+                                   int* which_out)
+{
+    PS_CHECK(c && k0 && k1 && v0 && v1 && work && which_out && n >= 0, "ps_debug_sort_pairs: bad argument");
+    PS_CHECK(key_bytes == 4 || key_bytes == 8, "ps_debug_sort_pairs: key_bytes must be 4 or 8");
+    PS_CHECK(bits >= 1 && bits <= 8 * key_bytes, "ps_debug_sort_pairs: bits must be 1..%d", 8 * key_bytes);
+    PS_HIP(hipSetDevice(c->device));
+    *which_out = key_bytes == 4
+                     ? radix_sort_pairs_u32(c->stream, static_cast<unsigned*>(k0), static_cast<unsigned*>(k1), v0, v1, (size_t)n, bits, work)
+                     : radix_sort_pairs_u64(c->stream, static_cast<unsigned long long*>(k0), static_cast<unsigned long long*>(k1), v0, v1, (size_t)n,
+                                            bits, work);
+    PS_HIP(hipGetLastError());
+    PS_HIP(hipStreamSynchronize(c->stream));
+    return PS_OK;
+}
+
+extern "C" int ps_debug_reduce_partials(ps_context* c, int form, const void* part, int n_part, int nv, int n0, void* out0, void* out1)
+{
+    PS_CHECK(c && part && out0 && n_part >= 0 && nv >= 0 && form >= 0 && form <= 3, "ps_debug_reduce_partials: bad argument");
+    PS_CHECK(form < 2 || (out1 && n0 >= 0 && n0 <= nv), "ps_debug_reduce_partials: forms 2 and 3 need out1 and 0 <= n0 <= nv");
+    PS_HIP(hipSetDevice(c->device));
+    if (nv == 0) return PS_OK;
+    const dim3 grid((unsigned)((nv + 15) / 16)), block(256);  // the grid of every caller
+    switch (form) {
+    case 0:
+        hipLaunchKernelGGL(reduce_partials_kernel<float>, grid, block, 0, c->stream, static_cast<const float*>(part), n_part, nv, static_cast<float*>(out0));
+        break;
+    case 1:
+        hipLaunchKernelGGL(reduce_partials_kernel<double>, grid, block, 0, c->stream, static_cast<const double*>(part), n_part, nv,
+                           static_cast<double*>(out0));
+        break;
+    case 2:
+        hipLaunchKernelGGL((reduce_partials2_kernel<float>), grid, block, 0, c->stream, static_cast<const float*>(part), n_part, nv, n0,
+                           static_cast<float*>(out0), static_cast<float*>(out1));
+        break;
+    default:
+        hipLaunchKernelGGL((reduce_partials2_kernel<float, double>), grid, block, 0, c->stream, static_cast<const float*>(part), n_part, nv, n0,
+                           static_cast<float*>(out0), static_cast<float*>(out1));
+        break;
+    }
+    PS_HIP(hipGetLastError());
+    PS_HIP(hipStreamSynchronize(c->stream));
     return PS_OK;
 }

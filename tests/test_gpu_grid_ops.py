@@ -60,6 +60,39 @@ def test_grid_sort_passes_and_ragged_tiles(oracle, n, dl):
     assert all(np.array_equal(a, b) for a, b in zip(got, want))
 
 
+def wide_key_cloud(n=5000, copies=4):
+    """The cloud of test_grid_sort_passes_and_ragged_tiles, every point `copies` times, shuffled: the copies are exact, so a cell holds several
+    points however fine the grid: its barycentre and label vote are taken over a run of the sorted keys, and a pass that misplaces a key
+    cuts or merges runs."""
+    rng = np.random.default_rng(n)
+    p = (rng.random((n, 3), dtype=np.float32) * np.array([1.0, 0.7, 1.3], np.float32) - 0.25).astype(np.float32)
+    f = rng.standard_normal((n, 2)).astype(np.float32)
+    l = rng.integers(0, 4, (n, 1)).astype(np.int32)
+    order = rng.permutation(np.repeat(np.arange(n), copies))
+    return p[order], f[order], l[order]
+
+
+def wide_key_bits(p, dl):
+    """The key width ps_grid_subsample sorts by (csrc/grid.hip): the bits of the cell count, from the same float32 quotients."""
+    dl = np.float32(dl)
+    org = np.floor(p.min(0) * (np.float32(1) / dl)) * dl
+    nx, ny, nz = (int(e) + 1 for e in np.floor((p.max(0) - org) / dl))
+    return (nx * ny * nz).bit_length()
+
+
+@pytest.mark.parametrize("dl, passes", [(2e-4, 5), (3e-5, 6), (1e-5, 7), (2e-6, 8)])
+def test_grid_wide_keys(oracle, dl, passes):
+    """A fine grid on a wide cloud: about 2^37, 2^45, 2^50 and 2^57 cells = 5, 6, 7 and 8 radix passes over 64-bit keys (the sizes above stop
+    at 4).  20 000 points in three tiles; rows equal the oracle's after the canonical sort, bit for bit."""
+    from point_unet_amd.helper_tool import DataProcessing as DP
+    p, f, l = wide_key_cloud()
+    assert -(-wide_key_bits(p, dl) // 8) == passes
+    want = oracle.canonical_rows(*oracle.grid_subsample(p, f, l, dl))
+    assert len(want[0]) == 5000  # no two base points share a cell: every cell is one point four times
+    got = _canon(oracle, DP.grid_sub_sampling(p, f, l, dl), True, True)
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))
+
+
 def test_grid_single_point_and_single_voxel(oracle):
     from point_unet_amd.helper_tool import DataProcessing as DP
     one = np.array([[0.3, -0.2, 0.9]], np.float32)

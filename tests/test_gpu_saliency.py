@@ -97,7 +97,9 @@ def _norm_case(x, gamma, beta):
     return got, want
 
 
-@pytest.mark.parametrize("V, C", [(1, 5), (400, 3), (400, 64), (5000, 1), (9001, 70), (4097, 130)])
+# (the last four: 49 and 113 slabs of 4096 voxels = 49 and 113 partials per value, where reduce_partials.h runs its unrolled loop once and twice;
+#  C = 5 on the float path, C = 8 on the 16-byte one)
+@pytest.mark.parametrize("V, C", [(1, 5), (400, 3), (400, 64), (5000, 1), (9001, 70), (4097, 130), (196609, 5), (196609, 8), (458753, 5), (458753, 8)])
 def test_instance_norm_relu_values(V, C):
     rng = np.random.default_rng(V + C)
     x = (rng.standard_normal((2, V, C)) * rng.uniform(0.5, 3.0, C) + rng.standard_normal(C)).astype(np.float32)

@@ -105,6 +105,17 @@ def test_conv3d_gradient_three_slabs_ragged():
     _conv_case((21, 20, 20), K333, 3, 5, B=1)
 
 
+def test_conv3d_gradient_114_partials():
+    """29 x 90 x 89 = 232 290 output voxels are 57 slabs, the last of 2914 voxels; two samples make 114 partials per weight, which
+    reduce_partials2_kernel<float, double> adds with its unrolled loop run once by some groups and twice by others (three slabs: never)."""
+    _conv_case((29, 90, 89), K333, 3, 5)
+
+
+def test_conv3d_gradient_113_slabs_of_one_sample():
+    """77 x 77 x 78 = 462 462 voxels: 113 slabs of one sample, the last of 3710 voxels; the smallest kernel."""
+    _conv_case((77, 77, 78), (1, 1, 1), 3, 5, B=1)
+
+
 @pytest.mark.parametrize("up, c1, c2, stride", [(1, 16, 48, 1), (2, 40, 0, 1), (4, 7, 0, 1), (2, 5, 30, 1), (3, 6, 0, 2)])
 def test_conv3d_gradient_fused_concat_and_upsampling(up, c1, c2, stride):
     (x, x2, w, b, dy), got = _conv_case((3, 4, 5), K333, c1, 24, stride=stride, seed=up * 100 + c1, c2=c2, up=up)
@@ -194,7 +205,8 @@ def _norm_case(x, gamma, beta, what, seed=0):
     return got
 
 
-@pytest.mark.parametrize("V, C", [(1, 5), (2, 3), (400, 3), (400, 64), (5000, 1), (9001, 70), (4097, 130)])
+# (the last four: 49 and 113 slabs per sample, the reducer's unrolled loop once and twice; C = 5 on the float path, C = 8 on the 16-byte one)
+@pytest.mark.parametrize("V, C", [(1, 5), (2, 3), (400, 3), (400, 64), (5000, 1), (9001, 70), (4097, 130), (196609, 5), (196609, 8), (458753, 5), (458753, 8)])
 def test_instance_norm_relu_gradient_values(V, C):
     rng = np.random.default_rng(V + C)
     x = (rng.standard_normal((2, V, C)) * rng.uniform(0.5, 3.0, C) + rng.standard_normal(C)).astype(np.float32)

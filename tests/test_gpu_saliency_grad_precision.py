@@ -120,6 +120,17 @@ def test_slabs(shape, cin, cout, mode):
     _check(mode, shape, K333, cin, cout, B=1)
 
 
+@pytest.mark.parametrize("mode, k, cin, cout", [("bf16", K333, 3, 5), ("bf16x3", (1, 1, 1), 64, 32)])
+def test_114_partials(mode, k, cin, cout):
+    """29 x 90 x 89 = 232 290 output voxels are 57 slabs per sample, the last of 2914 voxels: two samples make 114 partials per weight, where the
+    reducer runs its unrolled loop once in some groups and twice in others.  64 -> 32 is the smallest channel pair whose "bf16x3" weight
+    gradient runs the split kernel."""
+    try:
+        _check(mode, (29, 90, 89), k, cin, cout)
+    finally:
+        _case_once.cache_clear()  # (hundreds of megabytes of operands and references that no other test shares)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("up, c1, c2, stride, cout", [(1, 16, 48, 1, 24), (2, 5, 30, 1, 24), (4, 7, 0, 1, 24), (3, 6, 0, 2, 24), (2, 40, 24, 1, 40)])
 def test_fused_concat_and_upsampling(up, c1, c2, stride, cout, mode):

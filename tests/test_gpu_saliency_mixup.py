@@ -246,7 +246,8 @@ def _soft_case(V, C, kind="plain", dloss=0.75):
     return inputs, got
 
 
-@pytest.mark.parametrize("V, C", [(1, 2), (5, 2), (4097, 2), (9001, 4), (300, 16), (4500, 3)])
+# (the last four: 49 and 113 slabs per sample)
+@pytest.mark.parametrize("V, C", [(1, 2), (5, 2), (4097, 2), (9001, 4), (300, 16), (4500, 3), (196609, 2), (196609, 4), (458753, 2), (458753, 4)])
 def test_soft_loss_values(V, C):
     _soft_case(V, C)
 

@@ -191,7 +191,8 @@ def ca_reference(inputs, mask, dt):
     return {k: _np(v) for k, v in out.items()}, float(pre[0].abs().min())
 
 
-CA_CASES = [(1, 4, 1, 2), (7, 5, 3, 2), (7, 5, 3, 1), (4097, 8, 2, 2), (9001, 384, 96, 2)]
+# (the last four: 49 and 113 slabs per sample, where reduce_partials.h runs its unrolled loop once and twice)
+CA_CASES = [(1, 4, 1, 2), (7, 5, 3, 2), (7, 5, 3, 1), (4097, 8, 2, 2), (9001, 384, 96, 2), (196609, 5, 3, 2), (196609, 8, 2, 2), (458753, 5, 3, 2), (458753, 8, 2, 2)]
 
 
 @pytest.mark.parametrize("V, C, Ch, B", CA_CASES)
@@ -331,7 +332,8 @@ def _loss_case(V, C, kind="plain", dloss=0.75):
     return inputs, got
 
 
-@pytest.mark.parametrize("V, C", [(1, 2), (5, 2), (4097, 2), (9001, 4), (300, 16)])
+# (the last four: 49 and 113 slabs per sample)
+@pytest.mark.parametrize("V, C", [(1, 2), (5, 2), (4097, 2), (9001, 4), (300, 16), (196609, 2), (196609, 4), (458753, 2), (458753, 4)])
 def test_softmax_dice_loss_values(V, C):
     _loss_case(V, C)
 
