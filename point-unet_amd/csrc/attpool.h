@@ -37,15 +37,29 @@ struct AttStage {
     int64_t n_total = 0, n_cloud = 0;
     int d = 0, k = 16;
     const Att32Weights* p32 = nullptr;  // when set (d >= 64, pre-product formulation): the 32x32x2 kernels (attpool32.hip)
+    const float* lane = nullptr;        // when set (d = 16, direct formulation): the stage's plain fp32 image (attpool_lane.hip: pack_lane_image)
 };
+
+// Plain fp32 image of one d = 16 attention stage for att_lane_kernel (attpool_lane.hip), offsets in floats: b1 [8] | W1 [10, 8] | b2 [8] |
+// W2 [8, 8] | Wfc [16, 16] times log2(e), all row-major [cin, cout]: 13 chunks of 32 floats, the unit the kernel fetches.  b2 / W2 are zero
+// in a stage-1 image.
+constexpr int kLaneB1 = 0, kLaneW1 = 8, kLaneB2 = 88, kLaneW2 = 96, kLaneWfc = 160, kLaneImageFloats = 416;
+void pack_lane_image(const float* W1, const float* b1, const float* W2, const float* b2, const float* wfc_scaled, float* out);
 
 bool att_pool32_fits(const AttStage& s);
 int att_pool32_stage(ps_context* c, const AttStage& s);
 bool att_pool32b_fits(const AttStage& s);
 int att_pool32b_stage(ps_context* c, const AttStage& s);
 
-// the 32x32 forms when they fit (the split-bf16 one first, when the context asks for it), otherwise att_pool16_stage
+// the vector-ALU kernel of attpool_lane.hip (one lane per neighbour row): d = 16, K = 16, direct formulation, the context's att_lane switch on
+bool att_lane_fits(const ps_context* c, const AttStage& s);
+int att_lane_stage(ps_context* c, const AttStage& s);  // (PS_EINVAL outside d = 16 / K = 16 / direct, whatever the knob says)
+int att_lane_pass_points();  // points one pass of its grid covers (beyond that a wave loops)
+
+// the 32x32 forms when they fit (the split-bf16 one first, when the context asks for it), the lane form at d = 16 / K = 16, otherwise
+// att_pool16_stage; att_pool_form names the choice as ps_debug_att_stage numbers its forms (1 bf16x3, 2 32x32, 3 16x16x4, 4 lane)
 int att_pool_stage(ps_context* c, const AttStage& s);
+int att_pool_form(const ps_context* c, const AttStage& s);
 // the 16x16x4 kernels of attpool.hip: the direct formulation when wfull is set (d <= 32), otherwise the pre-product kernel att_kernel --
 // what a level too large for the 32x32 forms (2^24 rows, 4 GiB of fg) runs
 int att_pool16_stage(ps_context* c, const AttStage& s);

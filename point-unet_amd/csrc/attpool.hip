@@ -13,6 +13,7 @@
 // A 16x16 MFMA output tile is exactly (16 neighbours) x (16 channels) of one point.
 //
 // Bound: fp32 MFMA for d >= 64; latency/L2 for d = 16 (level 0).
+// Level 0 of the shipped network (d = 16, K = 16) runs on attpool_lane.hip's vector-ALU kernel; att_direct_kernel below is its K = 32 / d = 32 form.
 #include "attpool.h"
 #include "mfma_tile.h"
 
@@ -561,7 +562,15 @@ int att_pool_stage(ps_context* c, const AttStage& s)
 {
     if (c->att_bf16x3 && att_pool32b_fits(s)) return att_pool32b_stage(c, s);
     if (att_pool32_fits(s)) return att_pool32_stage(c, s);
+    if (att_lane_fits(c, s)) return att_lane_stage(c, s);
     return att_pool16_stage(c, s);
+}
+
+int att_pool_form(const ps_context* c, const AttStage& s)
+{
+    if (c->att_bf16x3 && att_pool32b_fits(s)) return 1;
+    if (att_pool32_fits(s)) return 2;
+    return att_lane_fits(c, s) ? 4 : 3;
 }
 
 int att_pool16_stage(ps_context* c, const AttStage& s)

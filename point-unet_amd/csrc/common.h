@@ -172,6 +172,8 @@ struct ps_context {
     bool att_bf16x3 = true;   // ps_set_att_bf16x3: attentive pooling at d = 64 / 128 on bf16 MFMA over three-way splits (attpool32b.hip)
     // (no public setter: a constant in the default build, PS_REGCHAIN_B3=0 under -DPS_TUNING_ENV, ps_debug_set_regchain_b3 for the tests)
     bool regchain_b3 = true;  // the routed layer-chain shapes (regchain.hip: kRcSplit) on bf16 MFMA over three-way splits instead of the fp32 MFMA
+    // (like regchain_b3: a constant in the default build, PS_ATT_LANE=0 under -DPS_TUNING_ENV, ps_debug_set_att_lane for the tests)
+    bool att_lane = true;     // forward attention at d = 16 / K = 16 on the vector-ALU kernel (attpool_lane.hip) instead of att_direct_kernel (16x16x4 MFMA)
     bool train_b3 = true;     // ps_set_train_gemm_b3: large fp32 op-level GEMMs on bf16 MFMA over exact three-way splits (gemm_b3.hip)
     bool conv_w_transposed = false;  // (internal, set around a call by the native trainer) ps_op_conv1x1_ex: w is stored [cout, cin]
     bool att_df_accum = false;  // (internal, set around a call by the native trainer) ps_op_att_pool_train_bwd_split*: dfr += instead of dfr =

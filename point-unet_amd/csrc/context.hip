@@ -250,6 +250,7 @@ int ps_create(int device, ps_context** out)
     ps::tuning_from_env(c->tune);  // (nothing in the default build: common.h, struct Tuning)
 #ifdef PS_TUNING_ENV
     if (const char* v = std::getenv("PS_REGCHAIN_B3")) c->regchain_b3 = std::atof(v) != 0;  // (a context switch, not a field of Tuning: common.h)
+    if (const char* v = std::getenv("PS_ATT_LANE")) c->att_lane = std::atof(v) != 0;        // (likewise)
 #endif
     *out = c;
     return PS_OK;

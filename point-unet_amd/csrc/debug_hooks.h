@@ -92,13 +92,23 @@ int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4);
 /* The operand policy of regchain's routed chain shapes on this context (on by default): 1 = bf16 MFMA over exact three-way splits, 0 = the fp32
  * MFMA for every shape.  ps_debug_chain forms 0 and 1 follow it; ps_debug_chain_plan has no context and reports the fp32 launch. */
 int ps_debug_set_regchain_b3(ps_context* ctx, int on);
+/* Where att_pool_stage sends a d = 16 / K = 16 stage of the direct formulation on this context (on by default): 1 = att_lane_kernel
+ * (attpool_lane.hip, the vector ALU), 0 = att_direct_kernel (16x16x4 MFMA).  ps_debug_att_stage form 0 and ps_debug_att_form follow it. */
+int ps_debug_set_att_lane(ps_context* ctx, int on);
 /* One attentive-pooling stage (1 or 2) of encoder level `level` of a live network with its weights set, on the network's own packed images
  * (log2(e) scaling and weight halves included); AttStage is filled as ps_randla_forward fills it.  xyz f32[n_total, 3], idx i32[n_total, K]
  * (cloud-local), order i32[n_total] or NULL, fg f32[n_total, d/2 + d] = [f | G] for d >= 64 and f32[n_total, d/2] = f below, agg f32[n_total, d]:
  * DEVICE pointers.  form 0: att_pool_stage (the product's dispatch), 1: att_pool32b_stage (split-bf16 32x32), 2: att_pool32_stage (fp32 32x32),
- * 3: att_pool16_stage (16x16x4: the direct kernel at d <= 32, att_kernel above).  PS_EINVAL when the level does not fit the form. */
+ * 3: att_pool16_stage (16x16x4: the direct kernel at d <= 32, att_kernel above), 4: att_lane_stage (the vector-ALU kernel of attpool_lane.hip,
+ * d = 16 and K = 16 only, whatever the context's att_lane switch says).  PS_EINVAL when the level does not fit the form. */
 int ps_debug_att_stage(ps_randla* net, int level, int stage, int form, const float* xyz, const int32_t* idx, const int32_t* order, const float* fg,
                        int64_t n_total, int64_t n_cloud, float* agg);
+/* The form (1 .. 4, numbered as above) att_pool_stage takes for stage 1 or 2 of encoder level `level` at k neighbours and n_total rows, on the
+ * network's context as its knobs stand -- bit-identical outputs cannot show which kernel ran.  Host only.  Returns the form, not a status: -1 on
+ * a bad argument. */
+int ps_debug_att_form(ps_randla* net, int level, int stage, int k, int64_t n_total);
+/* Points one pass of att_lane_kernel's largest grid covers (workgroups x waves x points per wave iteration): past it a wave walks on. */
+int ps_debug_att_lane_pass_points(void);
 
 /* The experiment knobs of one context (csrc/common.h, struct ps::Tuning), by C++ field name ("inv_bucket", "gemm32b_rw", ...).  Set accepts
  * exactly the values the kernels are compiled for (the rules of the -DPS_TUNING_ENV build, without its clamping) and refuses anything else,

@@ -242,6 +242,13 @@ extern "C" int ps_debug_set_regchain_b3(ps_context* c, int on)
     return PS_OK;
 }
 
+extern "C" int ps_debug_set_att_lane(ps_context* c, int on)
+{
+    PS_CHECK(c && (on == 0 || on == 1), "ps_debug_set_att_lane: bad argument");
+    c->att_lane = on != 0;
+    return PS_OK;
+}
+
 // --------------------------------------------------------------------------------------------------------
 // one attentive-pooling stage of a live network (randla_net.h), through each of its stage functions (attpool.h)
 // --------------------------------------------------------------------------------------------------------
@@ -250,7 +257,7 @@ extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form
 {
     PS_CHECK(net && xyz && idx && fg && agg, "ps_debug_att_stage: NULL argument");
     PS_CHECK(net->have_weights, "ps_debug_att_stage: weights not set");
-    PS_CHECK(level >= 0 && level < net->cfg.num_layers && (stage == 1 || stage == 2) && form >= 0 && form <= 3, "ps_debug_att_stage: bad level / stage / form");
+    PS_CHECK(level >= 0 && level < net->cfg.num_layers && (stage == 1 || stage == 2) && form >= 0 && form <= 4, "ps_debug_att_stage: bad level / stage / form");
     PS_CHECK(n_total >= 0 && n_cloud >= 1 && n_total % n_cloud == 0, "ps_debug_att_stage: n_total must be a whole number of clouds");
     ps_context* c = net->ctx;
     PS_HIP(hipSetDevice(c->device));
@@ -264,8 +271,10 @@ extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form
     s.lfa2 = stage == 2 ? &e.lfa2 : nullptr;
     s.wbot = use_g ? (stage == 1 ? &e.bot1 : &e.bot2) : nullptr;
     s.wfull = use_g ? nullptr : (stage == 1 ? &e.full1 : &e.full2);
+    s.lane = stage == 1 ? e.lane1 : e.lane2;
     int rc = PS_EINVAL;
-    if (form == 0) rc = att_pool_stage(c, s);
+    if (form == 4) rc = att_lane_stage(c, s);  // (refuses everything but d = 16 / K = 16 itself)
+    else if (form == 0) rc = att_pool_stage(c, s);
     else if (form == 1 && att_pool32b_fits(s)) rc = att_pool32b_stage(c, s);
     else if (form == 2 && att_pool32_fits(s)) rc = att_pool32_stage(c, s);
     else if (form == 3) rc = att_pool16_stage(c, s);
@@ -273,6 +282,27 @@ extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form
     (void)hipStreamSynchronize(c->stream);
     return rc;
 }
+
+extern "C" int ps_debug_att_form(ps_randla* net, int level, int stage, int k, int64_t n_total)
+{
+    if (!net || !net->have_weights || level < 0 || level >= net->cfg.num_layers || (stage != 1 && stage != 2) || k < 1 || n_total < 0) {
+        set_error("ps_debug_att_form: bad argument");
+        return -1;
+    }
+    const EncLevel& e = net->enc[level];
+    const int d = e.d, h = d / 2;
+    const bool use_g = d >= 64;
+    AttStage s;  // (the fields the dispatch reads, filled as ps_randla_forward fills them)
+    s.lfa1 = &e.lfa1; s.lfa2 = stage == 2 ? &e.lfa2 : nullptr;
+    s.wbot = use_g ? (stage == 1 ? &e.bot1 : &e.bot2) : nullptr;
+    s.wfull = use_g ? nullptr : (stage == 1 ? &e.full1 : &e.full2);
+    s.lane = stage == 1 ? e.lane1 : e.lane2;
+    s.p32 = e.has_p32 ? &e.p32 : nullptr;
+    s.n_total = n_total; s.n_cloud = n_total; s.d = d; s.k = k; s.ldf = use_g ? h + d : h;
+    return att_pool_form(net->ctx, s);
+}
+
+extern "C" int ps_debug_att_lane_pass_points(void) { return att_lane_pass_points(); }
 
 // --------------------------------------------------------------------------------------------------------
 // the knobs of struct Tuning (common.h) by field name.  X(field, accepted values of v): the rules of tuning_from_env (context.hip) without

@@ -7,6 +7,7 @@
 //                                                       score pre-product G = f . Wfc[:h,:], only for d >= 64, see attpool.hip;
 //                                                       at level 0 mlp1 rides on fc0's chain)
 //   att<1>   LocSE+gather+att-pool 1                  -> AGG[R,d]             (:325-329, :337-343, :394-398)
+//            (d = 16, K = 16 -- level 0 as shipped: att_lane_kernel, attpool_lane.hip, one lane per neighbour row on the vector ALU)
 //   chain    att_pooling_1 mlp [-> Wfc2[:h,:]]  AGG   -> FG2[:, 0:h] [, FG2[:, h:h+d]]   (:400)
 //   att<2>   LocSE+mlp2+gather+att-pool 2             -> AGG[R,d]             (:331-334)
 //   chain    att_pooling_2 mlp -> [mlp2 ; shortcut] over [that | X]   -> ENC_i[R,2d]  (+LeakyReLU)   (:400, :317-321)
@@ -293,6 +294,17 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
             emit(e.full2, sc.data(), nullptr, d, d, 0);
         }
         ++si;
+        e.lane1 = e.lane2 = nullptr;
+        if (d == 16) {  // the vector-ALU attention kernel's images: the floats of lfa1 / lfa2 and the same log2(e) products as full1 / full2
+            auto scaled16 = [&](const float* src) {
+                tmp.resize(256);
+                for (size_t t = 0; t < 256; ++t) tmp[t] = (float)((double)src[t] * 1.4426950408889634);
+                return tmp.data();
+            };
+            const size_t lfa1_i = si - 5, fc1_i = si - 4, lfa2_i = si - 2, fc2_i = si - 1;
+            pack_lane_image(W(lfa1_i), Bv(lfa1_i), nullptr, nullptr, scaled16(W(fc1_i)), emit_raw(&e.lane1, kLaneImageFloats));
+            pack_lane_image(W(lfa1_i), Bv(lfa1_i), W(lfa2_i), Bv(lfa2_i), scaled16(W(fc2_i)), emit_raw(&e.lane2, kLaneImageFloats));
+        }
         emit(e.att2mlp, W(si), Bv(si), d, d, 1); ++si;
         // [mlp2 ; shortcut] over the concatenated K axis, biases summed, LeakyReLU on the sum (RandLANet.py:317-321)
         tmp.assign((size_t)(d + d_in) * 2 * d + 2 * d, 0.f);
@@ -417,6 +429,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         s.xyz = pyr->xyz[i]; s.idx = pyr->neigh_idx[i]; s.order = pyr->order[i]; s.fg = fg; s.lfa1 = &e.lfa1; s.agg = agg;
         s.n_total = R; s.n_cloud = n[i]; s.d = d; s.k = cfg.k_n; s.ldf = ldf;
         s.p32 = e.has_p32 ? &e.p32 : nullptr;
+        s.lane = e.lane1;
         // f = act(x . W + b) [-> G = f . Wfc[:h]]: one chained launch when it fits
         auto feature_rows = [&](const PackedLinear& mlp, const PackedLinear& top, const RowSrc& in) -> int {
             ChainStep ch[2] = {step(mlp, fg, ldf), step(top, fg + h, ldf)};
@@ -453,6 +466,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
             std::snprintf(nm, sizeof nm, "enc%d_att2", i);
             Stage st(c, nm, 1);
             s.lfa2 = &e.lfa2; s.wbot = use_g ? &e.bot2 : nullptr; s.wfull = use_g ? nullptr : &e.full2;
+            s.lane = e.lane2;
             PS_TRY(att_pool_stage(c, s));
         }
         {

@@ -20,6 +20,7 @@ struct EncLevel {
     PackedLinear mlp1, top1, lfa1, bot1, full1, att1mlp, lfa2, top2, bot2, full2, att2mlp, mlp2sc;
     Att32Weights p32;  // d >= 64: weight images of the 32x32x2 attentive-pooling kernels
     bool has_p32 = false;
+    const float *lane1 = nullptr, *lane2 = nullptr;  // d = 16: plain fp32 images of the two attention stages (attpool_lane.hip: pack_lane_image)
     int d_in, d;
 };
 
