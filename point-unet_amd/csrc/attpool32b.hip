@@ -28,6 +28,17 @@ namespace ps {
 
 struct Att32bArgs : Att32ArgsT<uint4> {};  // w1: pack_b3_locse image; w2, wb: pack_b3 images
 
+// fg as a raw buffer of `bytes` bytes (descriptor from kernel arguments only: wave-uniform, four scalar registers) and one float of it at
+// a 32-bit byte offset: buffer_load_dword with the offset register as it is, a constant part of `off` in the instruction's immediate
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t fg_rsrc(const float* fg, unsigned bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(fg), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float fg_load(__amdgpu_buffer_rsrc_t r, unsigned off)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
+}
+
 __device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int lane)
 {
     B3Planes r;
@@ -35,6 +46,25 @@ __device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int 
     r.p[1] = img[(slot * 3 + 1) * 64 + lane];
     r.p[2] = img[(slot * 3 + 2) * 64 + lane];
     return r;
+}
+
+// Staging of an image of N uint4 by NT threads through registers: trip j is element tid + j NT.  A trip that only some threads take
+// (the last, when NT does not divide N) loads a clamped index -- an unconditional load stays a register -- and guards its write.
+template <int N, int NT, int R>
+__device__ __forceinline__ void stage_load(uint4 (&r)[R], const uint4* __restrict__ src, int tid)
+{
+#pragma unroll
+    for (int j = 0; j * NT < N; ++j) r[j] = src[(j + 1) * NT <= N ? tid + j * NT : min(tid + j * NT, N - 1)];
+}
+template <int N, int NT, bool WHOLE, int R>  // WHOLE: the trips every thread takes; else the partial one
+__device__ __forceinline__ void stage_write(uint4* dst, const uint4 (&r)[R], int tid)
+{
+#pragma unroll
+    for (int j = 0; j * NT < N; ++j) {
+        if ((j + 1) * NT <= N) {
+            if (WHOLE) dst[tid + j * NT] = r[j];
+        } else if (!WHOLE && tid + j * NT < N) dst[tid + j * NT] = r[j];
+    }
 }
 
 template <int D, int STAGE, int KN, int WAVES>
@@ -55,9 +85,27 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
     float* own = smem + WTOT + wave * (32 + TILE);
     int* NB = reinterpret_cast<int*>(own);
     float* T1 = own + 32;
-    for (int i = threadIdx.x; i < W1Q; i += WAVES * 64) Wq[i] = a.w1[i];
-    for (int i = threadIdx.x; i < W2Q; i += WAVES * 64) Wq[W1Q + i] = a.w2[i];
-    for (int i = threadIdx.x; i < WBQ; i += WAVES * 64) Wq[W1Q + W2Q + i] = a.wb[i];
+    // Staging: a thread's 16-byte loads of the three images are requested before the first LDS write (d = 128, stage 2: 1 + 3 + 6 of
+    // 512 threads; d = 64: one each) -- written as `Wq[i] = a.w1[i]` loops they were one load, one wait and one write per trip, ten
+    // dependent L2 round trips in front of the first tile.  The writes of the trips that every thread takes are one basic block with
+    // their loads (nine in flight at d = 128, stage 2); the compiler moves the load of a partial trip (d = 128: 384 uint4 of w1 over
+    // 512 threads) into the guarded block of its write, a round trip of its own: two in all.
+    {
+        constexpr int NT = WAVES * 64;
+        constexpr int N1 = (W1Q + NT - 1) / NT, N2 = (W2Q + NT - 1) / NT, NB3 = (WBQ + NT - 1) / NT;
+        static_assert(N1 + N2 + NB3 <= 12, "att32b: the staging loads of a thread are held in registers");
+        const int tid = threadIdx.x;
+        uint4 r1[N1], r2[N2 ? N2 : 1], rb[NB3];
+        stage_load<W1Q, NT>(r1, a.w1, tid);
+        stage_load<W2Q, NT>(r2, a.w2, tid);
+        stage_load<WBQ, NT>(rb, a.wb, tid);
+        stage_write<W1Q, NT, true>(Wq, r1, tid);
+        stage_write<W2Q, NT, true>(Wq + W1Q, r2, tid);
+        stage_write<WBQ, NT, true>(Wq + W1Q + W2Q, rb, tid);
+        stage_write<W1Q, NT, false>(Wq, r1, tid);
+        stage_write<W2Q, NT, false>(Wq + W1Q, r2, tid);
+        stage_write<WBQ, NT, false>(Wq + W1Q + W2Q, rb, tid);
+    }
     float* bias = smem + (W1Q + W2Q + WBQ) * 4;
     for (int i = threadIdx.x; i < H; i += WAVES * 64) {
         bias[i] = a.b1[i];
@@ -69,6 +117,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 
     constexpr int TPW = WAVES;
     const int tiw = wave;
+    const __amdgpu_buffer_rsrc_t fgr = fg_rsrc(a.fg, (unsigned)a.n_total * (unsigned)(LDF * 4));
 #include "att32_tile_walk.h"
     for (int t0 = t_first; t0 < t_end; t0 += t_step) {
 #include "att32_tile_row.h"
@@ -79,15 +128,20 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
         wave_lds_sync();
         unsigned off[16];  // of this lane's column of the first column block
         ATT32_ROW_OFFSETS(off, NB, LDF, (unsigned)c32 * 4u);
-        const char* fgb = reinterpret_cast<const char*>(a.fg);
+        // The gathers of the later blocks are issued in other basic blocks than the one that computes off[] (gstage and the guarded stores
+        // of the pooling split the tile), and as `fgb + off[r] + rel` only the FIRST block's loads were selected in the scalar-base +
+        // 32-bit-offset form: the sum base + zext(off[r]) is hoisted as ONE 64-bit value, and a later block sees a 64-bit pointer, not
+        // the zero-extension (d = 64: 16 of 48 gathers with a v_lshl_add_u64 and a zero high half each; d = 128: 64 of 96).  A raw buffer
+        // load takes the 32-bit offset as such wherever it is issued; the range of the descriptor is fg's n_total rows of LDF floats
+        // (32-bit byte offsets: att_pool32_fits).
         f32x2 gq[2][8], v[2][8];
         auto gather = [&](int i, f32x2 (&gdst)[8], f32x2 (&vdst)[8]) {
-            const int rel = i * 32 * 4;  // compile-time (the loop below is fully unrolled)
+            const int rel = i * 32 * 4;  // compile-time (the loop below is fully unrolled): the instruction's immediate
 #pragma unroll
-            for (int r = 0; r < 16; ++r) gdst[r >> 1][r & 1] = *reinterpret_cast<const float*>(fgb + off[r] + (rel + H * 4));
+            for (int r = 0; r < 16; ++r) gdst[r >> 1][r & 1] = fg_load(fgr, off[r] + (rel + H * 4));
             if (i * 32 < H) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) vdst[r >> 1][r & 1] = *reinterpret_cast<const float*>(fgb + off[r] + rel);
+                for (int r = 0; r < 16; ++r) vdst[r >> 1][r & 1] = fg_load(fgr, off[r] + rel);
             }
         };
         gather(0, gq[0], v[0]);  // the first block's G and value rows travel under the two small products
@@ -349,6 +403,7 @@ static int launch_att32b(ps_context* c, const Att32bArgs& a)
     // d = 128: 78 KB of weight planes + eight 8.8 KB tiles = 148 KB: one workgroup of eight waves per CU; d = 64: 21 KB + twelve 4.7 KB
     // tiles, one workgroup of twelve waves (134 registers: three waves per SIMD) in stage 2
     // (d = 64, stage 1: sixteen waves -- 126 registers, four waves per SIMD: 43.5 -> 41.2 us; stage 2 needs 134 and spills at sixteen: 50.0 -> 51.0)
+    // (with the gathers as buffer loads the counts are 116 and 124: sixteen waves would fit stage 2 now -- not measured)
     constexpr int WAVES = D == 128 ? 8 : (STAGE == 1 ? 16 : 12);
     constexpr int PER_CU = 1;
     constexpr size_t planes = (size_t)(CBH + (STAGE == 2 ? CBH * NQ : 0) + CBD * NQ) * 3 * 64 * 16;

@@ -47,6 +47,9 @@ int ps_debug_pack_weights(const float* W, int cin, int cout, int ntb, float* out
 /* Three-plane bfloat16 image of a row-major W[cin,cout] for the split-bf16 attention kernels (csrc/attpool32b.hip: pack_b3):
  * out = uint16 [cout/32][cin/16][3 planes][64 lanes][8]. */
 int ps_debug_pack_b3(const float* W, int cin, int cout, uint16_t* out);
+/* The three planes of the same W by the DEVICE split (csrc/b3_ops.h: b3_split8, through the training step's packing kernel, kind 5 =
+ * the K order of pack_b3); needs a GPU.  W, out: DEVICE pointers; out = uint16 [cin/16][cout/32][3 planes][64 lanes][8]. */
+int ps_debug_pack_b3_device(ps_context* ctx, const float* W, int cin, int cout, void* out);
 /* One dense layer of the deep levels, Y = act([X1[g1] | X2[g2]] . W + b), through gemm32b.hip (split_bf16 != 0: bf16 MFMA over exact
  * three-way splits) or gemm32.hip (fp32 MFMA); needs a GPU.  x1 / x2 / g1 / g2 / y: DEVICE pointers (g* may be NULL: plain rows; gm / gn:
  * batched gather, row r reads x[(r / gm) * gn + g[r]] when gm != 0), W [c1 + c2, cout] and bias [cout]: HOST.  Returns PS_EINVAL when the

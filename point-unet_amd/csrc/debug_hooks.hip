@@ -36,6 +36,22 @@ extern "C" int ps_debug_pack_b3(const float* W, int cin, int cout, uint16_t* out
     return PS_OK;
 }
 
+// the same image from the DEVICE split (b3_split8 through pack_batch_b3's kind 5, the accumulator K order that pack_b3 writes too)
+extern "C" int ps_debug_pack_b3_device(ps_context* c, const float* W, int cin, int cout, void* out)
+{
+    PS_CHECK(c && W && out && cin > 0 && cin % 32 == 0 && cout > 0 && cout % 32 == 0, "ps_debug_pack_b3_device: bad argument");
+    PS_HIP(hipSetDevice(c->device));
+    PackJob j{};
+    j.w = W; j.sk = cout; j.sn = 1; j.kind = 5; j.cin = cin; j.cout = cout; j.out = out;
+    j.total = (int64_t)(cin / 16) * (cout / 32) * 64;
+    PackJob* table = nullptr;
+    PS_HIP(hipMalloc(reinterpret_cast<void**>(&table), sizeof(PackJob)));
+    int rc = hipMemcpy(table, &j, sizeof(PackJob), hipMemcpyHostToDevice) == hipSuccess ? pack_batch_b3(c, table, 1) : PS_EINVAL;
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(table);
+    return rc;
+}
+
 // one dense layer through gemm32b.hip / gemm32.hip with freshly packed weight images (the product packs them once per network)
 extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, int ld1, int c1, const int32_t* g1, const float* x2, int ld2, int c2,
                                const int32_t* g2, int gm, int gn, const float* W, const float* bias, int64_t R, int cout, int leaky, float* y, int ldy)
