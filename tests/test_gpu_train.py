@@ -479,7 +479,8 @@ def test_fused_attentive_pooling_forward_backward(mode):
     """ps_op_att_pool_train_fwd / _bwd (score product + softmax over K + weighted sum in one kernel per direction; the backward
     recomputes scores and probabilities) against torch float64 autograd of  agg = sum_K softmax_K(F.W) * F  -- for the bf16 mode with
     the operands of the three products rounded exactly as the kernel rounds them (F, W for the scores; dS, W^T for dF; F, dS for dW).
-    Strided input (a column block of a wider buffer), ragged point counts, d = 16 / 32 / 64 (and 128 in the bf16 mode).  Bars: agg 2e-6 (fp32) / 2e-5 (bf16) of its
+    Strided input (a column block of a wider buffer), ragged point counts down to a single point, d = 16 / 32 / 64 (and 128 in the bf16
+    mode); at R = 37 also the plain form's per-element store path (a row pitch of d + 2), bit-identical to the row stores.  Bars: agg 2e-6 (fp32) / 2e-5 (bf16) of its
     max; dF and dW 2e-5 of their max in fp32; in the bf16 mode 2e-3 / 1e-3: dS is rounded to bfloat16 from its fp32 value in the
     kernel and from its float64 value here, and an element within fp32 noise of a rounding boundary lands on the neighbouring
     bfloat16 (a 4e-3 relative change of that one term).  The weight gradient is bit-identical from run to run (fixed summation order)."""
@@ -495,8 +496,12 @@ def test_fused_attentive_pooling_forward_backward(mode):
     try:
         _lib.check(L.ps_set_train_gemm_bf16(h, 1 if mode == "bf16" else 0))
         shapes = [(1000, 16, 16), (4097, 16, 32), (777, 32, 32), (2049, 64, 64), (300, 64, 128)]
+        # tiny point counts: one point (seven of a workgroup's eight waves idle), four, and 37 (the last workgroup ends mid-way)
+        shapes += [(1, 16, 16), (4, 16, 16), (37, 16, 32), (1, 32, 32), (4, 32, 32), (37, 32, 48)]
         if mode == "bf16":  # d = 128 (level 2) exists on the bf16 matrix pipe only: both weight orientations as bfloat16 in LDS
             shapes += [(1500, 128, 128), (333, 128, 192)]
+            # (the column-split backward: one live group of three / a second workgroup with one live group / a ragged end)
+            shapes += [(1, 128, 128), (4, 128, 128), (37, 128, 160)]
         for R, d, wide in shapes:
             assert L.ps_op_att_pool_train_supported_ex(K, d, 1 if mode == "bf16" else 0) == 1
             buf = torch.randn(R * K, wide, generator=g).cuda()
@@ -510,7 +515,15 @@ def test_fused_attentive_pooling_forward_backward(mode):
             _lib.check(L.ps_op_att_pool_train_bwd(h, p(F), wide, p(W), p(dagg), R, K, d, p(dF), d, p(dW)))
             _lib.check(L.ps_op_att_pool_train_bwd(h, p(F), wide, p(W), p(dagg), R, K, d, p(dF), d, p(dW2)))
             assert torch.equal(dW, dW2)
-            # float64 yardstick with the same operand rounding
+            if R == 37:
+                # a row pitch that is no multiple of four floats takes the per-element store path of the plain form (at d = 128: the
+                # one-wave backward): same accumulators, same grid, another store instruction -- the written columns and dW are
+                # bit-identical, the padding columns untouched
+                dFp, dWp = torch.full((R * K, d + 2), -7.5).cuda(), torch.empty(d, d).cuda()
+                _lib.check(L.ps_op_att_pool_train_bwd(h, p(F), wide, p(W), p(dagg), R, K, d, p(dFp), d + 2, p(dWp)))
+                assert torch.equal(dFp[:, :d], dF), (R, d)
+                assert bool((dFp[:, d:] == -7.5).all()), (R, d)
+                assert torch.equal(dWp, dW), (R, d)
             Fd, Wd = F.double().reshape(R, K, d), W.double()
             S = rb(Fd) @ rb(Wd)
             P = torch.softmax(S, 1)
