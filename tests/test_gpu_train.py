@@ -616,7 +616,9 @@ def test_wide_level_split_source_forms_equal_the_materialised_ones(mode):
     """ps_op_att_pool_gemm_fwd_split / _bwd_split and ps_op_linear_wgrad_split (gather_neighbour + concat folded into the wide-level fused
     pooling and into the loader of the split-bf16 weight-gradient kernel, RandLANet.py:326-333) against the SAME kernels fed the
     materialised concat buffer: same products in the same order, so agg, both halves of dF, dS and dW are bit-identical; the f_xyz half
-    is also checked in its accumulate form.  Two clouds (the gathered rows are cloud-local), 650 of 700 points queried, d = 128 / 256."""
+    is also checked in its accumulate form.  Two clouds (the gathered rows are cloud-local), 650 of 700 points queried, d = 128 / 256;
+    and three clouds of 37 queried points out of 40: 111 points are an odd number (the last wave with rows holds ONE point, the fourth
+    wave of the workgroup none) and a cloud ends inside a wave's pair of points (each point takes its own cloud's rows)."""
     import ctypes
     import torch
     from point_unet_amd import _lib, runtime
@@ -624,10 +626,10 @@ def test_wide_level_split_source_forms_equal_the_materialised_ones(mode):
     h = ctx.handle
     p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     g = torch.Generator().manual_seed(29)
-    B, N, M, K = 2, 700, 650, 16
+    K = 16
     try:
         _lib.check(L.ps_set_train_gemm_bf16(h, 1 if mode == "bf16" else 0))
-        for d in (128, 256):
+        for B, N, M, d in [(2, 700, 650, 128), (2, 700, 650, 256), (3, 40, 37, 128), (3, 40, 37, 256)]:
             hh = d // 2
             fsrc = torch.randn(B * N, hh, generator=g).cuda()
             fx = torch.randn(B * M * K, hh, generator=g).cuda()
@@ -645,14 +647,15 @@ def test_wide_level_split_source_forms_equal_the_materialised_ones(mode):
                                          torch.empty(B * M * K, d).cuda(), torch.empty(d, d).cuda())
             _lib.check(L.ps_op_att_pool_gemm_fwd_split(h, p(fsrc), hh, p(idx), B, N, M, p(fx), hh, p(W), K, d, p(agg1)))
             _lib.check(L.ps_op_att_pool_gemm_bwd_split(h, p(fsrc), hh, p(idx), B, N, M, p(fx), hh, p(W), p(dagg), K, d, p(rows), hh, p(dfx), hh, 0, p(dS1), d))
-            _lib.check(L.ps_op_linear_wgrad_split(h, p(fsrc), hh, p(idx), B, N, M, K, p(fx), hh, p(dS1), d, d, d, p(dW1)))
-            assert torch.equal(agg0, agg1), d
-            assert torch.equal(dcat[:, :hh].contiguous(), rows) and torch.equal(dcat[:, hh:].contiguous(), dfx) and torch.equal(dS0, dS1), d
-            assert torch.equal(dW0, dW1), d
+            assert torch.equal(agg0, agg1), (B, d)
+            assert torch.equal(dcat[:, :hh].contiguous(), rows) and torch.equal(dcat[:, hh:].contiguous(), dfx) and torch.equal(dS0, dS1), (B, d)
+            if B * M * K >= 16384:  # (the split-source weight-gradient product takes 16 384 rows or more)
+                _lib.check(L.ps_op_linear_wgrad_split(h, p(fsrc), hh, p(idx), B, N, M, K, p(fx), hh, p(dS1), d, d, d, p(dW1)))
+                assert torch.equal(dW0, dW1), (B, d)
             seed = torch.randn(B * M * K, hh, generator=g).cuda()
             acc = seed.clone()
             _lib.check(L.ps_op_att_pool_gemm_bwd_split(h, p(fsrc), hh, p(idx), B, N, M, p(fx), hh, p(W), p(dagg), K, d, p(rows), hh, p(acc), hh, 1, p(dS1), d))
-            assert torch.equal(acc, seed + dfx), d
+            assert torch.equal(acc, seed + dfx), (B, d)
     finally:
         _lib.check(L.ps_set_train_gemm_bf16(h, 0))
     torch.cuda.synchronize()
@@ -773,6 +776,45 @@ def test_bf16_storage_of_the_lfa_rows_changes_only_the_format():
                 _lib.check(L.ps_op_gather_reduce_rows_ordered(hd, p(rows16), h, p(off), p(src), B * N, h, p(got_o), h, accumulate, p(perm), N))
                 act(False)
                 assert torch.equal(want, got) and torch.equal(want, got_o), (h, accumulate)
+    finally:
+        _lib.check(L.ps_set_train_act_bf16(hd, 0))
+        _lib.check(L.ps_set_train_gemm_bf16(hd, 0))
+    torch.cuda.synchronize()
+
+
+def test_bf16_rows_of_the_level1_pooling_where_a_wave_takes_a_second_tile():
+    """ps_op_att_pool_train_fwd_split / _bwd_split_rows at d = 64 (attpool_gemm.hip's attg64_kernel) fed bfloat16 rows fr, at a size where
+    the persistent grid is capped (256 workgroups per resident workgroup of a CU) and waves walk on to a second tile: 2 x 3 100 points = 3 100
+    tiles against 3 072 waves of the forward and 2 048 of the eight-wave backward -- the prefetch of the next tile's rows and of the index two
+    tiles ahead.  The assertions of test_bf16_storage_of_the_lfa_rows_changes_only_the_format: bit for bit what the same values handed over
+    as fp32 rows give, both halves of the gradient as bfloat16(RNE) of the fp32 form's values."""
+    import ctypes
+    import torch
+    from point_unet_amd import _lib, runtime
+    L, ctx = _lib.lib(), runtime.default_context(0)
+    hd = ctx.handle
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    g = torch.Generator().manual_seed(43)
+    B, N, K, h = 2, 3100, 16, 32
+    R, d = B * N * K, 2 * h
+    idx = torch.randint(0, N, (B, N, K), generator=g, dtype=torch.int32).cuda()
+    fsrc = torch.randn(B * N, h, generator=g).cuda()
+    x16 = torch.randn(R, h, generator=g).cuda().bfloat16()
+    Wfc = (torch.randn(d, d, generator=g) / d ** 0.5).cuda(); dagg = torch.randn(B * N, d, generator=g).cuda()
+    try:
+        _lib.check(L.ps_set_train_gemm_bf16(hd, 1))
+        assert L.ps_op_att_pool_train_supported_ex(K, d, 1) == 1
+        res = {}
+        for on, fr in ((False, x16.float()), (True, x16)):
+            _lib.check(L.ps_set_train_act_bf16(hd, 1 if on else 0))
+            agg = torch.empty(B * N, d).cuda(); dW = torch.empty(d, d).cuda()
+            rows = torch.empty(R, h, dtype=torch.bfloat16 if on else torch.float32).cuda()
+            dfr = torch.empty(R, h, dtype=torch.bfloat16 if on else torch.float32).cuda()
+            _lib.check(L.ps_op_att_pool_train_fwd_split(hd, p(fsrc), h, p(idx), B, N, N, p(fr), h, p(Wfc), K, d, p(agg)))
+            _lib.check(L.ps_op_att_pool_train_bwd_split_rows(hd, p(fsrc), h, p(idx), B, N, N, p(fr), h, p(Wfc), p(dagg), K, d, p(rows), h, p(dfr), h, p(dW)))
+            res[on] = (agg, rows if on else rows.bfloat16(), dfr if on else dfr.bfloat16(), dW)
+        for a_, b_ in zip(res[False], res[True]):
+            assert torch.equal(a_, b_)
     finally:
         _lib.check(L.ps_set_train_act_bf16(hd, 0))
         _lib.check(L.ps_set_train_gemm_bf16(hd, 0))
