@@ -337,10 +337,11 @@ static bool att_train_ok(int64_t K, int64_t d, int64_t ld, const void* f)
     return K == 16 && (d == 16 || d == 32 || d == 64 || d == 128) && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0;
 }
 
-// both split-source backward entries: the gathered half's gradient scatter-added into dfl (dfl_rows == nullptr), or written as rows
-static int att_bwd_split_impl(ps_context* c, const float* fl, int64_t ldl, const int32_t* idx, int64_t B, int64_t n_src, int64_t n_q, const float* fr,
-                              int64_t ldr, const float* wfc, const float* dagg, int64_t K, int64_t d, float* dfl, int64_t lddl, float* dfr, int64_t lddr,
-                              float* dwfc, float* dfl_rows, int64_t ld_rows)
+// both split-source backward entries: the gathered half's gradient scatter-added into dfl (dfl_rows == nullptr), or written as rows;
+// df_accum: dfr += instead of dfr = (common.h)
+int att_bwd_split_impl(ps_context* c, const float* fl, int64_t ldl, const int32_t* idx, int64_t B, int64_t n_src, int64_t n_q, const float* fr,
+                       int64_t ldr, const float* wfc, const float* dagg, int64_t K, int64_t d, float* dfl, int64_t lddl, float* dfr, int64_t lddr,
+                       float* dwfc, float* dfl_rows, int64_t ld_rows, bool df_accum)
 {
     PS_CHECK(c && fl && idx && fr && wfc && dagg && dfl && dfr && dwfc, "ps_op_att_pool_train_bwd_split: NULL argument");
     PS_CHECK(att_train_ok(K, d, ldr, fr) && ldl % 4 == 0 && (reinterpret_cast<uintptr_t>(fl) & 15) == 0 && n_src * ldl < (1ll << 31) && lddl >= d / 2 && lddr >= d / 2 && n_src > 0,
@@ -355,7 +356,7 @@ static int att_bwd_split_impl(ps_context* c, const float* fl, int64_t ldl, const
     AttTrainArgs a = {};
     a.f = fr; a.ld = (int)ldr; a.fl = fl; a.ldl = (int)ldl; a.idx = idx; a.n_src = n_src; a.n_q = n_q;
     a.w = wfc; a.dagg = dagg; a.df = dfr; a.lddf = (int)lddr; a.dfl = dfl; a.lddl = (int)lddl; a.R = R; a.bf16 = c->train_bf16 ? 1 : 0;
-    a.dfl_rows = dfl_rows; a.ld_rows = (int)ld_rows; a.df_accum = c->att_df_accum ? 1 : 0;
+    a.dfl_rows = dfl_rows; a.ld_rows = (int)ld_rows; a.df_accum = df_accum ? 1 : 0;
     a.fr_bf16 = c->train_act_bf16 && c->train_bf16 ? 1 : 0;  // (fr as bfloat16 rows: ps_set_train_act_bf16)
     return att_train_dispatch(c, a, d, true, dwfc);
 }
@@ -422,7 +423,7 @@ extern "C" int ps_op_att_pool_train_bwd_split(ps_context* c, const float* fl, in
                                               int64_t lddl, float* dfr, int64_t lddr, float* dwfc)
 {
     PS_CHECK(dfl, "ps_op_att_pool_train_bwd_split: NULL argument");
-    return att_bwd_split_impl(c, fl, ldl, idx, B, n_src, n_q, fr, ldr, wfc, dagg, K, d, dfl, lddl, dfr, lddr, dwfc, nullptr, 0);
+    return att_bwd_split_impl(c, fl, ldl, idx, B, n_src, n_q, fr, ldr, wfc, dagg, K, d, dfl, lddl, dfr, lddr, dwfc, nullptr, 0, false);
 }
 
 extern "C" int ps_op_att_pool_train_bwd_split_rows(ps_context* c, const float* fl, int64_t ldl, const int32_t* idx, int64_t B, int64_t n_src, int64_t n_q,
@@ -430,5 +431,5 @@ extern "C" int ps_op_att_pool_train_bwd_split_rows(ps_context* c, const float* f
                                                    float* dfl_rows, int64_t ld_rows, float* dfr, int64_t lddr, float* dwfc)
 {
     PS_CHECK(dfl_rows && ld_rows >= d / 2, "ps_op_att_pool_train_bwd_split_rows: dfl_rows is NULL or its row stride below d/2");
-    return att_bwd_split_impl(c, fl, ldl, idx, B, n_src, n_q, fr, ldr, wfc, dagg, K, d, dfl_rows, ld_rows, dfr, lddr, dwfc, dfl_rows, ld_rows);
+    return att_bwd_split_impl(c, fl, ldl, idx, B, n_src, n_q, fr, ldr, wfc, dagg, K, d, dfl_rows, ld_rows, dfr, lddr, dwfc, dfl_rows, ld_rows, false);
 }

@@ -175,13 +175,6 @@ struct ps_context {
     // (like regchain_b3: a constant in the default build, PS_ATT_LANE=0 under -DPS_TUNING_ENV, ps_debug_set_att_lane for the tests)
     bool att_lane = true;     // forward attention at d = 16 / K = 16 on the vector-ALU kernel (attpool_lane.hip) instead of att_direct_kernel (16x16x4 MFMA)
     bool train_b3 = true;     // ps_set_train_gemm_b3: large fp32 op-level GEMMs on bf16 MFMA over exact three-way splits (gemm_b3.hip)
-    bool conv_w_transposed = false;  // (internal, set around a call by the native trainer) ps_op_conv1x1_ex: w is stored [cout, cin]
-    bool att_df_accum = false;  // (internal, set around a call by the native trainer) ps_op_att_pool_train_bwd_split*: dfr += instead of dfr =
-    // a hint of the trainer for the op it enqueues next: i32[B, walk_order_n], the spatially coherent processing order (ps_pyramid.order) of the
-    // walk_order_n points per cloud the op's destinations are; NULL = none (ops called through the C ABI on their own never see one)
-    const int32_t* walk_order = nullptr;
-    int64_t walk_order_n = 0;
-    bool pool_bwd_overwrite = false;  // ps_op_random_sample_bwd_inv (tie-count form) STORES the gradient instead of adding into a zeroed buffer (trainer.hip)
     bool train_bf16 = false;  // ps_set_train_gemm_bf16: the op-level GEMMs round their operands to bf16 (fp32 accumulate)
     bool train_act_bf16 = false;  // ps_set_train_act_bf16: the [N*K, h] activation rows of the LFA branch are STORED as bfloat16 (include/pointseg_train_ops.h)
     // per-device kernel attributes already raised by this context (dynamic LDS above the default limit)
@@ -266,6 +259,22 @@ inline uint64_t pyramid_stamp(const ps_pyramid* p)
 // random_sample forward, vector form (randla.hip): out[b, m, :] = max over k of feat[b, idx[b, m, k], :], ch % 4 == 0; order: optional row walk
 int pool_max(ps_context* c, const float* feat, const int32_t* idx, const int32_t* order, float* out, int64_t B, int64_t n, int64_t m, int K, int ch,
              unsigned char* ties = nullptr);
+
+// Three ops with the arguments only the native trainer passes; each C entry is the one-line call with the value the ABI always had.
+// ps_op_conv1x1_ex (ops.hip); w_transposed: w is stored [cout, cin] (C entry: false)
+int conv1x1(ps_context* c, const float* x, int64_t ldx, const float* w, bool w_transposed, const float* b, int64_t R, int64_t cin, int64_t cout, int leaky,
+            int accumulate, float* y, int64_t ldy);
+// ps_op_att_pool_train_bwd_split (dfl_rows == nullptr) / _bwd_split_rows (dfl = dfl_rows) (attpool_train.hip); df_accum: dfr += instead of
+// dfr = (C entries: false)
+int att_bwd_split_impl(ps_context* c, const float* fl, int64_t ldl, const int32_t* idx, int64_t B, int64_t n_src, int64_t n_q, const float* fr,
+                       int64_t ldr, const float* wfc, const float* dagg, int64_t K, int64_t d, float* dfl, int64_t lddl, float* dfr, int64_t lddr,
+                       float* dwfc, float* dfl_rows, int64_t ld_rows, bool df_accum);
+// ps_op_random_sample_bwd_inv (invidx.hip); order: i32[B, order_n], the spatially coherent processing order (ps_pyramid.order) of the order_n
+// points per cloud the op's destinations are, or NULL; overwrite: the tie-count form STORES the gradient instead of adding into a zeroed
+// buffer (C entry: nullptr, 0, false)
+int random_sample_bwd_inv(ps_context* c, const float* dout, const float* out, const float* feature, const int32_t* pool_idx, const int32_t* offsets,
+                          const int32_t* src, int64_t B, int64_t N, int64_t M, int64_t K, int64_t d, const uint8_t* ties, float* share_ws,
+                          float* dfeature, const int32_t* order, int64_t order_n, bool overwrite);
 
 // weight-gradient partials (ops_train.hip): the GEMM writes one [rows, cols] partial per row slab, wgrad_finish adds them up in slab
 // order for a whole table of jobs in one launch (the native training step finishes every gradient of a step with it)

@@ -724,9 +724,15 @@ int ps_op_gather_reduce_rows(ps_context* c, const float* rows, int64_t ldr, cons
     return ps_op_gather_reduce_rows_ordered(c, rows, ldr, offsets, src, n_dst, d, dst, ldd, accumulate, nullptr, 0);
 }
 
-int ps_op_random_sample_bwd_inv(ps_context* c, const float* dout, const float* out, const float* feature, const int32_t* pool_idx, const int32_t* offsets,
-                                const int32_t* src, int64_t B, int64_t N, int64_t M, int64_t K, int64_t d, const uint8_t* ties, float* share_ws,
-                                float* dfeature)
+}  // extern "C"
+
+// ps_op_random_sample_bwd_inv with the native trainer's two extras as arguments (common.h).  order / order_n: i32[B, order_n], the leaf order
+// of the order_n points per cloud of this level (the ordered kernel walks its destinations in it, XCD by XCD; used when order_n == N), or
+// NULL.  overwrite: the tie-count form STORES the gradient -- zeros where nothing was pooled from a row -- instead of adding into a
+// zero-filled buffer
+int ps::random_sample_bwd_inv(ps_context* c, const float* dout, const float* out, const float* feature, const int32_t* pool_idx, const int32_t* offsets,
+                              const int32_t* src, int64_t B, int64_t N, int64_t M, int64_t K, int64_t d, const uint8_t* ties, float* share_ws,
+                              float* dfeature, const int32_t* order, int64_t order_n, bool overwrite)
 {
     PS_CHECK(c && dout && out && feature && pool_idx && offsets && src && (ties || share_ws) && dfeature, "ps_op_random_sample_bwd_inv: NULL argument");
     const size_t rows = (size_t)B * M;
@@ -739,22 +745,21 @@ int ps_op_random_sample_bwd_inv(ps_context* c, const float* dout, const float* o
         const int mode = c->tune.maxpool_bwd_ordered;  // (A/B knob: 0 = the one-entry cloud-order walk)
         const int64_t d4 = d / 4;
         if (mode && d4 <= 256 && 256 % d4 == 0) {
-            // (c->walk_order: the trainer's hint for the op it is about to enqueue -- the leaf order of the N points of this level, or NULL)
-            const int32_t* order = c->walk_order && c->walk_order_n == N ? c->walk_order : nullptr;
+            if (order_n != N) order = nullptr;
             const int64_t dpw = 256 / d4;
             const int64_t wgs = std::min<int64_t>((ceil_div(B * N, dpw) + 7) / 8 * 8, 8 * 4096);
             hipLaunchKernelGGL(maxpool_bwd_inv4_ordered_kernel, dim3((unsigned)wgs), dim3(256), 0, c->stream, dout, ties, out, feature,
                                reinterpret_cast<const unsigned*>(offsets), src, order, (unsigned)(B * N), (unsigned)N, (unsigned)M, (unsigned)K, (unsigned)d4,
-                               dfeature, c->pool_bwd_overwrite ? 1 : 0);
+                               dfeature, overwrite ? 1 : 0);
         } else {
             hipLaunchKernelGGL(maxpool_bwd_inv4_kernel, dim3(iv_grid(B * N * (d / 4))), dim3(256), 0, c->stream, dout, ties, out, feature,
                                reinterpret_cast<const unsigned*>(offsets), src, (unsigned)(B * N), (unsigned)N, (unsigned)M, (unsigned)K, (unsigned)(d / 4),
-                               dfeature, c->pool_bwd_overwrite ? 1 : 0);
+                               dfeature, overwrite ? 1 : 0);
         }
         PS_HIP(hipGetLastError());
         return PS_OK;
     }
-    PS_CHECK(!c->pool_bwd_overwrite, "ps_op_random_sample_bwd_inv: the overwriting form needs tie counts, d % 4 == 0 and 16-byte aligned rows");
+    PS_CHECK(!overwrite, "ps_op_random_sample_bwd_inv: the overwriting form needs tie counts, d % 4 == 0 and 16-byte aligned rows");
     if (ties) {
         hipLaunchKernelGGL(maxpool_bwd_inv_kernel<true>, dim3(iv_grid(B * N * d)), dim3(256), 0, c->stream, dout, ties, out, feature,
                            reinterpret_cast<const unsigned*>(offsets), src, B * N, (int)N, (int)M, (int)K, (int)d, dfeature);
@@ -769,4 +774,9 @@ int ps_op_random_sample_bwd_inv(ps_context* c, const float* dout, const float* o
     return PS_OK;
 }
 
-}  // extern "C"
+extern "C" int ps_op_random_sample_bwd_inv(ps_context* c, const float* dout, const float* out, const float* feature, const int32_t* pool_idx,
+                                           const int32_t* offsets, const int32_t* src, int64_t B, int64_t N, int64_t M, int64_t K, int64_t d,
+                                           const uint8_t* ties, float* share_ws, float* dfeature)
+{
+    return ps::random_sample_bwd_inv(c, dout, out, feature, pool_idx, offsets, src, B, N, M, K, d, ties, share_ws, dfeature, nullptr, 0, false);
+}

@@ -425,18 +425,18 @@ static bool tinyconv_fits(int64_t R, int64_t cin, int64_t cout, const float* x, 
     return R >= (1 << 20) && (cin == 8 || cin == 16) && (cout == 8 || cout == 16) && ldx % 4 == 0 && ldy % 4 == 0 &&
            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
 }
-}  // namespace ps
 
-extern "C" int ps_op_conv1x1_ex(ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R, int64_t cin, int64_t cout, int leaky,
-                                int accumulate, float* y, int64_t ldy)
+// ps_op_conv1x1_ex with the layout of `w` as an argument (common.h).  w_transposed: `w` is stored [cout, cin] -- the transposed-convolution
+// kernels of the decoder in the native training step's forward pass, every other layer's kernel in its input-gradient GEMM; the packing
+// kernels read it through strides, no transposed copy
+int conv1x1(ps_context* c, const float* x, int64_t ldx, const float* w, bool w_transposed, const float* b, int64_t R, int64_t cin, int64_t cout, int leaky,
+            int accumulate, float* y, int64_t ldy)
 {
     PS_CHECK(c && x && w && y, "ps_op_conv1x1: NULL argument");
     PS_CHECK(R >= 0 && cin >= 1 && cout >= 1 && ldx >= cin && ldy >= cout, "ps_op_conv1x1: bad shape");
     if (!R) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
-    // (internal switch of the native training step: `w` is stored [cout, cin] -- the transposed-convolution kernels of the decoder in the
-    //  forward pass, every other layer's kernel in its input-gradient GEMM; the packing kernels read it through strides, no transposed copy)
-    const bool wt = c->conv_w_transposed;
+    const bool wt = w_transposed;
     const int64_t sk = wt ? 1 : cout, sn = wt ? cin : 1;
     if (tinyconv_fits(R, cin, cout, x, ldx, y, ldy)) {
         Stage st(c, "op_conv1x1", 1);
@@ -498,6 +498,13 @@ extern "C" int ps_op_conv1x1_ex(ps_context* c, const float* x, int64_t ldx, cons
     RowSrc s1, none;
     s1.x = x; s1.ld = (int)ldx; s1.c = L.cin;
     return rowgemm(c, L, s1, none, R, y, (int)ldy);
+}
+}  // namespace ps
+
+extern "C" int ps_op_conv1x1_ex(ps_context* c, const float* x, int64_t ldx, const float* w, const float* b, int64_t R, int64_t cin, int64_t cout, int leaky,
+                                int accumulate, float* y, int64_t ldy)
+{
+    return ps::conv1x1(c, x, ldx, w, false, b, R, cin, cout, leaky, accumulate, y, ldy);
 }
 
 extern "C" int ps_op_conv1x1(ps_context* c, const float* x, const float* w, const float* b, int64_t R, int64_t cin, int64_t cout, int leaky, float* y)

@@ -16,6 +16,7 @@
 // (gradient mean, BatchNorm statistics shared by the ranks) go through a callback the host supplies (ps_trainer_set_collective: the
 // library does not link a communication library; RCCL sits behind torch.distributed in bench.py, behind ncclAllReduce in a C++ host).
 #include "common.h"
+#include "train_pool.h"
 
 #include <cmath>
 #include <functional>
@@ -50,116 +51,18 @@ struct TrainError {
     } while (0)
 
 // ---- device memory pool -----------------------------------------------------------------------------------------------------------
-// First-fit over address-ordered free blocks with coalescing, in chunks obtained from hipMalloc.  Everything runs on ONE stream, so a
-// block can be handed out again the moment the host drops it: the kernels that still read it were enqueued before the kernels of its
-// next user.  Chunks are never returned; the first step grows the pool to its high-water mark (a handful of chunks), every later
-// step of the same shape repeats the same allocation sequence and finds the same places (steady state: no hipMalloc).
-struct Pool {
-    struct Chunk {
-        char* base;
-        size_t size;
-    };
-    std::vector<Chunk> chunks;
-    std::map<char*, size_t> free_;
-    std::unordered_map<char*, size_t> used;
-    size_t in_use = 0, peak = 0, total = 0;
-
-    void add_chunk(size_t bytes)
+// train_pool.h (first fit, coalescing, the steady state of a repeated step) over chunks from hipMalloc
+struct HipChunks {
+    void* get(size_t bytes)
     {
         void* p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            ps::set_error("training pool: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-            throw TrainError{PS_ENOMEM};
-        }
-        chunks.push_back({static_cast<char*>(p), bytes});
-        free_[static_cast<char*>(p)] = bytes;
-        total += bytes;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) ps::set_error("training pool: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        return e == hipSuccess ? p : nullptr;
     }
-    void* alloc(size_t bytes)
-    {
-        bytes = (bytes + 255) & ~size_t(255);
-        if (!bytes) bytes = 256;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            for (auto it = free_.begin(); it != free_.end(); ++it) {
-                if (it->second < bytes) continue;
-                char* p = it->first;
-                const size_t rest = it->second - bytes;
-                free_.erase(it);
-                if (rest) free_[p + bytes] = rest;
-                used[p] = bytes;
-                in_use += bytes;
-                if (in_use > peak) peak = in_use;
-                return p;
-            }
-            // grow: at least the request, at least 1 GiB, at least half of what there is (few chunks even for a first, unsized step)
-            size_t want = std::max(bytes, std::max<size_t>(size_t(1) << 30, total / 2));
-            add_chunk(want);
-        }
-        ps::set_error("training pool: allocation of %zu bytes failed", bytes);
-        throw TrainError{PS_ENOMEM};
-    }
-    void release(void* q)
-    {
-        char* p = static_cast<char*>(q);
-        auto u = used.find(p);
-        if (u == used.end()) return;
-        size_t bytes = u->second;
-        used.erase(u);
-        in_use -= bytes;
-        auto nx = free_.lower_bound(p);
-        // merge with the following block (same chunk only: chunks are separate allocations and never adjacent by contract)
-        if (nx != free_.end() && p + bytes == nx->first && same_chunk(p, nx->first)) {
-            bytes += nx->second;
-            nx = free_.erase(nx);
-        }
-        if (nx != free_.begin()) {
-            auto pv = std::prev(nx);
-            if (pv->first + pv->second == p && same_chunk(pv->first, p)) {
-                pv->second += bytes;
-                return;
-            }
-        }
-        free_[p] = bytes;
-    }
-    bool same_chunk(const char* a, const char* b) const
-    {
-        for (const Chunk& c : chunks)
-            if (a >= c.base && a < c.base + c.size) return b >= c.base && b < c.base + c.size;
-        return false;
-    }
-    // in front of a step: everything is free again
-    void begin_step()
-    {
-        if (!used.empty()) {  // a step that failed half-way
-            used.clear();
-            in_use = 0;
-            free_.clear();
-            for (const Chunk& c : chunks) free_[c.base] = c.size;
-        }
-        // (several chunks stay several chunks: the allocation sequence of a step is deterministic, so first-fit places every tensor of
-        //  the next step exactly where it was -- merging them into one allocation cost a 20 GB hipFree + hipMalloc, ~1.4 s, in step 2)
-        peak = 0;
-    }
-    void destroy()
-    {
-        if (!chunks.empty()) (void)hipDeviceSynchronize();
-        for (const Chunk& c : chunks) (void)hipFree(c.base);
-        chunks.clear();
-        free_.clear();
-        used.clear();
-        in_use = total = 0;
-    }
+    void put(void* p) { (void)hipFree(p); }
 };
-
-struct Block {
-    Pool* pool;
-    void* p;
-    Block(Pool* pl, void* q) : pool(pl), p(q) {}
-    ~Block() { pool->release(p); }
-    Block(const Block&) = delete;
-    Block& operator=(const Block&) = delete;
-};
+using TrainPool = Pool<HipChunks>;
 
 // a 2-D fp32 device tensor (rows contiguous, row stride ld >= C); `own` keeps the pool block alive (null: caller-owned memory)
 struct Tn {
@@ -168,15 +71,15 @@ struct Tn {
     int id = -1;
     bool req = false;  // takes part in the backward pass
     bool b16 = false;  // rows STORED as bfloat16 (ps_train_options.act_bf16): only ever handed to the ops that read them that way
-    std::shared_ptr<Block> own;
+    std::shared_ptr<Block<HipChunks>> own;
     bool contiguous() const { return ld == C; }
     bool vec_ok() const { return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }  // float4 rows: what the row kernels ask of an operand
     int64_t numel() const { return R * C; }
     explicit operator bool() const { return p != nullptr; }
 };
 
-// sets a field of the context -- a mode the ops read: the bf16-GEMM mode, bfloat16-stored [N*K, h] rows (ps_set_train_act_bf16), the stream -- for
-// the lifetime of the object, then puts the previous value back
+// sets a public mode of the context that the ops read (the bf16-GEMM mode, bfloat16-stored [N*K, h] rows: ps_set_train_act_bf16) or its stream for
+// the lifetime of the object, then puts the previous value back.  (What belongs to ONE call is an argument of that call: common.h, conv1x1 ...)
 template <class T>
 struct Scoped {
     T& field;
@@ -329,6 +232,64 @@ struct LayoutRow {
     int is_buffer;
 };
 
+// ---- the state of the step in flight.  Nothing here outlives the step; what does -- the pool's chunks, the weight images, the negative
+// prefix answers, the side stream, the profile rows and collective counters read after the step -- are members of the trainer itself
+struct TapeOp {
+    int out_id;
+    int section;
+    std::function<void(const Tn&)> bw;
+};
+// inverse index of a gather table (deterministic mode): built at its first use in the backward pass, kept to its end
+struct Inv {
+    Tn offsets, src;
+    int64_t n_dst;
+    const int32_t* order = nullptr;  // the destinations' spatially coherent processing order (ps_pyramid.order of their level), or NULL
+    int64_t n_cloud = 0;
+};
+struct StepState {
+    int next_id = 0;
+    std::vector<TapeOp> ops;
+    std::unordered_map<int, Tn> grad_of;
+    std::unordered_map<int, std::vector<std::function<void()>>> deferred;  // input-gradient GEMMs waiting for another consumer's plain store
+    std::map<const int32_t*, Inv> inv_cache;
+    std::map<const int32_t*, const int32_t*> order_of;  // gather table -> leaf order of the level it gathers FROM (set per step from the pyramid)
+    std::vector<WgradJob> wjobs;  // weight / bias gradient partials waiting for the step's one reduction launch
+    std::vector<Tn> wkeep;        // (their operands, alive until the reduction launch has been enqueued)
+    size_t forks_used = 0;        // events of the side stream taken so far
+    int section = 0;
+    std::vector<std::string> section_names;
+    std::vector<std::pair<std::string, hipEvent_t>> marks;           // profiled steps: an event per section boundary ...
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> coll_marks;       // ... and a pair around every collective
+    // the end of the backward pass: the tape and what its closures held (finish_wgrads and finish_profile still read the rest)
+    void drop_tape()
+    {
+        ops.clear();
+        grad_of.clear();
+        deferred.clear();
+        inv_cache.clear();
+    }
+    void destroy_marks()
+    {
+        for (auto& m : marks) (void)hipEventDestroy(m.second);
+        for (auto& m : coll_marks) (void)hipEventDestroy(m.first), (void)hipEventDestroy(m.second);
+        marks.clear();
+        coll_marks.clear();
+    }
+    // everything: in front of a step, behind a failed one (closures hold tensors: nothing of it may survive it; nobody reads its pending
+    // events) and at the trainer's end.  The caller has made sure that nothing of the step still runs on the side stream
+    void clear()
+    {
+        drop_tape();
+        destroy_marks();
+        wjobs.clear();
+        wkeep.clear();
+        order_of.clear();
+        section_names.clear();
+        next_id = section = 0;
+        forks_used = 0;
+    }
+};
+
 }  // namespace ps
 
 struct ps_trainer {
@@ -349,15 +310,13 @@ struct ps_trainer {
     // the callback, and -- on profiled steps -- the device time between an event pair around every call
     int64_t coll_calls = 0, coll_bytes = 0;
     double coll_host_ms = 0.0, coll_device_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> coll_marks;
     int64_t step = 0;
     // ---- second stream (ps_train_options.overlap_wgrad): the weight-gradient products of the backward pass feed nothing before the step's
     // one reduction launch, so they run on `side` behind an event of the main stream (their operands exist by then) while the main
     // stream goes on with the input-gradient chain; the reduction waits for the side stream.  The operands stay referenced until then
-    // (wkeep): the pool hands a released block to the NEXT main-stream kernel, which would overwrite it under a product still reading.
+    // (cur.wkeep): the pool hands a released block to the NEXT main-stream kernel, which would overwrite it under a product still reading.
     hipStream_t side = nullptr;
     std::vector<hipEvent_t> fork_events;
-    size_t forks_used = 0;
     hipEvent_t join_event = nullptr;
     bool side_busy = false;
     bool use_side() const { return opt.overlap_wgrad != 0; }
@@ -367,12 +326,12 @@ struct ps_trainer {
             TK_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
             TK_HIP(hipEventCreateWithFlags(&join_event, hipEventDisableTiming));
         }
-        if (forks_used == fork_events.size()) {
+        if (cur.forks_used == fork_events.size()) {
             hipEvent_t e;
             TK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             fork_events.push_back(e);
         }
-        hipEvent_t e = fork_events[forks_used++];
+        hipEvent_t e = fork_events[cur.forks_used++];
         TK_HIP(hipEventRecord(e, stream()));
         TK_HIP(hipStreamWaitEvent(side, e, 0));
         side_busy = true;
@@ -396,24 +355,21 @@ struct ps_trainer {
         if (join_event) (void)hipEventDestroy(join_event);
         join_event = nullptr;
     }
-    Pool pool;
+    TrainPool pool;
+    StepState cur;  // the step in flight
     DevBuf label_map;  // int32 [num_classes + ignored]
     int n_label_map = 0;
-    int next_id = 0;
 
     // ---- per-section device time of a step (ps_trainer_profile): hipEvents at the section boundaries of the forward pass, and in the
     // backward pass wherever the section of the op in hand changes
     bool profile = false;
-    int section = 0;
-    std::vector<std::string> section_names;
-    std::vector<std::pair<std::string, hipEvent_t>> marks;
     std::vector<std::pair<std::string, double>> profile_rows;
     int begin_section(const std::string& name)
     {
-        section_names.push_back(name);
-        section = (int)section_names.size() - 1;
+        cur.section_names.push_back(name);
+        cur.section = (int)cur.section_names.size() - 1;
         mark("fwd " + name);
-        return section;
+        return cur.section;
     }
     void mark(const std::string& name)
     {
@@ -421,7 +377,7 @@ struct ps_trainer {
         hipEvent_t e;
         TK_HIP(hipEventCreate(&e));
         TK_HIP(hipEventRecord(e, stream()));
-        marks.emplace_back(name, e);
+        cur.marks.emplace_back(name, e);
     }
     void finish_profile()
     {
@@ -430,36 +386,24 @@ struct ps_trainer {
         (void)hipStreamSynchronize(stream());
         std::map<std::string, double> acc;
         std::vector<std::string> order;
+        const auto& marks = cur.marks;
         for (size_t i = 0; i + 1 < marks.size(); ++i) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, marks[i].second, marks[i + 1].second);
             if (!acc.count(marks[i].first)) order.push_back(marks[i].first);
             acc[marks[i].first] += ms;
         }
-        for (auto& m : marks) (void)hipEventDestroy(m.second);
-        marks.clear();
         coll_device_ms = 0.0;
-        for (auto& m : coll_marks) {
+        for (auto& m : cur.coll_marks) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, m.first, m.second);
             coll_device_ms += ms;
-            (void)hipEventDestroy(m.first);
-            (void)hipEventDestroy(m.second);
         }
-        coll_marks.clear();
+        cur.destroy_marks();
         profile_rows.clear();
         for (const std::string& n : order) profile_rows.emplace_back(n, acc[n]);
     }
 
-    // ---- tape state of the step in flight
-    struct Op {
-        int out_id;
-        int section;
-        std::function<void(const Tn&)> bw;
-    };
-    std::vector<Op> ops;
-    std::unordered_map<int, Tn> grad_of;
-    std::unordered_map<int, std::vector<std::function<void()>>> deferred;  // input-gradient GEMMs waiting for another consumer's plain store
     // the wide levels without their concat buffers (attpool_gemm.hip, split-source forms).  Measured on MI355X, batch 8: the bf16-MLP step
     // 35.20 -> 34.97 ms with it, the fp32 step 39.71 -> 39.97 ms (the gathering loader of the weight-gradient kernel: 0.71 against 0.40 ms
     // per level-2 pooling, and the forward kernel drops from three to two waves per SIMD) -- on by default in the bf16-MLP mode only;
@@ -470,15 +414,6 @@ struct ps_trainer {
     bool att_gemm_on = true;  // attpool_gemm.hip
     bool merge_syncbn = true;  // shared BatchNorm statistics of INDEPENDENT layers in one all-reduce (mlp2 || shortcut, mlp1 || LocSE-mlp1)
     ps::PackCache pack;  // the step's weight images (recorded during the first step, then packed by one launch per step: common.h)
-    // inverse indices of the step's gather tables (deterministic mode): built at their first use in the backward pass, kept to its end
-    struct Inv {
-        Tn offsets, src;
-        int64_t n_dst;
-        const int32_t* order = nullptr;  // the destinations' spatially coherent processing order (ps_pyramid.order of their level), or NULL
-        int64_t n_cloud = 0;
-    };
-    std::map<const int32_t*, Inv> inv_cache;
-    std::map<const int32_t*, const int32_t*> order_of;  // gather table -> leaf order of the level it gathers FROM (set per step from the pyramid)
     void reduce_rows(const Inv& iv, const float* rows, int64_t ldr, int64_t d, float* dst, int64_t ldd, int accumulate)
     {
         TK(ps_op_gather_reduce_rows_ordered(c, rows, ldr, reinterpret_cast<const int32_t*>(iv.offsets.p), reinterpret_cast<const int32_t*>(iv.src.p), iv.n_dst, d, dst,
@@ -486,19 +421,19 @@ struct ps_trainer {
     }
     const Inv& inverse(const int32_t* idx, int64_t B, int64_t N, int64_t rows_per_cloud)
     {
-        auto it = inv_cache.find(idx);
-        if (it != inv_cache.end()) return it->second;
+        auto it = cur.inv_cache.find(idx);
+        if (it != cur.inv_cache.end()) return it->second;
         Inv v;
         v.n_dst = B * N;
         v.n_cloud = N;
-        auto oo = order_of.find(idx);
-        v.order = oo != order_of.end() ? oo->second : nullptr;
+        auto oo = cur.order_of.find(idx);
+        v.order = oo != cur.order_of.end() ? oo->second : nullptr;
         v.offsets = alloc(1, v.n_dst + 1, false);
         v.src = alloc(1, std::max<int64_t>(B * rows_per_cloud, 1), false);
         Tn ws = alloc(1, ps_op_inverse_index_workspace(v.n_dst, B * rows_per_cloud), false);
         TK(ps_op_inverse_index(c, idx, B, N, rows_per_cloud, reinterpret_cast<int32_t*>(v.offsets.p), reinterpret_cast<int32_t*>(v.src.p),
                                reinterpret_cast<int32_t*>(ws.p)));
-        return inv_cache.emplace(idx, v).first->second;
+        return cur.inv_cache.emplace(idx, v).first->second;
     }
     // Is sub_idx the prefix of neigh_idx (the precondition of the fixed-order max-pool backward)?  A pyramid ps_pyramid_build wrote says
     // so itself (ps_pyramid.built).  Any other pyramid is compared on EVERY step -- its tables may have been rewritten in place, or a
@@ -524,29 +459,27 @@ struct ps_trainer {
         if (h != 0) prefix_checked[key] = false;
         return h == 0;
     }
-    std::vector<WgradJob> wjobs;  // weight / bias gradient partials waiting for the step's one reduction launch
-    std::vector<Tn> wkeep;
     void queue_wgrad(const Tn& part, float* dst, int64_t slabs, int64_t rows, int64_t cols, bool transposed = false)
     {
-        wjobs.push_back(WgradJob{part.p, dst, (int)slabs, (int)rows, (int)cols, transposed ? 1 : 0});
-        wkeep.push_back(part);  // (alive until the reduction launch has been enqueued)
+        cur.wjobs.push_back(WgradJob{part.p, dst, (int)slabs, (int)rows, (int)cols, transposed ? 1 : 0});
+        cur.wkeep.push_back(part);  // (alive until the reduction launch has been enqueued)
     }
     void finish_wgrads()
     {
         join_side();  // (the partial products may still be running on the second stream)
-        if (wjobs.empty()) return;
+        if (cur.wjobs.empty()) return;
         Stage st(c, "train_wgrad", 1);
-        Tn table = alloc(1, (int64_t)((sizeof(WgradJob) * wjobs.size() + 3) / 4), false);
-        TK(c->upload_async(table.p, wjobs.data(), sizeof(WgradJob) * wjobs.size()));
+        Tn table = alloc(1, (int64_t)((sizeof(WgradJob) * cur.wjobs.size() + 3) / 4), false);
+        TK(c->upload_async(table.p, cur.wjobs.data(), sizeof(WgradJob) * cur.wjobs.size()));
         int64_t most = 1;
-        for (const WgradJob& j : wjobs) most = std::max<int64_t>(most, (int64_t)j.rows * j.cols);
+        for (const WgradJob& j : cur.wjobs) most = std::max<int64_t>(most, (int64_t)j.rows * j.cols);
         if (c->tune.wgrad_debug && step < 1)
-            for (const WgradJob& j : wjobs)
+            for (const WgradJob& j : cur.wjobs)
                 fprintf(stderr, "wgrad job: slabs %d rows %d cols %d transposed %d part%%16 %d dst%%16 %d\n", j.slabs, j.rows, j.cols, j.transposed,
                         (int)(reinterpret_cast<uintptr_t>(j.part) & 15), (int)(reinterpret_cast<uintptr_t>(j.dst) & 15));
-        TK(wgrad_finish(c, reinterpret_cast<const WgradJob*>(table.p), (int)wjobs.size(), most));
-        wjobs.clear();
-        wkeep.clear();
+        TK(wgrad_finish(c, reinterpret_cast<const WgradJob*>(table.p), (int)cur.wjobs.size(), most));
+        cur.wjobs.clear();
+        cur.wkeep.clear();
     }
 
     hipStream_t stream() const { return c->stream; }
@@ -562,10 +495,11 @@ struct ps_trainer {
     {
         Tn t;
         t.R = R; t.C = C; t.ld = C;
-        t.id = next_id++;
+        t.id = cur.next_id++;
         t.req = req;
         void* p = pool.alloc(sizeof(float) * (size_t)std::max<int64_t>(R * C, 1));
-        t.own = std::make_shared<Block>(&pool, p);
+        if (!p) throw TrainError{PS_ENOMEM};  // (the source refused a chunk: HipChunks::get has set the error text)
+        t.own = std::make_shared<Block<HipChunks>>(&pool, p);
         t.p = static_cast<float*>(p);
         return t;
     }
@@ -580,7 +514,7 @@ struct ps_trainer {
         Tn v = t;
         v.p = t.p + c0;
         v.C = nc;
-        if (fresh_id) v.id = next_id++;
+        if (fresh_id) v.id = cur.next_id++;
         return v;
     }
     Tn rows_of(const Tn& t, int64_t r0, int64_t nr)  // (row blocks of a parameter matrix: contiguous)
@@ -588,13 +522,13 @@ struct ps_trainer {
         Tn v = t;
         v.p = t.p + r0 * t.ld;
         v.R = nr;
-        v.id = next_id++;
+        v.id = cur.next_id++;
         return v;
     }
     Tn external(float* p, int64_t R, int64_t C, bool req)
     {
         Tn t;
-        t.p = p; t.R = R; t.C = C; t.ld = C; t.id = next_id++; t.req = req;
+        t.p = p; t.R = R; t.C = C; t.ld = C; t.id = cur.next_id++; t.req = req;
         return t;
     }
     void copy2d(const Tn& src, const Tn& dst, bool add)
@@ -621,7 +555,7 @@ struct ps_trainer {
     void allreduce(void* buf, int64_t count, int dtype)
     {
         if (!coll_active()) return;
-        struct EventPair {  // (owned until handed to coll_marks: nothing leaks when a HIP call in between throws)
+        struct EventPair {  // (owned until handed to cur.coll_marks: nothing leaks when a HIP call in between throws)
             hipEvent_t e0 = nullptr, e1 = nullptr;
             ~EventPair()
             {
@@ -641,7 +575,7 @@ struct ps_trainer {
         coll_bytes += count * (dtype == 1 ? 8 : 4);
         if (profile) {
             (void)hipEventRecord(ev.e1, stream());
-            coll_marks.emplace_back(ev.e0, ev.e1);
+            cur.coll_marks.emplace_back(ev.e0, ev.e1);
             ev.e0 = ev.e1 = nullptr;
         }
         if (rc != 0) {
@@ -653,9 +587,9 @@ struct ps_trainer {
     // ---- gradient bookkeeping (keys = tensor ids, like the identity keys of a Python tape)
     void accum(const Tn& t, const Tn& g)
     {
-        auto it = grad_of.find(t.id);
-        if (it == grad_of.end()) {
-            grad_of[t.id] = g;
+        auto it = cur.grad_of.find(t.id);
+        if (it == cur.grad_of.end()) {
+            cur.grad_of[t.id] = g;
             return;
         }
         Tn& have = it->second;
@@ -672,47 +606,68 @@ struct ps_trainer {
     // fresh zero tensor that becomes it
     Tn accum_buffer(const Tn& t)
     {
-        auto it = grad_of.find(t.id);
-        if (it != grad_of.end()) return it->second;
+        auto it = cur.grad_of.find(t.id);
+        if (it != cur.grad_of.end()) return it->second;
         Tn z = zeros(t.R, t.C);
-        grad_of[t.id] = z;
+        cur.grad_of[t.id] = z;
         return z;
     }
-    void record(const Tn& out, std::function<void(const Tn&)> bw) { ops.push_back({out.id, section, std::move(bw)}); }
+    // the gradient tensor of x for a kernel that can STORE its input gradient or ADD it in its epilogue: x's recorded gradient when there
+    // is one that `fits` (the caller's kernel's own demands on a tensor it adds into; it may throw) -- add --, else a fresh [R, C]
+    // tensor, which record_grad makes x's gradient (or folds into the one that did not fit) once the kernel has been enqueued
+    struct GradSlot { Tn t; bool add; };
+    template <class Fits>
+    GradSlot grad_slot(const Tn& x, int64_t R, int64_t C, Fits fits)
+    {
+        auto it = cur.grad_of.find(x.id);
+        if (it != cur.grad_of.end() && fits(it->second)) return {it->second, true};
+        return {alloc(R, C), false};
+    }
+    static bool any_layout(const Tn&) { return true; }
+    void record_grad(const Tn& x, const GradSlot& g) { if (!g.add) accum(x, g.t); }
+    // an input-gradient product of x that adds into the gradient another, later-running consumer STORES: parked on x until that store
+    // (run_deferred) when `park` is set and x has no gradient yet, else run now
+    template <class F>
+    void park_or_run(bool park, const Tn& x, const F& f)
+    {
+        if (park && !cur.grad_of.count(x.id))
+            cur.deferred[x.id].push_back(f);
+        else
+            f();
+    }
+    void record(const Tn& out, std::function<void(const Tn&)> bw) { cur.ops.push_back({out.id, cur.section, std::move(bw)}); }
     // runs the input-gradient products that were parked on tensor `id` (linear(..., defer_dgrad)): called once the consumer they waited
     // for has stored its own gradient, and in any case before the producer of `id` runs its backward
     void run_deferred(int id)
     {
-        auto it = deferred.find(id);
-        if (it == deferred.end()) return;
+        auto it = cur.deferred.find(id);
+        if (it == cur.deferred.end()) return;
         std::vector<std::function<void()>> fs = std::move(it->second);
-        deferred.erase(it);
+        cur.deferred.erase(it);
         for (auto& f : fs) f();
     }
     void backward(const Tn& out, const Tn& dout)
     {
-        grad_of[out.id] = dout;
-        int cur = -1;
+        cur.grad_of[out.id] = dout;
+        std::vector<TapeOp>& ops = cur.ops;
+        int sec = -1;
         for (size_t i = ops.size(); i-- > 0;) {
-            if (profile && ops[i].section != cur) {
-                cur = ops[i].section;
-                mark("bwd " + section_names[cur]);
+            if (profile && ops[i].section != sec) {
+                sec = ops[i].section;
+                mark("bwd " + cur.section_names[sec]);
             }
             run_deferred(ops[i].out_id);
-            auto it = grad_of.find(ops[i].out_id);
-            if (it == grad_of.end()) {
+            auto it = cur.grad_of.find(ops[i].out_id);
+            if (it == cur.grad_of.end()) {
                 ops[i].bw = nullptr;
                 continue;
             }
             Tn g = it->second;
-            grad_of.erase(it);
+            cur.grad_of.erase(it);
             ops[i].bw(g);
             ops[i].bw = nullptr;  // drops the activations only this op held
         }
-        ops.clear();
-        grad_of.clear();
-        deferred.clear();
-        inv_cache.clear();
+        cur.drop_tape();
         finish_wgrads();
     }
 
@@ -741,27 +696,17 @@ struct ps_trainer {
     Tn linear(const Tn& x, const Tn& W, const float* b, const Tn& gW, float* gb, bool transposed = false, const Tn* into = nullptr, bool fp32_only = false,
               bool defer_dgrad = false)
     {
-        // fp32_only switches the context's bf16-GEMM mode off around this layer's products; conv_w_transposed tells ps_op_conv1x1_ex that its
-        // weight matrix is stored [cout, cin] (read through strides while packing).  Only this function sets that flag, around single
-        // calls that do not nest: it is false on entry, which is what Scoped puts back
+        // fp32_only switches the context's bf16-GEMM mode off around this layer's products; `transposed` goes to the product itself: its
+        // weight matrix is stored [cout, cin] (conv2d_transpose kernels; read through strides while packing)
         Scoped<bool> fwd_scope(c->train_bf16, c->train_bf16 && !fp32_only);
         const int64_t R = x.R, cin = x.C, cout = transposed ? W.R : W.C;
-        Tn y;
-        {
-            Scoped<bool> wt(c->conv_w_transposed, transposed);  // conv2d_transpose kernels are stored [out, in]
-            if (!into) {
-                y = alloc(R, cout);
-                TK(ps_op_conv1x1_ex(c, x.p, x.ld, W.p, b, R, cin, cout, 0, 0, y.p, y.ld));
-            } else {
-                y = *into;
-                TK(ps_op_conv1x1_ex(c, x.p, x.ld, W.p, b, R, cin, cout, 0, 1, y.p, y.ld));
-            }
-        }
+        const Tn y = into ? *into : alloc(R, cout);
+        TK(ps::conv1x1(c, x.p, x.ld, W.p, transposed, b, R, cin, cout, 0, into ? 1 : 0, y.p, y.ld));
         const bool had_into = into != nullptr;
         const Tn into_t = had_into ? *into : Tn();
         record(y, [=](const Tn& dy) {
             Scoped<bool> bwd_scope(c->train_bf16, c->train_bf16 && !fp32_only);
-            if (had_into) grad_of[into_t.id] = dy;  // d(into + x.W)/d(into) = 1: the producer of `into` (earlier on the tape) gets the same gradient
+            if (had_into) cur.grad_of[into_t.id] = dy;  // d(into + x.W)/d(into) = 1: the producer of `into` (earlier on the tape) gets the same gradient
             {
                 // weight / bias gradient: per-slab partials now (plain stores), summed in slab order by the ONE wgrad_finish launch at the
                 // end of the backward pass -- deterministic, no memsets, and the [out, in] layout of the transposed kernels is just a flag
@@ -776,8 +721,8 @@ struct ps_trainer {
                     Stage st(c, "train_wgrad", 1);
                     TK(wgrad_partial(c, x.p, x.ld, dy.p, dy.ld, R, cin, cout, part.p, gb ? dbp.p : nullptr));
                     if (on_side) {
-                        wkeep.push_back(x);
-                        wkeep.push_back(dy);
+                        cur.wkeep.push_back(x);
+                        cur.wkeep.push_back(dy);
                     }
                 }
                 queue_wgrad(part, gW.p, nb, cin, cout, transposed);
@@ -785,24 +730,13 @@ struct ps_trainer {
             }
             if (x.req) {
                 // dx = dy . W^T: the GEMM's [cout, cin] matrix IS the stored kernel for the transposed layers and its transpose for all others
-                auto dgrad = [=]() {
+                // (a gradient x already has from another consumer is added to in the GEMM epilogue)
+                park_or_run(defer_dgrad, x, [=]() {
                     Scoped<bool> scope(c->train_bf16, c->train_bf16 && !fp32_only);
-                    Scoped<bool> wt(c->conv_w_transposed, !transposed);
-                    auto it = grad_of.find(x.id);
-                    if (it != grad_of.end()) {
-                        // x already has a gradient from another consumer: add this one in the GEMM epilogue
-                        Tn& have = it->second;
-                        TK(ps_op_conv1x1_ex(c, dy.p, dy.ld, W.p, nullptr, R, cout, cin, 0, 1, have.p, have.ld));
-                    } else {
-                        Tn dx = alloc(R, cin);
-                        TK(ps_op_conv1x1_ex(c, dy.p, dy.ld, W.p, nullptr, R, cout, cin, 0, 0, dx.p, dx.ld));
-                        accum(x, dx);
-                    }
-                };
-                if (defer_dgrad && !grad_of.count(x.id))
-                    deferred[x.id].push_back(dgrad);
-                else
-                    dgrad();
+                    const GradSlot dx = grad_slot(x, R, cin, any_layout);
+                    TK(ps::conv1x1(c, dy.p, dy.ld, W.p, !transposed, nullptr, R, cout, cin, 0, dx.add ? 1 : 0, dx.t.p, dx.t.ld));
+                    record_grad(x, dx);
+                });
             }
         });
         return y;
@@ -1089,31 +1023,27 @@ struct ps_trainer {
                 TK(ps_op_conv_bn_train_bwd_sums2(c, x.p, x.ld, W, b, R, h, mean, invstd, scale, beta, dz.p, dz.ld, acc.p));
             }
             Tn tot = recomp_bwd_sums("train_convbn_bwd", acc.p, h, ggamma, gbeta);
-            auto apply = [=]() {
-                auto it = grad_of.find(x.id);
-                const bool add = it != grad_of.end();
-                Tn dx = add ? it->second : alloc(R, h);
-                if (!add) dx.b16 = act16;
-                if (add && !(dx.ld % 4 == 0 && dx.R == R && dx.C == h && dx.b16 == act16)) {
-                    ps::set_error("trainer: conv_bn_fused: unexpected gradient layout");
-                    throw TrainError{PS_ESTATE};
-                }
-                {
-                    Scoped<bool> as(c->train_act_bf16, act16);
-                    TK(ps_op_conv_bn_train_bwd_apply_w(c, x.p, x.ld, W, b, R, h, mean, invstd, scale, beta, tot.p, 1.0f / (float)R_total, dz.p, dz.ld, add ? 1 : 0,
-                                                       dx.p, dx.ld, gW, gb));
-                }
-                if (!add) accum(x, dx);
-                (void)st4;
-            };
             if (!x.req) {
                 ps::set_error("trainer: conv_bn_fused on an input without gradient");
                 throw TrainError{PS_ESTATE};
             }
-            if (defer_dgrad && !grad_of.count(x.id))
-                deferred[x.id].push_back(apply);
-            else
-                apply();
+            park_or_run(defer_dgrad, x, [=]() {
+                GradSlot dx = grad_slot(x, R, h, [&](const Tn& have) {
+                    if (!(have.ld % 4 == 0 && have.R == R && have.C == h && have.b16 == act16)) {  // (no second form to fall back to)
+                        ps::set_error("trainer: conv_bn_fused: unexpected gradient layout");
+                        throw TrainError{PS_ESTATE};
+                    }
+                    return true;
+                });
+                if (!dx.add) dx.t.b16 = act16;
+                {
+                    Scoped<bool> as(c->train_act_bf16, act16);
+                    TK(ps_op_conv_bn_train_bwd_apply_w(c, x.p, x.ld, W, b, R, h, mean, invstd, scale, beta, tot.p, 1.0f / (float)R_total, dz.p, dz.ld,
+                                                       dx.add ? 1 : 0, dx.t.p, dx.t.ld, gW, gb));
+                }
+                record_grad(x, dx);
+                (void)st4;
+            });
         });
         z.req = true;
         return z;
@@ -1157,12 +1087,12 @@ struct ps_trainer {
                 const Tn dy = contig(dz_raw);
                 Tn ds = alloc(R, co);
                 TK(ps_op_add_lrelu_bwd(c, dy.p, z.p, z.numel(), ds.p));
-                if (grad_of.count(addend.id)) {
+                if (cur.grad_of.count(addend.id)) {
                     Tn ds2 = alloc(R, co);
                     TK_HIP(hipMemcpyAsync(ds2.p, ds.p, sizeof(float) * (size_t)z.numel(), hipMemcpyDeviceToDevice, stream()));
                     accum(addend, ds2);
                 } else {
-                    grad_of[addend.id] = ds;
+                    cur.grad_of[addend.id] = ds;
                 }
                 dz_in = ds;
             }
@@ -1171,16 +1101,11 @@ struct ps_trainer {
             Tn acc = alloc(1, 2 * co, false);
             TK(ps_op_convbn_train_bwd_sums(c, x.p, x.ld, W, b, R, ci, co, mean, invstd, scale, beta, leaky ? 1 : 0, dz.p, dz.ld, acc.p));
             Tn tot = recomp_bwd_sums("train_convbn_bwd", acc.p, co, ggamma, gbeta);
-            Tn dx;
-            int add = 0;
-            if (x.req) {
-                auto it = grad_of.find(x.id);
-                add = it != grad_of.end() && it->second.vec_ok() ? 1 : 0;
-                dx = add ? it->second : alloc(R, ci);
-            }
-            TK(ps_op_convbn_train_bwd_apply(c, x.p, x.ld, W, b, R, ci, co, mean, invstd, scale, beta, leaky ? 1 : 0, tot.p, 1.0f / (float)R_total, dz.p, dz.ld, add,
-                                            x.req ? dx.p : nullptr, x.req ? dx.ld : 0, gW, gb));
-            if (x.req && !add) accum(x, dx);
+            GradSlot dx{Tn(), false};
+            if (x.req) dx = grad_slot(x, R, ci, [](const Tn& have) { return have.vec_ok(); });
+            TK(ps_op_convbn_train_bwd_apply(c, x.p, x.ld, W, b, R, ci, co, mean, invstd, scale, beta, leaky ? 1 : 0, tot.p, 1.0f / (float)R_total, dz.p, dz.ld,
+                                            dx.add ? 1 : 0, x.req ? dx.t.p : nullptr, x.req ? dx.t.ld : 0, gW, gb));
+            if (x.req) record_grad(x, dx);
             (void)st4;
         });
         return z;
@@ -1192,11 +1117,10 @@ struct ps_trainer {
     void gathered_grad(const Tn& x, const int32_t* idx, int64_t B, int64_t N, int64_t rows_per_cloud, const float* rows, int64_t ldr, int64_t d)
     {
         if (opt.deterministic) {
-            const bool fresh = !grad_of.count(x.id);
-            Tn dst = fresh ? alloc(x.R, x.C) : accum_buffer(x);
+            const GradSlot dst = grad_slot(x, x.R, x.C, any_layout);
             const Inv& iv = inverse(idx, B, N, rows_per_cloud);
-            reduce_rows(iv, rows, ldr, d, dst.p, dst.ld, fresh ? 0 : 1);
-            if (fresh) grad_of[x.id] = dst;
+            reduce_rows(iv, rows, ldr, d, dst.t.p, dst.t.ld, dst.add ? 1 : 0);
+            record_grad(x, dst);
         } else {
             Tn dst = accum_buffer(x);
             TK(ps_op_scatter_add_rows_ex(c, rows, ldr, idx, B, N, rows_per_cloud, d, dst.p));
@@ -1213,8 +1137,8 @@ struct ps_trainer {
         TK(ps_op_gather_neighbour_ex(c, x.p, idx, B, N, M, K, d, o.p, o.ld));
         const Tn xin = x_in;
         record(o, [=](const Tn& dy) {
-            auto have = grad_of.find(xin.id);
-            if (have != grad_of.end() && !have->second.contiguous()) {
+            auto have = cur.grad_of.find(xin.id);
+            if (have != cur.grad_of.end() && !have->second.contiguous()) {
                 ps::set_error("trainer: scatter-add into a strided gradient");
                 throw TrainError{PS_ESTATE};
             }
@@ -1280,11 +1204,9 @@ struct ps_trainer {
             const Tn dy = contig(dy_in);
             Tn ds = alloc(RK, d, false);
             // fset's gradient so far (none in this graph: the pooling is the concat buffer's only consumer) is added to in the epilogue
-            auto have = grad_of.find(fset.id);
-            const bool add = have != grad_of.end() && have->second.R == RK && have->second.C == d && have->second.ld % 4 == 0;
-            Tn dfset = add ? have->second : alloc(RK, d);
-            TK(ps_op_att_pool_gemm_bwd(c, fset.p, fset.ld, W.p, dy.p, R, K, d, dfset.p, dfset.ld, add ? 1 : 0, ds.p, ds.ld));
-            if (!add) accum(fset, dfset);
+            const GradSlot dfset = grad_slot(fset, RK, d, [=](const Tn& have) { return have.R == RK && have.C == d && have.ld % 4 == 0; });
+            TK(ps_op_att_pool_gemm_bwd(c, fset.p, fset.ld, W.p, dy.p, R, K, d, dfset.t.p, dfset.t.ld, dfset.add ? 1 : 0, ds.p, ds.ld));
+            record_grad(fset, dfset);
             const int64_t nb = wgrad_partial_slabs(c, fset.p, fset.ld, ds.p, ds.ld, RK, d, d);
             Tn part = alloc(nb, d * d, false);
             {
@@ -1323,11 +1245,9 @@ struct ps_trainer {
         TK(ps_op_att_pool_gemm_fwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, K, d, agg.p));
         record(agg, [=](const Tn& dy_in) {
             const Tn dy = contig(dy_in);
-            auto have = grad_of.find(f_xyz.id);
-            const bool add_in_place = have != grad_of.end() && have->second.C == h && have->second.R == RK && have->second.ld % 4 == 0;
-            Tn dfx = add_in_place ? have->second : alloc(RK, h);
+            const GradSlot dfx = grad_slot(f_xyz, RK, h, [=](const Tn& have) { return have.C == h && have.R == RK && have.ld % 4 == 0; });
             Tn rows = alloc(RK, h, false), ds = alloc(RK, d, false);
-            TK(ps_op_att_pool_gemm_bwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.p, dfx.ld, add_in_place ? 1 : 0,
+            TK(ps_op_att_pool_gemm_bwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.t.p, dfx.t.ld, dfx.add ? 1 : 0,
                                              ds.p, ds.ld));
             gathered_grad(f_src, idx, B, N, M * K, rows.p, h, h);
             const int64_t nb = wgrad_split_slabs(c, f_src.p, f_src.ld, idx, f_xyz.p, f_xyz.ld, ds.p, ds.ld, RK, d, d);
@@ -1341,7 +1261,7 @@ struct ps_trainer {
                 TK(wgrad_b3_partial_split(c, f_src.p, f_src.ld, idx, N, M * K, f_xyz.p, f_xyz.ld, ds.p, ds.ld, RK, d, d, part.p));
             }
             queue_wgrad(part, gW.p, nb, d, d);
-            if (!add_in_place) accum(f_xyz, dfx);
+            record_grad(f_xyz, dfx);
             run_deferred(f_xyz.id);
         });
         return agg;
@@ -1371,21 +1291,21 @@ struct ps_trainer {
             const Tn dy = contig(dy_in);
             // f_xyz usually has a gradient already (the h -> h convolution's input gradient ran first): the kernel adds into it instead of
             // writing a second tensor that an axpy pass then folds in (4 passes over [N*K, h] -> 2)
-            auto have = grad_of.find(f_xyz.id);
-            const bool add_in_place = have != grad_of.end() && have->second.C == h && have->second.R == B * M * K && have->second.b16 == act16;
-            Tn dfx = add_in_place ? have->second : alloc(B * M * K, h);
-            if (!add_in_place) dfx.b16 = act16;  // (the gradient rows of the bfloat16-stored half are bfloat16 as well)
-            Scoped<bool> flag(c->att_df_accum, add_in_place);  // (set nowhere else, and this closure does not nest: false on entry)
+            GradSlot dfx = grad_slot(f_xyz, B * M * K, h, [=](const Tn& have) { return have.C == h && have.R == B * M * K && have.b16 == act16; });
+            if (!dfx.add) dfx.t.b16 = act16;  // (the gradient rows of the bfloat16-stored half are bfloat16 as well)
+            // (ps_op_att_pool_train_bwd_split_rows / _bwd_split with the one thing their C entries never do: adding into dfx)
             if (opt.deterministic) {
                 // the gathered half's gradient as plain rows first, then summed per source row in ascending row order (no float atomics)
                 Tn rows = alloc(B * M * K, h, false);
-                TK(ps_op_att_pool_train_bwd_split_rows(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.p, dfx.ld, gW.p));
+                TK(ps::att_bwd_split_impl(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, rows.p, h, dfx.t.p, dfx.t.ld, gW.p, rows.p, h,
+                                          dfx.add));
                 gathered_grad(f_src, idx, B, N, M * K, rows.p, h, h);
             } else {
                 Tn dsrc = accum_buffer(f_src);  // the gathered half's gradient is added in place
-                TK(ps_op_att_pool_train_bwd_split(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, dsrc.p, dsrc.ld, dfx.p, dfx.ld, gW.p));
+                TK(ps::att_bwd_split_impl(c, f_src.p, f_src.ld, idx, B, N, M, f_xyz.p, f_xyz.ld, W.p, dy.p, K, d, dsrc.p, dsrc.ld, dfx.t.p, dfx.t.ld, gW.p, nullptr,
+                                          0, dfx.add));
             }
-            if (!add_in_place) accum(f_xyz, dfx);
+            record_grad(f_xyz, dfx);
             run_deferred(f_xyz.id);
         });
         return agg;
@@ -1414,21 +1334,18 @@ struct ps_trainer {
             //  zero-filled buffer)
             // (the overwriting kernel's own conditions, csrc/invidx.hip maxpool_bwd_inv4_kernel: tie counts, 16-byte rows, 32-bit element and
             //  table offsets -- a batch beyond them takes the additive form instead of failing)
-            const bool fresh = by_inverse && ties && !grad_of.count(xin.id) && xin.contiguous() && d % 4 == 0 && B * N * d < (1ll << 32) &&
-                               B * N * K < (1ll << 31) &&
-                               ((reinterpret_cast<uintptr_t>(dy.p) | reinterpret_cast<uintptr_t>(out.p) | reinterpret_cast<uintptr_t>(x.p)) & 15) == 0;
-            Tn buf = fresh ? alloc(xin.R, xin.C) : accum_buffer(xin);
-            if (fresh) grad_of[xin.id] = buf;
-            Scoped<bool> flag(c->pool_bwd_overwrite, fresh);  // (set nowhere else: false on entry)
-            Scoped<const int32_t*> walk(c->walk_order, nullptr);  // the hint set below never outlives this op: NULL again behind it
+            const bool can_store = by_inverse && ties && xin.contiguous() && d % 4 == 0 && B * N * d < (1ll << 32) && B * N * K < (1ll << 31) &&
+                                   ((reinterpret_cast<uintptr_t>(dy.p) | reinterpret_cast<uintptr_t>(out.p) | reinterpret_cast<uintptr_t>(x.p)) & 15) == 0;
+            const GradSlot slot = can_store ? grad_slot(xin, xin.R, xin.C, any_layout) : GradSlot{accum_buffer(xin), true};
+            const Tn& buf = slot.t;
+            record_grad(xin, slot);
             if (by_inverse && buf.contiguous()) {
                 const Inv& iv = inverse(neigh, B, N, N * K);  // (shared with the level's gathers: the pooling rows are a prefix of every segment)
-                c->walk_order = iv.order;  // (the level's leaf order: the kernel walks its destinations in it, XCD by XCD)
-                c->walk_order_n = iv.n_cloud;
                 Tn share = ties ? Tn() : alloc(B * M, d, false);
-                TK(ps_op_random_sample_bwd_inv(c, dy.p, out.p, x.p, pool_idx, reinterpret_cast<const int32_t*>(iv.offsets.p),
-                                               reinterpret_cast<const int32_t*>(iv.src.p), B, N, M, K, d,
-                                               ties ? reinterpret_cast<const uint8_t*>(ties.p) : nullptr, ties ? nullptr : share.p, buf.p));
+                // (iv.order: the level's leaf order -- the kernel walks its destinations in it, XCD by XCD)
+                TK(ps::random_sample_bwd_inv(c, dy.p, out.p, x.p, pool_idx, reinterpret_cast<const int32_t*>(iv.offsets.p),
+                                             reinterpret_cast<const int32_t*>(iv.src.p), B, N, M, K, d, ties ? reinterpret_cast<const uint8_t*>(ties.p) : nullptr,
+                                             ties ? nullptr : share.p, buf.p, iv.order, iv.n_cloud, /*overwrite*/ !slot.add));
             } else {
                 TK(ps_op_random_sample_bwd(c, dy.p, out.p, x.p, pool_idx, B, N, M, K, d, buf.p));
             }
@@ -1447,15 +1364,15 @@ struct ps_trainer {
             // the same values are the gradient of both summands.  In this graph both (mlp2's and the shortcut's BatchNorm outputs) have no
             // other consumer, so nothing is ever added into either gradient: they share ONE read-only tensor.  Only where a summand already
             // holds a gradient (another graph) does the second one get its own copy.
-            if (grad_of.count(a.id) || grad_of.count(b.id)) {
+            if (cur.grad_of.count(a.id) || cur.grad_of.count(b.id)) {
                 Tn ds2 = alloc(a.R, a.C);
                 TK_HIP(hipMemcpyAsync(ds2.p, ds.p, sizeof(float) * (size_t)a.numel(), hipMemcpyDeviceToDevice, stream()));
                 accum(a, ds);
                 accum(b, ds2);
             } else {
-                grad_of[a.id] = ds;
+                cur.grad_of[a.id] = ds;
                 Tn alias = ds;
-                grad_of[b.id] = alias;
+                cur.grad_of[b.id] = alias;
             }
         });
         return y;
@@ -1664,7 +1581,7 @@ struct ps_trainer {
             Tn right = cols(cat, skip.C, f.C);
             Tn up = gather(f, pyr->interp_idx[lvl], B, M, 1, &right);
             Tn left = cols(cat, 0, skip.C, false);  // (same id as nothing recorded: the copy below has its own backward)
-            left.id = next_id++;
+            left.id = cur.next_id++;
             copy2d(skip, left, false);
             left.req = true;
             {
@@ -1775,24 +1692,17 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
     c->train_act_bf16 = false;
     int rc = PS_OK;
     try {
+        t->cur.clear();
         t->pool.begin_step();
         t->pyramid_vouched = pyr->built != 0 && pyr->built == pyramid_stamp(pyr);
-        t->order_of.clear();
         for (int i = 0; i < pyr->num_layers && t->pyramid_vouched; ++i) {  // (only orders ps_pyramid_build wrote are trusted as permutations)
             // (a table's destinations: neigh_idx[i] / sub_idx[i] gather from level i, interp_idx[i] from level i + 1)
-            if (pyr->order[i]) t->order_of[pyr->neigh_idx[i]] = pyr->order[i];
-            if (pyr->order[i] && pyr->sub_idx[i]) t->order_of[pyr->sub_idx[i]] = pyr->order[i];
-            if (i + 1 < pyr->num_layers && pyr->order[i + 1] && pyr->interp_idx[i]) t->order_of[pyr->interp_idx[i]] = pyr->order[i + 1];
+            if (pyr->order[i]) t->cur.order_of[pyr->neigh_idx[i]] = pyr->order[i];
+            if (pyr->order[i] && pyr->sub_idx[i]) t->cur.order_of[pyr->sub_idx[i]] = pyr->order[i];
+            if (i + 1 < pyr->num_layers && pyr->order[i + 1] && pyr->interp_idx[i]) t->cur.order_of[pyr->interp_idx[i]] = pyr->order[i + 1];
         }
-        t->forks_used = 0;
         t->coll_calls = t->coll_bytes = 0;
         t->coll_host_ms = 0.0;
-        t->next_id = 0;
-        t->ops.clear();
-        t->grad_of.clear();
-        t->deferred.clear();
-        t->section_names.clear();
-        t->section = 0;
         c->train_bf16 = bf16;
         // weight images: replay the recorded list (ONE packing launch per source file, the products then skip their own), or record it
         if (t->pack.mode == 2) {
@@ -1834,26 +1744,14 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
         const int prc = ps::pack_cache_finish_recording(c, t->pack);
         if (prc != PS_OK) ps::pack_cache_clear(t->pack);
     }
-    t->ops.clear();
-    t->grad_of.clear();
-    t->deferred.clear();  // (closures hold tensors: nothing of a failed step may survive it)
-    if (rc != PS_OK) {  // (a failed profiled step: its pending events are not read by anybody)
-        for (auto& m : t->marks) (void)hipEventDestroy(m.second);
-        t->marks.clear();
-        for (auto& m : t->coll_marks) {
-            (void)hipEventDestroy(m.first);
-            (void)hipEventDestroy(m.second);
+    if (rc != PS_OK) {
+        if (t->side_busy) {  // (nothing of the failed step may still run when its tensors go back to the pool)
+            (void)hipStreamSynchronize(t->side);
+            t->side_busy = false;
         }
-        t->coll_marks.clear();
+        t->cur.clear();
+        return rc;
     }
-    if (t->side_busy) {  // (a failed step: nothing of it may still run when its tensors go back to the pool)
-        (void)hipStreamSynchronize(t->side);
-        t->side_busy = false;
-    }
-    t->wjobs.clear();
-    t->wkeep.clear();
-    t->inv_cache.clear();
-    if (rc != PS_OK) return rc;
     try {
         if (!optimise) {
             t->finish_profile();
@@ -1934,13 +1832,10 @@ int ps_trainer_create(ps_context* c, const ps_randla_config* cfg, const ps_train
 int ps_trainer_destroy(ps_trainer* t)
 {
     if (!t) return PS_OK;
-    t->ops.clear();
-    t->grad_of.clear();
-    t->deferred.clear();
-    t->wkeep.clear();
-    t->inv_cache.clear();
+    t->destroy_side();  // (waits for the side stream)
+    t->cur.clear();
     ps::pack_cache_clear(t->pack);
-    t->destroy_side();
+    if (!t->pool.chunks.empty()) (void)hipDeviceSynchronize();
     t->pool.destroy();
     t->label_map.release();
     delete t;
