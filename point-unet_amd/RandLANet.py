@@ -21,9 +21,13 @@ def _ctx(t):
 
 
 class Network:
-    def __init__(self, config, params=None, device=0, seed=0, ctx=None):
+    def __init__(self, config, params=None, device=0, seed=0, ctx=None, precision="bf16x3"):
         """config: ConfigBraTS-like (k_n, num_layers, d_out, num_classes, in_channels).
-        params: dict of TF-named arrays (weights.init_params / a converted checkpoint); random init if None."""
+        params: dict of TF-named arrays (weights.init_params / a converted checkpoint); random init if None.
+        precision: the arithmetic of the inference forward's matrix products (include/pointseg_forward_precision.h) -- "bf16x3", the
+        default (fp32-level results), or "bf16": both operands of every product the header's rule names rounded once to bfloat16."""
+        if precision not in _lib.FORWARD_PRECISIONS:  # (before anything is created on the device)
+            raise ValueError("Network: precision must be one of %s, got %r" % (sorted(_lib.FORWARD_PRECISIONS), precision))
         self.config = config
         self.device = torch.device("cuda", device)
         self.ctx = ctx or runtime.default_context(device)
@@ -38,6 +42,21 @@ class Network:
         self._h = ctypes.c_void_p()
         _lib.check(_lib.lib().ps_randla_create(self.ctx.handle, ctypes.byref(cfg), ctypes.byref(self._h)))
         self.set_params(self.params)
+        self.set_precision(precision)
+
+    @property
+    def precision(self):
+        """"bf16x3" or "bf16": what the next inference runs at (ps_randla_get_precision)."""
+        v = ctypes.c_int32(-1)
+        _lib.check(_lib.lib().ps_randla_get_precision(self._h, ctypes.byref(v)))
+        return {n: k for k, n in _lib.FORWARD_PRECISIONS.items()}[v.value]
+
+    def set_precision(self, precision):
+        """"bf16x3" | "bf16" (include/pointseg_forward_precision.h), from the next inference on; the one-plane weight images of "bf16" are
+        packed by the first inference that needs them."""
+        if precision not in _lib.FORWARD_PRECISIONS:
+            raise ValueError("Network.set_precision: precision must be one of %s, got %r" % (sorted(_lib.FORWARD_PRECISIONS), precision))
+        _lib.check(_lib.lib().ps_randla_set_precision(self._h, _lib.FORWARD_PRECISIONS[precision]))
 
     def close(self):
         """Frees the packed weights and chain caches on the device (ps_randla_destroy); the context stays open."""

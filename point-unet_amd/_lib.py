@@ -6,7 +6,7 @@ The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (P
 (SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
 (SALIENCY_STEP_PROTOTYPES), include/pointseg_saliency_step_precision.h (SALIENCY_STEP_PRECISION_PROTOTYPES) and
 include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES), include/pointseg_saliency_map.h (SALIENCY_MAP_PROTOTYPES) and
-include/pointseg_saliency_view.h (SALIENCY_VIEW_PROTOTYPES).
+include/pointseg_saliency_view.h (SALIENCY_VIEW_PROTOTYPES) and include/pointseg_forward_precision.h (FORWARD_PRECISION_PROTOTYPES).
 The library is built in-tree by compile_op.sh (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -399,6 +399,14 @@ SALIENCY_VIEW_PROTOTYPES = {
     "ps_patch_sample_mixup_view": (ctypes.c_int, SALIENCY_MIXUP_PROTOTYPES["ps_patch_sample_mixup"][1][:-4] + [ctypes.c_int32, c_i32p] + [c_vp] * 4),
 }
 
+# every symbol include/pointseg_forward_precision.h declares (the point network's forward on one plane of rounded bfloat16 operands;
+# csrc/randla.hip): a per-network switch over the PS_PREC_* values above, of which the forward takes two
+FORWARD_PRECISIONS = {"bf16x3": PS_PREC_BF16X3, "bf16": PS_PREC_BF16}
+FORWARD_PRECISION_PROTOTYPES = {
+    "ps_randla_set_precision": (ctypes.c_int, [c_vp, ctypes.c_int32]),
+    "ps_randla_get_precision": (ctypes.c_int, [c_vp, c_i32p]),
+}
+
 _lib = None
 
 
@@ -424,7 +432,7 @@ def lib():
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items()) + list(SALIENCY_MAP_PROTOTYPES.items())
-                                  + list(SALIENCY_VIEW_PROTOTYPES.items())):
+                                  + list(SALIENCY_VIEW_PROTOTYPES.items()) + list(FORWARD_PRECISION_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -17,8 +17,13 @@ struct Att32Weights {
     const float* w2b = nullptr;
     const float* wb1b = nullptr;
     const float* wb2b = nullptr;
+    // w2, wb1, wb2 rounded once to bfloat16 as ONE-plane images (pack_b3 with planes = 1) for the P = 1 kernels of attpool32b.hip: only the
+    // images of a network at PS_PREC_BF16 carry them (LocSE has none: it stays on w1b)
+    const float* w2b1 = nullptr;
+    const float* wb1b1 = nullptr;
+    const float* wb2b1 = nullptr;
 };
-void pack_b3(const float* W, int cin, int cout, uint16_t* out);   // [cin, cout], cin % 32 == 0, cout % 32 == 0 -> cin*cout*3 uint16
+void pack_b3(const float* W, int cin, int cout, uint16_t* out, int planes = 3);   // [cin, cout], cin % 32 == 0, cout % 32 == 0 -> cin*cout*planes uint16
 void pack_b3_locse(const float* W1, int cout, uint16_t* out);     // [10, cout] -> (cout/32)*3*64*8 uint16
 void pack_p32(const float* W, int cin, int cout, float* out);   // [cin, cout] row-major, cin % 8 == 0, cout % 32 == 0 -> cin*cout floats
 void pack_p32_locse(const float* W1, int cout, float* out);     // [10, cout] -> (cout/32)*5*64 floats
@@ -38,6 +43,9 @@ struct AttStage {
     int d = 0, k = 16;
     const Att32Weights* p32 = nullptr;  // when set (d >= 64, pre-product formulation): the 32x32x2 kernels (attpool32.hip)
     const float* lane = nullptr;        // when set (d = 16, direct formulation): the stage's plain fp32 image (attpool_lane.hip: pack_lane_image)
+    // the network runs at PS_PREC_BF16: a stage the split-bf16 32x32 kernels fit (att_pool32b_fits) takes their one-plane form, whatever the
+    // context's att_bf16x3 says; any other stage runs as it does at the default precision
+    int one_plane = 0;
 };
 
 // Plain fp32 image of one d = 16 attention stage for att_lane_kernel (attpool_lane.hip), offsets in floats: b1 [8] | W1 [10, 8] | b2 [8] |
@@ -57,7 +65,7 @@ int att_lane_stage(ps_context* c, const AttStage& s);  // (PS_EINVAL outside d =
 int att_lane_pass_points();  // points one pass of its grid covers (beyond that a wave loops)
 
 // the 32x32 forms when they fit (the split-bf16 one first, when the context asks for it), the lane form at d = 16 / K = 16, otherwise
-// att_pool16_stage; att_pool_form names the choice as ps_debug_att_stage numbers its forms (1 bf16x3, 2 32x32, 3 16x16x4, 4 lane)
+// att_pool16_stage; att_pool_form names the choice as ps_debug_att_stage numbers its forms (1 bf16x3, 2 32x32, 3 16x16x4, 4 lane, 5 one-plane 32x32)
 int att_pool_stage(ps_context* c, const AttStage& s);
 int att_pool_form(const ps_context* c, const AttStage& s);
 // the 16x16x4 kernels of attpool.hip: the direct formulation when wfull is set (d <= 32), otherwise the pre-product kernel att_kernel --

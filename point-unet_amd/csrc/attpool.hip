@@ -560,7 +560,7 @@ static int dispatch_d(ps_context* c, int d, const AttArgs& a)
 
 int att_pool_stage(ps_context* c, const AttStage& s)
 {
-    if (c->att_bf16x3 && att_pool32b_fits(s)) return att_pool32b_stage(c, s);
+    if ((c->att_bf16x3 || s.one_plane) && att_pool32b_fits(s)) return att_pool32b_stage(c, s);
     if (att_pool32_fits(s)) return att_pool32_stage(c, s);
     if (att_lane_fits(c, s)) return att_lane_stage(c, s);
     return att_pool16_stage(c, s);
@@ -568,6 +568,7 @@ int att_pool_stage(ps_context* c, const AttStage& s)
 
 int att_pool_form(const ps_context* c, const AttStage& s)
 {
+    if (s.one_plane && att_pool32b_fits(s)) return 5;
     if (c->att_bf16x3 && att_pool32b_fits(s)) return 1;
     if (att_pool32_fits(s)) return 2;
     return att_lane_fits(c, s) ? 4 : 3;

@@ -39,12 +39,23 @@ __device__ __forceinline__ float fg_load(__amdgpu_buffer_rsrc_t r, unsigned off)
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
 }
 
-__device__ __forceinline__ B3Planes load_planes(const uint4* img, int slot, int lane)
+// (P = 3 written out as it always was: as a loop over the planes the split kernels of d >= 256 compiled to other code, with more registers)
+template <int P>
+__device__ __forceinline__ BPlanes<P> load_planes(const uint4* img, int slot, int lane);
+template <>
+__device__ __forceinline__ B3Planes load_planes<3>(const uint4* img, int slot, int lane)
 {
     B3Planes r;
     r.p[0] = img[(slot * 3 + 0) * 64 + lane];
     r.p[1] = img[(slot * 3 + 1) * 64 + lane];
     r.p[2] = img[(slot * 3 + 2) * 64 + lane];
+    return r;
+}
+template <>
+__device__ __forceinline__ BPlanes<1> load_planes<1>(const uint4* img, int slot, int lane)
+{
+    BPlanes<1> r;
+    r.p[0] = img[slot * 64 + lane];
     return r;
 }
 
@@ -67,12 +78,15 @@ __device__ __forceinline__ void stage_write(uint4* dst, const uint4 (&r)[R], int
     }
 }
 
-template <int D, int STAGE, int KN, int WAVES>
+// P = 3: the exact split.  P = 1 (PS_PREC_BF16): LFA mlp2 and the score product f_xyz . Wfc[H:, :] take both operands rounded once to bfloat16 --
+// one plane per operand, one MFMA per chunk, w2 / wb as one-plane images; the LocSE product keeps the exact split of both operands (w1 stays the
+// three-plane pack_b3_locse image): positions at 8 bits would quantise the volume.
+template <int D, int STAGE, int KN, int WAVES, int P>
 __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 {
     constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN;
     constexpr int CBH = H / 32, CBD = D / 32, NQ = H / 16;
-    constexpr int W1Q = CBH * 3 * 64, W2Q = STAGE == 2 ? CBH * NQ * 3 * 64 : 0, WBQ = CBD * NQ * 3 * 64;  // uint4 counts
+    constexpr int W1Q = CBH * 3 * 64, W2Q = STAGE == 2 ? CBH * NQ * P * 64 : 0, WBQ = CBD * NQ * P * 64;  // uint4 counts
     constexpr int TILE = 32 * PITCH;
     static_assert(H % 32 == 0 && (KN == 16 || KN == 32), "att32b: d_out >= 64, K in {16, 32}");
 
@@ -153,23 +167,23 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
         for (int cb = 0; cb < CBH; ++cb) {
             f32x16 acc;
             ATT32_BIAS_SEED(acc, b1, cb);
-            acc = b3_mfma6<3>(load_planes(w1, cb, lane), E, acc);
+            acc = b3_mfma6<3>(load_planes<3>(w1, cb, lane), E, acc);
 #pragma unroll
             for (int r = 0; r < 16; ++r) f1[cb][r] = leaky02(acc[r]);
         }
         gstage(1, t0 + t_step);
-        B3Planes P[NQ];  // the operand planes of the tile that feeds the scores (chunk q = accumulator registers 8 (q & 1) .. of block q >> 1)
-        auto split_block = [&](const f32x16& f, B3Planes& lo, B3Planes& hi) {
+        BPlanes<P> PL[NQ];  // the operand planes of the tile that feeds the scores (chunk q = accumulator registers 8 (q & 1) .. of block q >> 1)
+        auto split_block = [&](const f32x16& f, BPlanes<P>& lo, BPlanes<P>& hi) {
             const float x0[8] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]};
             const float x1[8] = {f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
-            lo = b3_split8<3>(x0);
-            hi = b3_split8<3>(x1);
+            lo = b3_split8<P>(x0);
+            hi = b3_split8<P>(x1);
         };
         auto store_block = [&](const f32x16& f, int cb) {  // -> fp32 tile (value reads of the weighted sum)
             ATT32_STORE_BLOCK(T1 + c32 * PITCH, cb, , f);
         };
 #pragma unroll
-        for (int cb = 0; cb < CBH; ++cb) split_block(f1[cb], P[2 * cb], P[2 * cb + 1]);
+        for (int cb = 0; cb < CBH; ++cb) split_block(f1[cb], PL[2 * cb], PL[2 * cb + 1]);
         if constexpr (STAGE == 1) {
 #pragma unroll
             for (int cb = 0; cb < CBH; ++cb) store_block(f1[cb], cb);
@@ -181,13 +195,13 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
                 f32x16 acc;
                 ATT32_BIAS_SEED(acc, b2, cb);
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(load_planes(w2, cb * NQ + q, lane), P[q], acc);
+                for (int q = 0; q < NQ; ++q) acc = b3_mfma6<P>(load_planes<P>(w2, cb * NQ + q, lane), PL[q], acc);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) f2[cb][r] = leaky02(acc[r]);
             }
 #pragma unroll
             for (int cb = 0; cb < CBH; ++cb) {
-                split_block(f2[cb], P[2 * cb], P[2 * cb + 1]);
+                split_block(f2[cb], PL[2 * cb], PL[2 * cb + 1]);
                 store_block(f2[cb], cb);
             }
         }
@@ -203,7 +217,7 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) acc = b3_mfma6<3>(P[q], load_planes(wb, cb * NQ + q, lane), acc);
+            for (int q = 0; q < NQ; ++q) acc = b3_mfma6<P>(PL[q], load_planes<P>(wb, cb * NQ + q, lane), acc);
             f32x2 (&vv)[8] = v[cb & 1];
             const f32x2 (&gs)[8] = gq[cb & 1];
 #include "att32_tile_pool.h"
@@ -217,12 +231,13 @@ __global__ __launch_bounds__(WAVES * 64) void att32b_kernel(Att32bArgs a)
 // stream from L2 (16-byte loads, one stage ahead), the tile's operand planes go through LDS ([chunk][plane][lane], 16 bytes per lane:
 // every wave needs all chunks but produces only its own blocks).  Each wave runs its two score blocks together, so an operand
 // plane read from LDS feeds both.
-template <int D, int STAGE, int KN, int WAVES>
+// (P as in att32b_kernel: one plane for LFA mlp2 and the score product, the LocSE product on the exact split)
+template <int D, int STAGE, int KN, int WAVES, int P>
 __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
 {
     constexpr int H = D / 2, LDF = H + D, PITCH = H + 4, PPT = 32 / KN;
     constexpr int CBH = H / 32, CBD = D / 32, NQ = H / 16;
-    constexpr int PLQ = NQ * 3 * 64;  // uint4s of one set of operand planes
+    constexpr int PLQ = NQ * P * 64;  // uint4s of one set of operand planes
     constexpr int NB_H = CBH / WAVES, NB_D = CBD / WAVES;  // blocks per wave
     static_assert(CBH % WAVES == 0 && NB_D == 2 && (KN == 16 || KN == 32), "att32s: two score blocks per wave");
 
@@ -248,11 +263,11 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         float x0[8], x1[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { x0[r] = leaky02(acc[r]); x1[r] = leaky02(acc[8 + r]); }
-        const B3Planes lo = b3_split8<3>(x0), hi = b3_split8<3>(x1);
+        const BPlanes<P> lo = b3_split8<P>(x0), hi = b3_split8<P>(x1);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            planes[((2 * cb) * 3 + pl) * 64 + lane] = lo.p[pl];
-            planes[((2 * cb + 1) * 3 + pl) * 64 + lane] = hi.p[pl];
+        for (int pl = 0; pl < P; ++pl) {
+            planes[((2 * cb) * P + pl) * 64 + lane] = lo.p[pl];
+            planes[((2 * cb + 1) * P + pl) * 64 + lane] = hi.p[pl];
         }
         if (values) {  // (ATT32_STORE_BLOCK from x0 | x1)
 #pragma unroll
@@ -263,10 +278,17 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         }
     };
     static_assert(NB_H == 1, "att32s: one transposed block per wave");
-    const B3Planes W1 = load_planes(a.w1, wave, lane);  // this wave's LocSE block: resident for the whole kernel
+    const B3Planes W1 = load_planes<3>(a.w1, wave, lane);  // this wave's LocSE block: resident for the whole kernel
     const f32x16 seed1 = seed(a.b1, wave);
-    constexpr int PD = D >= 512 ? 4 : 2;                // score-weight chunks in flight per block (measured: 2 at d = 256, 4 at d = 512)
-    constexpr int PD2 = STAGE == 2 ? (D >= 512 ? 4 : 8) : 1;  // mlp2-weight chunks in flight (measured: all 8 at d = 256, 4 at d = 512)
+    // P = 3: score-weight chunks in flight per block (measured: 2 at d = 256, 4 at d = 512) and mlp2-weight chunks in flight (measured: all 8
+    // at d = 256, 4 at d = 512).  P = 1: a chunk is 1 KB per wave instead of 3 and its product one MFMA instead of six, so the same bytes in
+    // flight against the same L2 latency are three times the chunks.  d = 256: all eight chunks of a block in both rings (16 + 8 uint4 per lane,
+    // 202-220 registers).  d = 512: eight spilled (76-236 bytes of scratch per lane next to the 32 accumulators of two score blocks and the 32
+    // gathered values); six does not divide the sixteen chunks of a block, so four, the split form's depth at a third of its registers.
+    // Reasoned from the sizes and the compiler's resource summary, not measured.
+    constexpr int PD = P == 1 ? (D >= 512 ? 4 : 8) : (D >= 512 ? 4 : 2);
+    constexpr int PD2 = STAGE == 2 ? (D >= 512 ? 4 : 8) : 1;  // (the same depths at P = 1, for the reasons above)
+    static_assert(NQ % PD == 0 && (STAGE == 1 || NQ % PD2 == 0), "att32s: the rings walk the K axis in whole passes");
     const int cbA = wave, cbB = wave + WAVES;
     for (int t0 = t_first; t0 < t_end; t0 += t_step) {
 #include "att32_tile_row.h"
@@ -275,15 +297,15 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
         if (hl == 0 && wave == 0) NB[c32] = nbr;
         gstage(0, t0 + t_step);
         // the first weight chunks of the next product do not depend on anything: they travel under LocSE and its barrier
-        B3Planes ring[PD2], rA[PD], rB[PD];
+        BPlanes<P> ring[PD2], rA[PD], rB[PD];
         if constexpr (STAGE == 2) {
 #pragma unroll
-            for (int q = 0; q < PD2; ++q) ring[q] = load_planes(a.w2, wave * NQ + q, lane);
+            for (int q = 0; q < PD2; ++q) ring[q] = load_planes<P>(a.w2, wave * NQ + q, lane);
         } else {
 #pragma unroll
             for (int q = 0; q < PD; ++q) {
-                rA[q] = load_planes(a.wb, cbA * NQ + q, lane);
-                rB[q] = load_planes(a.wb, cbB * NQ + q, lane);
+                rA[q] = load_planes<P>(a.wb, cbA * NQ + q, lane);
+                rB[q] = load_planes<P>(a.wb, cbB * NQ + q, lane);
             }
         }
 
@@ -303,16 +325,16 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             for (int q0 = 0; q0 + PD2 < NQ; q0 += PD2) {
 #pragma unroll
                 for (int j = 0; j < PD2; ++j) {
-                    acc = b3_mfma6<3>(ring[j], load_planes(PA, q0 + j, lane), acc);
-                    ring[j] = load_planes(a.w2, cb * NQ + q0 + j + PD2, lane);  // refilled in place, behind its last reader
+                    acc = b3_mfma6<P>(ring[j], load_planes<P>(PA, q0 + j, lane), acc);
+                    ring[j] = load_planes<P>(a.w2, cb * NQ + q0 + j + PD2, lane);  // refilled in place, behind its last reader
                 }
             }
 #pragma unroll
-            for (int j = 0; j < PD2; ++j) acc = b3_mfma6<3>(ring[j], load_planes(PA, NQ - PD2 + j, lane), acc);
+            for (int j = 0; j < PD2; ++j) acc = b3_mfma6<P>(ring[j], load_planes<P>(PA, NQ - PD2 + j, lane), acc);
 #pragma unroll
             for (int q = 0; q < PD; ++q) {  // the score product's first chunks, under the split + barrier
-                rA[q] = load_planes(a.wb, cbA * NQ + q, lane);
-                rB[q] = load_planes(a.wb, cbB * NQ + q, lane);
+                rA[q] = load_planes<P>(a.wb, cbA * NQ + q, lane);
+                rB[q] = load_planes<P>(a.wb, cbB * NQ + q, lane);
             }
             emit_block(acc, cb, PB, true);
             __syncthreads();
@@ -329,11 +351,11 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
             for (int q0 = 0; q0 + PD < NQ; q0 += PD) {
 #pragma unroll
                 for (int j = 0; j < PD; ++j) {
-                    const B3Planes x = load_planes(PB, q0 + j, lane);
-                    accA = b3_mfma6<3>(x, rA[j], accA);
-                    accB = b3_mfma6<3>(x, rB[j], accB);
-                    rA[j] = load_planes(a.wb, cbA * NQ + q0 + j + PD, lane);  // refilled in place, behind its last reader
-                    rB[j] = load_planes(a.wb, cbB * NQ + q0 + j + PD, lane);
+                    const BPlanes<P> x = load_planes<P>(PB, q0 + j, lane);
+                    accA = b3_mfma6<P>(x, rA[j], accA);
+                    accB = b3_mfma6<P>(x, rB[j], accB);
+                    rA[j] = load_planes<P>(a.wb, cbA * NQ + q0 + j + PD, lane);  // refilled in place, behind its last reader
+                    rB[j] = load_planes<P>(a.wb, cbB * NQ + q0 + j + PD, lane);
                 }
             }
             // last pass: nothing is refilled any more; the G rows of both blocks travel under its products
@@ -343,9 +365,9 @@ __global__ __launch_bounds__(WAVES * 64) void att32s_kernel(Att32bArgs a)
                 for (int r = 0; r < 16; ++r) gq[i][r >> 1][r & 1] = *reinterpret_cast<const float*>(fgb + off[r] + (i * WAVES * 32 * 4 + H * 4));
 #pragma unroll
             for (int j = 0; j < PD; ++j) {
-                const B3Planes x = load_planes(PB, NQ - PD + j, lane);
-                accA = b3_mfma6<3>(x, rA[j], accA);
-                accB = b3_mfma6<3>(x, rB[j], accB);
+                const BPlanes<P> x = load_planes<P>(PB, NQ - PD + j, lane);
+                accA = b3_mfma6<P>(x, rA[j], accA);
+                accB = b3_mfma6<P>(x, rB[j], accB);
             }
         }
         // value rows of the first block (columns < H: gathered neighbour features); the second block (f_xyz columns, LDS) goes first
@@ -372,15 +394,16 @@ static inline int kmap(int q, int g, int j)
     return 32 * (q >> 1) + (r & 3) + 8 * (r >> 2) + 4 * g;
 }
 
-void pack_b3(const float* W, int cin, int cout, uint16_t* out)
+void pack_b3(const float* W, int cin, int cout, uint16_t* out, int planes)  // planes = 1: the weights rounded to nearest even, 2 bytes each
 {
     const int nq = cin / 16, cbs = cout / 32;
     for (int cb = 0; cb < cbs; ++cb)
         for (int q = 0; q < nq; ++q)
-            for (int pl = 0; pl < 3; ++pl)
+            for (int pl = 0; pl < planes; ++pl)
                 for (int l = 0; l < 64; ++l)
                     for (int j = 0; j < 8; ++j)
-                        out[(((((size_t)cb * nq + q) * 3 + pl) * 64 + l) * 8) + j] = b3_piece_of(W[(size_t)kmap(q, l >> 5, j) * cout + 32 * cb + (l & 31)], pl);
+                        out[(((((size_t)cb * nq + q) * planes + pl) * 64 + l) * 8) + j] =
+                            b3_plane_of(W[(size_t)kmap(q, l >> 5, j) * cout + 32 * cb + (l & 31)], pl, planes);
 }
 
 void pack_b3_locse(const float* W1, int cout, uint16_t* out)
@@ -395,7 +418,7 @@ void pack_b3_locse(const float* W1, int cout, uint16_t* out)
                 }
 }
 
-template <int D, int STAGE, int KN>
+template <int D, int STAGE, int KN, int P>
 static int launch_att32b(ps_context* c, const Att32bArgs& a)
 {
     constexpr int H = D / 2, PITCH = H + 4, TILE = 32 * PITCH;
@@ -404,12 +427,16 @@ static int launch_att32b(ps_context* c, const Att32bArgs& a)
     // tiles, one workgroup of twelve waves (134 registers: three waves per SIMD) in stage 2
     // (d = 64, stage 1: sixteen waves -- 126 registers, four waves per SIMD: 43.5 -> 41.2 us; stage 2 needs 134 and spills at sixteen: 50.0 -> 51.0)
     // (with the gathers as buffer loads the counts are 116 and 124: sixteen waves would fit stage 2 now -- not measured)
-    constexpr int WAVES = D == 128 ? 8 : (STAGE == 1 ? 16 : 12);
+    // P = 1, derived from its own sizes: d = 128: 6 KB of LocSE planes + 8 + 16 KB of one-plane images = 30 KB, twelve 8.8 KB tiles = 136 KB (sixteen
+    // would be 171 KB); d = 64: 9 KB + sixteen 4.7 KB tiles = 84 KB in both stages.  The operand planes of a tile are a third of the split form's
+    // (d = 128: 16 registers for 48), which is what lets stage 2 keep the register budget of twelve (168) and sixteen (128) waves: the compiler's
+    // resource summary shows no scratch for any of them
+    constexpr int WAVES = P == 1 ? (D == 128 ? 12 : 16) : (D == 128 ? 8 : (STAGE == 1 ? 16 : 12));
     constexpr int PER_CU = 1;
-    constexpr size_t planes = (size_t)(CBH + (STAGE == 2 ? CBH * NQ : 0) + CBD * NQ) * 3 * 64 * 16;
+    constexpr size_t planes = (size_t)(CBH * 3 + ((STAGE == 2 ? CBH * NQ : 0) + CBD * NQ) * P) * 64 * 16;
     constexpr size_t smem = planes + sizeof(float) * (2 * H + (size_t)WAVES * (32 + TILE));
     static_assert(smem <= 160 * 1024, "att32b: weights + tiles exceed the LDS");
-    auto kern = att32b_kernel<D, STAGE, KN, WAVES>;
+    auto kern = att32b_kernel<D, STAGE, KN, WAVES, P>;
     PS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int tiles = ceil_div(a.n_total, 32 / KN);
     const int blocks = (std::min(ceil_div(tiles, WAVES), 256 * PER_CU) + 7) & ~7;
@@ -418,14 +445,14 @@ static int launch_att32b(ps_context* c, const Att32bArgs& a)
     return PS_OK;
 }
 
-template <int D, int STAGE, int KN>
+template <int D, int STAGE, int KN, int P>
 static int launch_att32s(ps_context* c, const Att32bArgs& a)
 {
     constexpr int H = D / 2, PITCH = H + 4, NQ = H / 16;
     constexpr int WAVES = D / 64;  // two score blocks per wave: 4 waves at d = 256, 8 at d = 512
-    constexpr size_t smem = sizeof(float) * 32 + (size_t)(STAGE == 2 ? 2 : 1) * NQ * 3 * 64 * 16 + sizeof(float) * 32 * PITCH;
+    constexpr size_t smem = sizeof(float) * 32 + (size_t)(STAGE == 2 ? 2 : 1) * NQ * P * 64 * 16 + sizeof(float) * 32 * PITCH;
     static_assert(smem <= 160 * 1024, "att32s: planes + value tile exceed the LDS");
-    auto kern = att32s_kernel<D, STAGE, KN, WAVES>;
+    auto kern = att32s_kernel<D, STAGE, KN, WAVES, P>;
     if (smem > 48 * 1024) PS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int tiles = ceil_div(a.n_total, 32 / KN);
     const int blocks = (std::min(tiles, 256 * 16) + 7) & ~7;
@@ -439,14 +466,23 @@ bool att_pool32b_fits(const AttStage& s)
     return att_pool32_fits(s) && s.p32->w1b && (s.d == 64 || s.d == 128 || s.d == 256 || s.d == 512);
 }
 
+template <int P>
+static int att32b_stage_p(ps_context* c, const AttStage& s, const Att32bArgs& a)
+{
+    if (s.d == 64) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<64, stage(), k(), P>(c, a); });
+    if (s.d == 128) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<128, stage(), k(), P>(c, a); });
+    if (s.d == 256) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<256, stage(), k(), P>(c, a); });
+    return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<512, stage(), k(), P>(c, a); });
+}
+
 int att_pool32b_stage(ps_context* c, const AttStage& s)
 {
     if (s.n_total <= 0) return PS_OK;
-    const Att32bArgs a = att32_args<Att32bArgs>(s, s.p32->w1b, s.p32->w2b, s.p32->wb1b, s.p32->wb2b);
-    if (s.d == 64) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<64, stage(), k()>(c, a); });
-    if (s.d == 128) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32b<128, stage(), k()>(c, a); });
-    if (s.d == 256) return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<256, stage(), k()>(c, a); });
-    return att32_stage_k(s, [&](auto stage, auto k) { return launch_att32s<512, stage(), k()>(c, a); });
+    if (s.one_plane) {  // PS_PREC_BF16: LFA mlp2 and the score product on one plane of rounded operands; LocSE on its three-plane image
+        PS_CHECK(s.p32->wb1b1 && s.p32->wb2b1 && s.p32->w2b1, "att_pool32b: the level has no one-plane images");
+        return att32b_stage_p<1>(c, s, att32_args<Att32bArgs>(s, s.p32->w1b, s.p32->w2b1, s.p32->wb1b1, s.p32->wb2b1));
+    }
+    return att32b_stage_p<3>(c, s, att32_args<Att32bArgs>(s, s.p32->w1b, s.p32->w2b, s.p32->wb1b, s.p32->wb2b));
 }
 
 }  // namespace ps

@@ -91,6 +91,10 @@ __device__ __forceinline__ f32x4 b3_mfma16(const uint4& a, const uint4& b, f32x4
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
+__device__ __forceinline__ f32x4 b3_mfma16_6(const BPlanes<1>& a, const BPlanes<1>& b, f32x4 acc)  // one plane: the one product
+{
+    return b3_mfma16(a.p[0], b.p[0], acc);
+}
 __device__ __forceinline__ f32x4 b3_mfma16_6(const B3Planes& a, const B3Planes& b, f32x4 acc)  // the six kept piece products, smallest first
 {
     acc = b3_mfma16(a.p[2], b.p[0], acc);
@@ -123,6 +127,26 @@ inline uint16_t b3_piece_of(float w, int plane)
     __builtin_memcpy(&u, &pick, 4);
     return (uint16_t)(u >> 16);
 }
+
+// Host: w rounded ONCE to bfloat16, round to nearest even (ties to even) -- what b3_rne_pair / v_cvt_pk_bf16_f32 give for a finite w: the
+// one plane of the P = 1 weight images packed on the host (pack_p32b, pack_b3 with planes = 1), and the same value as an fp32
+inline uint16_t b3_rne_of(float w)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &w, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);  // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline float b3_rounded(float w)
+{
+    const uint32_t u = (uint32_t)b3_rne_of(w) << 16;
+    float r;
+    __builtin_memcpy(&r, &u, 4);
+    return r;
+}
+// piece `plane` of w in an image of `planes` planes (3: the exact split, 1: the rounded value)
+inline uint16_t b3_plane_of(float w, int plane, int planes) { return planes == 1 ? b3_rne_of(w) : b3_piece_of(w, plane); }
 
 // the element function of gemm_b3_pack_kernel for the batched form (PackCache): thread i of job j.
 // KMAP: the K axis in the order in which a 32x32 accumulator tile hands its values on as the next product's operand (b3_ops.h:

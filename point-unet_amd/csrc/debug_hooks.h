@@ -53,12 +53,14 @@ int ps_debug_pack_b3_device(ps_context* ctx, const float* W, int cin, int cout, 
 /* One dense layer of the deep levels, Y = act([X1[g1] | X2[g2]] . W + b), through gemm32b.hip (split_bf16 != 0: bf16 MFMA over exact
  * three-way splits) or gemm32.hip (fp32 MFMA); needs a GPU.  x1 / x2 / g1 / g2 / y: DEVICE pointers (g* may be NULL: plain rows; gm / gn:
  * batched gather, row r reads x[(r / gm) * gn + g[r]] when gm != 0), W [c1 + c2, cout] and bias [cout]: HOST.  Returns PS_EINVAL when the
- * shape does not fit the kernel. */
+ * shape does not fit the kernel.  split_bf16 = 2: the ONE-plane form of gemm32b.hip -- both operands rounded once to bfloat16 (round to nearest
+ * even), fp32 accumulation: a layer of a network at PS_PREC_BF16 (include/pointseg_forward_precision.h). */
 int ps_debug_gemm32(ps_context* ctx, int split_bf16, const float* x1, int ld1, int c1, const int32_t* g1, const float* x2, int ld2, int c2,
                     const int32_t* g2, int gm, int gn, const float* W, const float* bias, int64_t R, int cout, int leaky, float* y, int ldy);
 /* The launch ps_debug_gemm32 (and the network's own dense layers) make on this context for R x cin x cout: out4 = {rw, cw, sk, pd} -- rw x cw
  * blocks of 32 x 32 per wave, sk waves splitting the K axis (chunks of 8 inputs for the fp32 kernel, 16 for the split form) into slices
- * [nq k / sk, nq (k + 1) / sk), pd chunks in flight.  Host only: no GPU work. */
+ * [nq k / sk, nq (k + 1) / sk), pd chunks in flight (split_bf16 = 2: the one-plane form -- the same tiles and slices, its own ring depth).  Host
+ * only: no GPU work. */
 int ps_debug_gemm32_plan(ps_context* ctx, int split_bf16, int64_t R, int cin, int cout, int* out4);
 
 /* A chain of 1..4 dense layers over R rows, act_l = act([act_{l-1} | extra_l] . W_l + b_l), act_{-1} = [x1[g1] | x2[g2]] (csrc/rowgemm.h: rowchain).
@@ -85,13 +87,21 @@ typedef struct ps_debug_chain_desc {
 /* Runs the chain with freshly packed weights (pack_weights + zero-padded bias, and the k-permuted image when cin % 16 == 0, as ps_randla_set_weights
  * packs every layer); needs a GPU.  form 0: rowchain() as the network calls it, with a weight-image cache; 1: regchain with the image re-ordered
  * inside the kernel (no cache); 2: rowchain_lds (the LDS-staged kernel); 3: layer by layer through rowgemm (16x16x4 kernels; un-stored rows go to
- * scratch).  Returns PS_EINVAL, with a message, when the chain does not fit the form. */
+ * scratch).  Returns PS_EINVAL, with a message, when the chain does not fit the form.
+ * forms 4..7 = forms 0..3 on the images of a network at PS_PREC_BF16 (include/pointseg_forward_precision.h): every layer whose cin is a multiple
+ * of 16 and at least 32 has both operands rounded once to bfloat16 -- its images hold the rounded weights and the kernel that takes it rounds the
+ * activations as it loads them; the other layers are what they are in forms 0..3.  Form 5 (regchain) takes a chain only when EVERY layer is
+ * rounded and the shape is one of the one-plane policy's; a mixed chain runs on forms 4 (which then picks rowchain_kernel), 6 and 7. */
 int ps_debug_chain(ps_context* ctx, const ps_debug_chain_desc* d, int form);
 /* The launch rowchain() makes for the same description: out4 = {form (0: the chain fits neither kernel, 1: regchain_kernel, 2: rowchain_kernel),
  * workgroups, dynamic LDS bytes, rowchain_kernel's float4 input staging (log2 of the float4s per row; 0 = scalar staging)}.  A workgroup is four
  * waves that each take one 16-row tile per round: past workgroups * 64 rows a wave walks to a second tile.  Host only: reads the channel counts
  * and the alignment of the pointers, never what they point to; W / bias may be NULL. */
 int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4);
+/* The same at a precision of include/pointseg_forward_precision.h: 1 (PS_PREC_BF16X3) = ps_debug_chain_plan, 2 (PS_PREC_BF16) = the launch of
+ * ps_debug_chain's form 4, where form 3 = regchain_kernel on one plane of rounded operands (every layer rounded: eight waves per workgroup, 2
+ * bytes per weight of LDS) and form 2 = rowchain_kernel, which rounds layer by layer. */
+int ps_debug_chain_plan_prec(const ps_debug_chain_desc* d, int precision, int* out4);
 /* The operand policy of regchain's routed chain shapes on this context (on by default): 1 = bf16 MFMA over exact three-way splits, 0 = the fp32
  * MFMA for every shape.  ps_debug_chain forms 0 and 1 follow it; ps_debug_chain_plan has no context and reports the fp32 launch. */
 int ps_debug_set_regchain_b3(ps_context* ctx, int on);
@@ -103,13 +113,20 @@ int ps_debug_set_att_lane(ps_context* ctx, int on);
  * (cloud-local), order i32[n_total] or NULL, fg f32[n_total, d/2 + d] = [f | G] for d >= 64 and f32[n_total, d/2] = f below, agg f32[n_total, d]:
  * DEVICE pointers.  form 0: att_pool_stage (the product's dispatch), 1: att_pool32b_stage (split-bf16 32x32), 2: att_pool32_stage (fp32 32x32),
  * 3: att_pool16_stage (16x16x4: the direct kernel at d <= 32, att_kernel above), 4: att_lane_stage (the vector-ALU kernel of attpool_lane.hip,
- * d = 16 and K = 16 only, whatever the context's att_lane switch says).  PS_EINVAL when the level does not fit the form. */
+ * d = 16 and K = 16 only, whatever the context's att_lane switch says), 5: att_pool32b_stage on ONE plane of rounded operands (LFA mlp2 and the
+ * score product; LocSE stays on the exact split), on the network's PS_PREC_BF16 images whatever its precision -- PS_EINVAL where form 1 is.  Form 0
+ * follows the network's precision.  PS_EINVAL when the level does not fit the form. */
 int ps_debug_att_stage(ps_randla* net, int level, int stage, int form, const float* xyz, const int32_t* idx, const int32_t* order, const float* fg,
                        int64_t n_total, int64_t n_cloud, float* agg);
-/* The form (1 .. 4, numbered as above) att_pool_stage takes for stage 1 or 2 of encoder level `level` at k neighbours and n_total rows, on the
+/* The form (1 .. 5, numbered as above; 5 only for a network at PS_PREC_BF16) att_pool_stage takes for stage 1 or 2 of encoder level `level` at k neighbours and n_total rows, on the
  * network's context as its knobs stand -- bit-identical outputs cannot show which kernel ran.  Host only.  Returns the form, not a status: -1 on
  * a bad argument. */
 int ps_debug_att_form(ps_randla* net, int level, int stage, int k, int64_t n_total);
+/* The kernel family rowgemm() takes, on the network's context and at the network's precision, for one of the network's OWN dense layers over R
+ * rows: which 0 = att_pooling_1 mlp of encoder level `level`, 1 = its att_pooling_2 mlp, 2 = its [mlp2 ; shortcut], 3 = decoder_0, 4 = decoder step
+ * `level`.  Returns 5 = gemm32b on one plane of rounded operands, 1 = gemm32b on the exact split, 2 = gemm32, 3 = the 16x16 kernels of rowgemm.hip;
+ * -1 on a bad argument.  Host only. */
+int ps_debug_dense_form(ps_randla* net, int which, int level, int64_t R);
 /* Points one pass of att_lane_kernel's largest grid covers (workgroups x waves x points per wave iteration): past it a wave walks on. */
 int ps_debug_att_lane_pass_points(void);
 

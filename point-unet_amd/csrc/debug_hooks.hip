@@ -13,6 +13,7 @@
 #include "kdtree_host.h"
 #include "rowgemm.h"
 #include "attpool.h"
+#include "b3_ops.h"
 #include "debug_hooks.h"
 #include "randla_net.h"
 #include "reduce_partials.h"
@@ -60,9 +61,11 @@ extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, i
     PS_HIP(hipSetDevice(c->device));
     const int cin = c1 + c2;
     // (gemm32_fits: 8-wide K chunks for the fp32 kernel, 16-wide for the split form)
+    PS_CHECK(split_bf16 >= 0 && split_bf16 <= 2, "ps_debug_gemm32: split_bf16 is 0, 1 or 2");
     PS_CHECK(cin % (split_bf16 ? 16 : 8) == 0 && cout % 32 == 0, "ps_debug_gemm32: cin %% %d and cout %% 32 must be 0", split_bf16 ? 16 : 8);
-    std::vector<float> img((size_t)cin * cout * (split_bf16 ? 3 : 2) / 2);
-    if (split_bf16) pack_p32b(W, cin, cout, reinterpret_cast<uint16_t*>(img.data()));
+    const bool one_plane = split_bf16 == 2;  // (the image of a rounded layer: pack_p32b rounds the weights itself)
+    std::vector<float> img((size_t)cin * cout * (one_plane ? 1 : (split_bf16 ? 3 : 2)) / 2);
+    if (split_bf16) pack_p32b(W, cin, cout, reinterpret_cast<uint16_t*>(img.data()), one_plane ? 1 : 3);
     else pack_p32(W, cin, cout, img.data());
     float *d_img = nullptr, *d_bias = nullptr;
     PS_HIP(hipMalloc(reinterpret_cast<void**>(&d_img), img.size() * sizeof(float)));
@@ -71,7 +74,9 @@ extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, i
     PS_HIP(hipMemcpyAsync(d_bias, bias, sizeof(float) * (size_t)cout, hipMemcpyHostToDevice, c->stream));
     PackedLinear L;
     L.cin = cin; L.cout = cout; L.leaky = leaky; L.bias = d_bias;
-    if (split_bf16) L.w32b = d_img; else L.w32 = d_img;
+    if (one_plane) { L.w32b1 = d_img; L.round = 1; }
+    else if (split_bf16) L.w32b = d_img;
+    else L.w32 = d_img;
     RowSrc s1, s2;
     s1.x = x1; s1.ld = ld1; s1.c = c1; s1.gather = g1; s1.gm = g1 ? gm : 0; s1.gn = g1 ? gn : 0;
     s2.x = x2; s2.ld = ld2; s2.c = c2; s2.gather = g2; s2.gm = g2 ? gm : 0; s2.gn = g2 ? gn : 0;
@@ -88,8 +93,9 @@ extern "C" int ps_debug_gemm32(ps_context* c, int split_bf16, const float* x1, i
 
 extern "C" int ps_debug_gemm32_plan(ps_context* c, int split_bf16, int64_t R, int cin, int cout, int* out4)
 {
-    PS_CHECK(c && out4 && R >= 1 && cin > 0 && cout > 0 && cin % (split_bf16 ? 16 : 8) == 0 && cout % 32 == 0, "ps_debug_gemm32_plan: bad argument");
-    const Gemm32Plan p = split_bf16 ? gemm32b_plan(c->tune, R, cin, cout) : gemm32_plan(c->tune, R, cin, cout);
+    PS_CHECK(c && out4 && R >= 1 && cin > 0 && cout > 0 && split_bf16 >= 0 && split_bf16 <= 2 && cin % (split_bf16 ? 16 : 8) == 0 && cout % 32 == 0,
+             "ps_debug_gemm32_plan: bad argument");
+    const Gemm32Plan p = split_bf16 ? gemm32b_plan(c->tune, R, cin, cout, split_bf16 == 2 ? 1 : 3) : gemm32_plan(c->tune, R, cin, cout);
     out4[0] = p.rw;
     out4[1] = p.cw;
     out4[2] = p.sk;
@@ -111,7 +117,8 @@ struct ChainBuild {
 
 // the description as ChainStep / RowSrc: the geometry emit() of ps_randla_set_weights gives a layer; the image pointers stay `image` (any non-null
 // pointer: the fits / plan functions only test them) until ps_debug_chain has packed them
-int chain_describe(const ps_debug_chain_desc* d, ChainBuild& b, const float* image)
+// (prec: the rule of PS_PREC_BF16 per layer, as pack_images of randla.hip applies it: round iff cin % 16 == 0 and cin >= 32)
+int chain_describe(const ps_debug_chain_desc* d, ChainBuild& b, const float* image, bool prec = false)
 {
     PS_CHECK(d && d->n_layers >= 1 && d->n_layers <= kChainMaxSteps, "ps_debug_chain: 1..%d layers", kChainMaxSteps);
     PS_CHECK(d->R >= 0 && d->c1 > 0 && d->c2 >= 0 && d->ld1 >= d->c1 && (d->c2 == 0 || d->ld2 >= d->c2), "ps_debug_chain: bad row sources");
@@ -132,6 +139,7 @@ int chain_describe(const ps_debug_chain_desc* d, ChainBuild& b, const float* ima
         L.ntb = choose_ntb(y.cout);
         L.cblocks = (y.cout + 16 * L.ntb - 1) / (16 * L.ntb);
         L.wp = image; L.bias = image;
+        L.round = (prec && y.cin % 16 == 0 && y.cin >= 32) ? 1 : 0;
         ChainStep& st = b.steps[i];
         st = ChainStep();
         st.L = &L; st.y = y.y; st.ldy = y.ldy;
@@ -158,11 +166,27 @@ extern "C" int ps_debug_chain_plan(const ps_debug_chain_desc* d, int* out4)
     return PS_OK;
 }
 
+extern "C" int ps_debug_chain_plan_prec(const ps_debug_chain_desc* d, int precision, int* out4)
+{
+    PS_CHECK(d && out4 && d->R >= 1 && (precision == 1 || precision == 2), "ps_debug_chain_plan_prec: bad argument");
+    static const float nothing = 0.f;
+    ChainBuild b;
+    PS_TRY(chain_describe(d, b, &nothing, precision == 2));
+    const ChainPlan p = rowchain_plan(b.steps, b.n, b.s1, b.s2, d->R);
+    out4[0] = p.form;
+    out4[1] = p.form ? p.blocks : 0;
+    out4[2] = p.form ? (int)p.lds_bytes : 0;
+    out4[3] = p.fast_in;
+    return PS_OK;
+}
+
 extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int form)
 {
-    PS_CHECK(c && d && form >= 0 && form <= 3, "ps_debug_chain: bad argument");
+    PS_CHECK(c && d && form >= 0 && form <= 7, "ps_debug_chain: bad argument");
+    const bool prec = form >= 4;  // forms 4..7 = forms 0..3 at PS_PREC_BF16
+    form &= 3;
     ChainBuild b;
-    PS_TRY(chain_describe(d, b, nullptr));
+    PS_TRY(chain_describe(d, b, nullptr, prec));
     PS_CHECK(d->x1 && (d->c2 == 0 || d->x2), "ps_debug_chain: NULL row source");
     for (int i = 0; i < b.n; ++i) PS_CHECK(d->layer[i].W, "ps_debug_chain: layer %d has no weights", i);
     if (form == 3) {  // (the chain forms refuse these in their fits tests; layer by layer they would show only after the first layers ran)
@@ -178,7 +202,7 @@ extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int f
     if (d->R == 0) return PS_OK;
     PS_HIP(hipSetDevice(c->device));
     // pack: wp + zero-padded bias (+ the k-permuted image) per layer, one upload; form 3 keeps its un-stored rows behind them
-    std::vector<float> host;
+    std::vector<float> host, wround;
     size_t wp_off[kChainMaxSteps], b_off[kChainMaxSteps], wq_off[kChainMaxSteps], tmp_off[kChainMaxSteps];
     auto grow = [&](size_t floats) {
         const size_t off = (host.size() + 63) & ~size_t(63);
@@ -189,10 +213,21 @@ extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int f
         const ps_debug_chain_layer& y = d->layer[i];
         PackedLinear& L = b.L[i];
         wp_off[i] = grow(L.packed_floats());
-        pack_weights(y.W, y.cin, y.cout, L.ntb, host.data() + wp_off[i]);
+        const float* Wl = y.W;
+        if (L.round) {  // a rounded layer: wp of the rounded weights and the direct-load bf16 image instead of the k-permuted one
+            wround.resize((size_t)y.cin * y.cout);
+            for (size_t t = 0; t < wround.size(); ++t) wround[t] = b3_rounded(y.W[t]);
+            Wl = wround.data();
+        }
+        pack_weights(Wl, y.cin, y.cout, L.ntb, host.data() + wp_off[i]);
         b_off[i] = grow((size_t)L.cout_pad());
         for (int k = 0; k < L.cout_pad(); ++k) host[b_off[i] + k] = (y.bias && k < y.cout) ? y.bias[k] : 0.f;
         wq_off[i] = 0;
+        if (L.round) {
+            wq_off[i] = grow(L.bf16_bytes() / 4);
+            pack_weights_bf16(Wl, y.cin, y.cout, L.ntb, reinterpret_cast<uint16_t*>(host.data() + wq_off[i]));
+            continue;
+        }
         // (no w32 / w32b / wb image on purpose: form 3 then stays on the 16x16x4 kernels of rowgemm.hip -- the direct-load one for 16-byte aligned
         //  rows of 16-multiple widths, the generic LDS one otherwise -- and never moves to gemm32, which has its own door)
         if (y.cin % 16 == 0) {
@@ -215,7 +250,8 @@ extern "C" int ps_debug_chain(ps_context* c, const ps_debug_chain_desc* d, int f
     for (int i = 0; i < b.n; ++i) {
         b.L[i].wp = dev + wp_off[i];
         b.L[i].bias = dev + b_off[i];
-        b.L[i].wq = wq_off[i] ? dev + wq_off[i] : nullptr;
+        if (b.L[i].round) b.L[i].wb = dev + wq_off[i];
+        else b.L[i].wq = wq_off[i] ? dev + wq_off[i] : nullptr;
     }
     if (rc == PS_OK) {
         if (form == 0) {
@@ -273,14 +309,22 @@ extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form
 {
     PS_CHECK(net && xyz && idx && fg && agg, "ps_debug_att_stage: NULL argument");
     PS_CHECK(net->have_weights, "ps_debug_att_stage: weights not set");
-    PS_CHECK(level >= 0 && level < net->cfg.num_layers && (stage == 1 || stage == 2) && form >= 0 && form <= 4, "ps_debug_att_stage: bad level / stage / form");
+    PS_CHECK(level >= 0 && level < net->cfg.num_layers && (stage == 1 || stage == 2) && form >= 0 && form <= 5, "ps_debug_att_stage: bad level / stage / form");
     PS_CHECK(n_total >= 0 && n_cloud >= 1 && n_total % n_cloud == 0, "ps_debug_att_stage: n_total must be a whole number of clouds");
     ps_context* c = net->ctx;
     PS_HIP(hipSetDevice(c->device));
-    const EncLevel& e = net->enc[level];
+    // form 5, and form 0 of a network at PS_PREC_BF16: that precision's images (packed here when no forward has asked for them yet)
+    const bool one_plane = form == 5 || (form == 0 && net->precision == 2);
+    const NetImages* images = net;
+    if (one_plane && net->enc[level].has_p32) {  // (a level without 32x32 images has no one-plane form: its stage is the default's)
+        PS_TRY(randla_bf16_images(net));
+        images = net->bf16.get();
+    }
+    const EncLevel& e = images->enc[level];
     const int d = e.d, h = d / 2;
     const bool use_g = d >= 64;
     AttStage s;
+    s.one_plane = one_plane ? 1 : 0;
     s.xyz = xyz; s.idx = idx; s.order = order; s.fg = fg; s.lfa1 = &e.lfa1; s.agg = agg;
     s.n_total = n_total; s.n_cloud = n_cloud; s.d = d; s.k = net->cfg.k_n; s.ldf = use_g ? h + d : h;
     s.p32 = e.has_p32 ? &e.p32 : nullptr;
@@ -294,6 +338,7 @@ extern "C" int ps_debug_att_stage(ps_randla* net, int level, int stage, int form
     else if (form == 1 && att_pool32b_fits(s)) rc = att_pool32b_stage(c, s);
     else if (form == 2 && att_pool32_fits(s)) rc = att_pool32_stage(c, s);
     else if (form == 3) rc = att_pool16_stage(c, s);
+    else if (form == 5 && att_pool32b_fits(s)) rc = att_pool32b_stage(c, s);
     else set_error("ps_debug_att_stage: the level (d = %d, %lld rows) does not fit the 32x32 form %d", d, (long long)n_total, form);
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -315,7 +360,30 @@ extern "C" int ps_debug_att_form(ps_randla* net, int level, int stage, int k, in
     s.lane = stage == 1 ? e.lane1 : e.lane2;
     s.p32 = e.has_p32 ? &e.p32 : nullptr;
     s.n_total = n_total; s.n_cloud = n_total; s.d = d; s.k = k; s.ldf = use_g ? h + d : h;
+    s.one_plane = net->precision == 2 ? 1 : 0;
     return att_pool_form(net->ctx, s);
+}
+
+// which: 0 = the level's att_pooling_1 mlp, 1 = its att_pooling_2 mlp, 2 = its [mlp2 ; shortcut], 3 = decoder_0, 4 = decoder step `level`
+extern "C" int ps_debug_dense_form(ps_randla* net, int which, int level, int64_t R)
+{
+    if (!net || !net->have_weights || which < 0 || which > 4 || level < 0 || level >= net->cfg.num_layers || R < 1) {
+        set_error("ps_debug_dense_form: bad argument");
+        return -1;
+    }
+    const NetImages* I = net;
+    if (net->precision == 2) {
+        if (randla_bf16_images(net) != PS_OK) return -1;
+        I = net->bf16.get();
+    }
+    const EncLevel& e = I->enc[level];
+    const PackedLinear& L = which == 0 ? e.att1mlp : which == 1 ? e.att2mlp : which == 2 ? e.mlp2sc : which == 3 ? I->decoder0 : I->dec[level];
+    static const float4 aligned = {0.f, 0.f, 0.f, 0.f};  // (the fits tests read the alignment of the row pointers, never the rows)
+    RowSrc s1, s2;
+    s1.x = &aligned.x; s1.c = s1.ld = L.cin;
+    if (which == 2) { s1.c = s1.ld = e.d; s2.x = &aligned.x; s2.c = s2.ld = e.d_in; }
+    if (which == 4) { s1.c = s1.ld = L.cout; s2.x = &aligned.x; s2.c = s2.ld = L.cin - L.cout; }
+    return rowgemm_form(net->ctx, L, s1, s2, R, L.cout);
 }
 
 extern "C" int ps_debug_att_lane_pass_points(void) { return att_lane_pass_points(); }

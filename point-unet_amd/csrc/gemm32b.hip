@@ -30,16 +30,23 @@ namespace {
 // ... for a whole RW x CW block of accumulators, piece product by piece product: consecutive MFMAs go to DIFFERENT accumulators.  Issued
 // accumulator by accumulator (six dependent instructions in a row) a wave spent 55 % of its cycles in issue stalls (SQ_WAIT_INST_ANY,
 // round 4 counters): a dependent MFMA waits for its predecessor's last pass, and with one wave per SIMD nothing else fills the gap.
-template <int RW, int CW>
-__device__ __forceinline__ void mfma6_all(const B3Planes (&A)[RW], const B3Planes (&B)[CW], f32x16 (&acc)[RW][CW])
+template <int P, int RW, int CW>
+__device__ __forceinline__ void mfma6_all(const BPlanes<P> (&A)[RW], const BPlanes<P> (&B)[CW], f32x16 (&acc)[RW][CW])
 {
-    constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};  // smallest products first
+    if constexpr (P == 3) {
+        constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};  // smallest products first
 #pragma unroll
-    for (int t = 0; t < 6; ++t)
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+            for (int i = 0; i < RW; ++i)
+#pragma unroll
+                for (int j = 0; j < CW; ++j) acc[i][j] = b3_mfma(A[i].p[pa[t]], B[j].p[pb[t]], acc[i][j]);
+    } else {  // one plane of rounded operands: the one product
 #pragma unroll
         for (int i = 0; i < RW; ++i)
 #pragma unroll
-            for (int j = 0; j < CW; ++j) acc[i][j] = b3_mfma(A[i].p[pa[t]], B[j].p[pb[t]], acc[i][j]);
+            for (int j = 0; j < CW; ++j) acc[i][j] = b3_mfma(A[i].p[0], B[j].p[0], acc[i][j]);
+    }
 }
 
 // PD chunks ahead: a wave's loop is a chain of dependent round trips to L2 / MALL (the weight planes of a layer are read once per 32-row
@@ -56,56 +63,66 @@ constexpr int gemm32b_pd(int rw, int cw)
 #endif
 }
 
+// One plane (P = 1: both operands rounded once to bfloat16, PS_PREC_BF16): a chunk is 16 weights of 2 bytes and ONE 32-cycle MFMA per block where
+// the split form has six behind 56 VALU instructions, so a chunk's products end ~6 x sooner while the round trip to L2 stays what it is: the
+// ring has to hold more chunks to cover the same latency.  Four for every tile shape: (2, 2) then keeps 4 x (16 + 8) = 96 registers of ring
+// next to its 64 accumulators, and the K slices of the network's layers (8-24 chunks) are multiples of four.  Reasoned, not measured.
+constexpr int gemm32b1_pd() { return 4; }
+
 // operand policy of the frame (gemm32_frame.h): a chunk is 16 inputs -- two float4 of activations per row block (row = lane & 31, eight
-// consecutive K values per lane half: exactly the operand layout of the instruction), split in registers, and the three pre-split planes
-// of the pack_p32b image per column block; six MFMAs of K = 16 per 32 x 32 block.
-struct Gemm32Split {
-    static constexpr int KC = 16, WV = 3;
+// consecutive K values per lane half: exactly the operand layout of the instruction), split in registers, and the P pre-split planes
+// of the pack_p32b image per column block; six MFMAs (P = 3) or one (P = 1) of K = 16 per 32 x 32 block.
+template <int P>
+struct Gemm32Planes {
+    static constexpr int KC = 16, WV = P;
     using wvec = uint4;
     template <int RW, int CW>
-    static constexpr int pd() { return gemm32b_pd(RW, CW); }
+    static constexpr int pd() { return P == 3 ? gemm32b_pd(RW, CW) : gemm32b1_pd(); }
     template <int RW, int CW>
-    static __device__ __forceinline__ void products(const float4 (&x)[RW][2], const uint4 (&w)[CW][3], f32x16 (&acc)[RW][CW])
+    static __device__ __forceinline__ void products(const float4 (&x)[RW][2], const uint4 (&w)[CW][P], f32x16 (&acc)[RW][CW])
     {
-        B3Planes A[RW], B[CW];
+        BPlanes<P> A[RW], B[CW];
 #pragma unroll
-        for (int i = 0; i < RW; ++i) A[i] = b3_split8<3>(x[i][0], x[i][1]);
+        for (int i = 0; i < RW; ++i) A[i] = b3_split8<P>(x[i][0], x[i][1]);
 #pragma unroll
-        for (int j = 0; j < CW; ++j) { B[j].p[0] = w[j][0]; B[j].p[1] = w[j][1]; B[j].p[2] = w[j][2]; }
-        mfma6_all<RW, CW>(A, B, acc);
+        for (int j = 0; j < CW; ++j)
+#pragma unroll
+            for (int pl = 0; pl < P; ++pl) B[j].p[pl] = w[j][pl];
+        mfma6_all<P, RW, CW>(A, B, acc);
     }
 };
+using Gemm32Split = Gemm32Planes<3>;
 
-template <int RW, int CW, int SK>
+template <int P, int RW, int CW, int SK>
 __global__ __launch_bounds__(SK > 4 ? 64 * SK : 256) void gemm32b_kernel(Gemm32Args a)
 {
-    using Op = Gemm32Split;
+    using Op = Gemm32Planes<P>;
 #include "gemm32_frame_body.h"
 }
 
 }  // namespace
 
-// [cin, cout] row-major, cin % 16 == 0, cout % 32 == 0  ->  cin * cout * 3 uint16:
-//   image[(((cb * nq + q) * 3 + plane) * 64 + lane) * 8 + t] = piece `plane` of W[16 q + 8 (lane >> 5) + t][32 cb + (lane & 31)]
-void pack_p32b(const float* W, int cin, int cout, uint16_t* out)
+// [cin, cout] row-major, cin % 16 == 0, cout % 32 == 0  ->  cin * cout * planes uint16 (planes = 3: the exact split, 1: rounded to nearest even):
+//   image[(((cb * nq + q) * planes + plane) * 64 + lane) * 8 + t] = piece `plane` of W[16 q + 8 (lane >> 5) + t][32 cb + (lane & 31)]
+void pack_p32b(const float* W, int cin, int cout, uint16_t* out, int planes)
 {
     const int nq = cin / 16, ncb = cout / 32;
     for (int cb = 0; cb < ncb; ++cb)
         for (int q = 0; q < nq; ++q)
-            for (int pl = 0; pl < 3; ++pl)
+            for (int pl = 0; pl < planes; ++pl)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int t = 0; t < 8; ++t) {
                         const int k = 16 * q + 8 * (lane >> 5) + t, n = 32 * cb + (lane & 31);
-                        out[((((size_t)cb * nq + q) * 3 + pl) * 64 + lane) * 8 + t] = b3_piece_of(W[(size_t)k * cout + n], pl);
+                        out[((((size_t)cb * nq + q) * planes + pl) * 64 + lane) * 8 + t] = b3_plane_of(W[(size_t)k * cout + n], pl, planes);
                     }
 }
 
 bool gemm32b_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy)
 {
-    return gemm32_fits_kc(L.w32b, Gemm32Split::KC, L, s1, s2, R, ldy);
+    return gemm32_fits_kc(L.round ? L.w32b1 : L.w32b, Gemm32Split::KC, L, s1, s2, R, ldy);
 }
 
-Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout)
+Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout, int planes)
 {
     Gemm32Plan p;
     const int rblocks = (int)((R + 31) / 32);
@@ -126,7 +143,7 @@ Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout)
     while (p.sk < 4 && units * p.sk < 1536 && cin / 16 / (p.sk * 2) >= 4) p.sk *= 2;
     const int ru_per_wg = 4 / p.sk;
     p.rgroups = (runits + ru_per_wg - 1) / ru_per_wg;
-    p.pd = gemm32b_pd(p.rw, p.cw);
+    p.pd = planes == 1 ? gemm32b1_pd() : gemm32b_pd(p.rw, p.cw);
     return p;
 }
 
@@ -134,19 +151,25 @@ int gemm32b(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc
 {
     if (R <= 0) return PS_OK;
     PS_CHECK(gemm32b_fits(L, s1, s2, R, ldy), "gemm32b: shape / alignment not supported (cin %d, cout %d)", L.cin, L.cout);
-    const Gemm32Plan p = gemm32b_plan(c->tune, R, L.cin, L.cout);
-    const Gemm32Args a = gemm32_args(L.w32b, L, s1, s2, R, y, ldy, p);
+    // a layer of rounded operands (PackedLinear::round, PS_PREC_BF16) runs the one-plane kernels on its one-plane image: the same plan
+    const int planes = L.round ? 1 : 3;
+    const Gemm32Plan p = gemm32b_plan(c->tune, R, L.cin, L.cout, planes);
+    const Gemm32Args a = gemm32_args(L.round ? L.w32b1 : L.w32b, L, s1, s2, R, y, ldy, p);
     const int rw = p.rw, cw = p.cw, sk = p.sk;
     const unsigned grid = 8u * (unsigned)((a.rgroups * a.cgroups + 7) / 8);
     const dim3 block(256);
-#define PS_G32B(RW_, CW_)                                                                                            \
-    if (sk == 1) hipLaunchKernelGGL((gemm32b_kernel<RW_, CW_, 1>), dim3(grid), block, 0, c->stream, a);              \
-    else if (sk == 2) hipLaunchKernelGGL((gemm32b_kernel<RW_, CW_, 2>), dim3(grid), block, 0, c->stream, a);         \
-    else hipLaunchKernelGGL((gemm32b_kernel<RW_, CW_, 4>), dim3(grid), block, 0, c->stream, a)
-    if (rw == 2 && cw == 2) { PS_G32B(2, 2); }
-    else if (rw == 2) { PS_G32B(2, 1); }
-    else if (cw == 2) { PS_G32B(1, 2); }
-    else { PS_G32B(1, 1); }
+#define PS_G32B_P(P_, RW_, CW_)                                                                                          \
+    if (sk == 1) hipLaunchKernelGGL((gemm32b_kernel<P_, RW_, CW_, 1>), dim3(grid), block, 0, c->stream, a);              \
+    else if (sk == 2) hipLaunchKernelGGL((gemm32b_kernel<P_, RW_, CW_, 2>), dim3(grid), block, 0, c->stream, a);         \
+    else hipLaunchKernelGGL((gemm32b_kernel<P_, RW_, CW_, 4>), dim3(grid), block, 0, c->stream, a)
+#define PS_G32B(RW_, CW_)                      \
+    if (planes == 1) { PS_G32B_P(1, RW_, CW_); } \
+    else { PS_G32B_P(3, RW_, CW_); }
+    if (rw == 2 && cw == 2) { PS_G32B(2, 2) }
+    else if (rw == 2) { PS_G32B(2, 1) }
+    else if (cw == 2) { PS_G32B(1, 2) }
+    else { PS_G32B(1, 1) }
+#undef PS_G32B_P
 #undef PS_G32B
     PS_HIP(hipGetLastError());
     return PS_OK;

@@ -15,9 +15,11 @@
 // decoder: rowgemm decoder_0 (:130-132); per level rowgemm over [skip | up[interp_idx]] (:137-141); the last decoder step and
 // the head (fc1, fc2, fc, :146-151; dropout is the identity in inference) are one chain over the level-0 rows.
 #include "attpool.h"
+#include "b3_ops.h"
 #include "common.h"
 #include "randla_net.h"
 #include "rowgemm.h"
+#include "../../include/pointseg_forward_precision.h"
 
 #include <memory>
 
@@ -156,6 +158,8 @@ void plan_specs(ps_randla* net)
     add(32, c.num_classes, 0);
 }
 
+int pack_images(ps_randla* net, const float* blob, bool bf, NetImages& I);
+
 }  // namespace
 
 extern "C" int ps_randla_create(ps_context* ctx, const ps_randla_config* cfg, ps_randla** out)
@@ -181,8 +185,8 @@ extern "C" int ps_randla_destroy(ps_randla* net)
     if (!net) return PS_OK;
     (void)hipSetDevice(net->ctx->device);
     (void)hipStreamSynchronize(net->ctx->stream);
-    net->wbuf.release();
-    net->chains.clear();
+    net->release();
+    if (net->bf16) net->bf16->release();
     delete net;
     return PS_OK;
 }
@@ -195,25 +199,66 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
     PS_CHECK(count == net->blob_floats, "ps_randla_set_weights: blob has %lld floats, expected %lld", (long long)count, (long long)net->blob_floats);
     ps_context* c = net->ctx;
     PS_HIP(hipSetDevice(c->device));
-    if (!net->chains.entries.empty()) {  // images derived from the old weights: drop them once nothing in flight reads them
+    if (!net->chains.entries.empty() || net->bf16) {  // images derived from the old weights: drop them once nothing in flight reads them
         PS_HIP(hipStreamSynchronize(c->stream));
         net->chains.clear();
+        if (net->bf16) net->bf16->release();
+        net->bf16.reset();  // (packed again by the next forward at PS_PREC_BF16)
     }
+    net->blob.assign(blob, blob + count);
+    PS_TRY(pack_images(net, net->blob.data(), false, *net));
+    net->have_weights = true;
+    return PS_OK;
+}
+
+namespace {
+
+// The rule of include/pointseg_forward_precision.h for a dense layer outside the attention kernels: both operands rounded once to bfloat16
+// iff its K axis (the summed width of a concatenated input) is a multiple of 16 and at least 32.
+inline bool round_rule(int cin) { return cin % 16 == 0 && cin >= 32; }
+
+// Every weight image of the network from the blob, into I.  bf: the images of PS_PREC_BF16 -- a layer the rule rounds gets `round` set and
+// holds the RNE-rounded value of the float the default images hold (BatchNorm folded, log2(e) applied): wp, the direct-load bf16 image wb and
+// the one-plane 32x32 image w32b1, and none of wq / w32 / w32b (8 bytes per weight where the default has up to 18); an attention level of the
+// 32x32 kernels gets the one-plane images of LFA mlp2 and Wfc[h:, :] next to the default ones.  Everything else is packed as at the default.
+int pack_images(ps_randla* net, const float* blob, bool bf, NetImages& I)
+{
+    ps_context* c = net->ctx;
     std::vector<float> host;  // packed image of everything, then one upload
-    struct Pending { PackedLinear* L; size_t wp_off, b_off, wq_off, w32_off, w32b_off; };
+    struct Pending { PackedLinear* L; size_t wp_off, b_off, wq_off, w32_off, w32b_off, wb_off, w32b1_off; };
     std::vector<Pending> pend;
-    auto emit = [&](PackedLinear& L, const float* W, const float* b, int cin, int cout, int leaky) {
+    std::vector<float> rounded;
+    auto emit = [&](PackedLinear& L, const float* W, const float* b, int cin, int cout, int leaky, bool round = false) {
         L = PackedLinear();
         L.cin = cin; L.cout = cout; L.leaky = leaky;
         L.ks = (cin + 3) / 4;
         L.ntb = choose_ntb(cout);
         L.cblocks = (cout + 16 * L.ntb - 1) / (16 * L.ntb);
+        L.round = round ? 1 : 0;
+        if (round) {
+            rounded.resize((size_t)cin * cout);
+            for (size_t t = 0; t < rounded.size(); ++t) rounded[t] = b3_rounded(W[t]);
+            W = rounded.data();
+        }
         size_t off = (host.size() + 63) & ~size_t(63);
         host.resize(off + L.packed_floats());
         pack_weights(W, cin, cout, L.ntb, host.data() + off);
         size_t boff = (host.size() + 63) & ~size_t(63);
         host.resize(boff + (size_t)L.cout_pad());
         for (int i = 0; i < L.cout_pad(); ++i) host[boff + i] = (b && i < cout) ? b[i] : 0.f;
+        if (round) {  // (cin % 16 == 0 by the rule)
+            const size_t woff = (host.size() + 63) & ~size_t(63);
+            host.resize(woff + L.bf16_bytes() / 4);
+            pack_weights_bf16(W, cin, cout, L.ntb, reinterpret_cast<uint16_t*>(host.data() + woff));
+            size_t b1off = 0;
+            if (cout % 32 == 0 && (size_t)cin * cout >= 4096) {  // the shapes of gemm32.hip / gemm32b.hip: one plane, 2 bytes per weight
+                b1off = (host.size() + 63) & ~size_t(63);
+                host.resize(b1off + (size_t)cin * cout / 2);
+                pack_p32b(W, cin, cout, reinterpret_cast<uint16_t*>(host.data() + b1off), 1);
+            }
+            pend.push_back({&L, off, boff, 0, 0, 0, woff, b1off});
+            return;
+        }
         size_t qoff = 0;
         if (cin % 16 == 0) {  // k-permuted image for the direct-load kernel
             qoff = (host.size() + 63) & ~size_t(63);
@@ -232,7 +277,7 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
             host.resize(boff3 + (size_t)cin * cout * 3 / 2);
             pack_p32b(W, cin, cout, reinterpret_cast<uint16_t*>(host.data() + boff3));
         }
-        pend.push_back({&L, off, boff, qoff, roff, boff3});
+        pend.push_back({&L, off, boff, qoff, roff, boff3, 0, 0});
     };
     struct PendingRaw { const float** dst; size_t off; };
     std::vector<PendingRaw> pend_raw;
@@ -246,13 +291,14 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
     auto W = [&](size_t i) { return blob + net->specs[i].w_off; };
     auto Bv = [&](size_t i) { return blob + net->specs[i].b_off; };
     const ps_randla_config& cfg = net->cfg;
-    emit(net->fc0, W(si), Bv(si), cfg.in_channels, 8, 1);
+    auto rr = [&](int cin) { return bf && round_rule(cin); };
+    emit(I.fc0, W(si), Bv(si), cfg.in_channels, 8, 1);  // (fc0 is none of the rule's layers)
     ++si;
-    net->enc.assign(cfg.num_layers, EncLevel());
+    I.enc.assign(cfg.num_layers, EncLevel());
     int d_in = 8;
     std::vector<float> tmp;
     for (int i = 0; i < cfg.num_layers; ++i) {
-        EncLevel& e = net->enc[i];
+        EncLevel& e = I.enc[i];
         const int d = cfg.d_out[i], h = d / 2;
         e.d = d; e.d_in = d_in;
         e.has_p32 = d >= 64;
@@ -272,11 +318,19 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
                 pack_b3(scaled(W(si + 2) + (size_t)h * d, (size_t)h * d), h, d, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.wb1b, (size_t)h * d * 3 / 2)));
                 pack_b3(W(si + 4), h, h, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.w2b, (size_t)h * h * 3 / 2)));
                 pack_b3(scaled(W(si + 5) + (size_t)h * d, (size_t)h * d), h, d, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.wb2b, (size_t)h * d * 3 / 2)));
+                if (bf) {  // one-plane images of the same three matrices (the scaled float is what gets rounded); 2 bytes per weight
+                    pack_b3(scaled(W(si + 2) + (size_t)h * d, (size_t)h * d), h, d, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.wb1b1, (size_t)h * d / 2)), 1);
+                    pack_b3(W(si + 4), h, h, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.w2b1, (size_t)h * h / 2)), 1);
+                    pack_b3(scaled(W(si + 5) + (size_t)h * d, (size_t)h * d), h, d, reinterpret_cast<uint16_t*>(emit_raw(&e.p32.wb2b1, (size_t)h * d / 2)), 1);
+                }
             }
         }
-        emit(e.mlp1, W(si), Bv(si), d_in, h, 1); ++si;
+        // the score pre-product G = f . Wfc[:h, :] follows the attention stage: rounded where the 32x32 kernels serve the level
+        const bool att_round = bf && e.has_p32;  // (d_out 64 .. 512: the level has the one-plane images above)
+        emit(e.mlp1, W(si), Bv(si), d_in, h, 1, rr(d_in)); ++si;
         emit(e.lfa1, W(si), Bv(si), 10, h, 1); ++si;
-        emit(e.top1, W(si), nullptr, h, d, 0);                      // Wfc1[:h, :]
+        emit(e.top1, W(si), nullptr, h, d, 0, att_round);           // Wfc1[:h, :]
+        if (att_round) emit(e.top1x, W(si), nullptr, h, d, 0);
         emit(e.bot1, W(si) + (size_t)h * d, nullptr, h, d, 0);      // Wfc1[h:, :]
         {   // Wfc1 (direct formulation, d <= 32): pre-multiplied by log2(e), att_direct_kernel's softmax is exp2(s' - max s')
             std::vector<float> sc((size_t)d * d);
@@ -284,9 +338,10 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
             emit(e.full1, sc.data(), nullptr, d, d, 0);
         }
         ++si;
-        emit(e.att1mlp, W(si), Bv(si), d, h, 1); ++si;
+        emit(e.att1mlp, W(si), Bv(si), d, h, 1, rr(d)); ++si;
         emit(e.lfa2, W(si), Bv(si), h, h, 1); ++si;
-        emit(e.top2, W(si), nullptr, h, d, 0);
+        emit(e.top2, W(si), nullptr, h, d, 0, att_round);
+        if (att_round) emit(e.top2x, W(si), nullptr, h, d, 0);
         emit(e.bot2, W(si) + (size_t)h * d, nullptr, h, d, 0);
         {
             std::vector<float> sc((size_t)d * d);
@@ -305,39 +360,78 @@ extern "C" int ps_randla_set_weights(ps_randla* net, const float* blob, int64_t 
             pack_lane_image(W(lfa1_i), Bv(lfa1_i), nullptr, nullptr, scaled16(W(fc1_i)), emit_raw(&e.lane1, kLaneImageFloats));
             pack_lane_image(W(lfa1_i), Bv(lfa1_i), W(lfa2_i), Bv(lfa2_i), scaled16(W(fc2_i)), emit_raw(&e.lane2, kLaneImageFloats));
         }
-        emit(e.att2mlp, W(si), Bv(si), d, d, 1); ++si;
+        emit(e.att2mlp, W(si), Bv(si), d, d, 1, rr(d)); ++si;
         // [mlp2 ; shortcut] over the concatenated K axis, biases summed, LeakyReLU on the sum (RandLANet.py:317-321)
         tmp.assign((size_t)(d + d_in) * 2 * d + 2 * d, 0.f);
         std::memcpy(tmp.data(), W(si), sizeof(float) * (size_t)d * 2 * d);
         std::memcpy(tmp.data() + (size_t)d * 2 * d, W(si + 1), sizeof(float) * (size_t)d_in * 2 * d);
         float* bsum = tmp.data() + (size_t)(d + d_in) * 2 * d;
         for (int k = 0; k < 2 * d; ++k) bsum[k] = Bv(si)[k] + Bv(si + 1)[k];
-        emit(e.mlp2sc, tmp.data(), bsum, d + d_in, 2 * d, 1);
+        emit(e.mlp2sc, tmp.data(), bsum, d + d_in, 2 * d, 1, rr(d + d_in));
         si += 2;
         d_in = 2 * d;
     }
-    emit(net->decoder0, W(si), Bv(si), d_in, d_in, 1); ++si;
-    net->dec.assign(cfg.num_layers, PackedLinear());
+    emit(I.decoder0, W(si), Bv(si), d_in, d_in, 1, rr(d_in)); ++si;
+    I.dec.assign(cfg.num_layers, PackedLinear());
     for (int j = 0; j < cfg.num_layers; ++j) {
-        emit(net->dec[j], W(si), Bv(si), net->specs[si].cin, net->specs[si].cout, 1);
+        emit(I.dec[j], W(si), Bv(si), net->specs[si].cin, net->specs[si].cout, 1, rr(net->specs[si].cin));
         ++si;
     }
-    emit(net->fc1, W(si), Bv(si), net->specs[si].cin, 64, 1); ++si;
-    emit(net->fc2, W(si), Bv(si), 64, 32, 1); ++si;
-    emit(net->fc, W(si), Bv(si), 32, cfg.num_classes, 0); ++si;
+    emit(I.fc1, W(si), Bv(si), net->specs[si].cin, 64, 1, rr(net->specs[si].cin)); ++si;
+    emit(I.fc2, W(si), Bv(si), 64, 32, 1, rr(64)); ++si;
+    emit(I.fc, W(si), Bv(si), 32, cfg.num_classes, 0, rr(32)); ++si;
 
-    PS_TRY(net->wbuf.reserve(host.size() * sizeof(float)));
-    PS_HIP(hipMemcpyAsync(net->wbuf.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    PS_TRY(I.wbuf.reserve(host.size() * sizeof(float)));
+    PS_HIP(hipMemcpyAsync(I.wbuf.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     PS_HIP(hipStreamSynchronize(c->stream));
     for (auto& p : pend) {
-        p.L->wp = net->wbuf.as<float>() + p.wp_off;
-        p.L->bias = net->wbuf.as<float>() + p.b_off;
-        p.L->wq = p.wq_off ? net->wbuf.as<float>() + p.wq_off : nullptr;
-        p.L->w32 = p.w32_off ? net->wbuf.as<float>() + p.w32_off : nullptr;
-        p.L->w32b = p.w32b_off ? net->wbuf.as<float>() + p.w32b_off : nullptr;
+        p.L->wp = I.wbuf.as<float>() + p.wp_off;
+        p.L->bias = I.wbuf.as<float>() + p.b_off;
+        p.L->wq = p.wq_off ? I.wbuf.as<float>() + p.wq_off : nullptr;
+        p.L->w32 = p.w32_off ? I.wbuf.as<float>() + p.w32_off : nullptr;
+        p.L->w32b = p.w32b_off ? I.wbuf.as<float>() + p.w32b_off : nullptr;
+        p.L->wb = p.wb_off ? I.wbuf.as<float>() + p.wb_off : nullptr;
+        p.L->w32b1 = p.w32b1_off ? I.wbuf.as<float>() + p.w32b1_off : nullptr;
     }
-    for (auto& p : pend_raw) *p.dst = net->wbuf.as<float>() + p.off;
-    net->have_weights = true;
+    for (auto& p : pend_raw) *p.dst = I.wbuf.as<float>() + p.off;
+    return PS_OK;
+}
+
+}  // namespace
+
+namespace ps {
+
+int randla_bf16_images(ps_randla* net)
+{
+    if (net->bf16) return PS_OK;
+    PS_CHECK(net->have_weights, "ps_randla: weights not set");
+    PS_HIP(hipSetDevice(net->ctx->device));
+    std::unique_ptr<NetImages> img(new NetImages());
+    const int rc = pack_images(net, net->blob.data(), true, *img);
+    if (rc != PS_OK) {
+        img->release();
+        return rc;
+    }
+    net->bf16 = std::move(img);
+    return PS_OK;
+}
+
+}  // namespace ps
+
+extern "C" int ps_randla_set_precision(ps_randla* net, int32_t precision)
+{
+    PS_CHECK(net, "ps_randla_set_precision: net is NULL");
+    PS_CHECK(precision == PS_PREC_BF16X3 || precision == PS_PREC_BF16,
+             "ps_randla_set_precision: precision %d is not PS_PREC_BF16X3 (1) or PS_PREC_BF16 (2); the fp32 MFMA forms of the forward are a switch of "
+             "the context, ps_set_att_bf16x3(ctx, 0)", (int)precision);
+    net->precision = precision;  // (the one-plane images are packed by the first forward that needs them)
+    return PS_OK;
+}
+
+extern "C" int ps_randla_get_precision(const ps_randla* net, int32_t* precision)
+{
+    PS_CHECK(net && precision, "ps_randla_get_precision: NULL argument");
+    *precision = net->precision;
     return PS_OK;
 }
 
@@ -354,6 +448,10 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
     PS_CHECK(pyr->num_layers == L && pyr->K == cfg.k_n, "ps_randla_forward: pyramid (layers %d, K %d) does not match the network (%d, %d)",
              pyr->num_layers, pyr->K, L, cfg.k_n);
     PS_HIP(hipSetDevice(c->device));
+    // the images of the network's precision; the one-plane ones are packed here the first time they are asked for
+    const bool bf = net->precision == PS_PREC_BF16;
+    if (bf) PS_TRY(randla_bf16_images(net));
+    NetImages& I = bf ? *net->bf16 : static_cast<NetImages&>(*net);
     const int64_t B = pyr->B;
     const int64_t* n = pyr->n;
 
@@ -376,7 +474,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         agg = A.take<float>(agg_max);
         tmp = A.take<float>(agg_max);
         dec0 = A.take<float>((size_t)B * n[L] * 2 * cfg.d_out[L - 1]);
-        for (int j = 0; j < L; ++j) decb[j] = A.take<float>((size_t)B * n[L - 1 - j] * net->dec[j].cout);
+        for (int j = 0; j < L; ++j) decb[j] = A.take<float>((size_t)B * n[L - 1 - j] * I.dec[j].cout);
         h1 = A.take<float>((size_t)B * n[0] * 64);
         h2 = A.take<float>((size_t)B * n[0] * 32);
         if (pass == 0) PS_TRY(A.buf.reserve(A.off));
@@ -398,19 +496,19 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         st.L = &Lr; st.y = y; st.ldy = ldy;
         return st;
     };
-    const int d0 = net->enc[0].d, ldf0 = d0 >= 64 ? d0 / 2 + d0 : d0 / 2;
+    const int d0 = I.enc[0].d, ldf0 = d0 >= 64 ? d0 / 2 + d0 : d0 / 2;
     bool mlp1_0_done = false;
     {
         // fc0 -> Encoder_layer_0 mlp1: fc0's rows are kept (shortcut input of the level), mlp1's go to the gather buffer
-        ChainStep ch[2] = {step(net->fc0, fc0, 8), step(net->enc[0].mlp1, fg, ldf0)};
+        ChainStep ch[2] = {step(I.fc0, fc0, 8), step(I.enc[0].mlp1, fg, ldf0)};
         const RowSrc in = src(features, cfg.in_channels, cfg.in_channels);
         if (rowchain_fits(ch, 2, in, none)) {
             Stage st(c, "fc0", 1);
-            PS_TRY(rowchain(c, ch, 2, in, none, B * n[0], &net->chains));
+            PS_TRY(rowchain(c, ch, 2, in, none, B * n[0], &I.chains));
             mlp1_0_done = true;
         } else {
             Stage st(c, "fc0", 1);
-            PS_TRY(rowgemm(c, net->fc0, in, none, B * n[0], fc0, 8));
+            PS_TRY(rowgemm(c, I.fc0, in, none, B * n[0], fc0, 8));
         }
     }
     tap(0, fc0, B * n[0] * 8);
@@ -418,7 +516,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
     const float* X = fc0;
     int d_in = 8;
     for (int i = 0; i < L; ++i) {
-        const EncLevel& e = net->enc[i];
+        const EncLevel& e = I.enc[i];
         const int d = e.d, h = d / 2;
         const int64_t R = B * n[i];
         // pre-product formulation (fg = [f | G]) only where the MFMA pipe is the limit; the wide levels gather f alone
@@ -430,12 +528,18 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         s.n_total = R; s.n_cloud = n[i]; s.d = d; s.k = cfg.k_n; s.ldf = ldf;
         s.p32 = e.has_p32 ? &e.p32 : nullptr;
         s.lane = e.lane1;
+        s.one_plane = bf ? 1 : 0;
+        s.wbot = use_g ? &e.bot1 : nullptr;  // (what the fits test below reads; set again per stage)
+        // PS_PREC_BF16: G is rounded with the stage it feeds -- where the 32x32 kernels do not fit the level's rows, both run as at the default
+        const bool g_round = bf && att_pool32b_fits(s);
+        const PackedLinear& top1 = (bf && use_g && !g_round) ? e.top1x : e.top1;
+        const PackedLinear& top2 = (bf && use_g && !g_round) ? e.top2x : e.top2;
         // f = act(x . W + b) [-> G = f . Wfc[:h]]: one chained launch when it fits
         auto feature_rows = [&](const PackedLinear& mlp, const PackedLinear& top, const RowSrc& in) -> int {
             ChainStep ch[2] = {step(mlp, fg, ldf), step(top, fg + h, ldf)};
             const int nsteps = use_g ? 2 : 1;
-            if (nsteps == 2 && rowchain_fits(ch, 2, in, none)) return rowchain(c, ch, 2, in, none, R, &net->chains);
-            if (nsteps == 1 && regchain_fits(ch, 1, in, none)) return rowchain(c, ch, 1, in, none, R, &net->chains);
+            if (nsteps == 2 && rowchain_fits(ch, 2, in, none)) return rowchain(c, ch, 2, in, none, R, &I.chains);
+            if (nsteps == 1 && regchain_fits(ch, 1, in, none)) return rowchain(c, ch, 1, in, none, R, &I.chains);
             PS_TRY(rowgemm(c, mlp, in, none, R, fg, ldf));
             if (use_g) PS_TRY(rowgemm(c, top, src(fg, ldf, h), none, R, fg + h, ldf));
             return PS_OK;
@@ -444,12 +548,12 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
             if (use_g) {  // mlp1's rows came out of the fc0 chain; the score pre-product still has to be formed
                 std::snprintf(nm, sizeof nm, "enc%d_dense", i);
                 Stage st(c, nm, 1);
-                PS_TRY(rowgemm(c, e.top1, src(fg, ldf, h), none, R, fg + h, ldf));
+                PS_TRY(rowgemm(c, top1, src(fg, ldf, h), none, R, fg + h, ldf));
             }
         } else {
             std::snprintf(nm, sizeof nm, "enc%d_dense", i);
             Stage st(c, nm, 1);
-            PS_TRY(feature_rows(e.mlp1, e.top1, src(X, d_in, d_in)));
+            PS_TRY(feature_rows(e.mlp1, top1, src(X, d_in, d_in)));
         }
         {
             std::snprintf(nm, sizeof nm, "enc%d_att1", i);
@@ -460,7 +564,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         {
             std::snprintf(nm, sizeof nm, "enc%d_dense", i);
             Stage st(c, nm, 1);
-            PS_TRY(feature_rows(e.att1mlp, e.top2, src(agg, d, d)));
+            PS_TRY(feature_rows(e.att1mlp, top2, src(agg, d, d)));
         }
         {
             std::snprintf(nm, sizeof nm, "enc%d_att2", i);
@@ -477,7 +581,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
             ch[1].extra = src(X, d_in, d_in);
             const RowSrc in = src(agg, d, d);
             if (rowchain_fits(ch, 2, in, none)) {
-                PS_TRY(rowchain(c, ch, 2, in, none, R, &net->chains));
+                PS_TRY(rowchain(c, ch, 2, in, none, R, &I.chains));
             } else {
                 PS_TRY(rowgemm(c, e.att2mlp, in, none, R, tmp, d));
                 PS_TRY(rowgemm(c, e.mlp2sc, src(tmp, d, d), src(X, d_in, d_in), R, encb[i], 2 * d));
@@ -496,7 +600,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
 
     {
         Stage st(c, "decoder_0", 1);
-        PS_TRY(rowgemm(c, net->decoder0, src(X, d_in, d_in), none, B * n[L], dec0, d_in));
+        PS_TRY(rowgemm(c, I.decoder0, src(X, d_in, d_in), none, B * n[L], dec0, d_in));
     }
     tap(30, dec0, B * n[L] * d_in);
 
@@ -505,7 +609,7 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
     for (int j = 0; j < L; ++j) {
         const int lvl = L - 1 - j;  // output lives on level `lvl` points
         const float* skip = lvl == 0 ? encb[0] : poolb[lvl - 1];
-        const int skip_c = net->dec[j].cout;
+        const int skip_c = I.dec[j].cout;
         RowSrc s2 = src(up, up_c, up_c);
         s2.gather = pyr->interp_idx[lvl];
         s2.gm = (int)n[lvl];
@@ -515,27 +619,27 @@ extern "C" int ps_randla_forward(ps_randla* net, const ps_pyramid* pyr, const fl
         if (j == L - 1) {
             // last decoder step + the whole head as one chain over the level-0 rows: [skip | up] -> dec -> fc1 -> fc2 -> fc
             // (the decoder step's own rows feed nothing but fc1: they stay in the chain's registers unless somebody wants the tap)
-            ChainStep ch[4] = {step(net->dec[j], net->keep_taps ? decb[j] : nullptr, skip_c), step(net->fc1, nullptr, 0), step(net->fc2, nullptr, 0),
-                               step(net->fc, logits, cfg.num_classes)};
+            ChainStep ch[4] = {step(I.dec[j], net->keep_taps ? decb[j] : nullptr, skip_c), step(I.fc1, nullptr, 0), step(I.fc2, nullptr, 0),
+                               step(I.fc, logits, cfg.num_classes)};
             const RowSrc s1 = src(skip, skip_c, skip_c);
             if (rowchain_fits(ch, 4, s1, s2)) {
                 Stage st(c, "head", 1);
-                PS_TRY(rowchain(c, ch, 4, s1, s2, B * n[lvl], &net->chains));
+                PS_TRY(rowchain(c, ch, 4, s1, s2, B * n[lvl], &I.chains));
                 if (net->keep_taps) tap(40 + j, decb[j], B * n[lvl] * skip_c);
                 return PS_OK;
             }
         }
         Stage st(c, nm, 1);
-        PS_TRY(rowgemm(c, net->dec[j], src(skip, skip_c, skip_c), s2, B * n[lvl], decb[j], skip_c));
+        PS_TRY(rowgemm(c, I.dec[j], src(skip, skip_c, skip_c), s2, B * n[lvl], decb[j], skip_c));
         tap(40 + j, decb[j], B * n[lvl] * skip_c);
         up = decb[j];
         up_c = skip_c;
     }
     {
         Stage st(c, "head", 3);
-        PS_TRY(rowgemm(c, net->fc1, src(up, up_c, up_c), none, B * n[0], h1, 64));
-        PS_TRY(rowgemm(c, net->fc2, src(h1, 64, 64), none, B * n[0], h2, 32));
-        PS_TRY(rowgemm(c, net->fc, src(h2, 32, 32), none, B * n[0], logits, cfg.num_classes));
+        PS_TRY(rowgemm(c, I.fc1, src(up, up_c, up_c), none, B * n[0], h1, 64));
+        PS_TRY(rowgemm(c, I.fc2, src(h1, 64, 64), none, B * n[0], h2, 32));
+        PS_TRY(rowgemm(c, I.fc, src(h2, 32, 32), none, B * n[0], logits, cfg.num_classes));
     }
     return PS_OK;
 }

@@ -151,20 +151,26 @@ struct RcF32 {
     }
 };
 
-struct RcB3 {
-    // (eight waves share one image: it is 1.5x the fp32 one, and the widest chain's 97 KB leave room for one workgroup per CU)
+// RcPlanes<3> = RcB3 (above).  RcPlanes<1> = RcB1: ONE plane of operands rounded once to bfloat16 (round to nearest even), the policy of the
+// chains whose layers all carry PackedLinear::round (PS_PREC_BF16) -- the same k-steps and layouts with one MFMA where RcB3 has six, and an
+// image of 2 bytes per weight (the widest chain, RcPair2: 32 KB where the fp32 image has 64 KB).
+template <int P>
+struct RcPlanes {
+    // (P = 3: eight waves share one image: it is 1.5x the fp32 one, and the widest chain's 97 KB leave room for one workgroup per CU.
+    //  P = 1: the image is a third of that and two workgroups of eight waves would fit the LDS, but rc_blocks caps a CU at 16 waves, which
+    //  the chains' register counts (above 64) already make two waves per SIMD: eight waves per workgroup, two workgroups per CU)
     static constexpr int kThreads = 512;
-    static constexpr int kPairFloats = 384;  // 16 x 16 weights of 6 bytes
+    static constexpr int kPairFloats = 128 * P;  // 16 x 16 weights of 2 P bytes
     template <int IT, int OT, int MT>
     static __device__ __forceinline__ void mma(f32x4 (&acc)[OT], const float (&act)[MT][4], const float* wl, int lane)
     {
         static_assert(IT % 2 == 0, "a k-step of the split-bf16 policy is a pair of 16-channel tiles");
         constexpr int KP = IT / 2;
         const uint4* w = reinterpret_cast<const uint4*>(wl) + lane;
-        B3Planes b[KP];
+        BPlanes<P> b[KP];
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp)
-            b[kp] = b3_split8<3>(make_float4(act[2 * kp][0], act[2 * kp][1], act[2 * kp][2], act[2 * kp][3]),
+            b[kp] = b3_split8<P>(make_float4(act[2 * kp][0], act[2 * kp][1], act[2 * kp][2], act[2 * kp][3]),
                                  make_float4(act[2 * kp + 1][0], act[2 * kp + 1][1], act[2 * kp + 1][2], act[2 * kp + 1][3]));
         // (four output tiles at a time with a scheduling fence between the groups, as in RcF32)
 #pragma unroll
@@ -173,15 +179,15 @@ struct RcB3 {
             for (int kp = 0; kp < KP; ++kp)
 #pragma unroll
                 for (int to = t0; to < (t0 + 4 < OT ? t0 + 4 : OT); ++to) {
-                    B3Planes a;
+                    BPlanes<P> a;
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) a.p[pl] = w[((to * KP + kp) * 3 + pl) * 64];
+                    for (int pl = 0; pl < P; ++pl) a.p[pl] = w[((to * KP + kp) * P + pl) * 64];
                     acc[to] = b3_mfma16_6(a, b[kp], acc[to]);
                 }
             if (t0 + 4 < OT) __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // 16-byte words: dst[w_off / 4 + ((t_out * KP + kp) * 3 + plane) * 64 + lane] = plane of the eight weights
+    // 16-byte words: dst[w_off / 4 + ((t_out * KP + kp) * P + plane) * 64 + lane] = plane of the eight weights
     // W[k(2 kp + (e >> 2), lane >> 4, e & 3)][16 t_out + (lane & 15)], e = 0..7
     static __device__ __forceinline__ void stage(const RcLayer& y, float* dst)
     {
@@ -203,12 +209,14 @@ struct RcB3 {
                 v[e] = 0.f;
                 if (kok && to * 16 + i < y.cout) v[e] = y.wp[(((size_t)cblk * y.ks + (k >> 2)) * 64 + ((k & 3) * 16 + i)) * y.ntb + j];
             }
-            const B3Planes p = b3_split8<3>(v);
+            const BPlanes<P> p = b3_split8<P>(v);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) out[(slot * 3 + pl) * 64 + ln] = p.p[pl];
+            for (int pl = 0; pl < P; ++pl) out[(slot * P + pl) * 64 + ln] = p.p[pl];
         }
     }
 };
+using RcB3 = RcPlanes<3>;
+using RcB1 = RcPlanes<1>;
 
 template <class S, class P, int L>
 __device__ __forceinline__ void rc_layer(const RcArgs& a, float (&act)[S::maxt()][4], const float* lds, int lane, int g, int row, int rr, bool ok)
@@ -342,6 +350,13 @@ template <class S>
 constexpr bool kRcSplit = std::is_same<S, RcHead>::value || std::is_same<S, RcEnc1>::value || std::is_same<S, RcPair1>::value ||
                           std::is_same<S, RcPair1b>::value;
 
+// The chains that take the one-plane policy when every layer's operands are rounded (PackedLinear::round): every compiled shape whose K axes
+// come in pairs of 16-channel tiles -- the four above and level 2's RcPair2.  The rule is per layer and the policy per chain: a chain that mixes
+// rounded and unrounded layers, or a rounded one of another shape, is none of regchain's (rc_build) and runs on rowchain_kernel or layer by layer,
+// which round per layer.
+template <class S>
+constexpr bool kRcOnePlane = kRcSplit<S> || std::is_same<S, RcPair2>::value;
+
 // the float offsets of every layer inside the LDS image of a policy; returns the image's bytes
 static size_t rc_layout(RcArgs& a, int pair_floats)
 {
@@ -354,9 +369,10 @@ static size_t rc_layout(RcArgs& a, int pair_floats)
     return (size_t)off * sizeof(float);
 }
 
-// (the offsets and lds_bytes are those of the fp32 policy: what the context-free plan reports)
-static bool rc_build(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, RcArgs& a, size_t& lds_bytes)
+// (the offsets and lds_bytes are those of the fp32 policy, or of the one-plane policy when `rounded` comes back set: what the context-free plan reports)
+static bool rc_build(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2, RcArgs& a, size_t& lds_bytes, bool& rounded)
 {
+    rounded = false;
     if (n_steps < 1 || n_steps > kChainMaxSteps) return false;
     a = RcArgs{};
     a.x1 = s1.x; a.g1 = s1.gather; a.ld1 = s1.ld; a.g1m = s1.gm; a.g1n = s1.gn;
@@ -378,6 +394,14 @@ static bool rc_build(const ChainStep* steps, int n_steps, const RowSrc& s1, cons
         y.ks = L->ks; y.ntb = L->ntb; y.leaky = L->leaky;
         prev = L->cout;
     }
+    int n_round = 0;
+    for (int i = 0; i < n_steps; ++i) n_round += steps[i].L->round != 0;
+    if (n_round) {  // rounded operands: all layers or none, and only the shapes of the one-plane policy
+        if (n_round != n_steps) return false;
+        rounded = true;
+        lds_bytes = rc_layout(a, RcB1::kPairFloats);
+        return rc_matches<RcPair1>(a) || rc_matches<RcPair1b>(a) || rc_matches<RcEnc1>(a) || rc_matches<RcPair2>(a) || rc_matches<RcHead>(a);
+    }
     lds_bytes = rc_layout(a, RcF32::kPairFloats);
     return rc_matches<RcFc0>(a) || rc_matches<RcEnc0>(a) || rc_matches<RcOne0>(a) || rc_matches<RcPair1>(a) || rc_matches<RcPair1b>(a) ||
            rc_matches<RcEnc1>(a) || rc_matches<RcPair2>(a) || rc_matches<RcHead>(a);
@@ -387,7 +411,8 @@ bool regchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const 
 {
     RcArgs a;
     size_t lds = 0;
-    return rc_build(steps, n_steps, s1, s2, a, lds);
+    bool rounded = false;
+    return rc_build(steps, n_steps, s1, s2, a, lds, rounded);
 }
 
 static int rc_blocks(int64_t R, size_t lds_bytes, int waves)
@@ -402,9 +427,10 @@ ChainPlan regchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, c
 {
     ChainPlan p;
     RcArgs a;
-    if (!rc_build(steps, n_steps, s1, s2, a, p.lds_bytes)) return ChainPlan();
-    p.form = 1;
-    p.blocks = rc_blocks(R, p.lds_bytes, RcF32::kThreads / 64);
+    bool rounded = false;
+    if (!rc_build(steps, n_steps, s1, s2, a, p.lds_bytes, rounded)) return ChainPlan();
+    p.form = rounded ? 3 : 1;
+    p.blocks = rc_blocks(R, p.lds_bytes, (rounded ? RcB1::kThreads : RcF32::kThreads) / 64);
     return p;
 }
 
@@ -412,17 +438,17 @@ ChainPlan regchain_plan(const ChainStep* steps, int n_steps, const RowSrc& s1, c
 template <class S, class P>
 static int rc_run(ps_context* c, RcArgs& a, ChainCache* cache)
 {
-    constexpr bool split = std::is_same<P, RcB3>::value;
+    constexpr int policy = std::is_same<P, RcB3>::value ? 1 : (std::is_same<P, RcB1>::value ? 2 : 0);
     const size_t lds_bytes = rc_layout(a, P::kPairFloats);
     if (cache) {
         // the re-ordered weight image depends only on the layers, the split of the first K axis and the policy: build it once per network
         ChainCache::Entry* hit = nullptr;
         for (auto& e : cache->entries)
-            if (e.wp0 == a.l[0].wp && e.wp_last == a.l[a.n - 1].wp && e.n == a.n && e.ca == a.l[0].ca && e.cb == a.l[0].cb && e.split == split) hit = &e;
+            if (e.wp0 == a.l[0].wp && e.wp_last == a.l[a.n - 1].wp && e.n == a.n && e.ca == a.l[0].ca && e.cb == a.l[0].cb && e.policy == policy) hit = &e;
         if (!hit) {
             cache->entries.emplace_back();
             hit = &cache->entries.back();
-            hit->wp0 = a.l[0].wp; hit->wp_last = a.l[a.n - 1].wp; hit->n = a.n; hit->ca = a.l[0].ca; hit->cb = a.l[0].cb; hit->split = split;
+            hit->wp0 = a.l[0].wp; hit->wp_last = a.l[a.n - 1].wp; hit->n = a.n; hit->ca = a.l[0].ca; hit->cb = a.l[0].cb; hit->policy = policy;
             PS_TRY(hit->img.reserve(lds_bytes));
             hipLaunchKernelGGL(rc_pack_kernel<P>, dim3(1), dim3(P::kThreads), 0, c->stream, a, hit->img.as<float>());
             PS_HIP(hipGetLastError());
@@ -442,8 +468,12 @@ static int rc_run(ps_context* c, RcArgs& a, ChainCache* cache)
 }
 
 template <class S>
-static int rc_route(ps_context* c, RcArgs& a, ChainCache* cache)
+static int rc_route(ps_context* c, RcArgs& a, ChainCache* cache, bool rounded)
 {
+    if constexpr (kRcOnePlane<S>) {
+        static_assert(rc_even_inputs<S>(), "the one-plane policy takes its K axis in pairs of 16-channel tiles");
+        if (rounded) return rc_run<S, RcB1>(c, a, cache);  // (whatever the context's regchain_b3 says: that switch is the default precision's)
+    }
     if constexpr (kRcSplit<S>) {
         static_assert(rc_even_inputs<S>(), "the split-bf16 policy takes its K axis in pairs of 16-channel tiles");
         if (c->regchain_b3) return rc_run<S, RcB3>(c, a, cache);
@@ -456,17 +486,18 @@ int regchain(ps_context* c, const ChainStep* steps, int n_steps, const RowSrc& s
     if (R <= 0) return PS_OK;
     RcArgs a;
     size_t lds_bytes = 0;
-    PS_CHECK(rc_build(steps, n_steps, s1, s2, a, lds_bytes), "regchain: not one of the compiled chain shapes");
+    bool rounded = false;
+    PS_CHECK(rc_build(steps, n_steps, s1, s2, a, lds_bytes, rounded), "regchain: not one of the compiled chain shapes");
     PS_CHECK(R < (int64_t)1 << 31, "regchain: too many rows");
     a.R = (int)R;
-    if (rc_matches<RcFc0>(a)) return rc_route<RcFc0>(c, a, cache);
-    if (rc_matches<RcEnc0>(a)) return rc_route<RcEnc0>(c, a, cache);
-    if (rc_matches<RcOne0>(a)) return rc_route<RcOne0>(c, a, cache);
-    if (rc_matches<RcPair1>(a)) return rc_route<RcPair1>(c, a, cache);
-    if (rc_matches<RcPair1b>(a)) return rc_route<RcPair1b>(c, a, cache);
-    if (rc_matches<RcEnc1>(a)) return rc_route<RcEnc1>(c, a, cache);
-    if (rc_matches<RcPair2>(a)) return rc_route<RcPair2>(c, a, cache);
-    return rc_route<RcHead>(c, a, cache);
+    if (rc_matches<RcFc0>(a)) return rc_route<RcFc0>(c, a, cache, rounded);
+    if (rc_matches<RcEnc0>(a)) return rc_route<RcEnc0>(c, a, cache, rounded);
+    if (rc_matches<RcOne0>(a)) return rc_route<RcOne0>(c, a, cache, rounded);
+    if (rc_matches<RcPair1>(a)) return rc_route<RcPair1>(c, a, cache, rounded);
+    if (rc_matches<RcPair1b>(a)) return rc_route<RcPair1b>(c, a, cache, rounded);
+    if (rc_matches<RcEnc1>(a)) return rc_route<RcEnc1>(c, a, cache, rounded);
+    if (rc_matches<RcPair2>(a)) return rc_route<RcPair2>(c, a, cache, rounded);
+    return rc_route<RcHead>(c, a, cache, rounded);
 }
 
 }  // namespace ps

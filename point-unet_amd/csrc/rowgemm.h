@@ -34,6 +34,12 @@ struct PackedLinear {
     const float* w32 = nullptr;
     // device, pack_p32b image (three bfloat16 planes, 6 bytes per weight) for the split-bf16 form of that kernel (gemm32b.hip); nullptr when not built
     const void* w32b = nullptr;
+    // round != 0 (PS_PREC_BF16, include/pointseg_forward_precision.h): BOTH operands of this layer's product are rounded once to bfloat16
+    // (round to nearest even), fp32 accumulation.  Every image of such a layer holds the rounded weights -- wp as fp32 values, wb, and
+    // w32b1, the ONE-plane pack_p32b image (2 bytes per weight; nullptr when not built) -- and whichever kernel takes the layer rounds
+    // the activations as it loads them: a product of two bfloat16 values is exact in fp32, so every kernel computes the same model.
+    const void* w32b1 = nullptr;
+    int round = 0;
     const float* bias = nullptr;  // device [cout_pad] (zeros when the layer has no bias)
     int cin = 0, cout = 0;
     int ks = 0;       // k-steps = ceil(cin/4)
@@ -70,17 +76,21 @@ struct Gemm32Plan {
     int rgroups = 0, cgroups = 0;  // workgroup grid
 };
 Gemm32Plan gemm32_plan(const Tuning& tn, int64_t R, int cin, int cout);
-Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout);
+Gemm32Plan gemm32b_plan(const Tuning& tn, int64_t R, int cin, int cout, int planes = 3);  // planes = 1: the one-plane kernels (ring depth)
 // the same layer on 32x32x2 tiles (gemm32.hip): few rows x wide channels (encoder levels 2-4, decoder); rowgemm() takes this
 // route by itself when the layer carries a w32 image and the shape qualifies
 bool gemm32_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy);
 int gemm32(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy);
 // ... and on v_mfma_f32_32x32x16_bf16 over exact three-way bfloat16 splits of both operands (gemm32b.hip): the products large enough
 // to be bound by the matrix pipe
-void pack_p32b(const float* W, int cin, int cout, uint16_t* out);  // [cin, cout], cin % 16 == 0, cout % 32 == 0 -> cin*cout*3 uint16
+void pack_p32b(const float* W, int cin, int cout, uint16_t* out, int planes = 3);  // [cin, cout], cin % 16 == 0, cout % 32 == 0 -> cin*cout*planes uint16
+// the rounded layer's image for the direct-load bf16 kernel (PackedLinear::wb's layout), from the host: bf16_bytes() bytes
+void pack_weights_bf16(const float* W, int cin, int cout, int ntb, uint16_t* out);
 bool gemm32b_fits(const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy);
 int gemm32b(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy);
 
+// the kernel family rowgemm() takes (5 one-plane gemm32b, 1 split gemm32b, 2 gemm32, 3 this file's 16x16 kernels): the test door ps_debug_dense_form
+int rowgemm_form(const ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy);
 // y[r, 0:cout] (row stride ldy) for r in [0, R)
 int rowgemm(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy);
 
@@ -102,9 +112,9 @@ bool rowchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const 
 bool regchain_fits(const ChainStep* steps, int n_steps, const RowSrc& s1, const RowSrc& s2);
 // per-network cache of the chains' re-ordered weight images (built on first use on the caller's stream; clear() when the
 // weights change).  Entries are keyed by the first / last layer's packed weights, the split of the first K axis and the operand policy
-// (split: the three-plane bfloat16 image of regchain.hip's RcB3).
+// (policy 0: RcF32's fp32 image, 1: the three-plane bfloat16 image of regchain.hip's RcB3, 2: the one-plane image of RcB1).
 struct ChainCache {
-    struct Entry { const float* wp0 = nullptr; const float* wp_last = nullptr; int n = 0, ca = 0, cb = 0; bool split = false; DevBuf img; };
+    struct Entry { const float* wp0 = nullptr; const float* wp_last = nullptr; int n = 0, ca = 0, cb = 0; int policy = 0; DevBuf img; };
     std::vector<Entry> entries;
     void clear()
     {
@@ -119,7 +129,8 @@ int rowchain_lds(ps_context* c, const ChainStep* steps, int n_steps, const RowSr
 // The launch regchain() / rowchain_lds() / rowchain() make for R rows of a chain: the launchers call these, and so does the test door
 // ps_debug_chain_plan (debug_hooks.h).  Host only.
 struct ChainPlan {
-    int form = 0;          // 0: the chain does not fit this form, 1: regchain_kernel, 2: rowchain_kernel
+    int form = 0;          // 0: the chain does not fit this form, 1: regchain_kernel, 2: rowchain_kernel, 3: regchain_kernel on one plane of
+                           // rounded operands (every layer's PackedLinear::round set)
     int blocks = 0;        // workgroups (each of four waves walking 16-row tiles)
     size_t lds_bytes = 0;  // dynamic LDS per workgroup
     int fast_in = 0;       // rowchain_kernel only: log2(float4s per input row) when the float4 staging applies, else 0 (scalar staging)

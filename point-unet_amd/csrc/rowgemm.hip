@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "b3_ops.h"
+#include "bf16_io.h"
 #include "mfma_tile.h"
 
 namespace ps {
@@ -30,6 +32,7 @@ struct RowGemmArgs {
     float* y; int ldy;
     int cin, cout, ks, R, leaky;
     int accum;  // y += act(x.W + b) instead of y = ...  (gradient accumulation of the training step)
+    int round;  // PackedLinear::round: the generic kernel rounds the activations to bfloat16 as it stages them (wp holds rounded weights)
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -422,7 +425,7 @@ __global__ __launch_bounds__(256) void rowgemm_kernel(RowGemmArgs a)
             float v = 0.f;
             if (row0 + r < a.R && k < kc)
                 v = kg < a.c1 ? a.x1[(size_t)sr1 * a.ld1 + kg] : a.x2[(size_t)sr2 * a.ld2 + (kg - a.c1)];
-            tile[r * kPitch + k] = v;
+            tile[r * kPitch + k] = a.round ? round_bf16(v) : v;
         }
         wave_lds_sync();
         // ---- MFMA over the chunk ----
@@ -468,6 +471,7 @@ struct ChainArgs {
     struct Lyr {
         const float* wp; const float* bias; float* y; const float* ex;
         int cout, ks, ntb, cblocks, leaky, ldy, ldex, cex;
+        int round;  // PackedLinear::round: this layer's activations are rounded to bfloat16 as they leave the LDS tile (wp holds rounded weights)
         int w_off, w_floats, b_off, b_floats;  // this layer's packed weights / bias inside the workgroup's LDS image
     } l[kChainMaxSteps];
     int tile_off;  // float offset of the activation tiles behind the weight image
@@ -487,19 +491,24 @@ __device__ __forceinline__ void chain_layer(const float* __restrict__ in, float*
         for (int j = 0; j < NTB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         const bfrag* wp = reinterpret_cast<const bfrag*>(wl) + (size_t)cb * y.ks * 64 + lane;  // B fragments from LDS
         const float* ap = in + arow * kChainPitch + ag;
+        const bool rb = y.round != 0;
         int s = 0;
         for (; s + 4 <= y.ks; s += 4) {  // four k-steps' operands in flight before the first MFMA needs them
             float av[4];
             bfrag bv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) { av[u] = ap[(s + u) * 4]; bv[u] = wp[(size_t)(s + u) * 64]; }
+            if (rb) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) av[u] = round_bf16(av[u]);
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int j = 0; j < NTB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bfrag_get<NTB>(bv[u], j), acc[j], 0, 0, 0);
         }
         for (; s < y.ks; ++s) {
-            const float av = ap[s * 4];
+            const float av = rb ? round_bf16(ap[s * 4]) : ap[s * 4];
             const bfrag bv = wp[(size_t)s * 64];
 #pragma unroll
             for (int j = 0; j < NTB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bfrag_get<NTB>(bv, j), acc[j], 0, 0, 0);
@@ -730,7 +739,7 @@ int rowchain_lds(ps_context* c, const ChainStep* steps, int n_steps, const RowSr
         ChainArgs::Lyr& y = a.l[i];
         y.wp = L.wp; y.bias = L.bias; y.y = steps[i].y; y.ldy = steps[i].ldy;
         y.ex = steps[i].extra.x; y.ldex = steps[i].extra.ld; y.cex = steps[i].extra.x ? steps[i].extra.c : 0;
-        y.cout = L.cout; y.ks = L.ks; y.ntb = L.ntb; y.cblocks = L.cblocks; y.leaky = L.leaky;
+        y.cout = L.cout; y.ks = L.ks; y.ntb = L.ntb; y.cblocks = L.cblocks; y.leaky = L.leaky; y.round = L.round;
     }
     a.fast_in = plan.fast_in;
     const size_t lds_bytes = plan.lds_bytes;
@@ -758,6 +767,23 @@ void pack_weights(const float* W, int cin, int cout, int ntb, float* out)
                 }
 }
 
+// wb[(((cb*NC + c)*2 + s)*64 + l)*NTB + j][t] = bf16(W[c*64 + 16*(l>>4) + 8s + t][(cb*NTB + j)*16 + (l&15)]), round to nearest even (rowgemm.h)
+void pack_weights_bf16(const float* W, int cin, int cout, int ntb, uint16_t* out)
+{
+    const int nc = (cin + 63) / 64;
+    const int cblocks = (cout + 16 * ntb - 1) / (16 * ntb);
+    for (int cb = 0; cb < cblocks; ++cb)
+        for (int c = 0; c < nc; ++c)
+            for (int s = 0; s < 2; ++s)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < ntb; ++j)
+                        for (int t = 0; t < 8; ++t) {
+                            const int k = c * 64 + 16 * (l >> 4) + 8 * s + t;
+                            const int col = (cb * ntb + j) * 16 + (l & 15);
+                            out[((((((size_t)cb * nc + c) * 2 + s) * 64 + l) * ntb) + j) * 8 + t] = (k < cin && col < cout) ? b3_rne_of(W[(size_t)k * cout + col]) : (uint16_t)0;
+                        }
+}
+
 void pack_weights_kperm(const float* W, int cin, int cout, int ntb, float* out)
 {
     const int nc = (cin + 63) / 64;
@@ -775,13 +801,26 @@ void pack_weights_kperm(const float* W, int cin, int cout, int ntb, float* out)
 }
 
 
+// the kernel family rowgemm() takes for this call (the first two tests of rowgemm below, and nothing else): 5 = gemm32b on one plane of
+// rounded operands, 1 = gemm32b on the exact split, 2 = gemm32 (fp32 MFMA), 3 = the 16x16 kernels of this file
+int rowgemm_form(const ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, int ldy)
+{
+    if (L.round) return gemm32b_fits(L, s1, s2, R, ldy) ? 5 : 3;
+    if (c->att_bf16x3 && 2.0 * (double)R * L.cin * L.cout >= c->tune.gemm32b_min_flops && gemm32b_fits(L, s1, s2, R, ldy)) return 1;
+    return gemm32_fits(L, s1, s2, R, ldy) ? 2 : 3;
+}
+
 int rowgemm(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc& s2, int64_t R, float* y, int ldy)
 {
     if (R <= 0) return PS_OK;
     PS_CHECK(s1.c + s2.c == L.cin, "rowgemm: sources give %d channels, layer expects %d", s1.c + s2.c, L.cin);
-    if (c->att_bf16x3 && 2.0 * (double)R * L.cin * L.cout >= c->tune.gemm32b_min_flops && gemm32b_fits(L, s1, s2, R, ldy))
-        return gemm32b(c, L, s1, s2, R, y, ldy);                                  // ... the large ones on split-bf16 MFMA (gemm32b.hip)
-    if (gemm32_fits(L, s1, s2, R, ldy)) return gemm32(c, L, s1, s2, R, y, ldy);  // deep levels: 32x32x2 tiles (gemm32.hip)
+    // rounded operands (PS_PREC_BF16): the one-plane form of gemm32b.hip wherever the 32x32 tiles fit -- the same population of shapes that goes
+    // to gemm32b / gemm32 at the default, whatever the context's switches say; the rest on the kernels of this file, which round as they load
+    // (the direct-load bf16 kernel on L.wb, the generic kernel on a.round).  Default: the large ones on split-bf16 MFMA (gemm32b.hip), the deep
+    // levels on 32x32x2 tiles (gemm32.hip).
+    const int form = rowgemm_form(c, L, s1, s2, R, ldy);
+    if (form == 5 || form == 1) return gemm32b(c, L, s1, s2, R, y, ldy);
+    if (form == 2) return gemm32(c, L, s1, s2, R, y, ldy);
     PS_CHECK(R < (1ll << 31), "rowgemm: too many rows");
     RowGemmArgs a;
     a.x1 = s1.x; a.g1 = s1.gather; a.ld1 = s1.ld; a.c1 = s1.c; a.g1m = s1.gm; a.g1n = s1.gn;
@@ -790,6 +829,7 @@ int rowgemm(ps_context* c, const PackedLinear& L, const RowSrc& s1, const RowSrc
     a.y = y; a.ldy = ldy;
     a.cin = L.cin; a.cout = L.cout; a.ks = L.ks; a.R = (int)R; a.leaky = L.leaky;
     a.accum = L.accum;
+    a.round = L.round;
 
     const bool direct = (L.wq || L.wb) && L.cin % 16 == 0 && s1.c % 16 == 0 && s1.ld % 4 == 0 && aligned16(s1.x) &&
                         (s2.c == 0 || (s2.ld % 4 == 0 && aligned16(s2.x)));

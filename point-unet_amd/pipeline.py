@@ -64,12 +64,12 @@ def _check_environment(lanes, reusing):
 
 
 class _Lane:
-    def __init__(self, config, params, device, seed, stream=None, ctx=None):
+    def __init__(self, config, params, device, seed, stream=None, ctx=None, precision="bf16x3"):
         self.stream = stream if stream is not None else torch.cuda.Stream(torch.device("cuda", device))
         self.ctx = ctx if ctx is not None else runtime.Context(device)
         self.ctx.set_stream(self.stream)
         self.ctx.set_deferred_checks(True)  # tree-build status words are validated at synchronize()
-        self.net = Network(config, params=params, device=device, seed=seed, ctx=self.ctx)
+        self.net = Network(config, params=params, device=device, seed=seed, ctx=self.ctx, precision=precision)
         self.pyramids = {}  # batch size -> Pyramid (buffers reused from cloud to cloud)
         self.done = None
         self.submissions = []  # global submission index of every pyramid build this lane's context has run, in order
@@ -87,8 +87,10 @@ class _Lane:
 
 
 class ForwardPipeline:
-    def __init__(self, config, params=None, device=0, seed=0, lanes=4, reuse=None, coalesce=1):
-        """reuse: a ForwardPipeline that is done (another network / configuration): its lanes' HIP streams and contexts (workspaces) are
+    def __init__(self, config, params=None, device=0, seed=0, lanes=4, reuse=None, coalesce=1, precision="bf16x3"):
+        """precision: "bf16x3" | "bf16", the arithmetic of every lane's network (Network, include/pointseg_forward_precision.h).
+
+        reuse: a ForwardPipeline that is done (another network / configuration): its lanes' HIP streams and contexts (workspaces) are
         taken over instead of creating new ones and it must not be used afterwards.  Every extra stream a process has touched costs:
         measured with this very class, a second pipeline on four NEW streams runs 2.33 ms pipelined / 4.3 ms serial per 262 144-point
         cloud against 1.93 / 2.63 ms for the same pipeline alone in a process (profiles/tools/exp_second_pipeline.py: four idle streams
@@ -104,7 +106,11 @@ class ForwardPipeline:
         cloud's logits are complete when its pair is (synchronize() launches a cloud still waiting alone), and no gain over a run as short
         as the driver's 20 steps (the pipeline's fill and drain are twice as long).  Per cloud the result is that of the batch-1 call up
         to summation order in the split-K dense layers (their K split depends on the row count)."""
+        from . import _lib
+        if precision not in _lib.FORWARD_PRECISIONS:
+            raise ValueError("ForwardPipeline: precision must be one of %s, got %r" % (sorted(_lib.FORWARD_PRECISIONS), precision))
         self.cfg = config
+        self.precision = precision
         self.device = torch.device("cuda", device)
         self.coalesce = 2 if int(coalesce) >= 2 else 1
         _check_environment(int(lanes), reuse is not None)
@@ -117,13 +123,13 @@ class ForwardPipeline:
             reuse.lanes = []
             for ln in old:
                 ln.net.close()
-            self.lanes = [_Lane(config, params, device, seed, stream=ln.stream, ctx=ln.ctx) for ln in old[:int(lanes)]]
+            self.lanes = [_Lane(config, params, device, seed, stream=ln.stream, ctx=ln.ctx, precision=precision) for ln in old[:int(lanes)]]
             for ln in old[int(lanes):]:
                 ln.ctx.close()
             while len(self.lanes) < int(lanes):
-                self.lanes.append(_Lane(config, params, device, seed))
+                self.lanes.append(_Lane(config, params, device, seed, precision=precision))
         else:
-            self.lanes = [_Lane(config, params, device, seed) for _ in range(int(lanes))]
+            self.lanes = [_Lane(config, params, device, seed, precision=precision) for _ in range(int(lanes))]
         self._n0 = None
         self._i = 0        # clouds submitted so far
         self._launch = 0   # launches so far: picks the lane (one launch = one cloud, or one coalesced pair)
