@@ -6,7 +6,8 @@ The signatures below are include/pointseg.h and pointseg_train_ops.h verbatim (P
 (SALIENCY_ATTENTION_PROTOTYPES), include/pointseg_saliency_data.h (SALIENCY_DATA_PROTOTYPES), include/pointseg_saliency_step.h
 (SALIENCY_STEP_PROTOTYPES), include/pointseg_saliency_step_precision.h (SALIENCY_STEP_PRECISION_PROTOTYPES) and
 include/pointseg_saliency_precision.h (SALIENCY_PRECISION_PROTOTYPES), include/pointseg_saliency_map.h (SALIENCY_MAP_PROTOTYPES) and
-include/pointseg_saliency_view.h (SALIENCY_VIEW_PROTOTYPES) and include/pointseg_forward_precision.h (FORWARD_PRECISION_PROTOTYPES).
+include/pointseg_saliency_view.h (SALIENCY_VIEW_PROTOTYPES), include/pointseg_forward_precision.h (FORWARD_PRECISION_PROTOTYPES) and
+include/pointseg_train_loss.h (TRAIN_LOSS_PROTOTYPES).
 The library is built in-tree by compile_op.sh (csrc/Makefile); a missing library is a hard error: there is no CPU fallback anywhere in this package.
 """
 import ctypes
@@ -407,6 +408,19 @@ FORWARD_PRECISION_PROTOTYPES = {
     "ps_randla_get_precision": (ctypes.c_int, [c_vp, c_i32p]),
 }
 
+# every symbol include/pointseg_train_loss.h declares (the objective of the point network's training step -- cross-entropy or the
+# reference's two Dice losses -- and the step's accuracy; csrc/point_loss.hip, csrc/trainer.hip)
+PS_LOSS_CE, PS_LOSS_DICE, PS_LOSS_DICE_WEIGHTED = 0, 1, 2
+TRAIN_LOSSES = {"ce": PS_LOSS_CE, "dice": PS_LOSS_DICE, "dice_weighted": PS_LOSS_DICE_WEIGHTED}
+_STEP_LOSS = [c_vp, ctypes.POINTER(PsPyramid), c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp]
+TRAIN_LOSS_PROTOTYPES = {
+    "ps_op_dice_sums": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "ps_op_dice_from_sums": (ctypes.c_int, [c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp, ctypes.c_float, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp]),
+    "ps_op_top1_counts": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp]),
+    "ps_randla_backward_loss": (ctypes.c_int, _STEP_LOSS),
+    "ps_randla_train_step_loss": (ctypes.c_int, _STEP_LOSS),
+}
+
 _lib = None
 
 
@@ -432,7 +446,8 @@ def lib():
                                   + list(SALIENCY_ATTENTION_PROTOTYPES.items()) + list(SALIENCY_DATA_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PROTOTYPES.items()) + list(SALIENCY_MIXUP_PROTOTYPES.items())
                                   + list(SALIENCY_STEP_PRECISION_PROTOTYPES.items()) + list(SALIENCY_MAP_PROTOTYPES.items())
-                                  + list(SALIENCY_VIEW_PROTOTYPES.items()) + list(FORWARD_PRECISION_PROTOTYPES.items())):
+                                  + list(SALIENCY_VIEW_PROTOTYPES.items()) + list(FORWARD_PRECISION_PROTOTYPES.items())
+                                  + list(TRAIN_LOSS_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -9,6 +9,7 @@
 #include "../../include/pointseg_saliency_attention.h"
 #include "../../include/pointseg_saliency_mixup.h"
 #include "../../include/pointseg_saliency_train.h"
+#include "dice_kit.h"
 #include "saliency_kit.h"
 
 namespace ps {
@@ -227,106 +228,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* dy, const fl
     }
 }
 
-// ---- softmax + weighted Dice -------------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ double wave_sum(double a)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    return a;
-}
-
-// Where a voxel's label row g_vc comes from -- the one thing the hard-label and the soft-label (mixup, include/pointseg_saliency_mixup.h)
-// forms of the two kernels below differ in.  at<MODE>(row, C) is voxel `row`; of it, has(c): g_vc can be non-zero, times(a, c) = a g_vc,
-// asked once per class, ascending.  HardLabels: an integer g, g_vc = [g = c] -- a class that is not the voxel's adds nothing and a product
-// by 1 is not made.  SoftLabels: C floats, moved like the logits (MODE 2: one 8-byte load; MODE 4: 16 bytes when the class enters a new
-// four, so that only four are in registers beside the 16 logits; MODE 1: floats).  A product by exactly 0 or 1 and the addition of +0 to a
-// float64 sum are exact, so one-hot soft rows give the bytes of the integer form.
-struct HardLabels {
-    const int* __restrict__ p;
-    struct At {
-        int g;
-        __device__ __forceinline__ bool has(int c) const { return g == c; }
-        __device__ __forceinline__ double times(double a, int) { return a; }
-    };
-    template <int MODE>
-    __device__ __forceinline__ At at(size_t row, int) const
-    {
-        return At{p[row]};
-    }
-};
-
-struct SoftLabels {
-    const float* __restrict__ p;
-    template <int MODE>
-    struct At {
-        const float* __restrict__ r;
-        float q[MODE == 1 ? 1 : MODE];
-        __device__ __forceinline__ bool has(int) const { return true; }
-        __device__ __forceinline__ double times(double a, int c)
-        {
-            if (MODE == 1) return a * (double)r[c];
-            if (MODE == 4 && (c & 3) == 0) {
-                const float4 f = *reinterpret_cast<const float4*>(r + c);
-                q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
-            }
-            return a * (double)q[c & (MODE - 1)];
-        }
-    };
-    template <int MODE>
-    __device__ __forceinline__ At<MODE> at(size_t row, int C) const
-    {
-        At<MODE> a;
-        a.r = p + row * C;
-        if (MODE == 2) {
-            const float2 f = *reinterpret_cast<const float2*>(a.r);
-            a.q[0] = f.x, a.q[1] = f.y;
-        }
-        return a;
-    }
-};
-
-// grid (slabs, B): thread t adds the voxels v0 + t, v0 + t + 256, ... of its slab, the 64 lanes of a wave meet in a butterfly, the four
-// waves are added ascending.  part [slab][B][C][3] = (S0, S1, S2).
-template <int MODE, class LAB>
-__global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ logits, LAB labels, const float* __restrict__ weight, int V, int C,
-                                                        double* __restrict__ part)
-{
-    constexpr int NC = Row<MODE>::NC;
-    __shared__ double red[4][3 * NC];
-    const int t = threadIdx.x, b = blockIdx.y, v0 = blockIdx.x * kSlab, v1 = min(V, v0 + kSlab);
-    double s0[NC], s1[NC], s2[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) s0[c] = s1[c] = s2[c] = 0.0;
-    for (int v = v0 + t; v < v1; v += 256) {
-        const size_t row = (size_t)b * V + v;
-        Row<MODE> p;
-        row_load<MODE>(logits + row * C, C, p);
-        row_softmax<MODE>(C, p);
-        auto g = labels.template at<MODE>(row, C);
-        const double w = weight ? (double)weight[row] : 1.0;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            if (c < C) {
-                const double pc = (double)p.v[c];
-                s1[c] += (w * pc) * pc;
-                if (g.has(c)) {
-                    const double wg = g.times(w, c);
-                    s0[c] += wg * pc;
-                    s2[c] += wg;
-                }
-            }
-    }
-    const int wave = t >> 6;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (c < C) {
-            const double a0 = wave_sum(s0[c]), a1 = wave_sum(s1[c]), a2 = wave_sum(s2[c]);
-            if ((t & 63) == 0) red[wave][c * 3] = a0, red[wave][c * 3 + 1] = a1, red[wave][c * 3 + 2] = a2;
-        }
-    __syncthreads();
-    if (t < 3 * C) part[((size_t)blockIdx.x * gridDim.y + b) * 3 * C + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-}
+// ---- softmax + weighted Dice: the kernels of dice_kit.h behind a softmax and a per-voxel weight map --------------------------------------------
 
 // one thread: the loss from the sums, samples and classes ascending
 __global__ void dice_finish_kernel(const double* __restrict__ sums, int B, int C, float* __restrict__ loss)
@@ -344,43 +246,6 @@ __global__ void dice_finish_kernel(const double* __restrict__ sums, int B, int C
     *loss = (float)(total / B);
 }
 
-// grid (ceil(V / 256), B), a thread per voxel.  G_vc = w (g_vc kA_c + kB_c p_vc) with kA_c = -k 2 / D_c, kB_c = k 2 num_c / D_c^2,
-// k = dloss / (B C); past the softmax everything is float64, rounded once.  A thread reads its rows before it writes: dlogits may be logits.
-template <int MODE, class LAB>
-__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* logits, LAB labels, const float* __restrict__ weight, const double* __restrict__ sums,
-                                                       const float* __restrict__ dloss, int B, int V, int C, float* dlogits)
-{
-    constexpr int NC = Row<MODE>::NC;
-    __shared__ double kA[NC], kB[NC];
-    const int t = threadIdx.x, b = blockIdx.y;
-    if (t < C) {
-        const double* s = sums + ((size_t)b * C + t) * 3;
-        const double D = s[1] + s[2] + 1e-5, k = (dloss ? (double)*dloss : 1.0) / ((double)B * C);
-        kA[t] = -k * 2.0 / D;
-        kB[t] = k * 2.0 * (2.0 * s[0]) / (D * D);
-    }
-    __syncthreads();
-    const int v = blockIdx.x * 256 + t;
-    if (v >= V) return;
-    const size_t row = (size_t)b * V + v;
-    Row<MODE> p;
-    row_load<MODE>(logits + row * C, C, p);
-    row_softmax<MODE>(C, p);
-    auto g = labels.template at<MODE>(row, C);
-    const double w = weight ? (double)weight[row] : 1.0;
-    double G[NC], dot = 0.0;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (c < C) {
-            const double pc = (double)p.v[c];
-            G[c] = w * ((g.has(c) ? g.times(kA[c], c) : 0.0) + kB[c] * pc);
-            dot += pc * G[c];
-        }
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (c < C) p.v[c] = (float)((double)p.v[c] * (G[c] - dot));
-    row_store<MODE>(dlogits + row * C, C, p);
-}
 
 // the vector MODE all of a call's rows can be moved in: the logits (read at a, written at b) and, soft labels, their rows
 inline int dice_mode_with(int C, const void* a, const void* b, const SoftLabels& l)
@@ -412,12 +277,13 @@ int dice_loss_run(const char* who, const char* what, ps_context* c, const void* 
     PS_HIP(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     Stage stg(c, who + 3, 3);  // (the stage is the entry's name without "ps_")
-    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight);
+    const float* lf = static_cast<const float*>(logits);
+    const MapWeight wt{static_cast<const float*>(weight)};
     const dim3 grid((unsigned)slabs, (unsigned)B);
     const int mode = dice_mode_with((int)C, logits, logits, labels);
-    if (mode == 2) hipLaunchKernelGGL((dice_sums_kernel<2, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
-    else if (mode == 4) hipLaunchKernelGGL((dice_sums_kernel<4, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
-    else hipLaunchKernelGGL((dice_sums_kernel<1, LAB>), grid, dim3(256), 0, sm, lf, labels, wf, (int)V, (int)C, part);
+    if (mode == 2) hipLaunchKernelGGL((dice_sums_kernel<2, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, sm, lf, labels, wt, (int)V, (int)C, part);
+    else if (mode == 4) hipLaunchKernelGGL((dice_sums_kernel<4, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, sm, lf, labels, wt, (int)V, (int)C, part);
+    else hipLaunchKernelGGL((dice_sums_kernel<1, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, sm, lf, labels, wt, (int)V, (int)C, part);
     hipLaunchKernelGGL(reduce_partials_kernel<double>, dim3((unsigned)ceil_div(nv, 16)), dim3(256), 0, sm, part, slabs, nv, static_cast<double*>(sums));
     hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, sm, static_cast<const double*>(sums), (int)B, (int)C, static_cast<float*>(loss));
     PS_HIP(hipGetLastError());
@@ -435,14 +301,16 @@ int dice_bwd_run(const char* who, const char* what, ps_context* c, const void* l
 
     PS_HIP(hipSetDevice(c->device));
     Stage stg(c, who + 3, 1);
-    const float *lf = static_cast<const float*>(logits), *wf = static_cast<const float*>(weight), *dl = static_cast<const float*>(dloss);
+    const float* lf = static_cast<const float*>(logits);
+    const MapWeight wt{static_cast<const float*>(weight)};
+    const MapWeight::Finish fin{static_cast<const float*>(dloss)};
     const double* sd = static_cast<const double*>(sums);
     float* out = static_cast<float*>(dlogits);
     const dim3 grid((unsigned)ceil_div(V, 256), (unsigned)B);
     const int mode = dice_mode_with((int)C, logits, dlogits, labels);
-    if (mode == 2) hipLaunchKernelGGL((dice_bwd_kernel<2, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
-    else if (mode == 4) hipLaunchKernelGGL((dice_bwd_kernel<4, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
-    else hipLaunchKernelGGL((dice_bwd_kernel<1, LAB>), grid, dim3(256), 0, c->stream, lf, labels, wf, sd, dl, (int)B, (int)V, (int)C, out);
+    if (mode == 2) hipLaunchKernelGGL((dice_bwd_kernel<2, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, c->stream, lf, labels, wt, sd, fin, (int)B, (int)V, (int)C, out);
+    else if (mode == 4) hipLaunchKernelGGL((dice_bwd_kernel<4, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, c->stream, lf, labels, wt, sd, fin, (int)B, (int)V, (int)C, out);
+    else hipLaunchKernelGGL((dice_bwd_kernel<1, LAB, SoftmaxAct, MapWeight>), grid, dim3(256), 0, c->stream, lf, labels, wt, sd, fin, (int)B, (int)V, (int)C, out);
     PS_HIP(hipGetLastError());
     return PS_OK;
 }

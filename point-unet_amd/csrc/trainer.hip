@@ -16,6 +16,7 @@
 // (gradient mean, BatchNorm statistics shared by the ranks) go through a callback the host supplies (ps_trainer_set_collective: the
 // library does not link a communication library; RCCL sits behind torch.distributed in bench.py, behind ncclAllReduce in a C++ host).
 #include "common.h"
+#include "../../include/pointseg_train_loss.h"
 #include "train_pool.h"
 
 #include <cmath>
@@ -140,6 +141,13 @@ __global__ __launch_bounds__(256) void tr_label_map_kernel(const int32_t* __rest
         const int v = lab[e];
         out[e] = (v >= 0 && v < nmap) ? map[v] : -1;
     }
+}
+
+// the step's accuracy from (n_valid, n_correct): float32(n_correct / n_valid) of the integer counts, 0 when nothing is valid
+__global__ void tr_accuracy_kernel(const double* __restrict__ counts, float* __restrict__ accuracy)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    *accuracy = counts[0] > 0.0 ? (float)(counts[1] / counts[0]) : 0.f;
 }
 
 // LocSE branch, forward finish: float64 sums of y and y^2 over all rows (of all ranks) -> mean, variance, invstd, scale = gamma invstd,
@@ -1675,10 +1683,13 @@ static void build_layout(ps_trainer* t)
     t->n_buffers = boff;
 }
 
-static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights, float* loss,
-                    float* logits_out, bool optimise)
+static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights, int32_t loss_kind,
+                    float* loss, float* accuracy, float* logits_out, bool optimise)
 {
     ps_context* c = t->c;
+    PS_CHECK(loss_kind == PS_LOSS_CE || loss_kind == PS_LOSS_DICE || loss_kind == PS_LOSS_DICE_WEIGHTED,
+             "trainer: loss_kind = %d, must be PS_LOSS_CE, PS_LOSS_DICE or PS_LOSS_DICE_WEIGHTED", (int)loss_kind);
+    PS_CHECK(loss_kind == PS_LOSS_CE || t->cfg.num_classes <= 16, "trainer: the Dice losses take at most 16 classes");
     PS_CHECK(t->params && t->grads && t->buffers, "trainer: ps_trainer_bind has not been called");
     PS_CHECK(!optimise || (t->adam_m && t->adam_v), "ps_randla_train_step: the Adam moment buffers are not bound");
     PS_CHECK(pyr && features && labels && class_weights && loss, "trainer: NULL argument");
@@ -1725,8 +1736,32 @@ static int run_step(ps_trainer* t, const ps_pyramid* pyr, const float* features,
         }
         t->mark("loss");
         Tn dlogits = t->alloc(R, C);
-        TK_HIP(hipMemsetAsync(loss, 0, sizeof(float), c->stream));
-        TK(ps_op_weighted_ce(c, logits.p, lab, class_weights, R, C, loss, dlogits.p));
+        const double* counts = nullptr;  // (n_valid, n_correct) of this rank's rows, where the accuracy is wanted
+        Tn sums;
+        if (loss_kind == PS_LOSS_CE) {
+            TK_HIP(hipMemsetAsync(loss, 0, sizeof(float), c->stream));
+            TK(ps_op_weighted_ce(c, logits.p, lab, class_weights, R, C, loss, dlogits.p));
+            if (accuracy) {
+                sums = t->alloc(1, 4, false);  // (two doubles)
+                TK(ps_op_top1_counts(c, logits.p, lab, R, C, reinterpret_cast<double*>(sums.p)));
+                counts = reinterpret_cast<const double*>(sums.p);
+            }
+        } else {
+            // the three sums per class and the counts in one read of the logits; with statistics shared by the ranks the sums are too, and
+            // the gradient is that of the ONE Dice over all ranks' rows (times the world size: the step takes the mean over the ranks)
+            sums = t->alloc(1, 2 * (3 * C + 2), false);  // (3 C + 2 doubles)
+            double* sd = reinterpret_cast<double*>(sums.p);
+            TK(ps_op_dice_sums(c, logits.p, lab, R, C, sd));
+            const bool shared = t->sync_bn && t->coll_active();
+            if (shared) t->allreduce(sd, 3 * C, 1);
+            TK(ps_op_dice_from_sums(c, loss_kind, logits.p, lab, class_weights, sd, shared ? (float)t->world : 1.f, R, C, loss, dlogits.p));
+            counts = sd + 3 * C;
+        }
+        if (accuracy) {
+            Stage st(c, "train_loss", 1);
+            hipLaunchKernelGGL(tr_accuracy_kernel, dim3(1), dim3(64), 0, c->stream, counts, accuracy);
+            TK_HIP(hipGetLastError());
+        }
         if (logits_out) TK_HIP(hipMemcpyAsync(logits_out, logits.p, sizeof(float) * (size_t)(R * C), hipMemcpyDeviceToDevice, c->stream));
         t->backward(logits, dlogits);
     } catch (const TrainError& e) {
@@ -1941,18 +1976,30 @@ int ps_trainer_profile(const ps_trainer* t, ps_timing_row* rows, int cap, int* n
     return PS_OK;
 }
 
+int ps_randla_backward_loss(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights,
+                            int32_t loss_kind, float* loss, float* accuracy, float* logits)
+{
+    PS_CHECK(t, "ps_randla_backward: trainer is NULL");
+    return run_step(t, pyr, features, labels, class_weights, loss_kind, loss, accuracy, logits, false);
+}
+
+int ps_randla_train_step_loss(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights,
+                              int32_t loss_kind, float* loss, float* accuracy, float* logits)
+{
+    PS_CHECK(t, "ps_randla_train_step: trainer is NULL");
+    return run_step(t, pyr, features, labels, class_weights, loss_kind, loss, accuracy, logits, true);
+}
+
 int ps_randla_backward(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights, float* loss,
                        float* logits)
 {
-    PS_CHECK(t, "ps_randla_backward: trainer is NULL");
-    return run_step(t, pyr, features, labels, class_weights, loss, logits, false);
+    return ps_randla_backward_loss(t, pyr, features, labels, class_weights, PS_LOSS_CE, loss, nullptr, logits);
 }
 
 int ps_randla_train_step(ps_trainer* t, const ps_pyramid* pyr, const float* features, const int32_t* labels, const float* class_weights, float* loss,
                          float* logits)
 {
-    PS_CHECK(t, "ps_randla_train_step: trainer is NULL");
-    return run_step(t, pyr, features, labels, class_weights, loss, logits, true);
+    return ps_randla_train_step_loss(t, pyr, features, labels, class_weights, PS_LOSS_CE, loss, nullptr, logits);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 """Training step of the PointSegment RandLA-Net on MI355X: forward in training mode (batch-statistics BatchNorm,
-dropout), class-weighted cross-entropy, backward, Adam -- the device counterpart of
+dropout), the loss (class-weighted cross-entropy, or one of the reference's two Dice losses: Trainer(loss=)), backward, Adam -- the device
+counterpart of
 
-    Network.__init__ loss / optimizer      PointSegment/RandLANet.py:62-90, 267-274
+    Network.__init__ loss / optimizer      PointSegment/RandLANet.py:62-90, 267-274, 276-312
+    Network.__init__ accuracy              PointSegment/RandLANet.py:93-94
     Network.train's sess.run([train_op, extra_update_ops, ...])   PointSegment/RandLANet.py:162-169
     tf.layers.batch_normalization(..., training=True)             helper_tf_util.py:167,246; RandLANet.py:115
 
@@ -39,6 +41,48 @@ def _rowmajor(t):
     """t as a 2-D tensor with contiguous rows (any row stride): column blocks of a wider tensor pass through untouched,
     the strided entry points (ps_op_*_ex) take the row stride."""
     return t if (t.dim() == 2 and t.stride(1) == 1) else t.contiguous()
+
+
+def point_loss(logits, labels, kind, class_weights=None, grad_scale=1.0, ctx=None):
+    """The point network's loss on logits f32 [R, C] and training labels i32 [R] (a label outside [0, C) is an ignored row), stand-alone, over
+    the three ops of include/pointseg_train_loss.h.  kind: "ce" | "dice" | "dice_weighted"; class_weights [C] (None: ones; "dice" does not
+    read them).  Returns (loss, accuracy, dlogits, sums): device tensors, loss and accuracy float32 scalars, dlogits the gradient times
+    grad_scale (the Dice kinds), sums float64 -- [3 C + 2] = per class (S0, S1, S2), then n_valid, n_correct for the Dice kinds, the two
+    counts alone for "ce"."""
+    if kind not in _lib.TRAIN_LOSSES:
+        raise ValueError("kind must be one of %s" % sorted(_lib.TRAIN_LOSSES))
+    L = _lib.lib()
+    ctx = ctx or runtime.default_context(logits.device.index or 0)
+    if getattr(ctx, "_stream", None) is None:
+        ctx.use_torch_stream()
+    h = ctx.handle
+    z = logits.float().contiguous()
+    R, C = z.shape
+    y = labels.reshape(-1).to(torch.int32).contiguous()
+    if class_weights is None:
+        cw = torch.ones(C, dtype=torch.float32, device=z.device)
+    else:
+        cw = torch.as_tensor(class_weights, dtype=torch.float32).reshape(-1).to(z.device).contiguous()
+    if cw.numel() != C:
+        raise ValueError("class_weights must hold one value per class")
+    loss = torch.zeros((), dtype=torch.float32, device=z.device)
+    dlogits = torch.empty_like(z)
+    if kind == "ce":
+        sums = torch.empty(2, dtype=torch.float64, device=z.device)
+        _lib.check(L.ps_op_weighted_ce(h, _p(z), _p(y), _p(cw), R, C, _p(loss), _p(dlogits)))
+        _lib.check(L.ps_op_top1_counts(h, _p(z), _p(y), R, C, _p(sums)))
+        if grad_scale != 1.0:
+            dlogits.mul_(grad_scale)
+    else:
+        sums = torch.empty(3 * C + 2, dtype=torch.float64, device=z.device)
+        _lib.check(L.ps_op_dice_sums(h, _p(z), _p(y), R, C, _p(sums)))
+        _lib.check(L.ps_op_dice_from_sums(h, _lib.TRAIN_LOSSES[kind], _p(z), _p(y), _p(cw), _p(sums), float(grad_scale), R, C, _p(loss), _p(dlogits)))
+    return loss, _accuracy(sums[-2:]), dlogits, sums
+
+
+def _accuracy(counts):
+    """float32(n_correct / n_valid) from the float64 counts (n_valid, n_correct); 0 when nothing is valid"""
+    return torch.where(counts[0] > 0, counts[1] / counts[0].clamp_min(1.0), torch.zeros_like(counts[0])).float()
 
 
 def allreduce_mean_(flat, dist):
@@ -471,8 +515,12 @@ class Trainer:
 
     def __init__(self, config, params=None, device=0, seed=0, learning_rate=None, class_weights=None, keep_prob=0.5, ctx=None, sync_bn=False,
                  mlp_dtype="fp32", ignored_label_inds=None, fused_att=True, fused_locse=True, fused_convbn=None, engine="native", deterministic=True,
-                 overlap_wgrad=False, act_bf16=None):
-        """sync_bn: with a `dist` passed to train_step, BatchNorm uses the statistics of all ranks' rows, which makes "W GPUs x
+                 overlap_wgrad=False, act_bf16=None, loss="ce"):
+        """loss: "ce" (default), the class-weighted cross-entropy; "dice" / "dice_weighted", the reference's dice_loss / get_loss_dice_weight
+        on the raw logits (include/pointseg_train_loss.h; "dice_weighted" takes class_weights as u, [4, 1, 1, 1] for BraTS).  With `dist`
+        and sync_bn the Dice sums are shared by the ranks like the BatchNorm statistics (one more all-reduce of 3 C doubles): W ranks x one
+        cloud is then the step of one rank x W clouds; without sync_bn every rank minimises the Dice of its own rows.
+        sync_bn: with a `dist` passed to train_step, BatchNorm uses the statistics of all ranks' rows, which makes "W GPUs x
         one cloud" numerically the same step as "one GPU x W clouds" (SURVEY 8e); off = per-GPU statistics.
         mlp_dtype: "fp32" (default) or "bf16" -- BASELINE configs[2]'s "bf16 MLPs": the shared-MLP GEMMs (forward, input gradient,
         weight gradient) round their operands to bf16 and accumulate in fp32 (ps_set_train_gemm_bf16); everything else stays fp32.
@@ -484,6 +532,10 @@ class Trainer:
             raise ValueError("mlp_dtype must be 'fp32' or 'bf16'")
         if engine not in ("native", "python"):
             raise ValueError("engine must be 'native' or 'python'")
+        if loss not in _lib.TRAIN_LOSSES:
+            raise ValueError("loss must be one of 'ce', 'dice', 'dice_weighted'")
+        self._loss = loss
+        self.last_accuracy = None  # device scalar after every step: this rank's top-1 accuracy over the rows that are not ignored
         self.engine = engine
         if fused_convbn is None:  # on in the native step (measured 47.9 -> 46.3 ms at batch 8), off in the Python tape (its older passes lose)
             fused_convbn = engine == "native"
@@ -566,6 +618,11 @@ class Trainer:
         self._rank = 0
         self._coll = None  # (callback object, dist) kept alive while the native trainer may call it
         self._warned_export = False
+
+    @property
+    def loss(self):
+        """"ce" | "dice" | "dice_weighted": the objective this trainer was created with"""
+        return self._loss
 
     def _options(self):
         o = _lib.PsTrainOptions()
@@ -818,9 +875,12 @@ class Trainer:
         lab = labels.reshape(-1).to(torch.int32).contiguous()
         loss = torch.zeros(1, dtype=torch.float32, device=feats.device)
         logits = torch.empty((B * n0, self.cfg.num_classes), dtype=torch.float32, device=feats.device)
-        _lib.check(lib.ps_randla_train_step(self._h, ctypes.byref(pyr.struct), _p(feats), _p(lab), _p(self.class_weights), _p(loss), _p(logits)))
+        acc = torch.zeros((), dtype=torch.float32, device=feats.device)
+        _lib.check(lib.ps_randla_train_step_loss(self._h, ctypes.byref(pyr.struct), _p(feats), _p(lab), _p(self.class_weights),
+                                                 _lib.TRAIN_LOSSES[self._loss], _p(loss), _p(acc), _p(logits)))
         self.step = int(lib.ps_trainer_get_step(self._h))
         self.last_logits = logits
+        self.last_accuracy = acc
         return loss
 
     def backward_only(self, pyr, features, labels):
@@ -837,8 +897,11 @@ class Trainer:
         own = getattr(self.ctx, "_stream", None)
         if own is None:
             self.ctx.use_torch_stream()
-        _lib.check(lib.ps_randla_backward(self._h, ctypes.byref(pyr.struct), _p(feats), _p(lab), _p(self.class_weights), _p(loss), _p(logits)))
+        acc = torch.zeros((), dtype=torch.float32, device=feats.device)
+        _lib.check(lib.ps_randla_backward_loss(self._h, ctypes.byref(pyr.struct), _p(feats), _p(lab), _p(self.class_weights),
+                                               _lib.TRAIN_LOSSES[self._loss], _p(loss), _p(acc), _p(logits)))
         self.last_logits = logits
+        self.last_accuracy = acc
         return loss
 
     def set_profile(self, on=True):
@@ -878,7 +941,21 @@ class Trainer:
             if self.label_map is not None:
                 inside = (lab >= 0) & (lab < self.label_map.numel())
                 lab = torch.where(inside, self.label_map[lab.clamp(0, self.label_map.numel() - 1).long()], torch.full_like(lab, -1)).contiguous()
-            _lib.check(lib.ps_op_weighted_ce(h, _p(logits), _p(lab), _p(self.class_weights), R, C, _p(loss), _p(dlogits)))
+            if self._loss == "ce":
+                counts = torch.empty(2, dtype=torch.float64, device=logits.device)
+                _lib.check(lib.ps_op_weighted_ce(h, _p(logits), _p(lab), _p(self.class_weights), R, C, _p(loss), _p(dlogits)))
+                _lib.check(lib.ps_op_top1_counts(h, _p(logits), _p(lab), R, C, _p(counts)))
+            else:
+                sums = torch.empty(3 * C + 2, dtype=torch.float64, device=logits.device)
+                _lib.check(lib.ps_op_dice_sums(h, _p(logits), _p(lab), R, C, _p(sums)))
+                counts = sums[3 * C:].clone()  # (this rank's)
+                scale = 1.0
+                if t.sync is not None:  # shared statistics: the ONE Dice over all ranks' rows (the gradient mean below divides by the world)
+                    t.sync.all_reduce(sums[:3 * C])
+                    scale = float(t.sync.get_world_size())
+                _lib.check(lib.ps_op_dice_from_sums(h, _lib.TRAIN_LOSSES[self._loss], _p(logits), _p(lab), _p(self.class_weights), _p(sums), scale,
+                                                    R, C, _p(loss), _p(dlogits)))
+            self.last_accuracy = _accuracy(counts)
             t.backward(logits, dlogits)
         finally:
             if self.mlp_bf16:  # the context may be shared with inference-side op calls: never leave the mode on
